@@ -2,7 +2,12 @@
 """Benchmark of the hot path: scene-frames/s of `TrackBuffer.track` (DBSCAN + gating /
 association + Kalman) over S concurrent synthetic scenes.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps of the headline workload and prints its line (with
+`--dump-outputs DIR`, the last timed step's outputs are written to DIR first).  Every further leg
+described below -- CPU baselines, the other population, cold start, shard legs, end-to-end, the
+configs[3] parity leg, the single scene, the host-fed legs -- runs only with `--full`.
 
 N > 1 needs no launcher: when WORLD_SIZE is unset the script starts one child process per GPU
 itself (before anything in this process touches the GPU) and prints rank 0's line; under
@@ -44,7 +49,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from mmwave_msc_amd.shard import shard_range  # noqa: E402  (no torch, no GPU)
-from mmwave_msc_amd.synth import make_scene  # noqa: E402
+from mmwave_msc_amd.synth import FRAME_DT, _place_targets, make_scene  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured copy)
 MFMA_FP32_PEAK_TF = 157.3   # dense fp32 matrix-core peak (MI355X_MICROARCH.md)
@@ -72,6 +77,122 @@ def generate(scene_ids, frames, n_pts, tracks, workers, population="mixed"):
     cnt = np.stack([r[1] for r in res], axis=1)
     dts = np.stack([r[2] for r in res], axis=1)
     return np.ascontiguousarray(pts), np.ascontiguousarray(cnt), np.ascontiguousarray(dts)
+
+
+# A run of F frames cycles through min(F, POOL_FRAMES) generated frames: frame f is pool frame p = f mod P with every target
+# row moved along its target's straight walk by vel * FRAME_DT * (f - p).  The walks (start, velocity) are make_scene's own, so
+# the tracks and the work per step are those of make_scene(F); only the per-point noise repeats every P frames.  For
+# F <= POOL_FRAMES the frames ARE make_scene(F)'s, bit for bit (tests/test_host_logic.py).  Host work stays that of
+# POOL_FRAMES frames however long the run, and the F resident frames are expanded on the device.
+POOL_FRAMES = 64
+INGEST_FRAMES = 200   # timed frames of the host-fed legs (--full) at most
+Y_MIN = np.float32(0.05)   # make_scene keeps every row at y >= 0.05 (inside normalize_data's scene filter)
+
+
+def _pool_one(args):
+    """make_scene(sid, frames, n_pts, k) with its draws in its order, y not yet clamped, plus which target each row
+    belongs to (-1: clutter) and the targets' velocities."""
+    sid, f, n_pts, k = args
+    rng = np.random.default_rng(int(sid))
+    per_t = int(np.floor(0.9 * n_pts / k)) if k > 0 else 0
+    n_clutter = n_pts - per_t * k
+    c0 = _place_targets(rng, k) if k > 0 else np.zeros((0, 2))
+    vel = rng.normal(0.0, 0.5, size=(k, 2))
+    dt = np.full(f, FRAME_DT, dtype=np.float64)
+    t = (np.cumsum(dt) - dt[0])[:, None, None]
+    centre = c0[None] + vel[None] * t
+    out = np.zeros((f, n_pts, 8), dtype=np.float64)
+    tid = np.full((f, n_pts), -1, dtype=np.int8)
+    if k > 0:
+        tp = np.empty((f, k, per_t, 8))
+        tp[..., 0:2] = centre[:, :, None, :] + rng.normal(0.0, 0.15, size=(f, k, per_t, 2))
+        tp[..., 2] = rng.uniform(0.05, 1.8, size=(f, k, per_t))
+        tp[..., 3:5] = vel[None, :, None, :] + rng.normal(0.0, 0.05, size=(f, k, per_t, 2))
+        tp[..., 5] = rng.normal(0.0, 0.05, size=(f, k, per_t))
+        out[:, : k * per_t] = tp.reshape(f, k * per_t, 8)
+        tid[:, : k * per_t] = np.repeat(np.arange(k, dtype=np.int8), per_t)[None]
+    cl = out[:, k * per_t:]
+    cl[..., 0] = rng.uniform(-3.0, 3.0, size=(f, n_clutter))
+    cl[..., 1] = rng.uniform(0.2, 8.0, size=(f, n_clutter))
+    cl[..., 2] = rng.uniform(0.05, 2.4, size=(f, n_clutter))
+    cl[..., 3:6] = rng.normal(0.0, 0.05, size=(f, n_clutter, 3))
+    out[..., 6] = rng.normal(0.0, 0.3, size=(f, n_pts))
+    out[..., 7] = rng.gamma(1.0, 30.0, size=(f, n_pts))
+    perm = np.argsort(rng.random(size=(f, n_pts)), axis=1)
+    out = np.take_along_axis(out, perm[:, :, None], axis=1)
+    tid = np.take_along_axis(tid, perm, axis=1)
+    return out.astype(np.float32), tid, vel
+
+
+def scene_pool(scene_ids, frames, n_pts, tracks, workers, population="mixed"):
+    """The frame pool of a run of `frames` frames: dict(pts[P,S,N,8] float32 (y unclamped), tid[P,S,N] int64 (target of each
+    row; `tracks` = clutter), vel[S,tracks+1,2] float64 (last row zero), frames, S, N)."""
+    P = min(int(frames), POOL_FRAMES)
+    ks = [tracks if population == "full" else 1 + int(s) % tracks for s in scene_ids]
+    jobs = [(int(s), P, n_pts, k) for s, k in zip(scene_ids, ks)]
+    if workers > 1 and len(jobs) > 8:
+        import multiprocessing as mp
+        with mp.get_context("fork").Pool(workers) as pool:
+            res = pool.map(_pool_one, jobs, chunksize=max(1, len(jobs) // (workers * 4)))
+    else:
+        res = [_pool_one(j) for j in jobs]
+    S = len(jobs)
+    vel = np.zeros((S, tracks + 1, 2))
+    for i, r in enumerate(res):
+        vel[i, : r[2].shape[0]] = r[2]
+    tid = np.stack([r[1] for r in res], axis=1).astype(np.int64)
+    tid[tid < 0] = tracks
+    return {"pts": np.ascontiguousarray(np.stack([r[0] for r in res], axis=1)), "tid": tid, "vel": vel,
+            "frames": int(frames), "S": S, "N": int(n_pts)}
+
+
+def pool_counts(pool):
+    """counts[F,S] int32, dt[F,S] float64 of the run (every frame full, FRAME_DT apart, as make_scene)."""
+    F, S = pool["frames"], pool["S"]
+    return np.full((F, S), pool["N"], dtype=np.int32), np.full((F, S), FRAME_DT, dtype=np.float64)
+
+
+def expand_host(pool, workers=1):
+    """points[F,S,N,8] float32 of the run on the host (what expand_device builds, bit for bit)."""
+    from concurrent.futures import ThreadPoolExecutor
+    pp, tid, vel, F = pool["pts"], pool["tid"], pool["vel"], pool["frames"]
+    P = pp.shape[0]
+    out = np.empty((F,) + pp.shape[1:], dtype=np.float32)
+
+    def one(f):
+        p = f % P
+        fr = out[f]
+        fr[...] = pp[p]
+        if f != p:
+            g = np.take_along_axis(vel * (FRAME_DT * (f - p)), tid[p][:, :, None], axis=1)
+            fr[..., :2] = (pp[p][..., :2].astype(np.float64) + g).astype(np.float32)
+        np.maximum(fr[..., 1], Y_MIN, out=fr[..., 1])
+    with ThreadPoolExecutor(max(1, workers)) as ex:
+        list(ex.map(one, range(F)))
+    return out
+
+
+def expand_device(pool, dev, dtype, out=None):
+    """points[F,S,N,8] of the run in HBM (dtype float64: promoted from the float32 rows), built from the pool on the device
+    (into `out` when given)."""
+    import torch
+    pp = torch.from_numpy(pool["pts"]).to(dev)
+    tid = torch.from_numpy(pool["tid"]).to(dev)
+    vel = torch.from_numpy(pool["vel"]).to(dev)
+    P, F = pp.shape[0], pool["frames"]
+    if out is None:
+        out = torch.empty((F,) + tuple(pp.shape[1:]), dtype=dtype, device=dev)
+    assert tuple(out.shape) == (F,) + tuple(pp.shape[1:]) and out.dtype == dtype
+    for f in range(F):
+        p = f % P
+        fr = pp[p].clone()
+        if f != p:
+            g = torch.gather(vel * (FRAME_DT * (f - p)), 1, tid[p].unsqueeze(-1).expand(-1, -1, 2))
+            fr[..., :2] = (fr[..., :2].double() + g).float()
+        fr[..., 1].clamp_min_(float(Y_MIN))
+        out[f] = fr
+    del pp, tid, vel
+    return out
 
 
 def effective_cores():
@@ -262,6 +383,52 @@ def dry_run(rank, world, lo, hi, S_total, scaling, slots):
     return 0 if ok else 1
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_NO_ROW = -9.0   # association / label entry of a row the step did not have (-1 and -2 are values of the outputs)
+
+
+def dump_outputs(out_dir, sb, d_assoc, d_lab, d_dbn, counts, scene_base, tracks, rank, world):
+    """What the last timed step handed its caller, as .npy files in float32 / float64: the association of every row
+    (DUMP_NO_ROW past the scene's point count), the DBSCAN labels (DUMP_NO_ROW past db_n), db_n, the track count and the
+    track state (x, P, lifetime / point_num / is_static / uid; zero past the track count).  Every value is finite; integers
+    are exact in float32.  When the
+    rank's scenes would need more than 64 MB, a fixed seeded sample of them is written (`scene_ids` names them)."""
+    import torch
+    torch.cuda.synchronize()
+    S, N = d_assoc.shape
+    UM = d_lab.shape[1]
+    ntr = sb.num_tracks()
+    cap = max(int(tracks), int(ntr.max()) if S else 0, 1)
+    per_scene = 4 * (N + UM + 2) + 8 * cap * (9 + 81 + 4) + 8
+    keep = np.arange(S)
+    if S * per_scene > DUMP_LIMIT_BYTES:
+        n_keep = max(1, DUMP_LIMIT_BYTES // per_scene)
+        keep = np.sort(np.random.default_rng(0).choice(S, n_keep, replace=False))
+    cnt = np.asarray(counts, dtype=np.int64)[keep]
+    dbn = d_dbn.cpu().numpy()[keep]
+    assoc = d_assoc.cpu().numpy()[keep].astype(np.float32)
+    assoc[np.arange(N)[None, :] >= cnt[:, None]] = DUMP_NO_ROW
+    labels = d_lab.cpu().numpy()[keep].astype(np.float32)
+    labels[np.arange(UM)[None, :] >= np.maximum(dbn, 0)[:, None]] = DUMP_NO_ROW
+    trk = sb.tracks(cap=cap)[keep]
+    n_k = ntr[keep]
+    absent = np.arange(cap)[None, :] >= n_k[:, None]
+    x = trk["x"].astype(np.float64)
+    P = trk["P"].astype(np.float64)
+    meta = np.stack([trk["lifetime"], trk["point_num"], trk["is_static"], trk["uid"]], axis=-1).astype(np.float64)
+    for a in (x, P, meta):
+        a[absent] = 0.0
+    out = {"scene_ids": (scene_base + keep).astype(np.float64), "association": assoc, "dbscan_labels": labels,
+           "dbscan_n": dbn.astype(np.float32), "num_tracks": n_k.astype(np.float32), "track_x": x, "track_P": P,
+           "track_meta": meta}
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES
+    assert all(np.isfinite(a).all() for a in out.values()), [k for k, a in out.items() if not np.isfinite(a).all()]
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -300,10 +467,22 @@ def main():
                     help="mmw_config.fused_step: 0 = the library's choice (k_scene for contexts whose scenes are all resident), 1 = on, -1 = off")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / shard / gather plumbing only, on the CPU with gloo (tests/test_dist_gloo.py): no GPU work, no metric")
+    ap.add_argument("--full", action="store_true",
+                    help="run every further leg too (CPU baselines, the other population, cold start, shard legs, end-to-end, "
+                         "configs[3] parity, single scene, host-fed legs; each --no-* flag still skips its own); a plain run "
+                         "times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (association, DBSCAN labels, the "
+                         "track state) to DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--gen-workers", type=int, default=-1,
                     help="processes for scene generation (-1 = auto; use 1 under rocprofv3: its preloaded tool initialises "
                          "the GPU before main(), and forking after that hangs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu = args.no_full = args.no_e2e = args.no_e2e_parity = args.no_cold = True
+        args.no_shards = args.no_single = args.no_ingest = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args, sys.argv[1:]))
@@ -335,7 +514,9 @@ def main():
     t_gen = time.perf_counter()
     ids = np.arange(lo, hi)
     workers = args.gen_workers if args.gen_workers > 0 else max(1, min(32, cores // max(world, 1)))
-    pts, cnt, dts = generate(ids, F, N, args.tracks, workers=workers, population=args.population)
+    pool = scene_pool(ids, F, N, args.tracks, workers=workers, population=args.population)
+    cnt, dts = pool_counts(pool)
+    pts = expand_host(pool, cores) if args.full else None   # (the host frames only the --full legs read)
     other_pop = "mixed" if args.population == "full" else "full"
     t_gen = time.perf_counter() - t_gen
     cpu, finals = {}, None
@@ -343,9 +524,11 @@ def main():
         cpu, finals = cpu_legs(pts, cnt, dts, args.tracks, cores, W, args.py_scenes_per_core, args.py_frames, args.c_scenes)
     full_host, cpu_full, finals_full = None, {}, None
     if single and not args.no_full:
-        full_host = generate(ids, F, N, args.tracks, workers=workers, population=other_pop)
+        pool_other = scene_pool(ids, F, N, args.tracks, workers=workers, population=other_pop)
+        full_host = pool_counts(pool_other)   # (its frames are built on the device; the host copy only feeds the CPU legs)
         if not args.no_cpu:
-            cpu_full, finals_full = cpu_legs(*full_host, args.tracks, cores, W, args.py_scenes_per_core, args.py_frames, args.c_scenes)
+            cpu_full, finals_full = cpu_legs(expand_host(pool_other, cores), *full_host, args.tracks, cores, W, args.py_scenes_per_core,
+                                             args.py_frames, args.c_scenes)
     def cpu_e2e_leg(p_, c_, d_, tracks_, what):
         """the end-to-end loop on the CPU port: oracle/py_tracker.py + reference-shaped relative_coordinates / format_single_frame
         + oracle/mars_torch.py (fp32, torch's CPU operators), one process per host core, on a bounded sample of the leg's scenes
@@ -411,18 +594,10 @@ def main():
     rows32 = args.rows == "f32"
     row_dtype = torch.float32 if rows32 else torch.float64
 
-    def resident(host_frames):
-        """the frames of a leg in HBM before its clock starts: as they are (fp32 rows) or promoted to fp64"""
-        d = torch.empty(host_frames.shape, dtype=row_dtype, device=dev)
-        for f_ in range(host_frames.shape[0]):
-            t_ = torch.from_numpy(host_frames[f_]).to(dev)
-            d[f_] = t_ if rows32 else t_.double()
-        return d
-
     def stepper(ctx):
         return ctx.step_dev_f32 if rows32 else ctx.step_dev
 
-    d_pts = resident(pts)
+    d_pts = expand_device(pool, dev, row_dtype)
     d_cnt = torch.from_numpy(cnt).to(dev)
     d_dt = torch.from_numpy(dts).to(dev)
     d_assoc = torch.empty((S, N), dtype=torch.int32, device=dev)
@@ -515,6 +690,8 @@ def main():
     side_workers = {0: "off", 1: "on", 2: "unchecked"}[sb.side_workers()]   # the DBSCAN chain workers on their side streams
     prof = {k: sb.profile_get(k) for k in (_lib.K_TRACK, _lib.K_DBSCAN, _lib.K_TABLE, _lib.K_PREDICT, _lib.K_POST)}
     gathered_rows = int(gathered.shape[0])
+    if args.dump_outputs:   # (before any further leg re-uses the context or the output buffers)
+        dump_outputs(args.dump_outputs, sb, d_assoc, d_lab, d_dbn, cnt[F - 1], lo, args.tracks, rank, world)
 
     def final_state_equal(ctx, want_states):
         """final track state of the context's first len(want_states) scenes against the oracle's, bit for bit"""
@@ -592,8 +769,10 @@ def main():
     #      every frame) ----
     full = None
     if full_host is not None:
-        fp_, fc_, fd_ = full_host
-        d_fp = resident(fp_)
+        fc_, fd_ = full_host
+        # (into the headline's buffer: two populations of a long run do not fit in HBM together; the headline's frames are
+        #  rebuilt in it after this leg)
+        d_fp = expand_device(pool_other, dev, row_dtype, out=d_pts)
         d_fc, d_fd = torch.from_numpy(fc_).to(dev), torch.from_numpy(fd_).to(dev)
         ctx = SceneBatch(_lib.default_config(tr_max_tracks=args.tracks, chain_side_stream=args.chain_side_stream, fused_step=args.fused_step),
                          S, N, device=local_rank)
@@ -617,6 +796,7 @@ def main():
             full["speedup_vs_cpu_native"] = round(full["value"] / cpu_full["cpu_baseline_native"]["value"], 1)
         ctx.close()
         del d_fp
+        expand_device(pool, dev, row_dtype, out=d_pts)
 
     # ---- end to end: the same scenes again from frame 0, estimate_posture after every track() ----
     e2e = None
@@ -659,8 +839,10 @@ def main():
         try:
             from bench_ingest import ingest_leg
             e2e_ms = e2e.get("ms_per_step") if isinstance(e2e, dict) else None
-            ingest = ingest_leg(sb, pts, cnt, dts, d_cnt, d_dt, (d_assoc, d_lab, d_dbn), W, F, S, world, barrier, max_over_ranks, dev, side,
-                                resident_ms=el / K * 1e3, e2e_resident_ms=e2e_ms, with_e2e=not args.no_e2e)
+            # (the host-fed legs pin and transform every frame they feed: at most INGEST_FRAMES timed frames of a long run)
+            Fi = W + min(K, INGEST_FRAMES)
+            ingest = ingest_leg(sb, pts[:Fi], cnt[:Fi], dts[:Fi], d_cnt, d_dt, (d_assoc, d_lab, d_dbn), W, Fi, S, world, barrier,
+                                max_over_ranks, dev, side, resident_ms=el / K * 1e3, e2e_resident_ms=e2e_ms, with_e2e=not args.no_e2e)
         except Exception as exc:  # never lose the headline line over a further leg
             ingest = {"error": repr(exc)[:300]}
 

@@ -28,6 +28,11 @@ def raw_rows_from_normalised(pts, tilt_cos, tilt_sin, s_height):
     (Utils.py:294-339) on the position, and as doppler what a radar measures of the row's velocity -- its RADIAL component
     (v . p) / |p| in the sensor's frame -- so that normalize_data (Utils.py:380-398: v = doppler * p / |p|) gives the tracker
     velocity columns that are consistent with the targets' motion, as for a real sensor.  float32 [..., 5]."""
+    if pts.ndim > 3:   # a frame at a time: fp64 temporaries of one frame, not of a whole long run
+        raw = np.empty(pts.shape[:-1] + (5,), dtype=np.float32)
+        for i in range(pts.shape[0]):
+            raw[i] = raw_rows_from_normalised(pts[i], tilt_cos, tilt_sin, s_height)
+        return raw
     p64 = pts.astype(np.float64)
     y1, z1 = p64[..., 1], p64[..., 2] - s_height
     x, y, z = p64[..., 0], tilt_cos * y1 + tilt_sin * z1, -tilt_sin * y1 + tilt_cos * z1
@@ -220,7 +225,9 @@ def ingest_leg(sb, pts, cnt, dts, d_cnt, d_dt, outs, W, F, S, world, barrier, ma
         from mmwave_msc_amd import radar
         ucp = {"rangeIdxToMeters": 0.0436, "dopplerResolutionMps": 0.01, "numDopplerBins": 65536.0}   # (no index above the wrap threshold)
         QF = 9
-        bodies = radar.encode_tlv_bodies(raw, np.maximum(cnt, 0), QF, ucp["dopplerResolutionMps"])   # [F, S, stride] uint8
+        # [F, S, stride] uint8, a frame at a time (the encoder's temporaries of a whole long run would not fit in host memory)
+        bodies = np.stack([radar.encode_tlv_bodies(raw[f_], np.maximum(cnt[f_], 0), QF, ucp["dopplerResolutionMps"])
+                           for f_ in range(raw.shape[0])])
         feed = HostFeed(sb, bodies, "tlv", d_cnt, d_dt, outs, dev, stream, max_pts=N, uart_cfg=radar.uart_cfg(ucp))
         sb.profile_reset()
         sb.profile(True, kernels=(_lib.K_NORMALIZE,))

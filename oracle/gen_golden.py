@@ -233,6 +233,44 @@ def gen_normalize():
     print(f"  normalize: {n} -> {out.shape[0]} rows")
 
 
+CONST_SKIP = ("MOTION_MODEL", "CONST_ACC_MODEL", "CONST_VEL_MODEL", "SCREEN_CONNECTED")
+CONST_DTS = (0.1, 0.2, 0.37, 1.2)
+
+
+def gen_constants():
+    """Every upper-case value of the reference's constants.py (but the motion-model classes and SCREEN_CONNECTED) and the
+    KF_F / KF_Q_DISCR / KF_H of both motion models at a few dt: what tests/test_host_logic.py pins constants.py on."""
+    const, _, _ = load_reference()
+    out = {}
+    for name in dir(const):
+        if name.isupper() and name not in CONST_SKIP:
+            out["c_" + name] = np.asarray(getattr(const, name))
+    for m in ("CONST_ACC_MODEL", "CONST_VEL_MODEL"):
+        model = getattr(const, m)
+        out[f"{m}.KF_H"] = np.asarray(model.KF_H)
+        for i, dt in enumerate(CONST_DTS):
+            out[f"{m}.KF_F.{i}"] = np.asarray(model.KF_F(dt))
+            out[f"{m}.KF_Q_DISCR.{i}"] = np.asarray(model.KF_Q_DISCR(dt))
+    np.savez_compressed(os.path.join(GOLDEN_DIR, "constants.npz"), dts=np.asarray(CONST_DTS), meta=_meta(), **out)
+    print(f"  constants: {sum(k.startswith('c_') for k in out)} values")
+
+
+def gen_normalize_nonfinite():
+    """normalize_data on tests/_fuzz.py's rows with NaN / +-inf planted (seeds 0..3): tests/test_reference_fuzz.py."""
+    from tests._fuzz import nonfinite_raw_rows
+    const, utils, _ = load_reference()
+    out = {}
+    for seed in range(4):
+        raw = nonfinite_raw_rows(seed)
+        det = {"x": list(raw[:, 0]), "y": list(raw[:, 1]), "z": list(raw[:, 2]), "doppler": list(raw[:, 3]), "peakVal": list(raw[:, 4])}
+        with np.errstate(all="ignore"):
+            out[f"out_{seed}"] = utils.normalize_data(det)
+        out[f"raw_{seed}"] = raw
+    np.savez_compressed(os.path.join(GOLDEN_DIR, "normalize_nonfinite.npz"), s_height=const.S_HEIGHT, s_tilt=const.S_TILT,
+                        meta=_meta(), **out)
+    print("  normalize_nonfinite: " + ", ".join(f"{out[f'raw_{i}'].shape[0]} -> {out[f'out_{i}'].shape[0]}" for i in range(4)))
+
+
 def gen_dbscan():
     const, utils, _ = load_reference()
     from sklearn.cluster import DBSCAN
@@ -713,9 +751,21 @@ def _tree_dump(root):
     return out
 
 
+class SortedListdirOs:
+    """`os` with a sorted listdir.  add_noise draws its noise in os.listdir order, which is the file system's own; the
+    recording and tests/test_dataset.py both run with names sorted, so that the noise lands on the same values anywhere."""
+
+    def __getattr__(self, name):
+        return getattr(os, name)
+
+    @staticmethod
+    def listdir(path="."):
+        return sorted(os.listdir(path))
+
+
 def gen_splitsets():
     """split_sets / add_noise (src/preprocessing.py:406-509) on a synthetic pre-processed tree, numpy's global generator
-    seeded: the resulting tree, file by file."""
+    seeded, directories listed in sorted order: the resulting tree, file by file."""
     import csv as _csv
     import json as _json
     import shutil as _shutil
@@ -729,7 +779,7 @@ def gen_splitsets():
                 for mode in ("training", "validate", "testing"):
                     os.makedirs(os.path.join(d, sub, mode))
             const.P_PREPROCESS_PATH, const.P_KINECT_DIR, const.P_MMWAVE_DIR = d + "/", "kinect/", "mmWave/"
-            ns = {"np": np, "os": os, "csv": _csv, "shutil": _shutil, "const": const}
+            ns = {"np": np, "os": SortedListdirOs(), "csv": _csv, "shutil": _shutil, "const": const}
             ref = _reference_functions(os.path.join(os.path.dirname(const.__file__), "preprocessing.py"), {"split_sets", "add_noise"}, ns)
             ref["split_sets"](prefixes)
             after_split = _tree_dump(d)
@@ -758,6 +808,10 @@ def main():
         gen_scenario(name, sc)
     if not args.only or args.only == "normalize":
         gen_normalize()
+    if not args.only or args.only == "constants":
+        gen_constants()
+    if not args.only or args.only == "normalize_nonfinite":
+        gen_normalize_nonfinite()
     if not args.only or args.only == "dbscan":
         gen_dbscan()
     if not args.only or args.only == "dbscan_huge":

@@ -30,6 +30,8 @@ cp(os.path.join(g, "pytest_gpu.txt"), "pytest_gpu.txt")
 cp(os.path.join(g, "smoke.txt"), "smoke.txt")
 for name in ("bench_default.json", "bench_256.json", "bench_160frames.json"):
     src = os.path.join(g, name)
+    if not os.path.exists(src):   # the bench / bench256 stages of scripts/gpu_round.sh write to $BENCH_OUT
+        src = os.path.join(root, os.environ.get("BENCH_OUT", "bench_out"), name)
     if os.path.exists(src) and os.path.getmtime(src) > os.path.getmtime(os.path.join(g, "pmc_summary.json")) - 3600:
         cp(src, name)
 vals = {}

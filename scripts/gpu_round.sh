@@ -3,6 +3,8 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+BENCH_OUT="${BENCH_OUT:-bench_out}"   # where the bench stages put their lines
+mkdir -p "$BENCH_OUT"
 STAGES="${@:-tests smoke bench}"
 for st in $STAGES; do
   case $st in
@@ -11,9 +13,9 @@ for st in $STAGES; do
     smoke)
       timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 | tee gpurun_out/smoke.txt ;;
     bench)
-      timeout 1500 python bench.py 2>&1 | tail -2 | tee gpurun_out/bench_default.json ;;
+      timeout 1500 python bench.py --full 2>&1 | tail -2 | tee "$BENCH_OUT/bench_default.json" ;;
     bench256)
-      timeout 900 python bench.py --scenes 256 --pts 256 --tracks 4 --c-scenes 256 --no-e2e --no-e2e-parity --no-shards --no-full --no-ingest --no-single 2>&1 | tail -2 | tee gpurun_out/bench_256.json ;;
+      timeout 900 python bench.py --full --scenes 256 --pts 256 --tracks 4 --c-scenes 256 --no-e2e --no-e2e-parity --no-shards --no-full --no-ingest --no-single 2>&1 | tail -2 | tee "$BENCH_OUT/bench_256.json" ;;
     bench160)
       timeout 900 python bench.py --no-cpu --no-e2e --no-e2e-parity --no-cold --no-shards --no-full --no-ingest --no-single --steps 150 --warmup 10 2>&1 | tail -1 | tee gpurun_out/bench_160frames.json ;;
     prof)

@@ -100,12 +100,14 @@ def test_preprocess_experiment_writes_the_reference_files(logs, gold):
     assert np.array_equal(np.load(tmp / "A1_centroid.npy"), gold["centroids"])
 
 
-def test_split_sets_and_add_noise_give_the_reference_tree(tmp_path):
+def test_split_sets_and_add_noise_give_the_reference_tree(tmp_path, monkeypatch):
     """split_sets / add_noise (preprocessing.py:406-509) on the synthetic pre-processed tree of tests/golden/splitsets.npz:
     the tree the reference's own functions left (recorded by oracle/gen_golden.py with numpy's global generator seeded),
-    file by file and byte for byte."""
+    file by file and byte for byte.  add_noise draws in os.listdir order, the file system's own: both sides list sorted."""
     import json
     from mmwave_msc_amd import dataset
+    from oracle.gen_golden import SortedListdirOs
+    monkeypatch.setattr(dataset, "os", SortedListdirOs())
     z = np.load(os.path.join(os.path.dirname(__file__), "golden", "splitsets.npz"))
     after_split, after_noise = json.loads(str(z["after_split"])), json.loads(str(z["after_noise"]))
     modes = ("training", "validate", "testing")

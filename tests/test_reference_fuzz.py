@@ -16,7 +16,7 @@ failed stays in the file's regression list.  Arms (tests/_fuzz.py: draw_case):
   threshold   cloud sizes around 11 | 12, 60 | 61, 120 | 121, 240 | 241 (brute force -> BallTree, one more tree level)
   nonfinite   NaN / +-inf planted in random columns of random rows, all three draws in turn
 
-`-m reference`: skipped where /root/reference is absent (the GPU box).  Integers -- association vectors, DBSCAN labels,
+`-m reference` (the window tests): skipped where the reference sources are absent (the GPU box).  Integers -- association vectors, DBSCAN labels,
 track count and order, point counts, ring lengths, static flags, feature owners -- must be equal; fp64 state within
 tests/_golden.py's tolerance (BLAS / LAPACK summation order differs from the oracle's fixed order by a few ULP).
 
@@ -31,7 +31,6 @@ import pytest
 from tests._fuzz import ARMS, draw_case, reference_overrides, scene_inputs
 from tests._golden import assert_feat_equal, assert_tracks_match
 
-pytestmark = pytest.mark.reference
 
 with open(os.path.join(os.path.dirname(__file__), "fuzz_window.json")) as _fh:
     WINDOW = json.load(_fh)
@@ -153,6 +152,7 @@ _CASES = _window()
 _TALLY = {}
 
 
+@pytest.mark.reference
 @pytest.mark.parametrize("chunk", range(-(-len(_CASES) // _CHUNK)))
 def test_live_reference_vs_c_oracle_on_this_rounds_window(chunk):
     """Sixteen (arm, seed) cases of the round's window per test id; a failure names its arm and seed in the assertion context
@@ -165,6 +165,7 @@ def test_live_reference_vs_c_oracle_on_this_rounds_window(chunk):
             t[k] = t.get(k, 0) + v
 
 
+@pytest.mark.reference
 def test_the_window_exercised_what_it_is_for():
     """Runs after the chunks (file order).  The arms must have reached the decisions they exist for: DBSCAN calls on clouds of
     n // 2 <= 5 points WITH clusters in the small arm, raised ValueErrors in the non-finite arm.  The tally goes to
@@ -188,16 +189,15 @@ def test_the_window_exercised_what_it_is_for():
 def test_live_reference_normalize_data_with_nonfinite_rows(seed):
     """normalize_data (Utils.py:342-434) on raw rows with NaN / +-inf planted in every column: the full 4x4 homogeneous products
     of point_transform_to_standard_axis turn ONE non-finite coordinate into three NaN coordinates (0 * inf), which the scene
-    filter drops; a non-finite doppler gives three NaN velocities on a row that is kept; peakVal passes through."""
+    filter drops; a non-finite doppler gives three NaN velocities on a row that is kept; peakVal passes through.  The reference's
+    output is recorded in tests/golden/normalize_nonfinite.npz (oracle/gen_golden.py)."""
     from oracle import c_oracle as co
-    from oracle.ref_import import load_reference
-    const, utils, _ = load_reference()
     from tests._fuzz import nonfinite_raw_rows
+    z = np.load(os.path.join(os.path.dirname(__file__), "golden", "normalize_nonfinite.npz"), allow_pickle=False)
     raw = nonfinite_raw_rows(seed)
-    det = {"x": list(raw[:, 0]), "y": list(raw[:, 1]), "z": list(raw[:, 2]), "doppler": list(raw[:, 3]), "peakVal": list(raw[:, 4])}
-    with np.errstate(all="ignore"):
-        want = utils.normalize_data(det)
-    cfg = co.default_config(s_height=float(const.S_HEIGHT), s_tilt=float(const.S_TILT))
+    assert np.array_equal(raw, z[f"raw_{seed}"], equal_nan=True)
+    want = z[f"out_{seed}"]
+    cfg = co.default_config(s_height=float(z["s_height"]), s_tilt=float(z["s_tilt"]))
     got = co.normalize(cfg, raw)
     assert got.shape == want.shape, (got.shape, want.shape)
     assert np.array_equal(np.isnan(got), np.isnan(want)) and np.array_equal(np.isinf(got), np.isinf(want))
