@@ -363,6 +363,82 @@ int mmw_get_inner(mmw_ctx *ctx, int32_t *n_calls, int32_t *rows, int32_t *labels
  * table[S][slots] (dev), scene ids offset by scene_base.  Async. */
 int mmw_track_table(mmw_ctx *ctx, mmw_track_summary *table, int32_t slots, int32_t scene_base);
 
+/* Snapshot / restore of scene state (format version 1).
+ *
+ * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global
+ * BatchedData each) in a layout-independent, CANONICAL form: its bytes depend only on the reference-visible state, never
+ * on which kernels produced it.  It can be restored into any scene slots of any context whose tracker semantics match;
+ * the restored scenes then continue bit for bit as if they had never left.
+ *
+ *   [mmw_snapshot_header][mmw_snapshot_entry x n_scenes][section of blob scene 0][section 1] ...
+ *
+ * Every section starts 16-byte aligned at its entry's `offset`; sections follow each other in blob order with no gap,
+ * and the last one ends at `total_bytes`.  A section holds, all little-endian, 16-byte aligned:
+ *   - the scene header (64 B, MMW_SNAP_SCENE_HDR_BYTES): n_tracks, g_len, g_n[4], g_slot[4], need_db, err, db_u,
+ *     next_uid, n_upd, flags -- canonical: g_slot[k] = k; need_db = db_u = n_upd = 0; flags = bits 8..15 the ring size
+ *     of BatchedData.change_buffer_size (0 = FB_FRAMES_BATCH + 1), bits 16..23 two per LOGICAL frame k of the global
+ *     ring (bit 16 + 2k: it holds a NaN, 17 + 2k: an infinite value), everything else 0;
+ *   - n_tracks track records of MMW_SNAP_TRACK_BYTES (1496 B of state + 8 B of zeros) in effective_tracks order --
+ *     canonical: ring_slot[k] = k, ring_n[k] = 0 for k >= ring_len, x / P entries beyond dim_x zero;
+ *   - each track's ring frames, oldest first, min(ring_n[k], ring_rows) rows of 8 fp64 each (the rows it stores);
+ *   - the global ring's frames, oldest first, g_n[k] rows of 8 fp64 each.
+ * Not state (not in the blob): per-step scheduling words and lists, queue epochs and tags, statistics, profile counters,
+ * the seek_inner diagnostics of mmw_get_inner.
+ *
+ * Ordering: mmw_snapshot / mmw_restore first wait for EVERYTHING queued on the context -- its stream and the side stream
+ * of the DBSCAN chain workers, which may poll the queues for a few ms after the last step.  A caller with posture work in
+ * flight on another stream (PosturePipeline) drains it first. */
+#define MMW_SNAP_MAGIC "MMWSNAP"            /* 8 bytes with the terminating 0 */
+#define MMW_SNAP_VERSION 1
+#define MMW_SNAP_SCENE_HDR_BYTES 64
+#define MMW_SNAP_TRACK_BYTES 1504
+typedef struct mmw_snapshot_header {
+    char magic[8];          /* MMW_SNAP_MAGIC */
+    uint32_t version;       /* MMW_SNAP_VERSION */
+    uint32_t header_bytes;  /* sizeof(mmw_snapshot_header) */
+    uint64_t total_bytes;   /* the whole blob */
+    int32_t n_scenes;       /* directory entries = sections */
+    int32_t entry_bytes;    /* sizeof(mmw_snapshot_entry) */
+    int32_t max_pts;        /* source context's dimensions */
+    int32_t ring;
+    int32_t ring_rows;
+    int32_t dim_x;
+    int32_t track_cap;
+    int32_t reserved_;
+    mmw_config config;      /* the source context's configuration, verbatim */
+} mmw_snapshot_header;
+typedef struct mmw_snapshot_entry {
+    uint64_t offset;        /* of the section, from the blob's start (16-byte aligned) */
+    uint64_t bytes;         /* of the section */
+    int32_t n_tracks;
+    int32_t g_len;          /* frames in the global ring */
+    int32_t max_g_rows;     /* largest global-ring frame, rows */
+    int32_t max_trk_rows;   /* largest track-ring frame, rows counted (ring_n; a frame stores min(ring_n, ring_rows) of them) */
+    int32_t err;            /* sticky error bits (MMW_ERRBIT_*) */
+    int32_t ring_size;      /* ring size of BatchedData.change_buffer_size (0 = FB_FRAMES_BATCH + 1) */
+    int32_t reserved_[2];
+} mmw_snapshot_entry;
+typedef struct mmw_snapshot_info {
+    mmw_snapshot_header header;
+    const mmw_snapshot_entry *entries;   /* points into the inspected blob: [header.n_scenes] */
+} mmw_snapshot_info;
+/* `scenes`: host array of n distinct scene indices, NULL = all scenes in order (n is then ignored).  Blob scene i is
+ * scenes[i]. */
+int mmw_snapshot_size(mmw_ctx *ctx, const int32_t *scenes, int32_t n, size_t *bytes);                        /* sync */
+/* writes the blob to dev_out (device memory, `cap` bytes, 16-byte aligned); *bytes = its size.  cap too small: MMW_E_ARG,
+ * *bytes = the size needed, nothing written (dev_out may be NULL with cap = 0: one call that only sizes). */
+int mmw_snapshot(mmw_ctx *ctx, const int32_t *scenes, int32_t n, void *dev_out, size_t cap, size_t *bytes);  /* sync */
+/* blob scene i -> scene scenes[i] of this context (NULL: scene i; n must equal the blob's scene count otherwise).  Refused
+ * with MMW_E_ARG before any device write (no scene changes) when: magic, version, sizes or offsets are bad; an index is
+ * duplicated or out of range; any mmw_config field differs from this context's bit for bit other than track_cap,
+ * ring_rows, kalman_dense_min_units, chain_side_stream, fused_step and reserved_; a scene's frames do not fit this
+ * context's max_pts / ring_rows (a track frame the source stored truncated needs the same ring_rows); a scene holds more
+ * tracks than this context's track_cap.  Restored scenes take their tracks from their header at the next step. */
+int mmw_restore(mmw_ctx *ctx, const void *dev_blob, size_t bytes, const int32_t *scenes, int32_t n);        /* sync */
+/* host only, no device: validates a blob's header and directory (the same checks as mmw_restore's, short of the target
+ * context's) and describes it.  MMW_E_ARG + mmw_last_error(NULL) when it is malformed. */
+int mmw_snapshot_inspect(const void *host_blob, size_t bytes, mmw_snapshot_info *out);
+
 /* Kernel timing with hipEvents on the context's stream (bench.py roofline).
  * ids: 0 k_track (association + DBSCAN cell-count screen), 1 k_dbscan_big (BallTree DBSCAN of large clouds), 2 features,
  * 3 normalize, 4 table, 5 k_predict, 6 k_post (Kalman update + BallTree DBSCAN of small clouds). */

@@ -38,6 +38,7 @@ EXPORTS = [
     "mmw_set_batch_size", "mmw_set_batch_frame", "mmw_mars_conv_split", "mmw_mars_dense1_split", "mmw_diag_queue", "mmw_set_chain_side_stream", "mmw_side_workers", "mmw_step_kind", "mmw_streams_concurrent", "mmw_reset_scenes", "mmw_get_errors",
     "mmw_kalman_layout", "mmw_step_f32", "mmw_normalize_f32", "mmw_frame_host", "mmw_mars_head_small", "mmw_mars_range_fixup",
     "mmw_attach_posture", "mmw_frame_posture_host", "mmw_clear_errors", "mmw_stream_wait", "mmw_wait_stream", "mmw_find_tlv", "mmw_normalize_tlv",
+    "mmw_snapshot_size", "mmw_snapshot", "mmw_restore", "mmw_snapshot_inspect",
 ]
 
 
@@ -74,6 +75,32 @@ class MmwConfig(C.Structure):
         ("v_screen_fade_size_max", C.c_double), ("v_screen_fade_size_min", C.c_double), ("v_screen_fade_weight", C.c_double),
         ("fused_step", C.c_int32), ("reserved_", C.c_int32),
     ]
+
+
+SNAP_MAGIC = b"MMWSNAP"   # MMW_SNAP_MAGIC (8 bytes with the terminating 0)
+SNAP_VERSION = 1
+SNAP_SCENE_HDR_BYTES = 64
+SNAP_TRACK_BYTES = 1504
+
+
+class MmwSnapshotHeader(C.Structure):
+    """struct mmw_snapshot_header (include/mmw.h): the head of a scene snapshot."""
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint32), ("header_bytes", C.c_uint32), ("total_bytes", C.c_uint64),
+                ("n_scenes", C.c_int32), ("entry_bytes", C.c_int32), ("max_pts", C.c_int32), ("ring", C.c_int32),
+                ("ring_rows", C.c_int32), ("dim_x", C.c_int32), ("track_cap", C.c_int32), ("reserved_", C.c_int32),
+                ("config", MmwConfig)]
+
+
+class MmwSnapshotEntry(C.Structure):
+    """struct mmw_snapshot_entry (include/mmw.h): one scene of a snapshot's directory."""
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint64), ("n_tracks", C.c_int32), ("g_len", C.c_int32),
+                ("max_g_rows", C.c_int32), ("max_trk_rows", C.c_int32), ("err", C.c_int32), ("ring_size", C.c_int32),
+                ("reserved_", C.c_int32 * 2)]
+
+
+class MmwSnapshotInfo(C.Structure):
+    """struct mmw_snapshot_info (include/mmw.h): what mmw_snapshot_inspect fills in."""
+    _fields_ = [("header", MmwSnapshotHeader), ("entries", C.c_void_p)]
 
 
 TRACK_DTYPE = np.dtype(
@@ -266,6 +293,10 @@ def load():
         "mmw_find_tlv": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
         "mmw_normalize_tlv": (C.c_int, [vp, vp, C.c_size_t, vp, vp, vp, vp]),
         "mmw_format_frames": (C.c_int, [vp, vp, vp, vp, vp, i32]),
+        "mmw_snapshot_size": (C.c_int, [vp, vp, i32, C.POINTER(C.c_size_t)]),
+        "mmw_snapshot": (C.c_int, [vp, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "mmw_restore": (C.c_int, [vp, vp, C.c_size_t, vp, i32]),
+        "mmw_snapshot_inspect": (C.c_int, [vp, C.c_size_t, C.POINTER(MmwSnapshotInfo)]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

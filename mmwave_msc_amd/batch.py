@@ -450,6 +450,73 @@ class SceneBatch:
         self.track_table_dev(b.ptr, slots, scene_base)
         return b.download((self.S, slots), SUMMARY_DTYPE)
 
+    # -- snapshot / restore ---------------------------------------------------
+    def _scene_list(self, scenes):
+        if scenes is None:
+            return None, 0
+        a = np.ascontiguousarray(np.asarray(scenes, dtype=np.int32).reshape(-1))
+        return a, len(a)
+
+    def snapshot_size(self, scenes=None) -> int:
+        """mmw_snapshot_size: bytes of the snapshot of `scenes` (default: all, in order); nothing is written."""
+        a, n = self._scene_list(scenes)
+        out = C.c_size_t(0)
+        self._chk(self.L.mmw_snapshot_size(self.h, a.ctypes.data if a is not None else None, n, C.byref(out)))
+        return int(out.value)
+
+    def _snapshot_into(self, scenes, out):
+        """One mmw_snapshot call into `out` (a DevBuf or None): (nbytes, written).  Too small a buffer writes nothing and
+        reports the size the blob needs."""
+        a, n = self._scene_list(scenes)
+        got = C.c_size_t(0)
+        cap = out.nbytes if out is not None else 0
+        rc = self.L.mmw_snapshot(self.h, a.ctypes.data if a is not None else None, n, out.ptr if out is not None else None, cap, C.byref(got))
+        if rc == _lib.E_ARG and got.value > cap:
+            return int(got.value), False
+        self._chk(rc)
+        return int(got.value), True
+
+    def snapshot_dev(self, scenes=None, out: DevBuf = None):
+        """mmw_snapshot into device memory: (DevBuf, nbytes) -- for device-to-device moves (`restore((buf, nbytes))` on
+        another context of the same device).  Pass the DevBuf of an earlier call as `out` to reuse it: a buffer large enough
+        costs one call (one drain, one size pass and its read-back, the pack); a missing or small one a sizing call first.
+        Waits for everything queued on the context, the side stream included."""
+        nbytes, done = self._snapshot_into(scenes, out)
+        if not done:
+            out = DevBuf(self, nbytes)
+            nbytes, done = self._snapshot_into(scenes, out)
+            assert done, nbytes
+        return out, nbytes
+
+    def snapshot(self, scenes=None) -> bytes:
+        """The state of `scenes` (default: all, in order) as a versioned, layout-independent blob (include/mmw.h)."""
+        nbytes, done = self._snapshot_into(scenes, self._bufs.get("snapshot"))
+        if not done:
+            nbytes, done = self._snapshot_into(scenes, self.buf("snapshot", nbytes))
+            assert done, nbytes
+        return self._bufs["snapshot"].download((nbytes,), np.uint8).tobytes()
+
+    def restore(self, blob, scenes=None):
+        """mmw_restore: blob scene i -> scene scenes[i] (default: scene i).  `blob`: bytes (host) or (DevBuf, nbytes) on the
+        device (what `snapshot_dev` returns).  Refused (MmwError, E_ARG) with no scene changed when the blob or the
+        configuration does not fit."""
+        a, n = self._scene_list(scenes)
+        tmp = None
+        if isinstance(blob, tuple):
+            buf, nbytes = blob
+            if not isinstance(buf, DevBuf) or int(nbytes) > buf.nbytes:
+                raise TypeError("restore((DevBuf, nbytes)): a device blob and its size")
+            ptr = buf.ptr
+        else:
+            b = np.frombuffer(bytes(blob), dtype=np.uint8)
+            tmp = DevBuf(self, max(len(b), 16)).upload(b)
+            ptr, nbytes = tmp.ptr, len(b)
+        try:
+            self._chk(self.L.mmw_restore(self.h, ptr, int(nbytes), a.ctypes.data if a is not None else None, n))
+        finally:
+            if tmp is not None:
+                tmp.free()
+
     # -- profiling ------------------------------------------------------------
     def stats(self) -> np.ndarray:
         out = np.zeros(8, dtype=np.uint64)

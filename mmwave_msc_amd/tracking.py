@@ -71,6 +71,14 @@ class BatchedData:
             return np.array([])  # state after clear() (Tracking.py:57-58)
         return np.concatenate(fr, axis=0)
 
+    # pickle / copy.deepcopy: the frames live in the bound TrackBuffer's snapshot; this object carries its own host fields and
+    # the binding (pickled together with its TrackBuffer, e.g. `pickle.dumps((tb, batch))`, the pair comes back bound)
+    def __getstate__(self):
+        return {"_owner": self._owner, "_init": self._init, "size": self.size, "_size_changed": self._size_changed}
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+
     def pop_frame(self):
         """Remove the oldest frame (Tracking.py:66-71; called by the dataset pre-processing between shards)."""
         if self._owner is not None and self._owner._sb is not None:
@@ -159,6 +167,29 @@ class TrackBuffer:
             self._dx = const.MOTION_MODEL.KF_DIM[0]
             self._sb = SceneBatch(cfg, 1, self._max_pts, self._device)
         return self._sb
+
+    # -- pickle / copy.deepcopy ------------------------------------------------------
+    # The device state travels as a scene snapshot (SceneBatch.snapshot, include/mmw.h), the host fields beside it, the
+    # configuration as the context's mmw_config.  Unpickling creates a fresh one-scene context on `device` and restores
+    # into it: the copy continues bit for bit where the original stood.  An attached posture model (attach_posture_model)
+    # and the device buffers of estimate_posture are NOT carried: the copy has no model attached.
+    _PICKLED = ("next_track_id", "dt", "t", "_max_pts", "_device", "_batch", "_colors", "_dx", "last_assoc", "last_db_labels", "_n_tracks")
+
+    def __getstate__(self):
+        state = {k: self.__dict__[k] for k in self._PICKLED}
+        if self._sb is not None:
+            state["_cfg"] = bytes(memoryview(self._sb.cfg))
+            state["_blob"] = self._sb.snapshot()
+        return state
+
+    def __setstate__(self, state):
+        state = dict(state)
+        cfg, blob = state.pop("_cfg", None), state.pop("_blob", None)
+        self.__init__(state["_max_pts"], state["_device"])
+        self.__dict__.update(state)
+        if cfg is not None:
+            self._sb = SceneBatch(_lib.MmwConfig.from_buffer_copy(cfg), 1, self._max_pts, self._device)
+            self._sb.restore(blob)
 
     def attach_posture_model(self, model):
         """The loop body of offline_main.py:53-60 as ONE round trip: with a `mars.MarsCNN` (3-frame model, on this GPU) attached,
