@@ -43,7 +43,7 @@ extern "C" {
 #define MMW_E_ARG (-1)        /* bad argument / size */
 #define MMW_E_SINGULAR (-2)   /* a 6x6 gate/innovation matrix was singular (numpy raises LinAlgError) */
 #define MMW_E_DIVZERO (-3)    /* (N_est-1)*N == 0 in _get_Rc (Python raises ZeroDivisionError) */
-#define MMW_E_CAPACITY (-4)   /* more tracks than track_cap */
+#define MMW_E_CAPACITY (-4)   /* more tracks than track_cap; mmw_parse_uart_cap: a packet that reaches past the buffer's capacity */
 #define MMW_E_HIP (-5)        /* HIP runtime error */
 #define MMW_E_NODEVICE (-6)   /* no usable gfx950 device: the library has no CPU path */
 #define MMW_E_NONFINITE (-7)  /* apply_DBscan was reached with a NaN or an infinite value in its cloud: sklearn's input validation raises
@@ -506,38 +506,57 @@ int mmw_mars_head_small(void *hip_stream, const float *act, int64_t lda, const f
 
 /* ReadIWR14xx.read (ReadDataIWR1443.py:27-201) on a byte buffer, host only (no context, no GPU work): the input
  * step before mmw_normalize.  Looks for the LAST 8-byte magic word 02 01 04 03 06 05 08 07 in buf[0 .. len-8),
- * needs more than 16 bytes from there and the whole packet (little-endian u32 totalPacketLen at offset 12).
- * If the header announces objects and the first TLV is MMWDEMO_UART_MSG_DETECTED_POINTS (type 1), the objects
- * (u16 count, u16 Q format, then int16 rangeIdx, dopplerIdx, peakVal, x, y, z each) become raw[n][5] =
- * (x, y, z, doppler, peakVal) -- the row layout mmw_normalize takes -- with x,y,z / 2^Q, doppler =
- * dopplerIdx * doppler_resolution_mps after the reference's wrap of indices above num_doppler_bins/2 - 1
- * (it subtracts 65535, in int16), and range_out[n] = rangeIdx * range_idx_to_meters (may be NULL).
- * Returns 1 (points parsed), 0 (no complete packet, no objects or another TLV first) or MMW_E_ARG;
- * *packet_start / *packet_len (0 when no complete packet) tell the caller what to drop from its buffer. */
+ * needs more than 16 bytes from there and at least totalPacketLen of them (little-endian u32 at offset 12; any value,
+ * 0 included: the packet is complete and decoded all the same, as there).  If the header announces objects and the
+ * first TLV is MMWDEMO_UART_MSG_DETECTED_POINTS (type 1), the objects (u16 count, u16 Q format, then int16 rangeIdx,
+ * dopplerIdx, peakVal, x, y, z each) become raw[n][5] = (x, y, z, doppler, peakVal) -- the row layout mmw_normalize
+ * takes -- with x, y, z divided by the reference's numpy-int64 `2 ** Q` (2^Q for Q <= 62, -2^63 for Q = 63, 0 for
+ * Q >= 64: +-inf / NaN), doppler = dopplerIdx * doppler_resolution_mps after the reference's wrap of indices above
+ * num_doppler_bins/2 - 1 (it subtracts 65535, in int16), and range_out[n] = rangeIdx * range_idx_to_meters (may be NULL).
+ * cap >= len is the size of the caller's buffer: the header words, TLV head and objects the packet announces are read
+ * wherever they lie in buf[0 .. cap) -- past len they are what the buffer still holds there, the reference's stale
+ * bytes (a caller that keeps the reference's buffer moves the packet to buf[0] before the decode that counts) --;
+ * one that reaches past cap gives MMW_E_CAPACITY (the reference raises ValueError).
+ * Returns MMW_UART_POINTS (points parsed, *n_obj of them), MMW_UART_PACKET (a complete packet without: no objects
+ * announced, or another TLV first), MMW_UART_NONE (no complete packet), MMW_E_ARG (bad arguments, or more than max_obj
+ * objects, which the reference decodes) or MMW_E_CAPACITY.  *packet_start = the magic word (0 when there is none),
+ * *packet_len = totalPacketLen (0 unless complete) tell the caller what to drop from its buffer. */
+#define MMW_UART_NONE 0
+#define MMW_UART_POINTS 1
+#define MMW_UART_PACKET 2
 typedef struct mmw_uart_cfg {
     double range_idx_to_meters;
     double doppler_resolution_mps;
     int32_t num_doppler_bins;
     int32_t reserved;
 } mmw_uart_cfg;
+int mmw_parse_uart_cap(const uint8_t *buf, size_t len, size_t cap, const mmw_uart_cfg *cfg, double *raw /*[max_obj][5]*/,
+                       double *range_out /*[max_obj]*/, int32_t max_obj, int32_t *n_obj, uint32_t *frame_number, size_t *packet_start,
+                       size_t *packet_len);
+/* The first form, kept for its callers: mmw_parse_uart_cap with cap = len (nothing past len is read), returning 1 for
+ * MMW_UART_POINTS, MMW_E_ARG as it does and 0 otherwise (no complete packet, one without points, or one whose words reach
+ * past len).  Its *packet_len = 0 cannot tell "incomplete" from a packet that declares totalPacketLen 0: use the _cap form. */
 int mmw_parse_uart(const uint8_t *buf, size_t len, const mmw_uart_cfg *cfg, double *raw /*[max_obj][5]*/, double *range_out /*[max_obj]*/,
                    int32_t max_obj, int32_t *n_obj, uint32_t *frame_number, size_t *packet_start, size_t *packet_len);
 
 /* The batched, device-side form of that input step: the host only FINDS the packet, the GPU decodes it.
- * mmw_find_tlv (host, no GPU work) = the packet part of mmw_parse_uart -- last magic word, whole packet present, objects
- * announced, first TLV = detected points, its objects inside the buffer -- without decoding an object: *body_offset = offset
- * from buf of the TLV BODY (u16 numObj, u16 xyzQFormat, numObj x six int16: rangeIdx, dopplerIdx, peakVal, x, y, z; 12 bytes per
- * object, ReadDataIWR1443.py:107-150), -1 if there is none; *n_obj = the count the body announces (the caller checks it
- * against max_pts); returns 1 / 0 / MMW_E_ARG and the packet position as mmw_parse_uart does.
+ * mmw_find_tlv (host, no GPU work) = the packet part of mmw_parse_uart_cap with cap = len -- it has no buffer history, so
+ * nothing past len is read -- without decoding an object: returns 1 with *body_offset = offset from buf of the TLV BODY (u16
+ * numObj, u16 xyzQFormat, numObj x six int16: rangeIdx, dopplerIdx, peakVal, x, y, z; 12 bytes per object,
+ * ReadDataIWR1443.py:107-150) and *n_obj = the count it announces (the caller checks it against max_pts) when the header, the
+ * body and every object it announces lie in buf[0 .. len); 0 otherwise (*body_offset = -1) -- a complete packet whose words
+ * reach past len, where the reference would read stale bytes of its buffer, is refused --; MMW_E_ARG for bad arguments.
+ * The packet position as mmw_parse_uart_cap gives it.
  * mmw_normalize_tlv = ReadIWR14xx.read's decode (ReadDataIWR1443.py:153-171) + Utils.normalize_data (Utils.py:342-434) for
  * every scene in ONE kernel, fused ahead of mmw_step: packets (dev) = the bytes as they arrived, all scenes' packets in one
  * buffer; tlv_offset[S] (dev) = byte offset into `packets` of each scene's TLV body (2-byte aligned), < 0 = no detected-points
- * TLV this frame (n_out = 0: mmw_step skips the scene's frame, offline_main.py:56); cfg (host) as for mmw_parse_uart;
- * pts[S][max_pts][8] / n_out[S] (dev) as mmw_normalize writes them -- bit-equal to mmw_parse_uart + mmw_normalize on the same
- * bytes.  12 bytes per object cross PCIe instead of 20 (fp32 raw rows) or 40 (fp64).  packets_bytes = the size of `packets`:
- * nothing outside it is read.  A body that does not lie inside it on a 2-byte boundary with every object it announces, or that
- * announces more than max_pts objects (mmw_parse_uart returns MMW_E_ARG for those bytes), gives n_out = MMW_BAD_FRAME: the
- * mmw_step that follows raises the scene's bad-count bit (MMW_E_ARG), the other scenes are unaffected. */
+ * TLV this frame (n_out = 0: mmw_step skips the scene's frame, offline_main.py:56); cfg (host) as for mmw_parse_uart_cap;
+ * pts[S][max_pts][8] / n_out[S] (dev) as mmw_normalize writes them -- bit-equal to mmw_parse_uart_cap + mmw_normalize on the same
+ * bytes, the Q format rule included.  12 bytes per object cross PCIe instead of 20 (fp32 raw rows) or 40 (fp64).
+ * packets_bytes = the size of `packets`: nothing outside it is read, whatever the offset (INT64_MAX included).  A body that
+ * does not lie inside it on a 2-byte boundary with every object it announces, or that announces more than max_pts objects
+ * (mmw_parse_uart returns MMW_E_ARG for those bytes), gives n_out = MMW_BAD_FRAME: the mmw_step that follows raises the
+ * scene's bad-count bit (MMW_E_ARG), the other scenes are unaffected. */
 #define MMW_BAD_FRAME (-3)
 int mmw_find_tlv(const uint8_t *buf, size_t len, int64_t *body_offset, int32_t *n_obj, uint32_t *frame_number, size_t *packet_start,
                  size_t *packet_len);

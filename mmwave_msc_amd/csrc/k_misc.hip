@@ -98,7 +98,8 @@ __global__ __launch_bounds__(256) void k_normalize(DevCfg cfg, const RT *__restr
 // The radar's own wire format in, ring rows out: per scene the body of the detected-points TLV of an IWR1443 UART packet
 // (MMWDEMO_UART_MSG_DETECTED_POINTS: u16 numObj, u16 xyzQFormat, then numObj x six little-endian int16 -- rangeIdx, dopplerIdx,
 // peakVal, x, y, z; 12 bytes per object, ReadDataIWR1443.py:107-150), decoded as ReadIWR14xx.read decodes it (153-171: doppler
-// indices above numDopplerBins / 2 - 1 get 65535 subtracted in int16, doppler = idx * dopplerResolutionMps, x, y, z / 2^Q) and
+// indices above numDopplerBins / 2 - 1 get 65535 subtracted in int16, doppler = idx * dopplerResolutionMps, x, y, z divided by
+// the numpy-int64 `2 ** Q`, xyz_q_divisor) and
 // normalised in the same registers.  packets: the bytes as they arrived (any 2-byte alignment of a body); tlv_offset[s] = byte
 // offset of scene s's TLV BODY, < 0 = no detected-points TLV this frame (n_out = 0: the scene's frame is skipped).  The host only
 // finds magic words (mmw_find_tlv).  Nothing outside packets[0 .. packets_bytes) is read: a body that does not lie inside it on a
@@ -116,14 +117,14 @@ __global__ __launch_bounds__(256) void k_normalize_tlv(DevCfg cfg, const uint8_t
     bool bad = false;
     double q = 1.0;
     const unsigned short *body = nullptr;
-    if (off >= 0) {   // uniform
-        bad = (off & 1) != 0 || off + 4 > packets_bytes;
+    if (off >= 0) {   // uniform.  (Bounds by subtraction: `off + 4` overflows for an offset near INT64_MAX.)
+        bad = (off & 1) != 0 || packets_bytes < 4 || off > packets_bytes - 4;
         if (!bad) {
             body = reinterpret_cast<const unsigned short *>(packets + off);
             const int num = body[0], qfmt = body[1];
-            bad = num > cfg.max_pts || off + 4 + 12LL * num > packets_bytes;
+            bad = num > cfg.max_pts || (packets_bytes - 4 - off) / 12 < num;
             n = bad ? 0 : num;
-            q = ldexp(1.0, qfmt);
+            q = xyz_q_divisor(qfmt);
         }
     }
     double v[R][5];

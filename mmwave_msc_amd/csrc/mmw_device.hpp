@@ -96,6 +96,9 @@ __device__ __forceinline__ int row_nonfinite_bits(const double2 (&r)[4])
 __host__ __device__ inline int nf_flags_with(int flags, int phys, int frame_bits) { return (flags & ~(3 << (2 * phys))) | ((frame_bits & 3) << (2 * phys)); }
 // which ValueError sklearn raises for a cloud with these bits (NaN takes precedence)
 __host__ __device__ inline int nf_error_of(int bits) { return (bits & 1) ? ERR_NONFINITE_NAN : ((bits & 2) ? ERR_NONFINITE_INF : 0); }
+// What the reference divides the detected-points TLV's x, y, z by: `2 ** xyzQFormat` with the u16 Q format as a numpy int64
+// (ReadDataIWR1443.py:118), which wraps -- 2^q for q <= 62, -2^63 for q = 63, 0 for q >= 64 (then x / 0 = +-inf, 0 / 0 = NaN).
+__host__ __device__ inline double xyz_q_divisor(unsigned q) { return q <= 62 ? (double)(1ull << q) : (q == 63 ? -9223372036854775808.0 : 0.0); }
 
 // One ClusterTrack.  187 doubles = 1496 B.
 struct TrackRec {

@@ -4,8 +4,13 @@
 range / doppler scales); `UartFrameParser` is `ReadIWR14xx.read` (27-201) without the serial port: the caller
 feeds whatever bytes arrived, the parser keeps the reference's byte buffer discipline (append if it fits, cut to
 the LAST magic word, parse one packet, drop it) and returns the same `(dataOK, frameNumber, detObj)` triple.
-The packet itself is decoded by the C-ABI's host function `mmw_parse_uart` (include/mmw.h).  Opening and
+The packet itself is decoded by the C-ABI's host function `mmw_parse_uart_cap` (include/mmw.h).  Opening and
 configuring the serial ports (pyserial, `__serialConfig`) stays with the application.
+
+Parity: pinned by a recording of the reference's own read() under numpy 1.26 (tests/golden/uart_decode.npz,
+oracle/gen_uart_golden.py) -- short and odd totalPacketLen values, objects read from the stale bytes of the 2^15-byte
+buffer, the int64 wrap of `2 ** xyzQFormat` included.  One declared difference: more than `max_obj` objects raise
+`_lib.MmwError` (MMW_E_ARG) where the reference decodes them.
 """
 from __future__ import annotations
 
@@ -61,7 +66,8 @@ def uart_cfg(config_parameters: dict) -> "_lib.MmwUartCfg":
 def find_tlv(buf) -> tuple:
     """mmw_find_tlv on a bytes-like object: (found, body_offset, n_obj, frame_number, packet_start, packet_len) -- the packet
     part of ReadIWR14xx.read (ReadDataIWR1443.py:47-113) without decoding an object: what the host does per packet when the
-    GPU decodes the detected-points TLV itself (SceneBatch.normalize_tlv_dev)."""
+    GPU decodes the detected-points TLV itself (SceneBatch.normalize_tlv_dev).  found only for a body that lies, with every
+    object it announces, inside `buf`: a packet the reference would complete from stale bytes of its buffer is refused."""
     a = np.frombuffer(buf, dtype=np.uint8)
     off, n = C.c_int64(-1), C.c_int32(0)
     frame = C.c_uint32(0)
@@ -98,20 +104,30 @@ def encode_tlv_bodies(raw: np.ndarray, counts: np.ndarray, qfmt: int, doppler_re
     return out
 
 
+def xyz_q_divisor(qfmt) -> np.ndarray:
+    """What the reference divides x, y, z by: `2 ** xyzQFormat` with the u16 Q format as a numpy int64 (ReadDataIWR1443.py:118),
+    which wraps -- 2^q for q <= 62, -2^63 for q = 63, 0 for q >= 64 (x / 0 = +-inf, 0 / 0 = NaN).  fp64, the shape of qfmt."""
+    q = np.asarray(qfmt, dtype=np.int64)
+    pow2 = np.left_shift(np.int64(1), np.minimum(q, 62)).astype(np.float64)
+    return np.where(q <= 62, pow2, np.where(q == 63, -(2.0 ** 63), 0.0))
+
+
 def decode_tlv_bodies_numpy(bodies: np.ndarray, cfg: dict):
-    """The reference's decode (ReadDataIWR1443.py:153-171, numpy-1.26 int16 wrap) of `encode_tlv_bodies`-shaped bodies, in numpy:
-    (raw[..., N, 5] float64, counts[...]).  The checker's restatement -- the product decodes on the device."""
+    """The reference's decode (ReadDataIWR1443.py:153-171 under its numpy 1.26: int16 wrap, the int64 `2 ** Q` of
+    `xyz_q_divisor`) of `encode_tlv_bodies`-shaped bodies, in numpy: (raw[..., N, 5] float64, counts[...]).  The checker's
+    restatement -- the product decodes on the device; tests/test_uart_decode.py pins it to the reference's recorded read()."""
     lead, stride = bodies.shape[:-1], bodies.shape[-1]
     words = np.ascontiguousarray(bodies).view(np.uint16).reshape(lead + (stride // 2,))
     cnt = words[..., 0].astype(np.int32)
-    q = np.ldexp(1.0, words[..., 1].astype(np.int32))
+    q = xyz_q_divisor(words[..., 1])
     N = (stride - 4) // 12
     obj = words[..., 2: 2 + 6 * N].reshape(lead + (N, 6)).view(np.int16)
     dop = obj[..., 1].copy()
     hi = dop > (cfg["numDopplerBins"] / 2 - 1)
     dop[hi] = (dop[hi].astype(np.int32) - 65535).astype(np.int16)
     raw = np.zeros(lead + (N, 5))
-    raw[..., 0:3] = obj[..., 3:6] / q[..., None, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        raw[..., 0:3] = obj[..., 3:6] / q[..., None, None]
     raw[..., 3] = dop * cfg["dopplerResolutionMps"]
     raw[..., 4] = obj[..., 2]
     return raw, cnt
@@ -127,44 +143,52 @@ class UartFrameParser:
                              int(config_parameters["numDopplerBins"]), 0)
         self._raw = np.zeros((self.max_obj, 5))
         self._rng = np.zeros(self.max_obj)
+        self._n, self._frame = C.c_int32(0), C.c_uint32(0)
+        self._start, self._plen = C.c_size_t(0), C.c_size_t(0)
 
     def feed(self, data: bytes):
-        """One call of `read()` with `data` as what the port delivered: (dataOK, frameNumber, detObj)."""
-        L = _lib.load()
+        """One call of `read()` with `data` as what the port delivered: (dataOK, frameNumber, detObj).  Raises ValueError where
+        the reference does (a packet that announces objects past the end of the 2^15-byte buffer) and _lib.MmwError (MMW_E_ARG)
+        for more than max_obj objects, which the reference decodes."""
         vec = np.frombuffer(data, dtype=np.uint8)
         if self.byteBufferLength + len(vec) < MAX_BUFFER:       # (a chunk that does not fit is dropped, as there)
             self.byteBuffer[self.byteBufferLength: self.byteBufferLength + len(vec)] = vec
             self.byteBufferLength += len(vec)
         if self.byteBufferLength <= 16:
             return 0, 0, {}
-        n = C.c_int32(0)
-        frame = C.c_uint32(0)
-        start, plen = C.c_size_t(0), C.c_size_t(0)
-        rc = L.mmw_parse_uart(self.byteBuffer.ctypes.data, self.byteBufferLength, C.byref(self._cfg), self._raw.ctypes.data,
-                              self._rng.ctypes.data, self.max_obj, C.byref(n), C.byref(frame), C.byref(start), C.byref(plen))
-        if rc < 0:
-            raise _lib.MmwError(rc, "mmw_parse_uart: more objects than max_obj or bad arguments")
-        if start.value > 0:                                     # cut to the last magic word
-            rest = self.byteBufferLength - start.value
-            self.byteBuffer[:rest] = self.byteBuffer[start.value: self.byteBufferLength].copy()
+        rc, start = self._parse()
+        if start > 0:                                           # cut to the last magic word, then decode there: words past
+            rest = self.byteBufferLength - start                # byteBufferLength are the stale bytes of the CUT buffer
+            self.byteBuffer[:rest] = self.byteBuffer[start: self.byteBufferLength].copy()
             self.byteBufferLength = rest
-        if plen.value == 0:                                     # no magic word, or the packet is not complete yet
+            rc, _ = self._parse()
+        if rc == _lib.E_CAPACITY:
+            raise ValueError("mmw_parse_uart_cap: the packet's words reach past the end of the 2^15-byte buffer")
+        if rc < 0:
+            raise _lib.MmwError(rc, "mmw_parse_uart_cap: more objects than max_obj or bad arguments")
+        if rc == _lib.UART_NONE:                                # no magic word, or the packet is not complete yet
             return 0, 0, {}
         det, ok, idx = {}, 0, 36
-        if self._num_detected() > 0:
-            idx = 44                                            # TLV type and length were read
-            if rc == 1:
-                k = n.value
-                r = self._raw[:k]
-                det = {"numObj": k, "range": self._rng[:k].copy(), "doppler": r[:, 3].copy(), "peakVal": r[:, 4].astype(np.int16),
-                       "x": r[:, 0].copy(), "y": r[:, 1].copy(), "z": r[:, 2].copy(), "timestamp": round(time.time() * 1000)}
-                ok, idx = 1, 48 + 12 * k
-        if self.byteBufferLength > idx:                         # "remove already processed data" (191-197)
-            total = plen.value
+        if rc == _lib.UART_POINTS:
+            k = self._n.value
+            r = self._raw[:k]
+            det = {"numObj": k, "range": self._rng[:k].copy(), "doppler": r[:, 3].copy(), "peakVal": r[:, 4].astype(np.int16),
+                   "x": r[:, 0].copy(), "y": r[:, 1].copy(), "z": r[:, 2].copy(), "timestamp": round(time.time() * 1000)}
+            ok, idx = 1, 48 + 12 * k
+        elif self._num_detected() > 0:
+            idx = 44                                            # TLV type and length were read: another TLV first
+        if self.byteBufferLength > idx:                         # "remove already processed data" (188-195), totalPacketLen
+            total = self._plen.value                            # bytes, whatever it is (0 drops nothing)
             rest = self.byteBufferLength - total
             self.byteBuffer[:rest] = self.byteBuffer[total: self.byteBufferLength].copy()
             self.byteBufferLength = rest
-        return ok, int(frame.value), det
+        return ok, int(self._frame.value), det
+
+    def _parse(self):
+        rc = _lib.load().mmw_parse_uart_cap(self.byteBuffer.ctypes.data, self.byteBufferLength, MAX_BUFFER, C.byref(self._cfg),
+                                            self._raw.ctypes.data, self._rng.ctypes.data, self.max_obj, C.byref(self._n),
+                                            C.byref(self._frame), C.byref(self._start), C.byref(self._plen))
+        return rc, int(self._start.value)
 
     def _num_detected(self) -> int:
         b = self.byteBuffer

@@ -566,7 +566,8 @@ def gen_uart():
     # reference's decode branch raises OverflowError at `dopplerIdx[...] - 65535` (ReadDataIWR1443.py:150-157)
     # for every detected-points packet, so that branch cannot be recorded here.  What IS recorded: the byte
     # buffer discipline (garbage before the magic word, packets split over reads, several packets per read --
-    # the LAST magic word wins --, the "remove processed data" rule) and the header fields.
+    # the LAST magic word wins --, the "remove processed data" rule) and the header fields.  The decode branch is
+    # recorded under the reference's own numpy 1.26 by oracle/gen_uart_golden.py (tests/golden/uart_decode.npz).
     p1, p2, p3 = _uart_packet(7, objs(0)), _uart_packet(8, objs(3), tlv_type=2), _uart_packet(9, objs(0))
     p4, p5 = _uart_packet(10, objs(6), tlv_type=6), _uart_packet(11, objs(0), num_det=0)
     chunks = [b"\x00\x11\x02\x01garbage" + p1, p2, p3[:30], p3[30:], p4 + p5, b"\x05" * 10, _uart_packet(13, objs(2), tlv_type=3),

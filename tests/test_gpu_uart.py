@@ -6,6 +6,8 @@ import struct
 import numpy as np
 import pytest
 
+from tests._uart_recording import DET_KEYS, load as load_recording, same_bits
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "uart.npz")
 
@@ -30,33 +32,86 @@ def test_buffer_discipline_matches_reference_recording():
         assert p.byteBufferLength == int(g[f"buflen{i}"]), (i, p.byteBufferLength, int(g[f"buflen{i}"]))
 
 
-def test_detected_points_decode():
-    """The decode branch against a restatement of ReadDataIWR1443.py:118-175 with numpy-1.26 semantics (u16 words
-    stored into int16 arrays wrap; indices above numDopplerBins/2 - 1 get 65535 subtracted, again in int16).
-    Parity with the reference itself is UNPINNED here: under numpy 2 that branch raises OverflowError."""
+def _replay(stream, max_obj=4096):
+    """Feed a recorded stream (tests/golden/uart_decode.npz) to UartFrameParser read by read: None, or the first read that
+    differs from the reference's -- raised or not, dataOK, frameNumber, byteBufferLength, the buffer's bytes, every detObj array."""
     from mmwave_msc_amd.radar import UartFrameParser
-    rng = np.random.default_rng(3)
-    cfgp = {"rangeIdxToMeters": 0.0436, "dopplerResolutionMps": 0.1252, "numDopplerBins": 16.0}
-    p = UartFrameParser(cfgp)
-    for frame, (n, q) in enumerate([(5, 9), (1, 7), (64, 9), (200, 8)]):
-        o = np.zeros((n, 6), dtype=np.int64)
-        o[:, 0] = rng.integers(0, 256, n)
-        o[:, 1] = rng.integers(-8, 16, n)
-        o[:, 2] = rng.integers(0, 4000, n)
-        o[:, 3:6] = rng.integers(-3000, 3000, size=(n, 3))
-        ok, fn, det = p.feed(b"xx" + _packet(100 + frame, o, qfmt=q))
-        assert ok == 1 and fn == 100 + frame and det["numObj"] == n
-        dop = o[:, 1].astype(np.int16)
-        hi = dop > (cfgp["numDopplerBins"] / 2 - 1)
-        dop[hi] = (dop[hi].astype(np.int32) - 65535).astype(np.int16)
-        assert np.array_equal(det["doppler"], dop * cfgp["dopplerResolutionMps"])
-        for k, col in (("x", 3), ("y", 4), ("z", 5)):
-            assert np.array_equal(det[k], o[:, col].astype(np.int16) / 2 ** q), k
-        assert np.array_equal(det["peakVal"], o[:, 2].astype(np.int16))
-        assert np.array_equal(det["range"], o[:, 0].astype(np.int16) * cfgp["rangeIdxToMeters"])
-        # (the reference only drops a packet when MORE bytes than it parsed are buffered, ReadDataIWR1443.py:191:
-        #  a packet that ends exactly at the end of the buffer stays until the next read cuts to a later magic word)
-        assert p.byteBufferLength == 48 + 12 * n
+    p = UartFrameParser(stream.cfg, max_obj=max_obj)
+    for r in stream.reads:
+        try:
+            ok, fn, det = p.feed(r.chunk)
+            raised = False
+        except ValueError:
+            ok, fn, det, raised = 0, 0, {}, True
+        if raised != r.raised or (ok, fn) != (r.ok, r.frame):
+            return r.index, "raised/dataOK/frameNumber", (raised, ok, fn), (r.raised, r.ok, r.frame)
+        if p.byteBufferLength != r.buflen or bytes(p.byteBuffer[: p.byteBufferLength]) != r.buf:
+            return r.index, "byteBuffer", p.byteBufferLength, r.buflen
+        if ok:
+            if det["numObj"] != r.num_obj:
+                return r.index, "numObj", det["numObj"], r.num_obj
+            for c, key in enumerate(DET_KEYS):
+                if not same_bits(det[key], r.det[:, c]):
+                    return r.index, key, det[key][:4], r.det[:4, c]
+    return None
+
+
+def test_detected_points_decode():
+    """UartFrameParser (mmw_parse_uart) replays every stream of the reference's read() recorded under its own numpy 1.26
+    (tests/golden/uart_decode.npz, oracle/gen_uart_golden.py): dataOK, frameNumber, byteBufferLength, the buffer's bytes and
+    x, y, z, doppler, peakVal, range bit-equal (NaN-aware) after every read, ValueError where the reference raised.  The
+    streams reach the int16 wrap of every field, the doppler wrap threshold for fractional / tiny numDopplerBins, Q 0..70
+    and up to 65535 (the int64 `2 ** Q` wraps: -2^63 at 63, 0 from 64 on), totalPacketLen 0 .. 48 with the bytes present,
+    objects past the packet and past the received bytes (the stale bytes of the 2^15-byte buffer), packets split at every
+    byte, several per chunk, garbage, and a chunk dropped by the maxBufferSize rule."""
+    failed = {}
+    for s in load_recording():
+        d = _replay(s)
+        if d is not None:
+            failed[s.name] = d
+    assert not failed, f"streams that differ from the reference's read() (first difference: read, what, got, want): {failed}"
+
+
+def test_more_than_max_obj_objects_is_the_declared_difference():
+    """The one declared difference of the host decode: a packet announcing more than max_obj objects raises MmwError
+    (MMW_E_ARG) where the reference decodes it (1100 objects at the default max_obj = 1024); every read before is the reference's."""
+    from mmwave_msc_amd import _lib
+    from mmwave_msc_amd.radar import UartFrameParser
+    s = next(s for s in load_recording() if s.name == "over_max_obj")
+    p = UartFrameParser(s.cfg)
+    for r in s.reads:
+        if r.ok and r.num_obj > p.max_obj:
+            with pytest.raises(_lib.MmwError) as ei:
+                p.feed(r.chunk)
+            assert ei.value.code == _lib.E_ARG
+            return
+        ok, fn, _ = p.feed(r.chunk)
+        assert (ok, fn, p.byteBufferLength) == (r.ok, r.frame, r.buflen), r.index
+    pytest.fail("the recording holds no packet over max_obj")
+
+
+def test_find_tlv_on_the_recording_finds_what_read_decoded_and_refuses_stale_bytes():
+    """mmw_find_tlv has no buffer history.  On the bytes each recorded read() saw (the buffer before it plus the chunk) it finds
+    the body the reference decoded whenever that body lies in those bytes -- same bytes, count and frame number --, refuses
+    every packet the reference completed from stale bytes of its 2^15-byte buffer or raised on, and never reports a body where
+    the reference decoded none."""
+    from mmwave_msc_amd import radar
+    refused = hits = 0
+    for s in load_recording():
+        prev = b""
+        for r in s.reads:
+            before = prev + r.chunk if len(prev) + len(r.chunk) < radar.MAX_BUFFER else prev
+            found, off, n, frame, start, plen = radar.find_tlv(before)
+            where = (s.name, r.index, found)
+            if r.ok and not r.raised and start + 48 + 12 * r.num_obj <= len(before):
+                assert found and n == r.num_obj and frame == r.frame, where
+                assert before[off: off + 4 + 12 * n] == r.body, where
+                hits += 1
+            else:
+                assert not found and off == -1 and n == 0, where
+                refused += int(r.ok or r.raised)
+            prev = r.buf
+    assert hits > 200 and refused >= 5, (hits, refused)
 
 
 def test_parse_config_file(tmp_path):
@@ -170,6 +225,111 @@ def test_device_tlv_decode_and_normalize_equals_host_parse_then_normalize(N):
     sb_dev.close(); sb_host.close()
 
 
+def _edge_packets(source, N):
+    """Packets (from the magic word on) that mmw_find_tlv accepts with at most N objects: every one of the recording
+    (tests/golden/uart_decode.npz, the streams with CFG A's configParameters), or synthetic ones with Q in {0, 62, 63, 64, 65535}
+    and, in half of them, all six fields over their full u16 range."""
+    from mmwave_msc_amd import radar
+    if source == "recording":
+        streams = load_recording()
+        cfgp = streams[0].cfg
+        out = []
+        for s in streams:
+            if s.cfg != cfgp:
+                continue
+            prev = b""
+            for r in s.reads:
+                before = prev + r.chunk if len(prev) + len(r.chunk) < radar.MAX_BUFFER else prev
+                found, off, n, _, start, _ = radar.find_tlv(before)
+                if found and n <= N:
+                    out.append(before[start:])
+                prev = r.buf
+        return cfgp, out
+    rng = np.random.default_rng(77)
+    cfgp = {"rangeIdxToMeters": 0.0436, "dopplerResolutionMps": 0.1252, "numDopplerBins": 32.0}
+    out = []
+    for i in range(96):
+        n = int(rng.integers(1, N + 1))          # (_packet announces len(objs) objects in the header: 0 would be no body)
+        if i % 2:
+            o = rng.integers(0, 65536, size=(n, 6))
+        else:
+            o = np.zeros((n, 6), dtype=np.int64)
+            o[:, 0] = rng.integers(0, 256, n)
+            o[:, 1] = rng.integers(-40, 41, n)
+            o[:, 2] = rng.integers(0, 4000, n)
+            o[:, 3:6] = rng.integers(-3000, 3000, size=(n, 3))
+            o[: n // 2, 4] = -o[: n // 2, 4]     # (y < 0 and Q = 63: y / -2^63 > 0, a row the scene filter keeps)
+        out.append(_packet(300 + i, o, qfmt=int((0, 62, 63, 64, 65535)[i % 5])))
+    return cfgp, out
+
+
+@pytest.mark.parametrize("source", ["recording", "q_edges"])
+def test_device_tlv_decode_equals_host_parse_on_edge_packets(source):
+    """mmw_find_tlv + mmw_normalize_tlv against mmw_parse_uart + mmw_normalize on the same bytes for the packets of the
+    reference recording and for Q formats 0, 62, 63, 64, 65535 with full-range fields: rows and counts bit-equal (NaN-aware)
+    scene by scene, then three mmw_steps on both paths -- association, sticky error bits (the reference's ValueError frames,
+    should a non-finite row reach apply_DBscan) and track state identical."""
+    import ctypes as C
+    from mmwave_msc_amd import _lib, radar
+    from mmwave_msc_amd.batch import SceneBatch
+    S, N = 48, 64
+    cfgp, packets = _edge_packets(source, N)
+    assert len(packets) >= S, len(packets)
+    ucfg = radar.uart_cfg(cfgp)
+    sb_dev = SceneBatch(_lib.default_config(db_min_samples=3), S, N)
+    sb_host = SceneBatch(_lib.default_config(db_min_samples=3), S, N)
+    L = _lib.load()
+    n_rows = nonfinite = 0
+    for frame in range(3):
+        chunks = [packets[(frame * S + s) % len(packets)] for s in range(S)]
+        raw = np.zeros((S, N, 5))
+        n_raw = np.zeros(S, np.int32)
+        for s, ch in enumerate(chunks):
+            a = np.frombuffer(ch, dtype=np.uint8)
+            rows = np.zeros((N, 5))
+            n = C.c_int32(0)
+            rc = L.mmw_parse_uart_cap(a.ctypes.data, len(a), len(a), C.byref(ucfg), rows.ctypes.data, None, N, C.byref(n), None, None, None)
+            assert rc == _lib.UART_POINTS, (frame, s, rc)
+            raw[s], n_raw[s] = rows, n.value
+            nonfinite += int((~np.isfinite(rows[: n.value, :3])).any())
+        want_pts, want_n = sb_host.normalize_host(raw, n_raw)
+        blob = b"".join(ch + b"\x00" * (len(ch) & 1) for ch in chunks)   # (bodies 2-byte aligned: every chunk starts at its magic word)
+        offs = np.full(S, -1, np.int64)
+        base = 0
+        for s, ch in enumerate(chunks):
+            found, off, n_obj, _, _, _ = radar.find_tlv(ch)
+            assert found and n_obj == n_raw[s], (frame, s)
+            offs[s] = base + off
+            base += len(ch) + (len(ch) & 1)
+        b_pk = sb_dev.buf("tlv_bytes", len(blob) + 16).upload(np.frombuffer(blob, dtype=np.uint8))
+        b_of = sb_dev.buf("tlv_off", S * 8).upload(offs)
+        b_out = sb_dev.buf("tlv_pts", S * N * 64)
+        b_no = sb_dev.buf("tlv_n", S * 4)
+        sb_dev.normalize_tlv_dev(b_pk.ptr, len(blob), b_of.ptr, ucfg, b_out.ptr, b_no.ptr)
+        got_n = b_no.download((S,), np.int32)
+        got_pts = b_out.download((S, N, 8), np.float64)
+        assert np.array_equal(got_n, want_n), (frame, got_n, want_n)
+        for s in range(S):
+            assert same_bits(got_pts[s, : got_n[s]], want_pts[s, : want_n[s]]), (frame, s)
+        n_rows += int(got_n.sum())
+        dt = np.full(S, 0.1)
+        b_dt = sb_dev.buf("tlv_dt", S * 8).upload(dt)
+        b_as = sb_dev.buf("tlv_assoc", S * N * 4)
+        sb_dev.step_dev(b_out.ptr, b_no.ptr, b_dt.ptr, b_as.ptr)
+        a_host, _, _ = sb_host.step_host(want_pts, want_n, dt, raise_nonfinite=False, check=False)
+        a_dev = b_as.download((S, N), np.int32)
+        for s in range(S):
+            assert np.array_equal(a_dev[s, : got_n[s]], a_host[s, : want_n[s]]), (frame, s)
+        assert np.array_equal(sb_dev.errors(), sb_host.errors()), frame
+    assert n_rows > 0 and (source == "recording" or nonfinite > 0), (n_rows, nonfinite)
+    nt_d, nt_h = sb_dev.num_tracks(), sb_host.num_tracks()
+    assert np.array_equal(nt_d, nt_h)
+    td, th = sb_dev.tracks(cap=max(int(nt_d.max()), 1)), sb_host.tracks(cap=max(int(nt_h.max()), 1))
+    for name in ("x", "P", "centroid", "spread_est", "group_disp_est", "lifetime", "point_num", "ring_n"):
+        assert same_bits(td[name], th[name]), name
+    sb_dev.close(); sb_host.close()
+
+
 def test_find_tlv_agrees_with_the_recorded_uart_session():
     """The byte chunks of the reference's recorded read() session (tests/golden/uart.npz).  The recording holds no DECODED packet
     -- under numpy 2 the reference's decode branch raises, so the generator could only record the other paths (no magic word,
@@ -231,4 +391,30 @@ def test_device_tlv_decode_refuses_bodies_outside_the_buffer_or_the_context():
     assert ei.value.code == _lib.E_ARG
     err = sb.errors()
     assert [bool(e & 8) for e in err] == [False, True, False, True, True, True], err
+    sb.close()
+
+    # Offsets at the ends of the int64 range and of the buffer (bounds are compared by subtraction: `off + 4` would overflow),
+    # and a body whose 4 + 12 num bytes end exactly at packets_bytes, which is accepted: it decodes as the same body does
+    # in the middle of the buffer.  Its last object's y word is 1, so the 4-byte head at packets_bytes - 4 announces one
+    # object that cannot fit.
+    tail = bytearray(body(20, 20))
+    tail[-4:-2] = struct.pack("<H", 1)
+    blob = bytes(tail) * 2
+    nbytes = len(blob)
+    i64 = np.iinfo(np.int64).max
+    offs = np.array([0, len(tail), i64, i64 - 3, nbytes - 3, nbytes - 4], np.int64)
+    sb = SceneBatch(_lib.default_config(), S, N)
+    b_pk = sb.buf("tlv_bytes", nbytes + 16).upload(np.frombuffer(blob, dtype=np.uint8))
+    b_of = sb.buf("tlv_off", S * 8).upload(offs)
+    b_out = sb.buf("tlv_pts", S * N * 64)
+    b_no = sb.buf("tlv_n", S * 4)
+    sb.normalize_tlv_dev(b_pk.ptr, nbytes, b_of.ptr, ucfg, b_out.ptr, b_no.ptr)
+    got = b_no.download((S,), np.int32)
+    pts = b_out.download((S, N, 8), np.float64)
+    assert got[0] > 0 and got[1] == got[0] and np.array_equal(pts[1, : got[1]], pts[0, : got[0]]), got
+    assert list(got[2:]) == [_lib.BAD_FRAME] * 4, got
+    b_dt = sb.buf("tlv_dt", S * 8).upload(np.full(S, 0.1))
+    sb.step_dev(b_out.ptr, b_no.ptr, b_dt.ptr)
+    err = sb.errors()
+    assert [bool(e & 8) for e in err] == [False, False, True, True, True, True], err
     sb.close()
