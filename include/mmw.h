@@ -208,6 +208,38 @@ int mmw_set_batch_size(mmw_ctx *ctx, const int32_t *scene_flags, int32_t new_siz
 /* BatchedData(init_data) (Tracking.py:38-41): the global ring of `scene` becomes ONE frame holding rows[n][8] (host,
  * n <= max_pts) instead of the empty frame a default BatchedData() starts with.  Sync. */
 int mmw_set_batch_frame(mmw_ctx *ctx, int32_t scene, const double *rows, int32_t n);
+/* ---- per-scene site parameters ----
+ * A *site* is the installation a scene's radar stands in: the eleven values of mmw_config that describe the sensor mounting
+ * (normalize_data: Utils.py:312-328, constants.py:41-42), the intensity scale of the feature maps (Utils.py:469,502; computed
+ * per data set in preprocessing.py:291-295) and the window / monitoring point of the output step (Utils.py:180-219,
+ * Visualizer.py:14-29, constants.py:31-33,48-50).  Field meaning = the mmw_config field of the same name; tilt_cos / tilt_sin
+ * are taken as given, as in mmw_config (the bit-exact values are numpy's cos / sin(radians(S_TILT))).  A context starts
+ * without a site table: every scene then uses the context's mmw_config and the kernels of a context that never heard of
+ * sites.  While a table is in use, mmw_normalize / _f32 / _tlv, mmw_frame_host / mmw_frame_posture_host, mmw_features /
+ * mmw_features_async and mmw_track_table read each scene's own site; the tracker itself (gating, Kalman, DBSCAN,
+ * maintenance) keeps reading mmw_config, and so do mmw_format_frames and mmw_dbscan (utilities on caller data, not scenes).
+ * A site belongs to the SLOT, not to the recording in it: mmw_reset / mmw_reset_scenes keep it, a snapshot blob does not
+ * carry it, and mmw_restore leaves the destination slots' sites alone. */
+typedef struct mmw_scene_site {          /* 96 bytes, all doubles */
+    double s_height, tilt_cos, tilt_sin;
+    double intensity_mu, intensity_std;
+    double m_x, m_y, m_z;
+    double v_screen_fade_size_max, v_screen_fade_size_min, v_screen_fade_weight;
+    double reserved_;                    /* must be 0 */
+} mmw_scene_site;
+/* Give the listed scenes (host array of n indices; NULL = scenes 0 .. n-1) the sites[n] (host).  The first call allocates the
+ * table and fills every scene with the config's own values; scenes never listed keep those.  Ordered on the context's
+ * stream: calls issued before it use the old sites, calls after it the new.  Tracker state is not touched.  Atomic refusal
+ * (MMW_E_ARG, mmw_last_error names the entry, no scene's site changes): an index out of range or listed twice, n < 0,
+ * n > n_scenes, sites == NULL with n > 0, a non-zero reserved_.  The values themselves are not judged (mmw_create does not
+ * judge these fields of mmw_config either).  Sync (the caller's arrays may go away). */
+int mmw_set_sites(mmw_ctx *ctx, const int32_t *scenes, int32_t n, const mmw_scene_site *sites);
+/* the effective site of every scene (host array of n_scenes): the config's values where none was set.  Read from the host mirror of the table: no device access. */
+int mmw_get_sites(mmw_ctx *ctx, mmw_scene_site *out);
+/* back to the context's config for every scene, and to the kernels of a context without sites */
+int mmw_clear_sites(mmw_ctx *ctx);
+/* 1 while a site table is in use, else 0 (MMW_E_ARG for a NULL context) */
+int mmw_has_sites(mmw_ctx *ctx);
 /* mmw_config.chain_side_stream at run time: on != 0 -> the small-cloud DBSCAN workers run on a second stream beside the
  * association kernel from the next mmw_step on, 0 -> in the post kernel only.  A caller that runs its own kernels beside
  * the tracker (the CNN of the previous frame on another stream) may prefer them off. */
@@ -383,7 +415,9 @@ int mmw_track_table(mmw_ctx *ctx, mmw_track_summary *table, int32_t slots, int32
  *   - each track's ring frames, oldest first, min(ring_n[k], ring_rows) rows of 8 fp64 each (the rows it stores);
  *   - the global ring's frames, oldest first, g_n[k] rows of 8 fp64 each.
  * Not state (not in the blob): per-step scheduling words and lists, queue epochs and tags, statistics, profile counters,
- * the seek_inner diagnostics of mmw_get_inner.
+ * the seek_inner diagnostics of mmw_get_inner.  Per-scene sites (mmw_set_sites) are not in the blob either: format version 1 is
+ * unchanged, a site belongs to the slot (as an attached posture model belongs to the context) and mmw_restore leaves the
+ * destination slots' sites as they are -- restored tracks arrive intact, the next frame is normalised with the destination's site.
  *
  * Ordering: mmw_snapshot / mmw_restore first wait for EVERYTHING queued on the context -- its stream and the side stream
  * of the DBSCAN chain workers, which may poll the queues for a few ms after the last step.  A caller with posture work in

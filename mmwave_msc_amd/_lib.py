@@ -40,6 +40,7 @@ EXPORTS = [
     "mmw_kalman_layout", "mmw_step_f32", "mmw_normalize_f32", "mmw_frame_host", "mmw_mars_head_small", "mmw_mars_range_fixup",
     "mmw_attach_posture", "mmw_frame_posture_host", "mmw_clear_errors", "mmw_stream_wait", "mmw_wait_stream", "mmw_find_tlv", "mmw_normalize_tlv",
     "mmw_snapshot_size", "mmw_snapshot", "mmw_restore", "mmw_snapshot_inspect",
+    "mmw_set_sites", "mmw_get_sites", "mmw_clear_sites", "mmw_has_sites",
 ]
 
 
@@ -77,6 +78,18 @@ class MmwConfig(C.Structure):
         ("fused_step", C.c_int32), ("reserved_", C.c_int32),
     ]
 
+
+SITE_FIELDS = ("s_height", "tilt_cos", "tilt_sin", "intensity_mu", "intensity_std", "m_x", "m_y", "m_z",
+               "v_screen_fade_size_max", "v_screen_fade_size_min", "v_screen_fade_weight")
+
+
+class MmwSceneSite(C.Structure):
+    """struct mmw_scene_site (include/mmw.h): the eleven values of mmw_config that describe a scene's installation --
+    sensor mounting, intensity scale, window / monitoring point -- and one reserved double that must be 0."""
+    _fields_ = [(f, C.c_double) for f in SITE_FIELDS] + [("reserved_", C.c_double)]
+
+
+SITE_DTYPE = np.dtype([(f, "f8") for f in SITE_FIELDS] + [("reserved_", "f8")])   # 12 x f8 = 96 bytes, the struct's layout
 
 SNAP_MAGIC = b"MMWSNAP"   # MMW_SNAP_MAGIC (8 bytes with the terminating 0)
 SNAP_VERSION = 1
@@ -299,6 +312,10 @@ def load():
         "mmw_snapshot": (C.c_int, [vp, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "mmw_restore": (C.c_int, [vp, vp, C.c_size_t, vp, i32]),
         "mmw_snapshot_inspect": (C.c_int, [vp, C.c_size_t, C.POINTER(MmwSnapshotInfo)]),
+        "mmw_set_sites": (C.c_int, [vp, vp, i32, vp]),
+        "mmw_get_sites": (C.c_int, [vp, vp]),
+        "mmw_clear_sites": (C.c_int, [vp]),
+        "mmw_has_sites": (C.c_int, [vp]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():
@@ -331,3 +348,25 @@ def apply_overrides(cfg: MmwConfig, overrides: dict):
                 raise AttributeError(f"mmw_config has no field {k!r}")
             setattr(cfg, k, v)
     return cfg
+
+
+def make_sites(cfg: MmwConfig, n: int, **columns) -> np.ndarray:
+    """SITE_DTYPE[n]: n sites that start as `cfg`'s own values.  Each keyword is a site field (SITE_FIELDS) given as a scalar or a
+    length-n array, or `s_tilt` in degrees -- turned into tilt_cos / tilt_sin per element the way apply_overrides does for a
+    config (np.cos(np.radians(.)), Utils.py:315), which is what makes a site bit-equal to a context created with that S_TILT."""
+    sites = np.zeros(int(n), SITE_DTYPE)
+    for f in SITE_FIELDS:
+        sites[f] = getattr(cfg, f)
+    for k, v in columns.items():
+        col = np.asarray(v, np.float64)
+        if col.ndim > 1 or (col.ndim == 1 and col.shape[0] != sites.shape[0]):
+            raise ValueError(f"make_sites: {k} must be a scalar or have length {sites.shape[0]}, not shape {col.shape}")
+        if k == "s_tilt":
+            # element by element, as apply_overrides does for one config (a vectorised np.cos need not round like the scalar call)
+            ang = [np.radians(float(a)) for a in np.broadcast_to(col, sites.shape)]
+            sites["tilt_cos"], sites["tilt_sin"] = [float(np.cos(a)) for a in ang], [float(np.sin(a)) for a in ang]
+        elif k in SITE_FIELDS:
+            sites[k] = col
+        else:
+            raise AttributeError(f"mmw_scene_site has no field {k!r}")
+    return sites

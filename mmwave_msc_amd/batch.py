@@ -183,6 +183,38 @@ class SceneBatch:
         rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 8)
         self._chk(self.L.mmw_set_batch_frame(self.h, int(scene), rows.ctypes.data, len(rows)))
 
+    # -- per-scene sites ------------------------------------------------------
+    def set_sites(self, sites, scenes=None):
+        """mmw_set_sites: give `scenes` (default: scenes 0 .. len(sites)-1) their own site -- sensor mounting, intensity scale,
+        window / monitoring point -- as a `_lib.SITE_DTYPE` array (`_lib.make_sites`).  From the next call on, normalisation,
+        feature maps and the track table use each scene's site; the tracker itself keeps reading the context's config.  Scenes
+        never listed keep the config's values.  Refused (MmwError, E_ARG) with no site changed for an index out of range or
+        listed twice, more sites than scenes, or a non-zero `reserved_`."""
+        a = np.ascontiguousarray(np.asarray(sites, dtype=_lib.SITE_DTYPE).reshape(-1))
+        idx = None
+        if scenes is not None:
+            idx = np.ascontiguousarray(np.asarray(scenes, dtype=np.int32).reshape(-1))
+            if len(idx) != len(a):
+                raise ValueError(f"set_sites: {len(a)} sites for {len(idx)} scenes")
+        self._chk(self.L.mmw_set_sites(self.h, idx.ctypes.data if idx is not None else None, len(a), a.ctypes.data if len(a) else None))
+
+    def sites(self) -> np.ndarray:
+        """mmw_get_sites: the effective site of every scene, SITE_DTYPE[S] (the config's values where none was set)."""
+        out = np.zeros(self.S, dtype=_lib.SITE_DTYPE)
+        self._chk(self.L.mmw_get_sites(self.h, out.ctypes.data))
+        return out
+
+    def clear_sites(self):
+        """mmw_clear_sites: every scene back to the context's config, and to the kernels of a context without sites."""
+        self._chk(self.L.mmw_clear_sites(self.h))
+
+    @property
+    def has_sites(self) -> bool:
+        rc = int(self.L.mmw_has_sites(self.h))
+        if rc < 0:
+            self._chk(rc)
+        return rc == 1
+
     def reset(self):
         self._chk(self.L.mmw_reset(self.h))
 

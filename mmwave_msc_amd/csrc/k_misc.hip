@@ -6,6 +6,8 @@
 //   k_pop_frame   BatchedData.pop_frame on the global ring         (Tracking.py:66-71)
 //   k_export      flatten effective_tracks for read-back
 //   k_table       fixed-size track summaries for the RCCL all-gather
+//   k_*_site      k_normalize / k_normalize_tlv / k_features / k_table with each scene's own site (mmw_set_sites) in place of the
+//                 context's: the same bodies, launched only while a site table is in use
 #include <cstddef>
 #include "mmw_device.hpp"
 #include "mmw_math.hpp"
@@ -76,11 +78,30 @@ __device__ __forceinline__ void normalize_rows(const DevCfg &cfg, int s, int n, 
     if (tid == 0) n_out[s] = total;
 }
 
-template <typename RT, int R>
-__global__ __launch_bounds__(256) void k_normalize(DevCfg cfg, const RT *__restrict__ raw, const int32_t *__restrict__ n_raw,
-                                                   double *__restrict__ out, int32_t *__restrict__ n_out)
+// Per-scene sites (mmw_set_sites): a kernel's `cfg` with the site's values in place of the context's, so that the site variants
+// below run the SAME bodies -- the operation order of normalize_rows, features_scene and table_slot (which takes the window as scalars) is what pins them to the
+// reference bit for bit.  The table is written by an earlier call on the same stream, never by the launch that reads it: it
+// may come through the scalar cache, and needs no invalidate (unlike the gate records of k_track).
+// Mounting (k_normalize*): one workgroup is one scene, so the site is wave-uniform -- `site` is sites + blockIdx.x of a
+// const __restrict__ kernel argument and arrives as scalar operands (s_load), like DevCfg itself.
+__device__ __forceinline__ DevCfg cfg_with_mounting(DevCfg cfg, const mmw_scene_site *__restrict__ site)
 {
-    __shared__ int wcnt[R * 4];
+    cfg.s_height = site->s_height;
+    cfg.tilt_cos = site->tilt_cos;
+    cfg.tilt_sin = site->tilt_sin;
+    return cfg;
+}
+// Intensity scale (k_features): wave-uniform as well.
+__device__ __forceinline__ DevCfg cfg_with_intensity(DevCfg cfg, const mmw_scene_site *__restrict__ site)
+{
+    cfg.intensity_mu = site->intensity_mu;
+    cfg.intensity_std = site->intensity_std;
+    return cfg;
+}
+template <typename RT, int R>
+__device__ __forceinline__ void normalize_scene(const DevCfg &cfg, const RT *__restrict__ raw, const int32_t *__restrict__ n_raw,
+                                                double *__restrict__ out, int32_t *__restrict__ n_out, int *wcnt /* LDS [R * 4] */)
+{
     const int s = blockIdx.x, tid = threadIdx.x;
     const int NP = cfg.max_pts;
     const int n = min(max(n_raw[s], 0), NP);
@@ -94,6 +115,20 @@ __global__ __launch_bounds__(256) void k_normalize(DevCfg cfg, const RT *__restr
     }
     normalize_rows<R>(cfg, s, n, v, out, n_out, wcnt);
 }
+template <typename RT, int R>
+__global__ __launch_bounds__(256) void k_normalize(DevCfg cfg, const RT *__restrict__ raw, const int32_t *__restrict__ n_raw,
+                                                   double *__restrict__ out, int32_t *__restrict__ n_out)
+{
+    __shared__ int wcnt[R * 4];
+    normalize_scene<RT, R>(cfg, raw, n_raw, out, n_out, wcnt);
+}
+template <typename RT, int R>
+__global__ __launch_bounds__(256) void k_normalize_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, const RT *__restrict__ raw,
+                                                        const int32_t *__restrict__ n_raw, double *__restrict__ out, int32_t *__restrict__ n_out)
+{
+    __shared__ int wcnt[R * 4];
+    normalize_scene<RT, R>(cfg_with_mounting(cfg, sites + blockIdx.x), raw, n_raw, out, n_out, wcnt);
+}
 
 // The radar's own wire format in, ring rows out: per scene the body of the detected-points TLV of an IWR1443 UART packet
 // (MMWDEMO_UART_MSG_DETECTED_POINTS: u16 numObj, u16 xyzQFormat, then numObj x six little-endian int16 -- rangeIdx, dopplerIdx,
@@ -106,11 +141,10 @@ __global__ __launch_bounds__(256) void k_normalize(DevCfg cfg, const RT *__restr
 // 2-byte boundary with all the objects it announces, or that announces more than max_pts objects (mmw_parse_uart: MMW_E_ARG),
 // gives n_out = MMW_BAD_FRAME -- the scene's ERR_BADCOUNT in the mmw_step that follows.
 template <int R>
-__global__ __launch_bounds__(256) void k_normalize_tlv(DevCfg cfg, const uint8_t *__restrict__ packets, long long packets_bytes,
-                                                       const long long *__restrict__ tlv_offset, double half_bins, double doppler_res,
-                                                       double *__restrict__ out, int32_t *__restrict__ n_out)
+__device__ __forceinline__ void normalize_tlv_scene(const DevCfg &cfg, const uint8_t *__restrict__ packets, long long packets_bytes,
+                                                    const long long *__restrict__ tlv_offset, double half_bins, double doppler_res,
+                                                    double *__restrict__ out, int32_t *__restrict__ n_out, int *wcnt /* LDS [R * 4] */)
 {
-    __shared__ int wcnt[R * 4];
     const int s = blockIdx.x, tid = threadIdx.x;
     const long long off = tlv_offset[s];
     int n = 0;
@@ -147,6 +181,22 @@ __global__ __launch_bounds__(256) void k_normalize_tlv(DevCfg cfg, const uint8_t
     }
     normalize_rows<R>(cfg, s, n, v, out, n_out, wcnt);
     if (bad && tid == 0) n_out[s] = -3;   // MMW_BAD_FRAME (the same thread wrote the 0 above)
+}
+template <int R>
+__global__ __launch_bounds__(256) void k_normalize_tlv(DevCfg cfg, const uint8_t *__restrict__ packets, long long packets_bytes,
+                                                       const long long *__restrict__ tlv_offset, double half_bins, double doppler_res,
+                                                       double *__restrict__ out, int32_t *__restrict__ n_out)
+{
+    __shared__ int wcnt[R * 4];
+    normalize_tlv_scene<R>(cfg, packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out, wcnt);
+}
+template <int R>
+__global__ __launch_bounds__(256) void k_normalize_tlv_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, const uint8_t *__restrict__ packets,
+                                                            long long packets_bytes, const long long *__restrict__ tlv_offset, double half_bins,
+                                                            double doppler_res, double *__restrict__ out, int32_t *__restrict__ n_out)
+{
+    __shared__ int wcnt[R * 4];
+    normalize_tlv_scene<R>(cfg_with_mounting(cfg, sites + blockIdx.x), packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out, wcnt);
 }
 
 // ---------------------------------------------------------------------------
@@ -252,9 +302,9 @@ __device__ inline void sort_rows_store(int lane, double v0, double v1, double v2
 // gives every eligible track its output row, and the (track, frame) items are then dealt over the four waves -- each item one
 // more round trip (its rows).  (Track after track with the waves over the frames, every step behind the previous one's loads,
 // this kernel took 120 us for 18 k tracks: 0.27 of the HBM rate for 290 MB.)
-__global__ __launch_bounds__(256) void k_features(DevCfg cfg, DevState st, const int32_t *__restrict__ row_off,
-                                                  float *__restrict__ feat, int32_t *__restrict__ owner, int32_t *__restrict__ uid,
-                                                  int cap_rows, const int32_t *__restrict__ n_in, int32_t *__restrict__ total_out)
+__device__ __forceinline__ void features_scene(const DevCfg &cfg, const DevState &st, const int32_t *__restrict__ row_off,
+                                               float *__restrict__ feat, int32_t *__restrict__ owner, int32_t *__restrict__ uid,
+                                               int cap_rows, const int32_t *__restrict__ n_in, int32_t *__restrict__ total_out)
 {
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const SceneHdr *hdr = st.hdr + s;
@@ -321,6 +371,19 @@ __global__ __launch_bounds__(256) void k_features(DevCfg cfg, DevState st, const
             atomicAdd(&sl[kStatFeatRows], (unsigned long long)ne);
         }
     }
+}
+__global__ __launch_bounds__(256) void k_features(DevCfg cfg, DevState st, const int32_t *__restrict__ row_off,
+                                                  float *__restrict__ feat, int32_t *__restrict__ owner, int32_t *__restrict__ uid,
+                                                  int cap_rows, const int32_t *__restrict__ n_in, int32_t *__restrict__ total_out)
+{
+    features_scene(cfg, st, row_off, feat, owner, uid, cap_rows, n_in, total_out);
+}
+__global__ __launch_bounds__(256) void k_features_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, DevState st,
+                                                       const int32_t *__restrict__ row_off, float *__restrict__ feat, int32_t *__restrict__ owner,
+                                                       int32_t *__restrict__ uid, int cap_rows, const int32_t *__restrict__ n_in,
+                                                       int32_t *__restrict__ total_out)
+{
+    features_scene(cfg_with_intensity(cfg, sites + blockIdx.x), st, row_off, feat, owner, uid, cap_rows, n_in, total_out);
 }
 
 // Utils.format_single_frame (+ relative_coordinates) on caller-provided frames:
@@ -424,22 +487,23 @@ __global__ void k_export(DevCfg cfg, DevState st, mmw_track_record *__restrict__
     if (sizeof(mmw_track_record) > kUsed) reinterpret_cast<int32_t *>(o)[kUsed / 4] = 0;
 }
 
-__global__ void k_table(DevCfg cfg, DevState st, mmw_track_summary *__restrict__ out, int slots, int scene_base)
+// One track slot of the table.  The window / monitoring point (m_x .. fade_weight) are the context's for k_table, the scene's own
+// for k_table_site; everything arrives as scalars, so that the plain kernel reads its arguments exactly as it always did.
+__device__ __forceinline__ void table_slot(const SceneHdr *hdrs, const int32_t *order, const TrackRec *trk, int t_cap, int dx,
+                                           mmw_track_summary *out, int slots, int scene_base, int s, int j, double m_x, double m_y,
+                                           double m_z, double fade_max, double fade_min, double fade_weight)
 {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int s = g / slots, j = g % slots;
-    if (s >= cfg.n_scenes) return;
     mmw_track_summary *o = out + (size_t)s * slots + j;
-    const SceneHdr *hdr = st.hdr + s;
+    const SceneHdr *hdr = hdrs + s;
     o->scene = scene_base + s;
     o->slot = j;
     const bool alive = j < hdr->n_tracks;
     o->alive = alive ? 1 : 0;
-    const TrackRec *rec = alive ? st.trk + (size_t)s * cfg.t_cap + st.order[(size_t)s * cfg.t_cap + j] : nullptr;
+    const TrackRec *rec = alive ? trk + (size_t)s * t_cap + order[(size_t)s * t_cap + j] : nullptr;
     o->is_static = alive ? rec->is_static : 0;
     o->point_num = alive ? rec->point_num : 0;
     o->lifetime = alive ? (float)rec->lifetime : 0.f;
-    for (int e = 0; e < 9; e++) o->x[e] = (alive && e < cfg.dx) ? (float)rec->x[e] : 0.f;
+    for (int e = 0; e < 9; e++) o->x[e] = (alive && e < dx) ? (float)rec->x[e] : 0.f;
     for (int e = 0; e < 6; e++) o->centroid[e] = alive ? (float)rec->centroid[e] : 0.f;
     for (int e = 0; e < MMW_NKP; e++) o->keypoints[e] = alive ? rec->kp[e] : 0.f;
     // calc_fade_square (Visualizer.py:14-29) over calc_projection_points (Utils.py:180-219), in the reference's
@@ -447,15 +511,35 @@ __global__ void k_table(DevCfg cfg, DevState st, mmw_track_summary *__restrict__
     double px = 0, pz = 0, size = 0;
     if (alive) {
         const double xo = rec->x[0] + (double)rec->kp[3], yo = rec->x[1] + (double)rec->kp[41], zo = (double)rec->kp[22];
-        const double xd = xo - cfg.m_x, yd = yo - cfg.m_y, zd = zo - cfg.m_z;
-        px = xd == 0 ? xo : -cfg.m_y / (yd / xd) + cfg.m_x;
-        pz = zd == 0 ? zo : -cfg.m_y / (yd / zd) + cfg.m_z;
-        const double sz = cfg.fade_max - (rec->x[1] + (double)rec->kp[12]) * cfg.fade_weight;
-        size = fmax(cfg.fade_min, fmin(cfg.fade_max, sz));
+        const double xd = xo - m_x, yd = yo - m_y, zd = zo - m_z;
+        px = xd == 0 ? xo : -m_y / (yd / xd) + m_x;
+        pz = zd == 0 ? zo : -m_y / (yd / zd) + m_z;
+        const double sz = fade_max - (rec->x[1] + (double)rec->kp[12]) * fade_weight;
+        size = fmax(fade_min, fmin(fade_max, sz));
     }
     o->fade_x = (float)px;
     o->fade_z = (float)pz;
     o->fade_size = (float)size;
+}
+__global__ void k_table(DevCfg cfg, DevState st, mmw_track_summary *__restrict__ out, int slots, int scene_base)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = g / slots, j = g % slots;
+    if (s >= cfg.n_scenes) return;
+    table_slot(st.hdr, st.order, st.trk, cfg.t_cap, cfg.dx, out, slots, scene_base, s, j, cfg.m_x, cfg.m_y, cfg.m_z, cfg.fade_max, cfg.fade_min,
+               cfg.fade_weight);
+}
+// a thread is one track slot and neighbouring threads may be different scenes: the site is an ordinary per-lane load, behind the
+// bounds check (the table has n_scenes entries)
+__global__ void k_table_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, DevState st, mmw_track_summary *__restrict__ out, int slots,
+                             int scene_base)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = g / slots, j = g % slots;
+    if (s >= cfg.n_scenes) return;
+    const mmw_scene_site *w = sites + s;
+    table_slot(st.hdr, st.order, st.trk, cfg.t_cap, cfg.dx, out, slots, scene_base, s, j, w->m_x, w->m_y, w->m_z, w->v_screen_fade_size_max,
+               w->v_screen_fade_size_min, w->v_screen_fade_weight);
 }
 
 // flags == nullptr: every scene (mmw_reset); else only the scenes whose flag is non-zero (mmw_reset_scenes), and nothing of the
@@ -505,32 +589,43 @@ void launch_poison(hipStream_t stream)
 }
 #endif
 
-void launch_normalize(const DevCfg &cfg, const void *raw, bool f32, const int32_t *n_raw, double *out, int32_t *n_out, hipStream_t st)
+// sites: the context's site table (device, [n_scenes]) while one is in use, else nullptr -- the kernels of a context without sites
+void launch_normalize(const DevCfg &cfg, const mmw_scene_site *sites, const void *raw, bool f32, const int32_t *n_raw, double *out, int32_t *n_out,
+                      hipStream_t st)
 {
     static_assert(MMW_MAX_PTS_LIMIT <= 4 * 256, "k_normalize (and k_track / k_scene) take at most four rows per thread: a larger limit needs a round loop");
     const int r = (cfg.max_pts + 255) / 256;   // rows per thread: 1, 2 or 4 (max_pts <= 1024)
 #define MMW_NORM(RT, R) mmw_launch(k_normalize<RT, R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, reinterpret_cast<const RT *>(raw), n_raw, out, n_out)
-    if (f32) { if (r <= 1) MMW_NORM(float, 1); else if (r == 2) MMW_NORM(float, 2); else MMW_NORM(float, 4); }
+#define MMW_NORM_SITE(RT, R) mmw_launch(k_normalize_site<RT, R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, reinterpret_cast<const RT *>(raw), n_raw, out, n_out)
+    if (sites) {
+        if (f32) { if (r <= 1) MMW_NORM_SITE(float, 1); else if (r == 2) MMW_NORM_SITE(float, 2); else MMW_NORM_SITE(float, 4); }
+        else { if (r <= 1) MMW_NORM_SITE(double, 1); else if (r == 2) MMW_NORM_SITE(double, 2); else MMW_NORM_SITE(double, 4); }
+    } else if (f32) { if (r <= 1) MMW_NORM(float, 1); else if (r == 2) MMW_NORM(float, 2); else MMW_NORM(float, 4); }
     else { if (r <= 1) MMW_NORM(double, 1); else if (r == 2) MMW_NORM(double, 2); else MMW_NORM(double, 4); }
 #undef MMW_NORM
+#undef MMW_NORM_SITE
 }
-void launch_normalize_tlv(const DevCfg &cfg, const uint8_t *packets, long long packets_bytes, const long long *tlv_offset, double half_bins,
-                          double doppler_res, double *out, int32_t *n_out, hipStream_t st)
+void launch_normalize_tlv(const DevCfg &cfg, const mmw_scene_site *sites, const uint8_t *packets, long long packets_bytes, const long long *tlv_offset,
+                          double half_bins, double doppler_res, double *out, int32_t *n_out, hipStream_t st)
 {
     const int r = (cfg.max_pts + 255) / 256;
 #define MMW_NORM_TLV(R) mmw_launch(k_normalize_tlv<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out)
-    if (r <= 1) MMW_NORM_TLV(1); else if (r == 2) MMW_NORM_TLV(2); else MMW_NORM_TLV(4);
+#define MMW_NORM_TLV_SITE(R) mmw_launch(k_normalize_tlv_site<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out)
+    if (sites) { if (r <= 1) MMW_NORM_TLV_SITE(1); else if (r == 2) MMW_NORM_TLV_SITE(2); else MMW_NORM_TLV_SITE(4); }
+    else if (r <= 1) MMW_NORM_TLV(1); else if (r == 2) MMW_NORM_TLV(2); else MMW_NORM_TLV(4);
 #undef MMW_NORM_TLV
+#undef MMW_NORM_TLV_SITE
 }
 void launch_feat_scan(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st)
 {
     hipLaunchKernelGGL(k_feat_count, dim3((cfg.n_scenes + 3) / 4), dim3(256), 0, st, cfg, s, row_off);
     hipLaunchKernelGGL(k_feat_scan, dim3(1), dim3(1024), 0, st, cfg, row_off);
 }
-void launch_features(const DevCfg &cfg, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner, int32_t *uid, int cap,
-                     hipStream_t st, const int32_t *n_in, int32_t *total_out)
+void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner,
+                     int32_t *uid, int cap, hipStream_t st, const int32_t *n_in, int32_t *total_out)
 {
-    hipLaunchKernelGGL(k_features, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, row_off, feat, owner, uid, cap, n_in, total_out);
+    if (sites) hipLaunchKernelGGL(k_features_site, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, s, row_off, feat, owner, uid, cap, n_in, total_out);
+    else hipLaunchKernelGGL(k_features, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, row_off, feat, owner, uid, cap, n_in, total_out);
 }
 void launch_format_frames(const DevCfg &cfg, const double *frames, const int32_t *counts, const double *ref, float *feat, int B, hipStream_t st)
 {
@@ -553,10 +648,11 @@ void launch_export(const DevCfg &cfg, const DevState &s, mmw_track_record *out, 
     const int tot = cfg.n_scenes * cap;
     hipLaunchKernelGGL(k_export, dim3((tot + 127) / 128), dim3(128), 0, st, cfg, s, out, cap);
 }
-void launch_table(const DevCfg &cfg, const DevState &s, mmw_track_summary *out, int slots, int base, hipStream_t st)
+void launch_table(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, mmw_track_summary *out, int slots, int base, hipStream_t st)
 {
     const int tot = cfg.n_scenes * slots;
-    hipLaunchKernelGGL(k_table, dim3((tot + 127) / 128), dim3(128), 0, st, cfg, s, out, slots, base);
+    if (sites) hipLaunchKernelGGL(k_table_site, dim3((tot + 127) / 128), dim3(128), 0, st, cfg, sites, s, out, slots, base);
+    else hipLaunchKernelGGL(k_table, dim3((tot + 127) / 128), dim3(128), 0, st, cfg, s, out, slots, base);
 }
 // BatchedData.pop_frame() (Tracking.py:66-71) on the global ring of the scenes whose flag is set: the oldest frame
 // goes, its physical slot moves behind the live ones (the same rotation add_frame does when the ring is full).

@@ -42,19 +42,21 @@ size_t dbscan_huge_slab_bytes(int UM, int t_cap, int min_samples);
 void launch_dbscan_huge(const DevCfg &cfg, const DevState &st, int UM, int u_bound, int parity, int32_t *labels, int32_t *db_n, hipStream_t stream);
 void launch_dbscan_only(const DevCfg &cfg, const DevState &st, int UM, const double *pts, const int32_t *n, int max_n, double eps, int min_samples,
                         int32_t *labels, int32_t *ncl, hipStream_t stream);
-void launch_normalize(const DevCfg &cfg, const void *raw, bool f32, const int32_t *n_raw, double *out, int32_t *n_out, hipStream_t st);
-void launch_normalize_tlv(const DevCfg &cfg, const uint8_t *packets, long long packets_bytes, const long long *tlv_offset, double half_bins,
-                          double doppler_res, double *out, int32_t *n_out, hipStream_t st);
+// (sites: the context's site table while one is in use -- the k_*_site kernels --, else nullptr)
+void launch_normalize(const DevCfg &cfg, const mmw_scene_site *sites, const void *raw, bool f32, const int32_t *n_raw, double *out, int32_t *n_out,
+                      hipStream_t st);
+void launch_normalize_tlv(const DevCfg &cfg, const mmw_scene_site *sites, const uint8_t *packets, long long packets_bytes, const long long *tlv_offset,
+                          double half_bins, double doppler_res, double *out, int32_t *n_out, hipStream_t st);
 void launch_feat_scan(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st);
-void launch_features(const DevCfg &cfg, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner, int32_t *uid, int cap,
-                     hipStream_t st, const int32_t *n_in = nullptr, int32_t *total_out = nullptr);
+void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner,
+                     int32_t *uid, int cap, hipStream_t st, const int32_t *n_in = nullptr, int32_t *total_out = nullptr);
 void launch_set_kp_uid(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, const int32_t *uid, int n_rows,
                        hipStream_t st);
 void launch_format_frames(const DevCfg &cfg, const double *frames, const int32_t *counts, const double *ref, float *feat, int B, hipStream_t st);
 void launch_set_kp(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, int n_rows, hipStream_t st,
                    const int32_t *dev_rows = nullptr);
 void launch_export(const DevCfg &cfg, const DevState &s, mmw_track_record *out, int cap, hipStream_t st);
-void launch_table(const DevCfg &cfg, const DevState &s, mmw_track_summary *out, int slots, int base, hipStream_t st);
+void launch_table(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, mmw_track_summary *out, int slots, int base, hipStream_t st);
 void launch_reset(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st);
 void launch_probe_wait(int32_t *w, int slot, int polls, hipStream_t st);
 void launch_probe_set(int32_t *w, hipStream_t st);
@@ -124,6 +126,9 @@ struct mmw_ctx {
     double *d_pts = nullptr; int32_t *d_n = nullptr; double *d_dt = nullptr;      // (views into d_in / d_out)
     int32_t *d_assoc = nullptr, *d_labels = nullptr, *d_dbn = nullptr, *d_nout = nullptr, *d_prows = nullptr;
     mmw_track_record *d_export = nullptr; int export_cap = 0;
+    mmw_scene_site *d_sites = nullptr;   // [S] per-scene sites (mmw_set_sites; lazy).  Kept allocated by mmw_clear_sites ...
+    int sites_on = 0;                    // ... which only turns this off: the kernels of a context without sites run again
+    std::vector<mmw_scene_site> h_sites; // host mirror of d_sites while sites_on (mmw_get_sites reads it)
     char *d_snap = nullptr;           // mmw_snapshot / mmw_restore scratch (lazy): [S] scene list | [S] flags | [4] check word | [S + 2] u64 sizes | [S] directory
     // mmw_attach_posture: the model and the chain's buffers ([cap] rows: feature tensors, owners, conv output, hidden, keypoints)
     bool has_model = false;
@@ -531,7 +536,7 @@ int mmw_destroy(mmw_ctx *c)
     prof_fold(c);
     for (auto &ep : c->pool) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
     void *ptrs[] = {c->st.hdr, c->st.order, c->st.trk, c->st.trk_ring, c->st.g_ring, c->d_posture, c->d_row_off, c->d_stats, c->d_db_list, c->d_db_count, c->d_q, c->d_probe, c->st.gate_buf, c->st.perm, c->st.upd_count, c->st.upd_list, c->st.spc_count, c->st.spc_list, c->st.inner_buf, c->d_in, c->d_out, c->d_raw, c->d_pchain,
-                    c->d_export, c->st.huge_scratch, c->d_snap};
+                    c->d_export, c->st.huge_scratch, c->d_snap, c->d_sites};
     for (void *p : ptrs) if (p) hipFree(p);
     void *pinned[] = {c->h_in, c->h_out, c->h_hdr, c->h_q};
     for (void *p : pinned) if (p) hipHostFree(p);
@@ -654,6 +659,76 @@ int mmw_set_batch_frame(mmw_ctx *c, int32_t scene, const double *rows, int32_t n
     return MMW_OK;
 }
 
+// ---- per-scene sites ----
+static mmw_scene_site site_of_config(const mmw_config &g)
+{
+    mmw_scene_site s;
+    s.s_height = g.s_height; s.tilt_cos = g.tilt_cos; s.tilt_sin = g.tilt_sin;
+    s.intensity_mu = g.intensity_mu; s.intensity_std = g.intensity_std;
+    s.m_x = g.m_x; s.m_y = g.m_y; s.m_z = g.m_z;
+    s.v_screen_fade_size_max = g.v_screen_fade_size_max; s.v_screen_fade_size_min = g.v_screen_fade_size_min;
+    s.v_screen_fade_weight = g.v_screen_fade_weight;
+    s.reserved_ = 0.0;
+    return s;
+}
+static_assert(sizeof(mmw_scene_site) == 96, "mmw_scene_site");
+
+int mmw_set_sites(mmw_ctx *c, const int32_t *scenes, int32_t n, const mmw_scene_site *sites)
+{
+    if (!c) return fail(nullptr, MMW_E_ARG, "mmw_set_sites: null context");
+    const int S = c->dc.n_scenes;
+    // every check first: a refused call changes no scene's site (and does not allocate or switch the table on)
+    if (n < 0 || n > S) return fail(c, MMW_E_ARG, "mmw_set_sites: n = %d, the context has %d scenes", n, S);
+    if (n > 0 && !sites) return fail(c, MMW_E_ARG, "mmw_set_sites: sites is NULL with n = %d", n);
+    std::vector<char> seen(scenes ? (size_t)S : 0, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = scenes ? scenes[i] : i;
+        if (s < 0 || s >= S) return fail(c, MMW_E_ARG, "mmw_set_sites: entry %d names scene %d, the context has %d scenes", i, s, S);
+        if (scenes) {
+            if (seen[s]) return fail(c, MMW_E_ARG, "mmw_set_sites: entry %d names scene %d a second time", i, s);
+            seen[s] = 1;
+        }
+        // (as bits: -0.0 and NaN are not 0)
+        unsigned long long r;
+        memcpy(&r, &sites[i].reserved_, sizeof(r));
+        if (r != 0) return fail(c, MMW_E_ARG, "mmw_set_sites: entry %d (scene %d) has a non-zero reserved_", i, s);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // The new table is put together on the host (a copy of the mirror: a failure below leaves the context as it was) and
+    // travels as ONE copy, ordered on the context's stream: what was queued before this call reads the old table.
+    std::vector<mmw_scene_site> next = c->h_sites;
+    if (!c->sites_on) next.assign((size_t)S, site_of_config(c->cfg));   // the first call, or the first after mmw_clear_sites: every scene starts from the config's own values
+    for (int i = 0; i < n; i++) next[scenes ? scenes[i] : i] = sites[i];
+    if (!c->d_sites) HIPCHK(c, hipMalloc((void **)&c->d_sites, sizeof(mmw_scene_site) * (size_t)S));
+    HIPCHK(c, hipMemcpyAsync(c->d_sites, next.data(), sizeof(mmw_scene_site) * (size_t)S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (`next` is pageable and goes away)
+    c->h_sites.swap(next);
+    c->sites_on = 1;
+    return MMW_OK;
+}
+
+int mmw_get_sites(mmw_ctx *c, mmw_scene_site *out)
+{
+    if (!c || !out) return fail(c, MMW_E_ARG, "mmw_get_sites: null argument");
+    const size_t S = (size_t)c->dc.n_scenes;
+    const mmw_scene_site own = site_of_config(c->cfg);
+    for (size_t i = 0; i < S; i++) out[i] = c->sites_on ? c->h_sites[i] : own;   // (the host mirror of the device table)
+    return MMW_OK;
+}
+
+int mmw_clear_sites(mmw_ctx *c)
+{
+    if (!c) return fail(nullptr, MMW_E_ARG, "mmw_clear_sites: null context");
+    c->sites_on = 0;   // (launches already queued carry the table's pointer: it stays allocated until mmw_destroy)
+    return MMW_OK;
+}
+
+int mmw_has_sites(mmw_ctx *c)
+{
+    if (!c) return fail(nullptr, MMW_E_ARG, "mmw_has_sites: null context");
+    return c->sites_on ? 1 : 0;
+}
+
 int mmw_set_chain_side_stream(mmw_ctx *c, int32_t on)
 {
     if (!c) return MMW_E_ARG;
@@ -758,7 +833,7 @@ static int normalize_impl(mmw_ctx *c, const void *raw, bool f32, const int32_t *
     HIPCHK(c, hipSetDevice(c->device));
     EventPair ep;
     prof_arm(c, MMW_K_NORMALIZE, ep);
-    launch_normalize(c->dc, raw, f32, n_raw, pts, n_out, c->stream);
+    launch_normalize(c->dc, c->sites_on ? c->d_sites : nullptr, raw, f32, n_raw, pts, n_out, c->stream);
     prof_armed_done(c, ep);
     HIPCHK(c, hipGetLastError());
     return MMW_OK;
@@ -775,7 +850,7 @@ int mmw_normalize_tlv(mmw_ctx *c, const uint8_t *packets, size_t packets_bytes, 
     EventPair ep;
     prof_arm(c, MMW_K_NORMALIZE, ep);
     static_assert(sizeof(long long) == sizeof(int64_t), "tlv offsets");
-    launch_normalize_tlv(c->dc, packets, (long long)packets_bytes, reinterpret_cast<const long long *>(tlv_offset), cfg->num_doppler_bins / 2.0 - 1,
+    launch_normalize_tlv(c->dc, c->sites_on ? c->d_sites : nullptr, packets, (long long)packets_bytes, reinterpret_cast<const long long *>(tlv_offset), cfg->num_doppler_bins / 2.0 - 1,
                          cfg->doppler_resolution_mps, pts, n_out, c->stream);
     prof_armed_done(c, ep);
     HIPCHK(c, hipGetLastError());
@@ -944,7 +1019,7 @@ static int frame_impl(mmw_ctx *c, const double *raw, const double *pts, const in
         const mmw_posture_model &m = c->model;
         const int cap = c->dc.t_cap;
         constexpr int kFlat = 3 * 64 * 32;
-        launch_features(c->dc, c->st, nullptr, c->pc_feat, c->pc_owner, nullptr, cap, c->stream, raw ? c->d_nout : c->d_n, c->d_prows);
+        launch_features(c->dc, c->sites_on ? c->d_sites : nullptr, c->st, nullptr, c->pc_feat, c->pc_owner, nullptr, cap, c->stream, raw ? c->d_nout : c->d_n, c->d_prows);
         launch_mars_conv(c->pc_feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, c->pc_act, cap, c->stream, c->d_prows);
         launch_mars_head_small(c->pc_act, kFlat, m.dense1_w, m.dense1_ld, m.dense1_b, m.dense2_w, m.dense2_b, c->pc_hidden, c->pc_kp, cap, kFlat, 1536,
                                MMW_NKP, c->stream, c->d_prows);
@@ -1032,7 +1107,7 @@ int mmw_features_async(mmw_ctx *c, float *feat, int32_t *owner, int32_t *uid, in
     EventPair ep;
     launch_feat_scan(c->dc, c->st, c->d_row_off, c->stream);
     prof_begin(c, MMW_K_FEATURES, ep);
-    launch_features(c->dc, c->st, c->d_row_off, feat, owner, uid, cap_rows, c->stream);
+    launch_features(c->dc, c->sites_on ? c->d_sites : nullptr, c->st, c->d_row_off, feat, owner, uid, cap_rows, c->stream);
     prof_end(c, ep);
     HIPCHK(c, hipGetLastError());
     // the total travels to pinned host memory behind the kernels; only mmw_features_wait(ticket) waits for it
@@ -1224,7 +1299,7 @@ int mmw_track_table(mmw_ctx *c, mmw_track_summary *table, int32_t slots, int32_t
     HIPCHK(c, hipSetDevice(c->device));
     EventPair ep;
     prof_begin(c, MMW_K_TABLE, ep);
-    launch_table(c->dc, c->st, table, slots, scene_base, c->stream);
+    launch_table(c->dc, c->sites_on ? c->d_sites : nullptr, c->st, table, slots, scene_base, c->stream);
     prof_end(c, ep);
     HIPCHK(c, hipGetLastError());
     return MMW_OK;

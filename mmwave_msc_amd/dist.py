@@ -119,6 +119,14 @@ class ShardedTracker:
     def step_dev(self, pts_ptr, n_ptr, dt_ptr, assoc_ptr=None, labels_ptr=None, dbn_ptr=None, f32: bool = False):
         (self.sb.step_dev_f32 if f32 else self.sb.step_dev)(pts_ptr, n_ptr, dt_ptr, assoc_ptr, labels_ptr, dbn_ptr)
 
+    def set_sites(self, sites):
+        """Per-scene sites for the whole job: `sites` is the job-wide `_lib.SITE_DTYPE` array [n_total], the same on every rank;
+        this rank applies its rows [lo, hi) (`SceneBatch.set_sites`)."""
+        sites = np.asarray(sites).reshape(-1)
+        if len(sites) != self.n_total:
+            raise ValueError(f"set_sites: {len(sites)} sites for a job of {self.n_total} scenes")
+        self.sb.set_sites(sites[self.lo: self.hi])
+
     def after_step(self):
         if self.pipe is not None:
             self.pipe.after_step()
@@ -198,6 +206,13 @@ class LocalShardedTracker:
     def run(self, fn):
         """fn(g, shard_dict) on every shard's own thread; returns the results in shard order (exceptions propagate)."""
         return [f.result() for f in [self._pool.submit(fn, sh["g"], sh) for sh in self.shards]]
+
+    def set_sites(self, sites):
+        """The job-wide `_lib.SITE_DTYPE` array [n_total]: every shard gets its rows [lo, hi)."""
+        sites = np.asarray(sites).reshape(-1)
+        if len(sites) != self.n_total:
+            raise ValueError(f"set_sites: {len(sites)} sites for a job of {self.n_total} scenes")
+        self.run(lambda g, sh: sh["sb"].set_sites(sites[sh["lo"]: sh["hi"]]))
 
     def gather_table(self, slots: int) -> np.ndarray:
         tabs = self.run(lambda g, sh: sh["sb"].track_table_host(int(slots), scene_base=sh["lo"]))
