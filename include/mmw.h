@@ -335,6 +335,35 @@ int mmw_attach_posture(mmw_ctx *ctx, const mmw_posture_model *model);
 int mmw_frame_posture_host(mmw_ctx *ctx, const double *raw, const double *pts, const int32_t *n, const double *dt, double *pts_out,
                            int32_t *n_out, int32_t *assoc, int32_t *db_labels, int32_t *db_n, int32_t *n_tracks, int32_t *posture_rows);
 
+/* The BATCHED TrackBuffer.estimate_posture (Tracking.py:705-734; the second half of the loop body, offline_main.py:57-60) for a
+ * context of ANY number of scenes, with no torch tensor on the path: what posture.PosturePipeline(overlap=False) + mars.MarsCNN
+ * string together in Python, as three C entries.
+ * mmw_posture_attach hands the context the define_CNN_3D model (train.py:71-106) -- the SAME struct mmw_posture_model as
+ * mmw_attach_posture: fp32 DEVICE pointers in Keras layout, BatchNormalization folded into the Dense layers, valid and unchanged in
+ * place until detached -- and lets it allocate the chain's buffers for cap_rows rows (rounded up to 256): feature tensors, owners,
+ * uids, the split activation (2 * 6144 + 256 fp16 per row), hidden, keypoints, the fix-up list and MMW_RANGE_FIXUP_SCRATCH; the
+ * split-fp16 Dense-1 operand (1536 x 12288 fp16) is built once on the device (mmw_mars_split_weights).  Refused with MMW_E_ARG, a
+ * message and nothing changed (an earlier model stays attached): FB_FRAMES_BATCH != 2 (the single-frame model define_CNN is not
+ * served here), cap_rows < 1, a null pointer, Dense-1 / Dense-2 not 16-byte aligned, dense1_ld < 6144 or not a multiple of 4, and a
+ * conv or Dense-1 weight (conv biases included) that is not finite or of magnitude >= 65 504 -- the split arithmetic is exact inside
+ * fp16's range only, and there is no silent fp32 fallback.  model == NULL detaches and frees.  Independent of mmw_attach_posture: a
+ * one-scene context may hold both.  Sync.
+ * mmw_estimate_posture runs, on the context's stream behind whatever was queued last (normally the frame's mmw_step): the feature
+ * tensors of every track with more than MODEL_MIN_INPUT ring points (Tracking.py:718-730; each scene's own site while a site table is
+ * in use) -> the host waits for the ROW COUNT only (a copy into pinned memory, not the stream: the matrix kernels need their exact
+ * batch size) -> mmw_mars_conv_split's kernel -> mmw_mars_dense1_split's kernel -> mmw_mars_dense2's kernel (model.predict,
+ * Tracking.py:732) -> mmw_mars_range_fixup's kernels -> track.keypoints = rows (Tracking.py:733-734, mmw_set_keypoints).  The serial
+ * schedule on one stream.  *n_rows (host, may be NULL) = the tracks estimated.  No eligible track: nothing is launched behind the
+ * features, returns 0.  More eligible tracks than cap_rows: MMW_E_CAPACITY, no keypoint changed.  No model attached: MMW_E_ARG.
+ * Returns WITHOUT waiting for the stream: the keypoints are in place for whatever the caller queues on the context next
+ * (mmw_get_tracks, mmw_track_table, the next mmw_step), as with the other asynchronous entries.
+ * mmw_posture_range reads and clears this path's sticky range word -- MarsCNN.range_overflow() --: bit 0 = a sample's input or
+ * activation left fp16's range and its keypoints were recomputed in fp32 (valid), bit 1 = more than MMW_RANGE_FIXUP_CAP such
+ * samples in one call, the surplus keeps meaningless keypoints.  Sync. */
+int mmw_posture_attach(mmw_ctx *ctx, const mmw_posture_model *model, int32_t cap_rows);
+int mmw_estimate_posture(mmw_ctx *ctx, int32_t *n_rows);
+int mmw_posture_range(mmw_ctx *ctx, int32_t *word);
+
 /* Utils.apply_DBscan (Utils.py:250-291) on arbitrary clouds: pts[S][max_n][8], n[S]
  * -> labels[S][max_n], n_clusters[S] (dev pointers; max_n <= ring*max_pts; max_n > 1920: the global-memory path).
  * A cloud that holds a NaN or an infinite value in any of its 8 columns is refused as sklearn's input validation refuses it
@@ -528,6 +557,20 @@ int mmw_mars_range_fixup(void *hip_stream, const float *feat, int32_t *sample_fl
  * the batch may hold anything: a row only feeds its own output row), k of 32, n of 128; lda, ldw >= 2 k.  hip_stream as above. */
 int mmw_mars_dense1_split(void *hip_stream, const void *a2, int64_t lda, const void *w2, int64_t ldw, const float *bias, float *out,
                           int32_t rows_padded, int32_t k, int32_t n);
+
+/* Dense-2 of the MARS CNN at any batch size (train.py:92: Dense(57); BatchNormalization folded in), one kernel on the fp32 matrix
+ * cores: kp[n_rows][57] = bias2 + hidden[n_rows][ldh] . w2[57][k]^T, fp32 fused multiply-adds in a summation order that is fixed per
+ * output (the same for every row, batch size and run), fp32 out.  `hidden` is read once with 16-byte loads; rows past n_rows are
+ * neither read nor written; a row only feeds its own output row.  All dev pointers; hidden and w2 16-byte aligned, k and ldh
+ * multiples of 4, ldh >= k (k = 1536 for the 3-frame model).  hip_stream as above. */
+int mmw_mars_dense2(void *hip_stream, const float *hidden, int64_t ldh, const float *w2, const float *bias2, float *kp, int32_t n_rows,
+                    int32_t k);
+/* The split-fp16 operand of mmw_mars_dense1_split from fp32 weights, on the device (what mars.interleave_split builds with torch,
+ * bit for bit): w[n][ldw] fp32 (K contiguous) -> w16[n][ld16] fp16, every value a carried as hi = fp16(a), lo' = fp16((a - hi) * 2^11)
+ * in runs of [hi 32 | lo' 32].  k a multiple of 32, ldw >= k a multiple of 4, ld16 >= 2 k a multiple of 8, both 16-byte aligned.
+ * range_flag (device pointer, may be NULL) gets bit 0 set when a value is not finite or of magnitude >= 65 504: the split is exact
+ * inside fp16's range only; nothing clears it but the caller. */
+int mmw_mars_split_weights(void *hip_stream, const float *w, int64_t ldw, void *w16, int64_t ld16, int32_t n, int32_t k, int32_t *range_flag);
 
 /* The head of the MARS CNN for a SMALL batch (n_rows <= 64: one scene's tracks, TrackBuffer.estimate_posture of the offline
  * loop): Dense-1 + ReLU (train.py:49,87) and Dense-2 (train.py:54,92), both with their BatchNormalization folded in, in fp32

@@ -41,6 +41,7 @@ EXPORTS = [
     "mmw_attach_posture", "mmw_frame_posture_host", "mmw_clear_errors", "mmw_stream_wait", "mmw_wait_stream", "mmw_find_tlv", "mmw_normalize_tlv",
     "mmw_snapshot_size", "mmw_snapshot", "mmw_restore", "mmw_snapshot_inspect",
     "mmw_set_sites", "mmw_get_sites", "mmw_clear_sites", "mmw_has_sites",
+    "mmw_posture_attach", "mmw_estimate_posture", "mmw_posture_range", "mmw_mars_dense2", "mmw_mars_split_weights",
 ]
 
 
@@ -316,6 +317,11 @@ def load():
         "mmw_get_sites": (C.c_int, [vp, vp]),
         "mmw_clear_sites": (C.c_int, [vp]),
         "mmw_has_sites": (C.c_int, [vp]),
+        "mmw_posture_attach": (C.c_int, [vp, vp, i32]),
+        "mmw_estimate_posture": (C.c_int, [vp, i32p]),
+        "mmw_posture_range": (C.c_int, [vp, i32p]),
+        "mmw_mars_dense2": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, i32, i32]),
+        "mmw_mars_split_weights": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

@@ -65,6 +65,7 @@ class SceneBatch:
         self._bufs = {}
         self._frame_out = None      # frame_host(reuse_out=True): the result arrays of the last call
         self._posture_model = None
+        self._posture_batch = None   # attach_posture_batch: the weights' device buffers
 
     # -- plumbing -------------------------------------------------------------
     def _chk(self, rc):
@@ -76,6 +77,7 @@ class SceneBatch:
             for b in list(self._bufs.values()):
                 b.free()
             self._bufs.clear()
+            self._free_posture_batch()
             self.L.mmw_destroy(self.h)
             self.h = None
 
@@ -298,6 +300,54 @@ class SceneBatch:
                                  model.dense2.bias.data_ptr())
         self._chk(self.L.mmw_attach_posture(self.h, C.byref(m)))
         self._posture_model = model   # (keeps the tensors alive)
+
+    def attach_posture_batch(self, weights=None, cap_rows: int = None):
+        """mmw_posture_attach: the batched `TrackBuffer.estimate_posture` for every scene of this context, no torch on the path.
+        `weights`: Keras-convention tensors of the 3-frame model as a dict, an `.npz` or a Keras `.h5` path (what
+        `MarsCNN.from_keras_weights` / `MarsCNN.load` take); both BatchNorms are folded on the host in fp64
+        (`marsweights.fold_keras_weights`), the fp32 tensors uploaded and kept by this object, the split-fp16 Dense-1 operand built
+        on the device.  `cap_rows` (default: S * track_cap) = the most tracks one call can estimate.  None detaches and frees.
+        Refused (MmwError, E_ARG): FB_FRAMES_BATCH != 2, cap_rows < 1, a weight outside fp16's range."""
+        if weights is None:
+            self._chk(self.L.mmw_posture_attach(self.h, None, 0))
+            self._free_posture_batch()
+            return
+        from .marsweights import fold_keras_weights, load_keras_weights
+        f = fold_keras_weights(load_keras_weights(weights))
+        if f["frames"] != 3:
+            raise ValueError(f"attach_posture_batch: the 3-frame model (define_CNN_3D) only, these weights are the {f['frames']}-frame model's")
+        cap = int(cap_rows if cap_rows is not None else self.S * self.track_cap)
+        keys = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "dense1_w", "dense1_b", "dense2_w", "dense2_b")
+        bufs = {k: DevBuf(self, f[k].nbytes).upload(f[k]) for k in keys}
+        m = _lib.MmwPostureModel(bufs["conv1_w"].ptr, bufs["conv1_b"].ptr, bufs["conv2_w"].ptr, bufs["conv2_b"].ptr, bufs["dense1_w"].ptr,
+                                 f["dense1_w"].shape[1], bufs["dense1_b"].ptr, bufs["dense2_w"].ptr, bufs["dense2_b"].ptr)
+        rc = self.L.mmw_posture_attach(self.h, C.byref(m), cap)
+        if rc != 0:   # (refused atomically: an earlier model stays attached, with its own buffers)
+            for b in bufs.values():
+                b.free()
+            self._chk(rc)
+        self._free_posture_batch()
+        self._posture_batch = bufs
+
+    def _free_posture_batch(self):
+        if self._posture_batch:
+            for b in self._posture_batch.values():
+                b.free()
+        self._posture_batch = None
+
+    def estimate_posture(self) -> int:
+        """mmw_estimate_posture: features -> CNN -> `track.keypoints` for every eligible track of every scene, queued behind the
+        last step on the context's stream (the host waits for the row count only).  Returns the tracks estimated."""
+        rows = C.c_int32(0)
+        self._chk(self.L.mmw_estimate_posture(self.h, C.byref(rows)))
+        return int(rows.value)
+
+    def posture_range(self) -> int:
+        """mmw_posture_range: reads and clears the sticky range word of `estimate_posture` -- bit 0: a sample left fp16's range and
+        was recomputed in fp32 (valid), bit 1: more than 64 such samples in one call, the surplus is meaningless.  Synchronises."""
+        word = C.c_int32(0)
+        self._chk(self.L.mmw_posture_range(self.h, C.byref(word)))
+        return int(word.value)
 
     def frame_host(self, n: np.ndarray, dt: np.ndarray, raw: np.ndarray = None, pts: np.ndarray = None, want_rows: bool = False,
                    want_labels: bool = True, posture: bool = False, reuse_out: bool = False):

@@ -73,6 +73,9 @@ int launch_mars_head_small(const float *act, long long lda, const float *w1, lon
                            float *hidden, float *kp, int n_rows, int K, int N1, int NOUT, hipStream_t stream, const int32_t *dev_rows = nullptr);
 int launch_mars_conv16(int nz, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, void *out16, long long ld_out,
                         int B, int32_t *range_flag, int32_t *sample_flags, hipStream_t stream);
+void launch_mars_dense2(const float *hidden, long long ldh, const float *w2, const float *bias2, float *kp, int n_rows, int K, hipStream_t stream);
+void launch_split_weights(const float *w, long long ldw, void *w16, long long ld16, int n, int k, int32_t *range_flag, hipStream_t stream);
+void launch_range_check(const float *a, long long count, int32_t *range_flag, hipStream_t stream);
 void launch_snap_size(const DevCfg &cfg, const DevState &st, const int32_t *sel, int n, mmw_snapshot_entry *dir, unsigned long long *bytes,
                       unsigned long long base, hipStream_t stream);
 void launch_snap_pack(const DevCfg &cfg, const DevState &st, const int32_t *sel, int n, const mmw_snapshot_entry *dir, char *blob, int max_tracks,
@@ -87,6 +90,18 @@ using namespace mmw;
 static thread_local std::string g_last_error;
 
 struct EventPair { hipEvent_t a, b; int kid; };
+
+// mmw_posture_attach: the model, its split Dense-1 operand and the buffers of the batched CNN chain ([cap] rows, cap a multiple of 256)
+struct PostureBatch {
+    mmw_posture_model model = {};
+    int32_t cap = 0;
+    float *feat = nullptr, *hidden = nullptr, *kp = nullptr;
+    int32_t *owner = nullptr, *uid = nullptr;
+    int32_t *words = nullptr;         // [0] the sticky range word, [1] the attach-time weight check, [2 ..] the fix-up list (2 + MMW_RANGE_FIXUP_CAP)
+    void *act16 = nullptr, *w16 = nullptr, *fix_scratch = nullptr;
+    int32_t *h_total = nullptr;       // pinned: the eligible-track total of the call in flight
+    hipEvent_t total_ev = nullptr;
+};
 
 struct mmw_ctx {
     mmw_config cfg;
@@ -136,6 +151,7 @@ struct mmw_ctx {
     char *d_pchain = nullptr;
     float *pc_feat = nullptr, *pc_act = nullptr, *pc_hidden = nullptr, *pc_kp = nullptr;
     int32_t *pc_owner = nullptr;
+    PostureBatch *pb = nullptr;       // mmw_posture_attach (any number of scenes); independent of the one-scene chain above
     // profiling
     unsigned prof_mask = 0;           // bit k: time kernel id k (mmw_profile_enable)
     std::vector<EventPair> pending;
@@ -225,6 +241,16 @@ static void prof_end(mmw_ctx *c, EventPair &ep)
 }
 
 static int read_headers(mmw_ctx *c, std::vector<SceneHdr> &h);
+
+static void posture_batch_free(PostureBatch *b)
+{
+    if (!b) return;
+    void *ptrs[] = {b->feat, b->hidden, b->kp, b->owner, b->uid, b->words, b->act16, b->w16, b->fix_scratch};
+    for (void *p : ptrs) if (p) hipFree(p);
+    if (b->h_total) hipHostFree(b->h_total);
+    if (b->total_ev) hipEventDestroy(b->total_ev);
+    delete b;
+}
 
 // Which step a context runs is decided in ONE place: the one-workgroup step (k_scene) when it was chosen at creation and
 // neither the side-stream workers are asked for (they claim scenes while the association kernel runs) nor a global ring has
@@ -544,6 +570,7 @@ int mmw_destroy(mmw_ctx *c)
     if (c->handoff_ev) hipEventDestroy(c->handoff_ev);
     if (c->handback_ev) hipEventDestroy(c->handback_ev);
     if (c->h_rows) hipHostFree(c->h_rows);
+    posture_batch_free(c->pb);
     if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->side_gate) hipEventDestroy(c->side_gate);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -1376,6 +1403,152 @@ int mmw_mars_range_fixup(void *hip_stream, const float *feat, int32_t *sample_fl
     launch_range_scatter(kps, sample_flags, kp, kCap, MMW_NKP, n, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, MMW_E_HIP, "mmw_mars_range_fixup launch -> %s", hipGetErrorString(e));
+    return MMW_OK;
+}
+
+// ---- the batched TrackBuffer.estimate_posture (Tracking.py:705-734) behind the C-ABI: any number of scenes, no torch ----
+constexpr int kPbFlat = 3 * 64 * 32, kPbHidden = 1536, kPbPer = 3 * 8 * 8 * 5;
+constexpr long long kPbActLd = 2 * kPbFlat + 256;   // the activation's row stride: mars.MarsCNN.ROW_PAD
+constexpr int kPbWordRange = 0, kPbWordWeights = 1, kPbWordList = 2;
+
+int mmw_posture_attach(mmw_ctx *c, const mmw_posture_model *m, int32_t cap_rows)
+{
+    if (!c) return fail(c, MMW_E_ARG, "mmw_posture_attach: null context");
+    if (!m) {
+        if (c->pb) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            posture_batch_free(c->pb);
+            c->pb = nullptr;
+        }
+        return MMW_OK;
+    }
+    if (c->dc.ring != 3) return fail(c, MMW_E_ARG, "mmw_posture_attach: the 3-frame model only (FB_FRAMES_BATCH = 2), this context has FB_FRAMES_BATCH = %d", c->dc.ring - 1);
+    if (cap_rows < 1) return fail(c, MMW_E_ARG, "mmw_posture_attach: cap_rows = %d must be >= 1", cap_rows);
+    if (cap_rows > INT32_MAX - 255) return fail(c, MMW_E_ARG, "mmw_posture_attach: cap_rows = %d is too large", cap_rows);
+    if (!m->conv1_w || !m->conv1_b || !m->conv2_w || !m->conv2_b || !m->dense1_w || !m->dense1_b || !m->dense2_w || !m->dense2_b ||
+        m->dense1_ld < kPbFlat || (m->dense1_ld & 3) != 0 || ((uintptr_t)m->dense1_w & 15) != 0 || ((uintptr_t)m->dense2_w & 15) != 0)
+        return fail(c, MMW_E_ARG, "mmw_posture_attach: null weight pointer, or Dense-1 / Dense-2 not 16-byte aligned, or Dense-1's leading dimension not a multiple of 4 that is >= 6144");
+    HIPCHK(c, hipSetDevice(c->device));
+    PostureBatch *b = new (std::nothrow) PostureBatch();
+    if (!b) return fail(c, MMW_E_HIP, "mmw_posture_attach: out of host memory");
+    const size_t cap = ((size_t)cap_rows + 255) & ~(size_t)255;
+    b->model = *m;
+    b->cap = cap_rows;
+    const size_t n_words = kPbWordList + 2 + MMW_RANGE_FIXUP_CAP;
+    hipError_t e = hipSuccess;
+    auto grab = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
+    grab((void **)&b->feat, cap * kPbPer * sizeof(float));
+    grab((void **)&b->owner, cap * 2 * sizeof(int32_t));
+    grab((void **)&b->uid, cap * sizeof(int32_t));
+    grab(&b->act16, cap * (size_t)kPbActLd * 2);
+    grab((void **)&b->hidden, cap * kPbHidden * sizeof(float));
+    grab((void **)&b->kp, cap * MMW_NKP * sizeof(float));
+    grab((void **)&b->words, n_words * sizeof(int32_t));
+    grab(&b->fix_scratch, MMW_RANGE_FIXUP_SCRATCH);
+    grab(&b->w16, (size_t)kPbHidden * 2 * kPbFlat * 2);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_total, sizeof(int32_t));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&b->total_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(b->words, 0, n_words * sizeof(int32_t), c->stream);
+    int32_t bad = 0;
+    if (e == hipSuccess) {
+        // the split Dense-1 operand, once; every weight that meets the split arithmetic must lie inside fp16's range
+        int32_t *flag = b->words + kPbWordWeights;
+        launch_split_weights(m->dense1_w, m->dense1_ld, b->w16, 2 * kPbFlat, kPbHidden, kPbFlat, flag, c->stream);
+        launch_range_check(m->conv1_w, 27 * 5 * 16, flag, c->stream);
+        launch_range_check(m->conv1_b, 16, flag, c->stream);
+        launch_range_check(m->conv2_w, 27 * 16 * 32, flag, c->stream);
+        launch_range_check(m->conv2_b, 32, flag, c->stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    if (e != hipSuccess) {
+        posture_batch_free(b);
+        return fail(c, MMW_E_HIP, "mmw_posture_attach: %s (cap_rows = %d)", hipGetErrorString(e), cap_rows);
+    }
+    if (bad) {
+        posture_batch_free(b);
+        return fail(c, MMW_E_ARG, "mmw_posture_attach: a conv or Dense-1 weight is not finite or has a magnitude >= 65504: outside fp16's range, where the split arithmetic of this path is not exact (use a one-scene context's fp32 path, mmw_attach_posture, for such a model)");
+    }
+    if (c->pb) posture_batch_free(c->pb);   // (the stream was waited for above: nothing of the old chain is running)
+    c->pb = b;
+    return MMW_OK;
+}
+
+int mmw_estimate_posture(mmw_ctx *c, int32_t *n_rows)
+{
+    if (n_rows) *n_rows = 0;
+    if (!c) return fail(c, MMW_E_ARG, "mmw_estimate_posture: null context");
+    PostureBatch *b = c->pb;
+    if (!b) return fail(c, MMW_E_ARG, "mmw_estimate_posture: no model attached (mmw_posture_attach)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const mmw_posture_model &m = b->model;
+    EventPair ep;
+    launch_feat_scan(c->dc, c->st, c->d_row_off, c->stream);
+    prof_begin(c, MMW_K_FEATURES, ep);
+    launch_features(c->dc, c->sites_on ? c->d_sites : nullptr, c->st, c->d_row_off, b->feat, b->owner, b->uid, b->cap, c->stream);
+    prof_end(c, ep);
+    HIPCHK(c, hipGetLastError());
+    // the matrix kernels need their exact batch size: the host waits for the total (not for the stream)
+    HIPCHK(c, hipMemcpyAsync(b->h_total, c->d_row_off + c->dc.n_scenes, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(b->total_ev, c->stream));
+    HIPCHK(c, hipEventSynchronize(b->total_ev));
+    const int32_t total = *b->h_total;
+    if (total > b->cap) return fail(c, MMW_E_CAPACITY, "mmw_estimate_posture: %d eligible tracks but cap_rows=%d (no keypoint was changed)", total, b->cap);
+    if (total <= 0) return MMW_OK;
+    const int rows_padded = (total + 255) & ~255;
+    int32_t *range = b->words + kPbWordRange, *list = b->words + kPbWordList;
+    if (launch_mars_conv16(3, b->feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, b->act16, kPbActLd, total, range, list, c->stream) != 0 ||
+        launch_mars_dense1(b->act16, kPbActLd, b->w16, 2 * kPbFlat, m.dense1_b, b->hidden, rows_padded, kPbFlat, kPbHidden, c->stream) != 0)
+        return fail(c, MMW_E_HIP, "mmw_estimate_posture: hipFuncSetAttribute(max dynamic LDS) failed on this device");
+    launch_mars_dense2(b->hidden, kPbHidden, m.dense2_w, m.dense2_b, b->kp, total, kPbHidden, c->stream);
+    HIPCHK(c, hipGetLastError());
+    const int rc = mmw_mars_range_fixup(c->stream, b->feat, list, total, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, m.dense1_w, m.dense1_ld, m.dense1_b,
+                                        m.dense2_w, m.dense2_b, b->fix_scratch, b->kp, range);
+    if (rc) return fail(c, rc, "mmw_estimate_posture: %s", g_last_error.c_str());
+    launch_set_kp(c->dc, c->st, b->kp, b->owner, total, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if (n_rows) *n_rows = total;
+    return MMW_OK;
+}
+
+int mmw_posture_range(mmw_ctx *c, int32_t *word)
+{
+    if (!c || !word) return fail(c, MMW_E_ARG, "mmw_posture_range: null argument");
+    if (!c->pb) return fail(c, MMW_E_ARG, "mmw_posture_range: no model attached (mmw_posture_attach)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int32_t w = 0;
+    { const int rc_ = d2h_after_kernels(c, &w, c->pb->words + kPbWordRange, sizeof(w)); if (rc_) return rc_; }
+    if (w) {
+        HIPCHK(c, hipMemsetAsync(c->pb->words + kPbWordRange, 0, sizeof(int32_t), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    *word = w;
+    return MMW_OK;
+}
+
+int mmw_mars_dense2(void *hip_stream, const float *hidden, int64_t ldh, const float *w2, const float *bias2, float *kp, int32_t n_rows, int32_t k)
+{
+    if (n_rows < 0 || k < 4 || (k & 3) != 0 || ldh < k || (ldh & 3) != 0 || !hidden || !w2 || !bias2 || !kp ||
+        (((uintptr_t)hidden | (uintptr_t)w2) & 15) != 0)
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_dense2: n_rows >= 0, k a multiple of 4, 16-byte aligned fp32 operands, ldh >= k and a multiple of 4");
+    if (n_rows == 0) return MMW_OK;
+    launch_mars_dense2(hidden, ldh, w2, bias2, kp, n_rows, k, (hipStream_t)hip_stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, MMW_E_HIP, "mmw_mars_dense2 launch -> %s", hipGetErrorString(e));
+    return MMW_OK;
+}
+
+int mmw_mars_split_weights(void *hip_stream, const float *w, int64_t ldw, void *w16, int64_t ld16, int32_t n, int32_t k, int32_t *range_flag)
+{
+    if (n < 0 || k < 32 || (k & 31) != 0 || ldw < k || (ldw & 3) != 0 || ld16 < 2 * (int64_t)k || (ld16 & 7) != 0 || !w || !w16 ||
+        (((uintptr_t)w | (uintptr_t)w16) & 15) != 0)
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_split_weights: n >= 0, k a multiple of 32, w fp32 16-byte aligned with ldw >= k a multiple of 4, w16 16-byte aligned with ld16 >= 2 k a multiple of 8");
+    if (n == 0) return MMW_OK;
+    launch_split_weights(w, ldw, w16, ld16, n, k, range_flag, (hipStream_t)hip_stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, MMW_E_HIP, "mmw_mars_split_weights launch -> %s", hipGetErrorString(e));
     return MMW_OK;
 }
 
