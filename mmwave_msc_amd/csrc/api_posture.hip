@@ -1,0 +1,324 @@
+// api_posture.hip -- the C-ABI (include/mmw.h): posture.  Feature tensors and keypoints of the tracks, the one-scene fp32 chain's
+// model (mmw_attach_posture; mmw_frame_posture_host runs it), the batched chain (mmw_posture_attach / mmw_estimate_posture) and
+// the stateless mmw_mars_* entries over the CNN kernels.
+#include <new>
+
+#include "mmw_ctx.hpp"
+
+constexpr long long kPbActLd = 2 * kCnnFlat + 256;   // the batched chain's activation row stride: mars.MarsCNN.ROW_PAD
+constexpr int kPbWordRange = 0, kPbWordWeights = 1, kPbWordList = 2;
+
+void posture_batch_free(PostureBatch *b)
+{
+    if (!b) return;
+    void *ptrs[] = {b->feat, b->hidden, b->kp, b->owner, b->uid, b->words, b->act16, b->w16, b->fix_scratch};
+    for (void *p : ptrs) if (p) hipFree(p);
+    if (b->h_total) hipHostFree(b->h_total);
+    if (b->total_ev) hipEventDestroy(b->total_ev);
+    delete b;
+}
+
+// what both chains ask of a model: every weight present, Dense-1 16-byte aligned with a leading dimension >= kCnnFlat that is a
+// multiple of 4; the batched chain's Dense-2 kernel reads its weights 16 bytes at a time as well
+static bool posture_model_ok(const mmw_posture_model *m, bool dense2_aligned)
+{
+    return m->conv1_w && m->conv1_b && m->conv2_w && m->conv2_b && m->dense1_w && m->dense1_b && m->dense2_w && m->dense2_b &&
+           m->dense1_ld >= kCnnFlat && (m->dense1_ld & 3) == 0 && ((uintptr_t)m->dense1_w & 15) == 0 &&
+           (!dense2_aligned || ((uintptr_t)m->dense2_w & 15) == 0);
+}
+
+// The eligible tracks' feature tensors (scan, then k_features) and, behind the kernels, their total into pinned host memory with
+// an event: whoever needs the total waits for the event, not for the stream
+static int features_and_total(mmw_ctx *c, float *feat, int32_t *owner, int32_t *uid, int32_t cap_rows, int32_t *h_total, hipEvent_t ev)
+{
+    EventPair ep;
+    launch_feat_scan(c->dc, c->st, c->d_row_off, c->stream);
+    prof_begin(c, MMW_K_FEATURES, ep);
+    launch_features(c->dc, sites_or_null(c), c->st, c->d_row_off, feat, owner, uid, cap_rows, c->stream);
+    prof_end(c, ep);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_total, c->d_row_off + c->dc.n_scenes, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(ev, c->stream));
+    return MMW_OK;
+}
+
+// the tail of a stateless entry: what its launches left behind
+static int launches_done(const char *who)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MMW_OK : fail(nullptr, MMW_E_HIP, "%s launch -> %s", who, hipGetErrorString(e));
+}
+
+int mmw_features_async(mmw_ctx *c, float *feat, int32_t *owner, int32_t *uid, int32_t cap_rows, int32_t ticket)
+{
+    if (!c || !feat || !owner || cap_rows < 0 || ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_features_async: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    // only mmw_features_wait(ticket) waits for the total
+    MMW_TRY(features_and_total(c, feat, owner, uid, cap_rows, c->h_rows + ticket, c->feat_ev[ticket]));
+    c->feat_cap[ticket] = cap_rows;
+    return MMW_OK;
+}
+
+int mmw_features_wait(mmw_ctx *c, int32_t ticket, int32_t *n_rows)
+{
+    if (!c || !n_rows || ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_features_wait: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->feat_ev[ticket]));
+    const int32_t total = c->h_rows[ticket], cap_rows = c->feat_cap[ticket];
+    *n_rows = total < cap_rows ? total : cap_rows;
+    if (total > cap_rows) return fail(c, MMW_E_CAPACITY, "mmw_features: %d eligible tracks but cap_rows=%d", total, cap_rows);
+    return MMW_OK;
+}
+
+int mmw_features(mmw_ctx *c, float *feat, int32_t *owner, int32_t cap_rows, int32_t *n_rows)
+{
+    if (!c || !feat || !owner || !n_rows || cap_rows < 0) return fail(c, MMW_E_ARG, "mmw_features: bad argument");
+    const int rc = mmw_features_async(c, feat, owner, nullptr, cap_rows, kTickets - 1);
+    return rc ? rc : mmw_features_wait(c, kTickets - 1, n_rows);
+}
+
+int mmw_format_frames(mmw_ctx *c, const double *frames, const int32_t *counts, const double *ref, float *feat, int32_t n_items)
+{
+    if (!c || n_items < 0 || (n_items > 0 && (!frames || !counts || !ref || !feat))) return fail(c, MMW_E_ARG, "mmw_format_frames: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_format_frames(c->dc, frames, counts, ref, feat, n_items, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MMW_OK;
+}
+
+int mmw_set_keypoints(mmw_ctx *c, const float *kp, const int32_t *owner, int32_t n_rows)
+{
+    if (!c || (n_rows > 0 && (!kp || !owner)) || n_rows < 0) return fail(c, MMW_E_ARG, "mmw_set_keypoints: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_set_kp(c->dc, c->st, kp, owner, n_rows, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MMW_OK;
+}
+
+int mmw_set_keypoints_uid(mmw_ctx *c, const float *kp, const int32_t *owner, const int32_t *uid, int32_t n_rows)
+{
+    if (!c || (n_rows > 0 && (!kp || !owner || !uid)) || n_rows < 0) return fail(c, MMW_E_ARG, "mmw_set_keypoints_uid: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_set_kp_uid(c->dc, c->st, kp, owner, uid, n_rows, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MMW_OK;
+}
+
+// ---- the one-scene fp32 chain (mmw_frame_posture_host, api_step.hip, runs it behind the step) ----
+int mmw_attach_posture(mmw_ctx *c, const mmw_posture_model *m)
+{
+    if (!c) return fail(c, MMW_E_ARG, "mmw_attach_posture: null context");
+    if (!m) { c->has_model = false; return MMW_OK; }
+    if (c->dc.n_scenes != 1 || c->dc.ring != 3 || c->dc.t_cap > 64)
+        return fail(c, MMW_E_ARG, "mmw_attach_posture: a one-scene context of the 3-frame model (FB_FRAMES_BATCH = 2) with track_cap <= 64");
+    if (!posture_model_ok(m, false))
+        return fail(c, MMW_E_ARG, "mmw_attach_posture: null weight pointer, or Dense-1 not 16-byte aligned with a leading dimension >= 6144 that is a multiple of 4");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_pchain) {
+        const size_t cap = (size_t)c->dc.t_cap, per = kCnnPer + kCnnFlat + kCnnHidden + kCnnKpPad;   // floats per row
+        HIPCHK(c, hipMalloc((void **)&c->d_pchain, cap * (per * sizeof(float) + 2 * sizeof(int32_t))));
+        c->pc_feat = reinterpret_cast<float *>(c->d_pchain);
+        c->pc_act = c->pc_feat + cap * kCnnPer;
+        c->pc_hidden = c->pc_act + cap * kCnnFlat;
+        c->pc_kp = c->pc_hidden + cap * kCnnHidden;
+        c->pc_owner = reinterpret_cast<int32_t *>(c->pc_kp + cap * kCnnKpPad);
+    }
+    c->model = *m;
+    c->has_model = true;
+    return MMW_OK;
+}
+
+// ---- the stateless entries over the CNN kernels ----
+int mmw_mars_conv3d(void *hip_stream, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2,
+                    float *out, int32_t n)
+{
+    if (n < 0 || (n > 0 && (!feat || !w1 || !b1 || !w2 || !b2 || !out))) return fail(nullptr, MMW_E_ARG, "mmw_mars_conv3d: bad argument");
+    launch_mars_conv(feat, w1, b1, w2, b2, out, n, (hipStream_t)hip_stream);
+    return launches_done("mmw_mars_conv3d");
+}
+
+int mmw_mars_conv_split(void *hip_stream, int32_t frames, const float *feat, const float *w1, const float *b1, const float *w2,
+                        const float *b2, void *out16, int64_t ld_out, int32_t n, int32_t *range_flag, int32_t *sample_flags)
+{
+    if ((frames != 3 && frames != 1) || n < 0 || ld_out < 2 * (int64_t)frames * 2048 || (ld_out & 7) != 0 || ((uintptr_t)out16 & 15) != 0 ||
+        (n > 0 && (!feat || !w1 || !b1 || !w2 || !b2 || !out16)))
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_conv_split: bad argument (frames must be 3 or 1, ld_out >= 2 * frames * 2048 and a multiple of 8)");
+    if (launch_mars_conv16(frames, feat, w1, b1, w2, b2, out16, ld_out, n, range_flag, sample_flags, (hipStream_t)hip_stream) != 0)
+        return fail(nullptr, MMW_E_HIP, "mmw_mars_conv_split: hipFuncSetAttribute(max dynamic LDS) failed on this device");
+    return launches_done("mmw_mars_conv_split");
+}
+
+int mmw_mars_dense1_split(void *hip_stream, const void *a2, int64_t lda, const void *w2, int64_t ldw, const float *bias, float *out,
+                          int32_t rows_padded, int32_t k, int32_t n)
+{
+    if (rows_padded < 0 || (rows_padded & 255) != 0 || k < 32 || (k & 31) != 0 || n < 128 || (n & 127) != 0 || lda < 2 * (int64_t)k || ldw < 2 * (int64_t)k ||
+        ((lda | ldw) & 7) != 0 || (rows_padded > 0 && (!a2 || !w2 || !bias || !out)) || (((uintptr_t)a2 | (uintptr_t)w2) & 15) != 0)
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_dense1_split: rows_padded must be a multiple of 256, k of 32, n of 128; fp16 operands 16-byte aligned with leading dimensions >= 2 k that are multiples of 8");
+    if (rows_padded == 0) return MMW_OK;
+    if (launch_mars_dense1(a2, lda, w2, ldw, bias, out, rows_padded, k, n, (hipStream_t)hip_stream) != 0)
+        return fail(nullptr, MMW_E_HIP, "mmw_mars_dense1_split: hipFuncSetAttribute failed");
+    return launches_done("mmw_mars_dense1_split");
+}
+
+int mmw_mars_head_small(void *hip_stream, const float *act, int64_t lda, const float *w1, int64_t ldw, const float *bias1, const float *w2,
+                        const float *bias2, float *hidden, float *kp, int32_t n_rows, int32_t k, int32_t n1)
+{
+    if (n_rows < 0 || n_rows > 64 || k < 4 || (k & 3) != 0 || n1 < 1 || lda < k || ldw < k || ((lda | ldw) & 3) != 0 ||
+        (n_rows > 0 && (!act || !w1 || !bias1 || !w2 || !bias2 || !hidden || !kp)) || (((uintptr_t)act | (uintptr_t)w1) & 15) != 0)
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_head_small: n_rows in [0, 64], k a multiple of 4, 16-byte aligned fp32 operands with leading dimensions >= k that are multiples of 4");
+    if (n_rows == 0) return MMW_OK;
+    launch_mars_head_small(act, lda, w1, ldw, bias1, w2, bias2, hidden, kp, n_rows, k, n1, MMW_NKP, (hipStream_t)hip_stream);
+    return launches_done("mmw_mars_head_small");
+}
+
+int mmw_mars_range_fixup(void *hip_stream, const float *feat, int32_t *sample_flags, int32_t n, const float *cw1, const float *cb1,
+                         const float *cw2, const float *cb2, const float *w1, int64_t ldw, const float *bias1, const float *w2, const float *bias2,
+                         void *scratch, float *kp, int32_t *range_flag)
+{
+    constexpr int kCap = MMW_RANGE_FIXUP_CAP;
+    if (n < 0 || (n > 0 && (!feat || !sample_flags || !cw1 || !cb1 || !cw2 || !cb2 || !w1 || !bias1 || !w2 || !bias2 || !scratch || !kp)) ||
+        ldw < kCnnFlat || (ldw & 3) != 0 || (((uintptr_t)scratch | (uintptr_t)w1) & 15) != 0)
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_range_fixup: bad argument");
+    if (n == 0) return MMW_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    // scratch: small_feat[64][960], act[64][6144], hidden[64][1536], kp_small[64][57] floats (behind 512 spare bytes);
+    // sample_flags = the fix-up list k_mars_conv16 appended to: [0] running count, [1] taken by this call, [2 ..] sample indices
+    float *small = reinterpret_cast<float *>(reinterpret_cast<char *>(scratch) + 512);
+    float *act = small + (size_t)kCap * kCnnPer, *hidden = act + (size_t)kCap * kCnnFlat, *kps = hidden + (size_t)kCap * kCnnHidden;
+    const int32_t *taken = sample_flags + 1;
+    launch_range_gather(feat, sample_flags, n, kCnnPer, kCap, small, range_flag, st);
+    launch_mars_conv(small, cw1, cb1, cw2, cb2, act, kCap, st, taken);
+    launch_mars_head_small(act, kCnnFlat, w1, ldw, bias1, w2, bias2, hidden, kps, kCap, kCnnFlat, kCnnHidden, MMW_NKP, st, taken);
+    launch_range_scatter(kps, sample_flags, kp, kCap, MMW_NKP, n, st);
+    return launches_done("mmw_mars_range_fixup");
+}
+
+int mmw_mars_dense2(void *hip_stream, const float *hidden, int64_t ldh, const float *w2, const float *bias2, float *kp, int32_t n_rows, int32_t k)
+{
+    if (n_rows < 0 || k < 4 || (k & 3) != 0 || ldh < k || (ldh & 3) != 0 || !hidden || !w2 || !bias2 || !kp ||
+        (((uintptr_t)hidden | (uintptr_t)w2) & 15) != 0)
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_dense2: n_rows >= 0, k a multiple of 4, 16-byte aligned fp32 operands, ldh >= k and a multiple of 4");
+    if (n_rows == 0) return MMW_OK;
+    launch_mars_dense2(hidden, ldh, w2, bias2, kp, n_rows, k, (hipStream_t)hip_stream);
+    return launches_done("mmw_mars_dense2");
+}
+
+int mmw_mars_split_weights(void *hip_stream, const float *w, int64_t ldw, void *w16, int64_t ld16, int32_t n, int32_t k, int32_t *range_flag)
+{
+    if (n < 0 || k < 32 || (k & 31) != 0 || ldw < k || (ldw & 3) != 0 || ld16 < 2 * (int64_t)k || (ld16 & 7) != 0 || !w || !w16 ||
+        (((uintptr_t)w | (uintptr_t)w16) & 15) != 0)
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_split_weights: n >= 0, k a multiple of 32, w fp32 16-byte aligned with ldw >= k a multiple of 4, w16 16-byte aligned with ld16 >= 2 k a multiple of 8");
+    if (n == 0) return MMW_OK;
+    launch_split_weights(w, ldw, w16, ld16, n, k, range_flag, (hipStream_t)hip_stream);
+    return launches_done("mmw_mars_split_weights");
+}
+
+// ---- the batched TrackBuffer.estimate_posture (Tracking.py:705-734) behind the C-ABI: any number of scenes, no torch ----
+int mmw_posture_attach(mmw_ctx *c, const mmw_posture_model *m, int32_t cap_rows)
+{
+    if (!c) return fail(c, MMW_E_ARG, "mmw_posture_attach: null context");
+    if (!m) {
+        if (c->pb) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            posture_batch_free(c->pb);
+            c->pb = nullptr;
+        }
+        return MMW_OK;
+    }
+    if (c->dc.ring != 3) return fail(c, MMW_E_ARG, "mmw_posture_attach: the 3-frame model only (FB_FRAMES_BATCH = 2), this context has FB_FRAMES_BATCH = %d", c->dc.ring - 1);
+    if (cap_rows < 1) return fail(c, MMW_E_ARG, "mmw_posture_attach: cap_rows = %d must be >= 1", cap_rows);
+    if (cap_rows > INT32_MAX - 255) return fail(c, MMW_E_ARG, "mmw_posture_attach: cap_rows = %d is too large", cap_rows);
+    if (!posture_model_ok(m, true))
+        return fail(c, MMW_E_ARG, "mmw_posture_attach: null weight pointer, or Dense-1 / Dense-2 not 16-byte aligned, or Dense-1's leading dimension not a multiple of 4 that is >= 6144");
+    HIPCHK(c, hipSetDevice(c->device));
+    PostureBatch *b = new (std::nothrow) PostureBatch();
+    if (!b) return fail(c, MMW_E_HIP, "mmw_posture_attach: out of host memory");
+    const size_t cap = ((size_t)cap_rows + 255) & ~(size_t)255;
+    b->model = *m;
+    b->cap = cap_rows;
+    const size_t n_words = kPbWordList + 2 + MMW_RANGE_FIXUP_CAP;
+    hipError_t e = hipSuccess;
+    auto grab = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
+    grab((void **)&b->feat, cap * kCnnPer * sizeof(float));
+    grab((void **)&b->owner, cap * 2 * sizeof(int32_t));
+    grab((void **)&b->uid, cap * sizeof(int32_t));
+    grab(&b->act16, cap * (size_t)kPbActLd * 2);
+    grab((void **)&b->hidden, cap * kCnnHidden * sizeof(float));
+    grab((void **)&b->kp, cap * MMW_NKP * sizeof(float));
+    grab((void **)&b->words, n_words * sizeof(int32_t));
+    grab(&b->fix_scratch, MMW_RANGE_FIXUP_SCRATCH);
+    grab(&b->w16, (size_t)kCnnHidden * 2 * kCnnFlat * 2);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_total, sizeof(int32_t));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&b->total_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(b->words, 0, n_words * sizeof(int32_t), c->stream);
+    int32_t bad = 0;
+    if (e == hipSuccess) {
+        // the split Dense-1 operand, once; every weight that meets the split arithmetic must lie inside fp16's range
+        int32_t *flag = b->words + kPbWordWeights;
+        launch_split_weights(m->dense1_w, m->dense1_ld, b->w16, 2 * kCnnFlat, kCnnHidden, kCnnFlat, flag, c->stream);
+        launch_range_check(m->conv1_w, 27 * 5 * 16, flag, c->stream);
+        launch_range_check(m->conv1_b, 16, flag, c->stream);
+        launch_range_check(m->conv2_w, 27 * 16 * 32, flag, c->stream);
+        launch_range_check(m->conv2_b, 32, flag, c->stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    if (e != hipSuccess) {
+        posture_batch_free(b);
+        return fail(c, MMW_E_HIP, "mmw_posture_attach: %s (cap_rows = %d)", hipGetErrorString(e), cap_rows);
+    }
+    if (bad) {
+        posture_batch_free(b);
+        return fail(c, MMW_E_ARG, "mmw_posture_attach: a conv or Dense-1 weight is not finite or has a magnitude >= 65504: outside fp16's range, where the split arithmetic of this path is not exact (use a one-scene context's fp32 path, mmw_attach_posture, for such a model)");
+    }
+    if (c->pb) posture_batch_free(c->pb);   // (the stream was waited for above: nothing of the old chain is running)
+    c->pb = b;
+    return MMW_OK;
+}
+
+int mmw_estimate_posture(mmw_ctx *c, int32_t *n_rows)
+{
+    if (n_rows) *n_rows = 0;
+    if (!c) return fail(c, MMW_E_ARG, "mmw_estimate_posture: null context");
+    PostureBatch *b = c->pb;
+    if (!b) return fail(c, MMW_E_ARG, "mmw_estimate_posture: no model attached (mmw_posture_attach)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const mmw_posture_model &m = b->model;
+    // the matrix kernels need their exact batch size: the host waits for the total (not for the stream)
+    MMW_TRY(features_and_total(c, b->feat, b->owner, b->uid, b->cap, b->h_total, b->total_ev));
+    HIPCHK(c, hipEventSynchronize(b->total_ev));
+    const int32_t total = *b->h_total;
+    if (total > b->cap) return fail(c, MMW_E_CAPACITY, "mmw_estimate_posture: %d eligible tracks but cap_rows=%d (no keypoint was changed)", total, b->cap);
+    if (total <= 0) return MMW_OK;
+    const int rows_padded = (total + 255) & ~255;
+    int32_t *range = b->words + kPbWordRange, *list = b->words + kPbWordList;
+    if (launch_mars_conv16(3, b->feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, b->act16, kPbActLd, total, range, list, c->stream) != 0 ||
+        launch_mars_dense1(b->act16, kPbActLd, b->w16, 2 * kCnnFlat, m.dense1_b, b->hidden, rows_padded, kCnnFlat, kCnnHidden, c->stream) != 0)
+        return fail(c, MMW_E_HIP, "mmw_estimate_posture: hipFuncSetAttribute(max dynamic LDS) failed on this device");
+    launch_mars_dense2(b->hidden, kCnnHidden, m.dense2_w, m.dense2_b, b->kp, total, kCnnHidden, c->stream);
+    HIPCHK(c, hipGetLastError());
+    const int rc = mmw_mars_range_fixup(c->stream, b->feat, list, total, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, m.dense1_w, m.dense1_ld, m.dense1_b,
+                                        m.dense2_w, m.dense2_b, b->fix_scratch, b->kp, range);
+    if (rc) return fail(c, rc, "mmw_estimate_posture: %s", mmw_last_error(nullptr));
+    launch_set_kp(c->dc, c->st, b->kp, b->owner, total, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if (n_rows) *n_rows = total;
+    return MMW_OK;
+}
+
+int mmw_posture_range(mmw_ctx *c, int32_t *word)
+{
+    if (!c || !word) return fail(c, MMW_E_ARG, "mmw_posture_range: null argument");
+    if (!c->pb) return fail(c, MMW_E_ARG, "mmw_posture_range: no model attached (mmw_posture_attach)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int32_t w = 0;
+    MMW_TRY(d2h_after_kernels(c, &w, c->pb->words + kPbWordRange, sizeof(w)));
+    if (w) {
+        HIPCHK(c, hipMemsetAsync(c->pb->words + kPbWordRange, 0, sizeof(int32_t), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    *word = w;
+    return MMW_OK;
+}

@@ -31,6 +31,7 @@
 #include "mmw_cloud.hpp"
 #include "mmw_kalman.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_kernels.hpp"
 
 namespace mmw {
 
@@ -1843,7 +1844,7 @@ __global__ __launch_bounds__(NT, MMW_POST_OCC) void k_post(DevCfg cfg, DevState 
 // The chain workers of the side stream: 512-thread workgroups that serve BOTH queues while k_track and k_post run -- the
 // large clouds first (the longer chains), then the small ones (pair-count screen, then the BallTree on the thread-per-point
 // build).  One kernel, one stream: every further stream with a spinning kernel is one more hardware queue the context's
-// stream must not share (see probe_side_stream in mmw_api.hip).
+// stream must not share (see probe_side_streams in api_context.hip).
 __global__ __launch_bounds__(kBigThreads) void k_chain(DevCfg cfg, DevState st, int UMc, int CL, int UM_out, int parity, int epoch,
                                                int32_t *__restrict__ labels_out, int32_t *__restrict__ db_n_out)
 {

@@ -31,6 +31,8 @@
 #include <mutex>
 #include <type_traits>
 
+#include "mmw_kernels.hpp"
+
 namespace mmw {
 
 typedef _Float16 dh8 __attribute__((ext_vector_type(8)));

@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mmw_kernels.hpp"
+
 namespace mmw {
 
 namespace dense2 {

@@ -17,6 +17,7 @@
 // The arithmetic per matrix element is unchanged (same operations in the same order as the CPU oracle).
 #include "mmw_kalman.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_kernels.hpp"
 
 namespace mmw {
 

@@ -15,6 +15,8 @@
 #include <stdint.h>
 #include <mutex>
 
+#include "mmw_kernels.hpp"
+
 namespace mmw {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -12,6 +12,7 @@
 #include "mmw_device.hpp"
 #include "mmw_math.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_kernels.hpp"
 
 namespace mmw {
 
@@ -705,7 +706,7 @@ void launch_reset(const DevCfg &cfg, const DevState &s, const int32_t *flags, hi
 
 // Do kernels of stream B run while a kernel of stream A is spinning?  Streams are multiplexed onto a few hardware queues, and
 // two streams that share one execute in order: a chain worker (side stream) that polls for what k_track (context's stream)
-// publishes would then hold k_track back until its bounded wait runs out.  mmw_api.hip probes once per stream set-up:
+// publishes would then hold k_track back until its bounded wait runs out.  api_context.hip probes once per stream set-up:
 // waiters on the side streams, one setter on the context's stream.
 __global__ void k_probe_wait(int32_t *w, int slot, int polls)
 {

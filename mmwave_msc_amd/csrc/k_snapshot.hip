@@ -24,6 +24,7 @@
 // perm[] is a schedule, any permutation gives the same results.
 #include "mmw_device.hpp"
 #include "mmw_kalman.hpp"
+#include "mmw_kernels.hpp"
 
 namespace mmw {
 

@@ -16,6 +16,7 @@
 #include "mmw_cloud.hpp"
 #include "mmw_kalman.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_kernels.hpp"
 
 namespace mmw {
 

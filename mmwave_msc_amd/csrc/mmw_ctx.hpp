@@ -1,0 +1,162 @@
+// mmw_ctx.hpp -- what the api_*.hip files share: the context behind the C-ABI's opaque mmw_ctx, error reporting, the
+// profiling-event bookkeeping and a few one-line helpers.  Host code only; nothing here is part of the ABI.
+#pragma once
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mmw_device.hpp"
+#include "mmw_launch.hpp"
+#include "mmw_kernels.hpp"
+
+using namespace mmw;
+
+struct EventPair { hipEvent_t a, b; int kid; };
+
+// the posture CNN's shapes, floats per row: feature tensor, conv output, hidden layer, keypoints (MMW_NKP = 57, padded)
+constexpr int kCnnPer = 3 * 8 * 8 * 5, kCnnFlat = 3 * 64 * 32, kCnnHidden = 1536, kCnnKpPad = 64;
+constexpr int kTickets = 4;
+// the counters of mmw_stats_get in st.stats (the probe words of the diagnostic build lie behind them)
+constexpr size_t kStatBytes = (size_t)kStatSlots * kStatWords * sizeof(unsigned long long);
+
+// mmw_posture_attach: the model, its split Dense-1 operand and the buffers of the batched CNN chain ([cap] rows, cap a multiple of 256)
+struct PostureBatch {
+    mmw_posture_model model = {};
+    int32_t cap = 0;
+    float *feat = nullptr, *hidden = nullptr, *kp = nullptr;
+    int32_t *owner = nullptr, *uid = nullptr;
+    int32_t *words = nullptr;         // [0] the sticky range word, [1] the attach-time weight check, [2 ..] the fix-up list (2 + MMW_RANGE_FIXUP_CAP)
+    void *act16 = nullptr, *w16 = nullptr, *fix_scratch = nullptr;
+    int32_t *h_total = nullptr;       // pinned: the eligible-track total of the call in flight
+    hipEvent_t total_ev = nullptr;
+};
+
+struct mmw_ctx {
+    mmw_config cfg;
+    DevCfg dc;
+    DevState st;
+    int device;
+    int UM;                      // ring * max_pts
+    hipStream_t own_stream, stream;
+    hipStream_t side_stream = nullptr;   // k_chain beside k_track (contexts with dc.side_worker)
+    hipEvent_t side_gate = nullptr;      // (gate_side only) recorded on the context's stream at the head of a step: k_chain does not start before it
+    int gate_side = 0;                   // mmw_config.chain_side_stream == 3
+    int side_wanted = 0;                 // what the configuration / mmw_set_chain_side_stream asked for
+    int fused_wanted = 0;                // the one-workgroup step (k_scene) is what this context runs unless a ring was resized or the side workers were asked for
+    int side_trusted = 0;                // mmw_config.chain_side_stream == 2: the side stream is used without the concurrency check
+    int side_probed = 0;                 // the side streams have been checked against the current context stream (probe_side_streams)
+    int32_t *d_probe = nullptr;          // [4] flag + results of that check
+    int epoch = 0;                       // step number (queue protocol of list 3, k_dbscan.hip)
+    std::string err;
+    // internal scratch
+    int32_t *d_row_off = nullptr;     // [S+1]
+    int32_t *h_rows = nullptr;        // pinned [kTickets]: eligible-track totals of the outstanding mmw_features_async calls
+    hipEvent_t feat_ev[kTickets] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t handoff_ev = nullptr;     // mmw_stream_wait: recorded on the context's stream, waited for by the caller's
+    hipEvent_t handback_ev = nullptr;    // mmw_wait_stream: recorded on the caller's stream, waited for by the context's
+    int32_t feat_cap[kTickets] = {0, 0, 0, 0};
+    float *d_posture = nullptr;
+    int step_parity = 0;
+    int ring_frames_bound = 0;   // no scene's global ring holds more frames than this (host-side knowledge: steps since the last reset)
+    // host-convenience staging (lazy): one device block in [rows | dt | n], one out [assoc | db_n | n_out | labels], their pinned
+    // host mirrors, and pinned copies of the scene headers and the queue words -- mmw_frame_host moves each with ONE copy
+    char *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
+    double *d_raw = nullptr;          // [S][max_pts][8]: normalize_data's rows in the raw form of mmw_frame_host (the raw rows arrive in d_in's row area)
+    SceneHdr *h_hdr = nullptr;        // pinned [S]
+    int32_t *h_q = nullptr;           // pinned [kQWords]
+    double *d_pts = nullptr; int32_t *d_n = nullptr; double *d_dt = nullptr;      // (views into d_in / d_out)
+    int32_t *d_assoc = nullptr, *d_labels = nullptr, *d_dbn = nullptr, *d_nout = nullptr, *d_prows = nullptr;
+    mmw_track_record *d_export = nullptr; int export_cap = 0;
+    mmw_scene_site *d_sites = nullptr;   // [S] per-scene sites (mmw_set_sites; lazy).  Kept allocated by mmw_clear_sites ...
+    int sites_on = 0;                    // ... which only turns this off: the kernels of a context without sites run again
+    std::vector<mmw_scene_site> h_sites; // host mirror of d_sites while sites_on (mmw_get_sites reads it)
+    char *d_snap = nullptr;           // mmw_snapshot / mmw_restore scratch (lazy): [S] scene list | [S] flags | [4] check word | [S + 2] u64 sizes | [S] directory
+    // mmw_attach_posture: the model and the chain's buffers ([cap] rows: feature tensors, owners, conv output, hidden, keypoints)
+    bool has_model = false;
+    mmw_posture_model model = {};
+    char *d_pchain = nullptr;
+    float *pc_feat = nullptr, *pc_act = nullptr, *pc_hidden = nullptr, *pc_kp = nullptr;
+    int32_t *pc_owner = nullptr;
+    PostureBatch *pb = nullptr;       // mmw_posture_attach (any number of scenes); independent of the one-scene chain above
+    // profiling
+    unsigned prof_mask = 0;           // bit k: time kernel id k (mmw_profile_enable)
+    std::vector<EventPair> pending;
+    std::vector<EventPair> pool;
+    double tot_ms[MMW_K_COUNT] = {0};
+    int64_t launches[MMW_K_COUNT] = {0};
+};
+
+// ---- shared between the api_*.hip files, not exported ----
+#pragma GCC visibility push(hidden)
+int fail(mmw_ctx *ctx, int code, const char *fmt, ...);            // api_context.hip: the message into ctx->err and mmw_last_error(NULL)
+int probe_side_streams(mmw_ctx *c);                                // api_context.hip
+int read_headers(mmw_ctx *c, std::vector<SceneHdr> &h);            // api_query.hip
+int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q);   // api_query.hip
+void posture_batch_free(PostureBatch *b);                          // api_posture.hip
+#pragma GCC visibility pop
+
+#define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)
+// (a helper that has already reported through fail)
+#define MMW_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// a timing pair for kernel id `kid`, from the pool; false (ep.kid = -1) when that id is not being timed
+static inline bool prof_acquire(mmw_ctx *c, int kid, EventPair &ep)
+{
+    ep.kid = -1;
+    if (!((c->prof_mask >> kid) & 1u)) return false;
+    if (!c->pool.empty()) { ep = c->pool.back(); c->pool.pop_back(); }
+    else { hipEventCreate(&ep.a); hipEventCreate(&ep.b); }
+    ep.kid = kid;
+    return true;
+}
+static inline void prof_begin(mmw_ctx *c, int kid, EventPair &ep) { if (prof_acquire(c, kid, ep)) hipEventRecord(ep.a, c->stream); }
+// for an id that is exactly ONE launch: the events ride on the kernel's own packet (mmw_launch.hpp)
+static inline void prof_arm(mmw_ctx *c, int kid, EventPair &ep) { if (prof_acquire(c, kid, ep)) { g_launch_prof.a = ep.a; g_launch_prof.b = ep.b; } }
+static inline void prof_armed_done(mmw_ctx *c, EventPair &ep)
+{
+    if (ep.kid < 0) return;
+    if (g_launch_prof.a) {  // nothing was launched (e.g. no large-cloud class exists): nothing to time
+        g_launch_prof = LaunchProf{};
+        c->pool.push_back(ep);
+        return;
+    }
+    c->pending.push_back(ep);  // (folded by mmw_profile_get / the event-pair path)
+}
+static inline void prof_fold(mmw_ctx *c)
+{
+    for (auto &ep : c->pending) {
+        hipEventSynchronize(ep.b);
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ep.a, ep.b) == hipSuccess) { c->tot_ms[ep.kid] += ms; c->launches[ep.kid]++; }
+        c->pool.push_back(ep);
+    }
+    c->pending.clear();
+}
+static inline void prof_end(mmw_ctx *c, EventPair &ep)
+{
+    if (ep.kid < 0) return;
+    hipEventRecord(ep.b, c->stream);
+    c->pending.push_back(ep);
+    if (c->pending.size() >= 2048) prof_fold(c);
+}
+
+// the context's site table while one is in use (the k_*_site kernels), else nullptr
+static inline const mmw_scene_site *sites_or_null(const mmw_ctx *c) { return c->sites_on ? c->d_sites : nullptr; }
+
+// Which step a context runs is decided in ONE place: the one-workgroup step (k_scene) when it was chosen at creation and
+// neither the side-stream workers are asked for (they claim scenes while the association kernel runs) nor a global ring has
+// been resized (k_track's INNER instantiations read the sizes per ring).  What was ASKED for counts, not what the stream
+// probe left of it: a context whose probe turned the workers off keeps the bulk kernels, as derive_dev_cfg's `can` has it.
+static inline void refresh_step_kind(mmw_ctx *c) { c->dc.fused = (c->fused_wanted && !c->side_wanted && !c->dc.var_ring) ? 1 : 0; }
+
+// Read-back into the caller's (pageable) memory of what the context's stream has written: the stream is waited for first, then the
+// copy runs on it alone and is waited for.  (On the context's stream, not as a blocking hipMemcpy: that one runs on the legacy default
+// stream and would also wait for whatever another runtime -- torch -- has queued there.)
+static inline int d2h_after_kernels(mmw_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMW_OK;
+}

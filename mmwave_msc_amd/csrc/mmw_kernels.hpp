@@ -1,0 +1,68 @@
+// mmw_kernels.hpp -- every host-callable launcher and sizing function of the k_*.hip files, declared ONCE: the kernel file
+// that defines one includes this header (the compiler checks the definition against it), and so do the api_*.hip files.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/mmw.h"
+
+namespace mmw {
+struct DevCfg;     // mmw_device.hpp (the CNN's kernel files do without it)
+struct DevState;
+// k_track.hip, k_kalman.hip, k_scene.hip: the step
+size_t track_lds_bytes(const DevCfg &c);
+hipError_t prepare_track(const DevCfg &cfg);
+void launch_predict(const DevCfg &cfg, const DevState &st, const int32_t *n_pts, const double *dt, int parity, hipStream_t stream);
+void launch_track(const DevCfg &cfg, const DevState &st, const void *pts, bool f32, const int32_t *n_pts, const double *dt, int32_t *assoc, int32_t *db_n, int32_t *db_labels, int UM, int parity, hipStream_t stream);
+size_t scene_lds_bytes(const DevCfg &c);
+hipError_t prepare_scene(const DevCfg &cfg);
+void launch_scene(const DevCfg &cfg, const DevState &st, const void *pts, bool f32, const int32_t *n_pts, const double *dt, int32_t *assoc, int32_t *db_n, int32_t *db_labels, int UM, int parity, hipStream_t stream);
+// k_dbscan.hip
+void launch_post(const DevCfg &cfg, const DevState &st, const int32_t *n_pts, int UM, int u_bound, int parity, int epoch, int32_t *labels, int32_t *db_n, hipStream_t stream);
+void launch_chain(const DevCfg &cfg, const DevState &st, int UM, int u_bound, int parity, int epoch, int32_t *labels, int32_t *db_n, hipStream_t side);
+size_t dbscan_lds_bytes(int cls, int UM, int t_cap, int min_samples);
+size_t dbscan_only_lds_bytes(int UM);
+hipError_t prepare_dbscan(int UM, int t_cap, int min_samples);
+void launch_dbscan_big(const DevCfg &cfg, const DevState &st, int UM, int u_bound, int parity, int32_t *labels, int32_t *db_n, hipStream_t stream);
+hipError_t prepare_inner(const DevCfg &cfg);
+size_t inner_lds_demand(const DevCfg &cfg);
+int inner_um(const DevCfg &cfg);
+void launch_inner(const DevCfg &cfg, const DevState &st, const int32_t *n_pts, int32_t *db_n, hipStream_t stream);
+int dbscan_huge_workers(int n_scenes);
+size_t dbscan_huge_slab_bytes(int UM, int t_cap, int min_samples);
+void launch_dbscan_huge(const DevCfg &cfg, const DevState &st, int UM, int u_bound, int parity, int32_t *labels, int32_t *db_n, hipStream_t stream);
+void launch_dbscan_only(const DevCfg &cfg, const DevState &st, int UM, const double *pts, const int32_t *n, int max_n, double eps, int min_samples, int32_t *labels, int32_t *ncl, hipStream_t stream);
+// k_misc.hip
+// (sites: the context's site table while one is in use -- the k_*_site kernels --, else nullptr)
+void launch_normalize(const DevCfg &cfg, const mmw_scene_site *sites, const void *raw, bool f32, const int32_t *n_raw, double *out, int32_t *n_out, hipStream_t st);
+void launch_normalize_tlv(const DevCfg &cfg, const mmw_scene_site *sites, const uint8_t *packets, long long packets_bytes, const long long *tlv_offset, double half_bins, double doppler_res, double *out, int32_t *n_out, hipStream_t st);
+void launch_feat_scan(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st);
+void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner, int32_t *uid, int cap, hipStream_t st, const int32_t *n_in = nullptr, int32_t *total_out = nullptr);
+void launch_set_kp_uid(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, const int32_t *uid, int n_rows, hipStream_t st);
+void launch_format_frames(const DevCfg &cfg, const double *frames, const int32_t *counts, const double *ref, float *feat, int B, hipStream_t st);
+void launch_set_kp(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, int n_rows, hipStream_t st, const int32_t *dev_rows = nullptr);
+void launch_export(const DevCfg &cfg, const DevState &s, mmw_track_record *out, int cap, hipStream_t st);
+void launch_table(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, mmw_track_summary *out, int slots, int base, hipStream_t st);
+void launch_reset(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st);
+void launch_probe_wait(int32_t *w, int slot, int polls, hipStream_t st);
+void launch_probe_set(int32_t *w, hipStream_t st);
+void launch_pop_frame(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st);
+void launch_clear_errors(const DevCfg &cfg, const DevState &s, const int32_t *flags, int bits, hipStream_t st);
+void launch_set_batch_size(const DevCfg &cfg, const DevState &s, const int32_t *flags, int new_size, hipStream_t st);
+// k_mars.hip, k_dense.hip, k_dense2.hip: the posture CNN
+void launch_mars_conv(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
+void launch_range_gather(const float *feat, int32_t *list, int n, int per, int cap, float *small, int32_t *range_flag, hipStream_t stream);
+void launch_range_scatter(const float *kp_small, const int32_t *list, float *kp, int cap, int nout, int n, hipStream_t stream);
+int launch_mars_dense1(const void *a2, long long lda, const void *w2, long long ldw, const float *bias, float *out, int rows_padded, int K, int N, hipStream_t stream);
+int launch_mars_head_small(const float *act, long long lda, const float *w1, long long ldw, const float *bias1, const float *w2, const float *bias2, float *hidden, float *kp, int n_rows, int K, int N1, int NOUT, hipStream_t stream, const int32_t *dev_rows = nullptr);
+int launch_mars_conv16(int nz, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, void *out16, long long ld_out, int B, int32_t *range_flag, int32_t *sample_flags, hipStream_t stream);
+void launch_mars_dense2(const float *hidden, long long ldh, const float *w2, const float *bias2, float *kp, int n_rows, int K, hipStream_t stream);
+void launch_split_weights(const float *w, long long ldw, void *w16, long long ld16, int n, int k, int32_t *range_flag, hipStream_t stream);
+void launch_range_check(const float *a, long long count, int32_t *range_flag, hipStream_t stream);
+// k_snapshot.hip
+void launch_snap_size(const DevCfg &cfg, const DevState &st, const int32_t *sel, int n, mmw_snapshot_entry *dir, unsigned long long *bytes, unsigned long long base, hipStream_t stream);
+void launch_snap_pack(const DevCfg &cfg, const DevState &st, const int32_t *sel, int n, const mmw_snapshot_entry *dir, char *blob, int max_tracks, hipStream_t stream);
+void launch_snap_check(const DevCfg &cfg, const char *blob, const mmw_snapshot_entry *dir, int n, int src_ring_rows, int32_t *bad, hipStream_t stream);
+void launch_snap_restore(const DevCfg &cfg, const DevState &st, const char *blob, const mmw_snapshot_entry *dir, const int32_t *dst, const int32_t *flags, int n, int max_tracks, int src_ring_rows, hipStream_t stream);
+}  // namespace mmw

@@ -3,7 +3,7 @@
 // Timing a kernel with hipEventRecord before and after its launch puts two marker packets into the stream and
 // costs ~10 us of idle time per pair.  hipExtLaunchKernel attaches the two events to the kernel's own AQL packet
 // instead: same hipEventElapsedTime afterwards, no extra packets, so bench.py can time launches inside its
-// timed region without stretching it.  mmw_api.hip arms `g_launch_prof` right before a launch_* call; the one
+// timed region without stretching it.  mmw_ctx.hpp (prof_arm) arms `g_launch_prof` right before a launch_* call; the one
 // launch that follows consumes it.
 #pragma once
 
