@@ -424,6 +424,61 @@ int mmw_get_inner(mmw_ctx *ctx, int32_t *n_calls, int32_t *rows, int32_t *labels
  * table[S][slots] (dev), scene ids offset by scene_base.  Async. */
 int mmw_track_table(mmw_ctx *ctx, mmw_track_summary *table, int32_t slots, int32_t scene_base);
 
+/* ---- live-track report ----
+ * Who is in the scenes, without reading everything back: one compact row per LIVE track -- no dead slots, 324 bytes against the
+ * table's 336 per slot -- with the track's creation ordinal, and the tracks that appeared or left since the previous report as
+ * events.  Rows are compacted in (scene, slot) order: scenes ascending, inside a scene effective_tracks order.  Every field a row
+ * shares with mmw_track_summary equals the mmw_track_table row of that (scene, slot) from the same state bit for bit -- one
+ * device function fills both, the fade square and each scene's own site (mmw_set_sites) included; uid = mmw_track_record.uid, the
+ * handle mmw_set_keypoints_uid matches by: a slot moves whenever _maintain_tracks drops an earlier track, the uid never does.
+ *
+ * mmw_report_enable(ctx, 1) allocates the per-scene BASELINE -- the uid list [n_scenes][track_cap] of the previous report, its
+ * length, a generation word -- and fills it, ordered on the context's stream, with the tracks live at that moment: those produce
+ * no event (enabling again takes the baseline anew).  on = 0 waits for the stream and frees it.  A context that never enables
+ * reports launches exactly what it did before reports existed.
+ *
+ * Events: each report compares the live uid list of every scene with its baseline -- neither list is assumed sorted -- and the
+ * baseline then becomes the current list.  Events are ordered by scene; inside a scene MMW_EV_GONE first, in baseline order, then
+ * MMW_EV_BORN in current order.  The report is a DIFFERENCE OF STATES, not a log: a track that was born and expired between two
+ * reports appears in neither.  mmw_reset, mmw_reset_scenes and mmw_restore bump the generation of the scenes they touch (a
+ * kernel of their own, launched only while reports are enabled): uids restart there, so the next report emits exactly ONE
+ * MMW_EV_REBASED for such a scene and no BORN / GONE -- a uid of before never aliases one of after -- and takes the scene's
+ * current tracks as its baseline; their rows are reported as always.  Row flag bit 1 is set on exactly the rows whose uid has a
+ * MMW_EV_BORN in the same report.
+ *
+ * Capacity is decided on the DEVICE: if the live rows exceed cap_rows or the events exceed cap_events, nothing is written into
+ * either buffer, the baseline and the generations stay as they were, and mmw_report_wait returns MMW_E_CAPACITY with the counts
+ * needed in *n_rows / *n_events: a retry with larger buffers loses nothing.
+ * mmw_report_async queues the kernels behind whatever was queued last (normally the frame's mmw_step); the two counts follow them
+ * into pinned host memory, and mmw_report_wait(ticket) waits for THAT copy only, not for the stream.  ticket in [0,4): up to four
+ * reports may be outstanding (ticket 3 is the one mmw_report itself uses).  rows / events: dev pointers, 4-byte aligned, scene ids
+ * offset by scene_base.  MMW_E_ARG: reports not enabled, a NULL buffer with a positive cap, a negative cap, a bad ticket, a wait
+ * for a ticket with no report outstanding. */
+typedef struct mmw_track_report {   /* one LIVE track; 324 bytes */
+    int32_t scene;      /* global scene id (scene_base + local index) */
+    int32_t slot;       /* position in effective_tracks */
+    int32_t uid;        /* creation ordinal in its scene (mmw_track_record.uid) */
+    int32_t flags;      /* bit 0 is_static, bit 1 born since the previous report */
+    int32_t point_num;
+    float lifetime;
+    float x[9];
+    float centroid[6];
+    float fade_x, fade_z, fade_size;   /* as mmw_track_summary's */
+    float keypoints[MMW_NKP];
+} mmw_track_report;
+#define MMW_REPORT_STATIC 1
+#define MMW_REPORT_BORN 2
+typedef struct mmw_track_event { int32_t scene, uid, kind, slot; } mmw_track_event;
+#define MMW_EV_BORN 1     /* uid is live now and was not at the previous report; slot = its position now */
+#define MMW_EV_GONE 2     /* uid was live at the previous report and is not now; slot = its position then */
+#define MMW_EV_REBASED 3  /* the scene was reset or restored since the previous report; uid = -1, slot = n_tracks now */
+int mmw_report_enable(mmw_ctx *ctx, int32_t on);
+int mmw_report_async(mmw_ctx *ctx, mmw_track_report *rows, int32_t cap_rows, mmw_track_event *events, int32_t cap_events,
+                     int32_t scene_base, int32_t ticket);
+int mmw_report_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n_events);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_report(mmw_ctx *ctx, mmw_track_report *rows, int32_t cap_rows, mmw_track_event *events, int32_t cap_events,
+               int32_t scene_base, int32_t *n_rows, int32_t *n_events);                   /* async + wait */
+
 /* Snapshot / restore of scene state (format version 1).
  *
  * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global

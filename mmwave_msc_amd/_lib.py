@@ -42,6 +42,7 @@ EXPORTS = [
     "mmw_snapshot_size", "mmw_snapshot", "mmw_restore", "mmw_snapshot_inspect",
     "mmw_set_sites", "mmw_get_sites", "mmw_clear_sites", "mmw_has_sites",
     "mmw_posture_attach", "mmw_estimate_posture", "mmw_posture_range", "mmw_mars_dense2", "mmw_mars_split_weights",
+    "mmw_report_enable", "mmw_report_async", "mmw_report_wait", "mmw_report",
 ]
 
 
@@ -133,6 +134,30 @@ SUMMARY_DTYPE = np.dtype(
      ("fade_x", "f4"), ("fade_z", "f4"), ("fade_size", "f4")],
     align=True,
 )
+# struct mmw_track_report / mmw_track_event (include/mmw.h): the live-track report's rows (324 bytes, no padding) and events
+TRACK_REPORT_DTYPE = np.dtype(
+    [("scene", "i4"), ("slot", "i4"), ("uid", "i4"), ("flags", "i4"), ("point_num", "i4"), ("lifetime", "f4"),
+     ("x", "f4", (9,)), ("centroid", "f4", (6,)), ("fade_x", "f4"), ("fade_z", "f4"), ("fade_size", "f4"),
+     ("keypoints", "f4", (NKP,))],
+    align=True,
+)
+TRACK_EVENT_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("kind", "i4"), ("slot", "i4")], align=True)
+REPORT_STATIC, REPORT_BORN = 1, 2             # MMW_REPORT_*: bits of mmw_track_report.flags
+EV_BORN, EV_GONE, EV_REBASED = 1, 2, 3        # MMW_EV_*: mmw_track_event.kind
+REPORT_TICKETS = 4                            # reports that may be outstanding (mmw_report itself uses the last ticket)
+
+
+class MmwTrackReport(C.Structure):
+    """struct mmw_track_report (include/mmw.h): one live track of a report."""
+    _fields_ = [("scene", C.c_int32), ("slot", C.c_int32), ("uid", C.c_int32), ("flags", C.c_int32), ("point_num", C.c_int32),
+                ("lifetime", C.c_float), ("x", C.c_float * 9), ("centroid", C.c_float * 6), ("fade_x", C.c_float),
+                ("fade_z", C.c_float), ("fade_size", C.c_float), ("keypoints", C.c_float * NKP)]
+
+
+class MmwTrackEvent(C.Structure):
+    """struct mmw_track_event (include/mmw.h): a track that appeared or left, or a scene whose uids restarted."""
+    _fields_ = [("scene", C.c_int32), ("uid", C.c_int32), ("kind", C.c_int32), ("slot", C.c_int32)]
+
 
 _lib = None
 
@@ -322,6 +347,10 @@ def load():
         "mmw_posture_range": (C.c_int, [vp, i32p]),
         "mmw_mars_dense2": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, i32, i32]),
         "mmw_mars_split_weights": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp]),
+        "mmw_report_enable": (C.c_int, [vp, i32]),
+        "mmw_report_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
+        "mmw_report_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_report": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

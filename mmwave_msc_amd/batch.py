@@ -532,6 +532,52 @@ class SceneBatch:
         self.track_table_dev(b.ptr, slots, scene_base)
         return b.download((self.S, slots), SUMMARY_DTYPE)
 
+    # -- live-track report ----------------------------------------------------
+    def enable_report(self, on: bool = True):
+        """mmw_report_enable: the tracks live now become the baseline of the next report (they produce no event); on=False
+        frees it.  Until enabled, the report calls are refused (E_ARG) and the context launches nothing of them."""
+        self._chk(self.L.mmw_report_enable(self.h, 1 if on else 0))
+
+    def report_async(self, rows_ptr, cap_rows: int, events_ptr, cap_events: int, scene_base: int = 0, ticket: int = 0):
+        """mmw_report_async: one `_lib.TRACK_REPORT_DTYPE` row per live track in (scene, slot) order and the
+        `_lib.TRACK_EVENT_DTYPE` events since the previous report into device buffers, queued behind the last step on the
+        context's stream -- no host wait.  Tickets 0 .. 3 (`report_host` uses 3)."""
+        self._chk(self.L.mmw_report_async(self.h, rows_ptr, int(cap_rows), events_ptr, int(cap_events), int(scene_base), int(ticket)))
+
+    def report_wait(self, ticket: int = 0):
+        """(n_rows, n_events) of the `report_async` call with this ticket: waits for its counts only, not for the stream.
+        Buffers too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written and the
+        baseline is unchanged, so the same report can be asked for again with room."""
+        nr, ne = C.c_int32(0), C.c_int32(0)
+        rc = self.L.mmw_report_wait(self.h, int(ticket), C.byref(nr), C.byref(ne))
+        if rc == _lib.E_CAPACITY:
+            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
+            err.needed = (int(nr.value), int(ne.value))
+            raise err
+        self._chk(rc)
+        return int(nr.value), int(ne.value)
+
+    def report_host(self, scene_base: int = 0):
+        """The report as two structured arrays: (rows[n_rows] TRACK_REPORT_DTYPE, events[n_events] TRACK_EVENT_DTYPE).  A
+        difference of states, not a log: a track born and gone between two reports appears in neither.  The buffers grow to
+        what the device says it needs (a refused report loses nothing)."""
+        rdt, edt = _lib.TRACK_REPORT_DTYPE, _lib.TRACK_EVENT_DTYPE
+        cap_r, cap_e = getattr(self, "_report_caps", (64, 64))
+        while True:
+            b_r, b_e = self.buf("report_rows", cap_r * rdt.itemsize), self.buf("report_events", cap_e * edt.itemsize)
+            self.report_async(b_r.ptr, cap_r, b_e.ptr, cap_e, scene_base, _lib.REPORT_TICKETS - 1)
+            try:
+                n_r, n_e = self.report_wait(_lib.REPORT_TICKETS - 1)
+                break
+            except MmwError as e:
+                if e.code != _lib.E_CAPACITY:
+                    raise
+                cap_r, cap_e = max(cap_r, e.needed[0]), max(cap_e, e.needed[1])
+                self._report_caps = (cap_r, cap_e)
+        rows = b_r.download((n_r,), rdt) if n_r else np.zeros(0, rdt)
+        events = b_e.download((n_e,), edt) if n_e else np.zeros(0, edt)
+        return rows, events
+
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):
         if scenes is None:

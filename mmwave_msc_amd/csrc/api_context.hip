@@ -402,6 +402,7 @@ int mmw_destroy(mmw_ctx *c)
     if (c->handback_ev) hipEventDestroy(c->handback_ev);
     if (c->h_rows) hipHostFree(c->h_rows);
     posture_batch_free(c->pb);
+    report_free(c->rep);
     if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->side_gate) hipEventDestroy(c->side_gate);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -415,6 +416,7 @@ int mmw_reset(mmw_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     launch_reset(c->dc, c->st, nullptr, c->stream);
     HIPCHK(c, hipGetLastError());
+    MMW_TRY(report_rebase(c, nullptr));
     c->dc.var_ring = 0;   // fresh BatchedData objects: default sizes again
     refresh_step_kind(c);
     c->ring_frames_bound = 0;
@@ -425,7 +427,10 @@ int mmw_reset_scenes(mmw_ctx *c, const int32_t *scene_flags)
 {
     if (!c || !scene_flags) return fail(c, MMW_E_ARG, "mmw_reset_scenes: null argument");
     HIPCHK(c, hipSetDevice(c->device));
-    return with_scene_flags(c, scene_flags, [&](const int32_t *f) { launch_reset(c->dc, c->st, f, c->stream); });
+    return with_scene_flags(c, scene_flags, [&](const int32_t *f) {
+        launch_reset(c->dc, c->st, f, c->stream);
+        if (c->rep) launch_report_rebase(c->dc, c->rep->rs, f, c->stream);   // (reports enabled: the reset scenes' uids restart)
+    });
 }
 
 int mmw_clear_errors(mmw_ctx *c, const int32_t *scene_flags, int32_t bits)

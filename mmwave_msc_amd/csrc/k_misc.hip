@@ -11,6 +11,7 @@
 #include <cstddef>
 #include "mmw_device.hpp"
 #include "mmw_math.hpp"
+#include "mmw_summary.hpp"
 #include "mmw_launch.hpp"
 #include "mmw_kernels.hpp"
 
@@ -489,7 +490,8 @@ __global__ void k_export(DevCfg cfg, DevState st, mmw_track_record *__restrict__
 }
 
 // One track slot of the table.  The window / monitoring point (m_x .. fade_weight) are the context's for k_table, the scene's own
-// for k_table_site; everything arrives as scalars, so that the plain kernel reads its arguments exactly as it always did.
+// for k_table_site; everything arrives as scalars, so that the plain kernel reads its arguments exactly as it always did.  The
+// fields a live-track report row shares with the table come from summary_fields (mmw_summary.hpp), which k_report.hip calls too.
 __device__ __forceinline__ void table_slot(const SceneHdr *hdrs, const int32_t *order, const TrackRec *trk, int t_cap, int dx,
                                            mmw_track_summary *out, int slots, int scene_base, int s, int j, double m_x, double m_y,
                                            double m_z, double fade_max, double fade_min, double fade_weight)
@@ -502,25 +504,7 @@ __device__ __forceinline__ void table_slot(const SceneHdr *hdrs, const int32_t *
     o->alive = alive ? 1 : 0;
     const TrackRec *rec = alive ? trk + (size_t)s * t_cap + order[(size_t)s * t_cap + j] : nullptr;
     o->is_static = alive ? rec->is_static : 0;
-    o->point_num = alive ? rec->point_num : 0;
-    o->lifetime = alive ? (float)rec->lifetime : 0.f;
-    for (int e = 0; e < 9; e++) o->x[e] = (alive && e < dx) ? (float)rec->x[e] : 0.f;
-    for (int e = 0; e < 6; e++) o->centroid[e] = alive ? (float)rec->centroid[e] : 0.f;
-    for (int e = 0; e < MMW_NKP; e++) o->keypoints[e] = alive ? rec->kp[e] : 0.f;
-    // calc_fade_square (Visualizer.py:14-29) over calc_projection_points (Utils.py:180-219), in the reference's
-    // operation order, fp64 with the float32 keypoints widened (numpy 1.26, the reference's pinned version)
-    double px = 0, pz = 0, size = 0;
-    if (alive) {
-        const double xo = rec->x[0] + (double)rec->kp[3], yo = rec->x[1] + (double)rec->kp[41], zo = (double)rec->kp[22];
-        const double xd = xo - m_x, yd = yo - m_y, zd = zo - m_z;
-        px = xd == 0 ? xo : -m_y / (yd / xd) + m_x;
-        pz = zd == 0 ? zo : -m_y / (yd / zd) + m_z;
-        const double sz = fade_max - (rec->x[1] + (double)rec->kp[12]) * fade_weight;
-        size = fmax(fade_min, fmin(fade_max, sz));
-    }
-    o->fade_x = (float)px;
-    o->fade_z = (float)pz;
-    o->fade_size = (float)size;
+    summary_fields(o, rec, dx, m_x, m_y, m_z, fade_max, fade_min, fade_weight);
 }
 __global__ void k_table(DevCfg cfg, DevState st, mmw_track_summary *__restrict__ out, int slots, int scene_base)
 {

@@ -32,6 +32,15 @@ struct PostureBatch {
     hipEvent_t total_ev = nullptr;
 };
 
+// mmw_report_enable: the baseline and scratch of the live-track report, the pinned counts of the outstanding reports
+struct ReportCtx {
+    ReportState rs = {};
+    char *d_block = nullptr;          // one allocation behind rs
+    int32_t *h_counts = nullptr;      // pinned [kTickets][4]: rows, events, fits -- as ReportState::totals
+    hipEvent_t ev[kTickets] = {nullptr, nullptr, nullptr, nullptr};
+    bool issued[kTickets] = {false, false, false, false};
+};
+
 struct mmw_ctx {
     mmw_config cfg;
     DevCfg dc;
@@ -79,6 +88,7 @@ struct mmw_ctx {
     float *pc_feat = nullptr, *pc_act = nullptr, *pc_hidden = nullptr, *pc_kp = nullptr;
     int32_t *pc_owner = nullptr;
     PostureBatch *pb = nullptr;       // mmw_posture_attach (any number of scenes); independent of the one-scene chain above
+    ReportCtx *rep = nullptr;         // mmw_report_enable; nullptr = reports are off and nothing of them is launched
     // profiling
     unsigned prof_mask = 0;           // bit k: time kernel id k (mmw_profile_enable)
     std::vector<EventPair> pending;
@@ -94,6 +104,8 @@ int probe_side_streams(mmw_ctx *c);                                // api_contex
 int read_headers(mmw_ctx *c, std::vector<SceneHdr> &h);            // api_query.hip
 int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q);   // api_query.hip
 void posture_batch_free(PostureBatch *b);                          // api_posture.hip
+void report_free(ReportCtx *r);                                    // api_report.hip
+int report_rebase(mmw_ctx *c, const int32_t *dev_flags);           // api_report.hip: the scenes' uids restart (no-op while reports are off)
 #pragma GCC visibility pop
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)

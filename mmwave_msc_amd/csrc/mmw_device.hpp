@@ -150,6 +150,15 @@ struct DevState {
     char *huge_scratch;            // [workers][huge_stride] BallTree carve-ups of the clouds of more than kBigCloudMax points (k_dbscan_huge); null when no ring of the context can hold one
     size_t huge_stride;
 };
+// mmw_report_enable: what the live-track report keeps between two reports (k_report.hip).  All device memory.
+struct ReportState {
+    int32_t *base_uid;    // [S][t_cap] the uids live at the previous report, in effective_tracks order as it was then (the BASELINE)
+    int32_t *base_len;    // [S] ... and how many
+    int32_t *gen;         // [S] generation of the scene's uids: bumped by mmw_reset / mmw_reset_scenes / mmw_restore (uids restart there)
+    int32_t *seen;        // [S] the generation the baseline was taken in
+    int32_t *off;         // [2][S + 1] rows / events per scene of the report in flight, scanned in place; [S] = the total
+    int32_t *totals;      // [4] rows, events, 1 = both fit the caller's buffers (the device's capacity decision)
+};
 // The update lists (track-wise Kalman kernels).  A scene's workgroup of k_track appends its T tracks to the list of its SHARD
 // (workgroup index mod shards: eight counters instead of one word that every workgroup of the launch adds to) with one atomicAdd;
 // the consumers' unit w serves shard w mod shards, entries 4 (w / shards) .. + 3, so the list entry and the list's length are ONE

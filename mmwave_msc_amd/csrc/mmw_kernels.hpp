@@ -10,6 +10,7 @@
 namespace mmw {
 struct DevCfg;     // mmw_device.hpp (the CNN's kernel files do without it)
 struct DevState;
+struct ReportState;
 // k_track.hip, k_kalman.hip, k_scene.hip: the step
 size_t track_lds_bytes(const DevCfg &c);
 hipError_t prepare_track(const DevCfg &cfg);
@@ -50,6 +51,10 @@ void launch_probe_set(int32_t *w, hipStream_t st);
 void launch_pop_frame(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st);
 void launch_clear_errors(const DevCfg &cfg, const DevState &s, const int32_t *flags, int bits, hipStream_t st);
 void launch_set_batch_size(const DevCfg &cfg, const DevState &s, const int32_t *flags, int new_size, hipStream_t st);
+// k_report.hip: the live-track report
+void launch_report_baseline(const DevCfg &cfg, const DevState &s, const ReportState &rp, hipStream_t st);
+void launch_report_rebase(const DevCfg &cfg, const ReportState &rp, const int32_t *flags, hipStream_t st);
+void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ReportState &rp, mmw_track_report *rows, int cap_rows, mmw_track_event *events, int cap_events, int scene_base, hipStream_t st);
 // k_mars.hip, k_dense.hip, k_dense2.hip: the posture CNN
 void launch_mars_conv(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
 void launch_range_gather(const float *feat, int32_t *list, int n, int per, int cap, float *small, int32_t *range_flag, hipStream_t stream);
