@@ -695,6 +695,54 @@ int mmw_find_tlv(const uint8_t *buf, size_t len, int64_t *body_offset, int32_t *
 int mmw_normalize_tlv(mmw_ctx *ctx, const uint8_t *packets, size_t packets_bytes, const int64_t *tlv_offset, const mmw_uart_cfg *cfg, double *pts,
                       int32_t *n_out);
 
+/* Device-resident radar readers: ReadIWR14xx.read (ReadDataIWR1443.py:27-201) + Utils.normalize_data for EVERY scene in one
+ * kernel, the first line of the online loop (`dataOk, _, detObj = IWR1443.read()`, main.py:42) included.  Each scene owns
+ * what a ReadIWR14xx object keeps between two calls -- the 2^15-byte byteBuffer (zeroed at open, stale bytes and all) and
+ * byteBufferLength -- and main.py's `t` (44-47), on the device; the host ships whatever bytes arrived and reads nothing back.
+ * mmw_uart_open: cfg[n_cfg] (host), n_cfg = 1 (every scene) or n_scenes; buffers zeroed, lengths 0, t_last = t0
+ * (Tracking.py:511).  On the context's stream; calling it again replaces the state.  mmw_uart_close frees it.
+ * mmw_uart_read (asynchronous, on the context's stream): chunks (dev, 4-byte aligned) = all scenes' new bytes in one buffer
+ * of chunks_bytes bytes, read in whole aligned 4-byte words that hold a byte of a scene's chunk; chunk_off[S + 1] (dev) =
+ * scene s's chunk is chunks[chunk_off[s] .. chunk_off[s + 1]); scene_flags[S] (dev; NULL = every scene) = the scenes that
+ * read; now = the time of this call.  Every flagged scene performs exactly ONE read() with its chunk as what the port
+ * delivered (an empty chunk is still a read): append if byteBufferLength + count < 2^15, cut to the LAST magic word, decode
+ * one complete packet -- objects are read wherever they lie in the 2^15 bytes, past byteBufferLength they are the buffer's
+ * stale bytes --, drop totalPacketLen bytes.  On dataOK the rows are normalised with the scene's mounting (its site while
+ * mmw_set_sites is in use): pts[S][max_pts][8] / n_out[S] (dev) as mmw_normalize_tlv writes them, bit-equal to it on the same
+ * body.  dt_out[S] (dev): on MMW_UART_POINTS now - t_last (one fp64 subtraction, main.py:45-47), and t_last = now; otherwise 0
+ * and t_last stays.  n_out = 0 makes mmw_step skip the scene (main.py:44,52).  frame_number[S] (dev): the header's, 0 without
+ * a complete packet.  status[S] (dev), low byte:
+ *   MMW_UART_NONE / MMW_UART_POINTS / MMW_UART_PACKET  as mmw_parse_uart_cap
+ *   MMW_UART_OVERFLOW  more than max_pts objects announced, which the reference decodes: the buffer is handled exactly as the
+ *                      reference handles the decoded packet, the drop included; n_out = MMW_BAD_FRAME.  The ONE declared
+ *                      difference of this path (radar.UartFrameParser differs from it: it raises and leaves the packet in place)
+ *   MMW_UART_RAISED    the announced objects reach past byte 2^15 (mmw_parse_uart_cap: MMW_E_CAPACITY), where the reference
+ *                      raises ValueError; takes precedence over OVERFLOW.  The state is as the exception leaves it: cut done,
+ *                      nothing dropped.  n_out = 0, frame_number = 0
+ *   MMW_UART_SKIPPED   the scene was not flagged: nothing of it is touched.  n_out = 0
+ *   MMW_UART_BADCHUNK  chunk_off[s] < 0, chunk_off[s + 1] < chunk_off[s] or chunk_off[s + 1] > chunks_bytes (compared without
+ *                      adding to an offset): no read() happens, the state is untouched, the other scenes are unaffected.  n_out = 0
+ * bit 8, MMW_UART_CHUNK_DROPPED: the chunk did not fit (byteBufferLength + count >= 2^15) and was discarded, as there.
+ * mmw_uart_get_state / mmw_uart_set_state (sync): one scene's whole byteBuffer (all 2^15 bytes), byteBufferLength
+ * (0 .. 2^15 - 1) and t_last -- for tests, and to move a scene between contexts.  mmw_uart_set_time (sync): t_last = t for the
+ * scenes flagged in scene_flags[S] (HOST; NULL = every scene), e.g. after mmw_reset_scenes.
+ * The readers are no part of a scene's tracker state (the reference keeps them in another object): mmw_reset*, mmw_restore
+ * and mmw_clear_sites leave them alone, snapshots do not hold them.  MMW_E_ARG (nothing touched) before mmw_uart_open or for
+ * a NULL argument other than scene_flags. */
+#define MMW_UART_OVERFLOW 3
+#define MMW_UART_RAISED 4
+#define MMW_UART_SKIPPED 5
+#define MMW_UART_BADCHUNK 6
+#define MMW_UART_CHUNK_DROPPED 256
+#define MMW_UART_BUFFER 32768
+int mmw_uart_open(mmw_ctx *ctx, const mmw_uart_cfg *cfg, int32_t n_cfg, double t0);
+int mmw_uart_close(mmw_ctx *ctx);
+int mmw_uart_read(mmw_ctx *ctx, const uint8_t *chunks, const int64_t *chunk_off, size_t chunks_bytes, const int32_t *scene_flags, double now,
+                  double *pts, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number);
+int mmw_uart_get_state(mmw_ctx *ctx, int32_t scene, uint8_t *buf /*[MMW_UART_BUFFER]*/, int32_t *len, double *t_last);
+int mmw_uart_set_state(mmw_ctx *ctx, int32_t scene, const uint8_t *buf /*[MMW_UART_BUFFER]*/, int32_t len, double t_last);
+int mmw_uart_set_time(mmw_ctx *ctx, const int32_t *scene_flags, double t);
+
 /* Work counters accumulated by the kernels since the last reset (sync):
  * [0] k_track algorithmic bytes  [1] k_dbscan algorithmic bytes  [2] scene-frames stepped
  * [3] apply_DBscan calls  [4] sum of U over those calls  [5] sum of tracks entering track()

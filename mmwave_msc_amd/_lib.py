@@ -27,6 +27,9 @@ K_TRACK, K_DBSCAN, K_FEATURES, K_NORMALIZE, K_TABLE, K_PREDICT, K_POST = range(7
 EMPTY_FRAME = -1   # MMW_EMPTY_FRAME (include/mmw.h)
 BAD_FRAME = -3     # MMW_BAD_FRAME: n_out of mmw_normalize_tlv for a TLV body it refused to decode
 UART_NONE, UART_POINTS, UART_PACKET = 0, 1, 2   # MMW_UART_*: what mmw_parse_uart_cap found
+UART_OVERFLOW, UART_RAISED, UART_SKIPPED, UART_BADCHUNK = 3, 4, 5, 6   # ... and the other outcomes of mmw_uart_read (status, low byte)
+UART_CHUNK_DROPPED = 256                        # MMW_UART_CHUNK_DROPPED: bit 8 of that status
+UART_BUFFER = 32768                             # MMW_UART_BUFFER: the reference's maxBufferSize
 
 EXPORTS = [
     "mmw_config_default", "mmw_create", "mmw_destroy", "mmw_last_error", "mmw_reset", "mmw_pop_frame", "mmw_set_stream",
@@ -43,6 +46,7 @@ EXPORTS = [
     "mmw_set_sites", "mmw_get_sites", "mmw_clear_sites", "mmw_has_sites",
     "mmw_posture_attach", "mmw_estimate_posture", "mmw_posture_range", "mmw_mars_dense2", "mmw_mars_split_weights",
     "mmw_report_enable", "mmw_report_async", "mmw_report_wait", "mmw_report",
+    "mmw_uart_open", "mmw_uart_close", "mmw_uart_read", "mmw_uart_get_state", "mmw_uart_set_state", "mmw_uart_set_time",
 ]
 
 
@@ -351,6 +355,12 @@ def load():
         "mmw_report_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
         "mmw_report_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_report": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
+        "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
+        "mmw_uart_close": (C.c_int, [vp]),
+        "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),
+        "mmw_uart_get_state": (C.c_int, [vp, i32, vp, i32p, f64p]),
+        "mmw_uart_set_state": (C.c_int, [vp, i32, vp, i32, C.c_double]),
+        "mmw_uart_set_time": (C.c_int, [vp, vp, C.c_double]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

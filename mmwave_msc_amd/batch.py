@@ -7,6 +7,7 @@ single-scene, reference-shaped face built on top of it.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -45,6 +46,16 @@ class DevBuf:
             self.free()
         except Exception:
             pass
+
+
+class RadarRead(NamedTuple):
+    """What `SceneBatch.read_radars` leaves on the device: pts[S][max_pts][8] fp64, n[S] int32, dt[S] fp64 -- `step_dev`'s input --,
+    status[S] int32 (`_lib.UART_*`, bit 8 = `_lib.UART_CHUNK_DROPPED`) and frame_number[S] uint32."""
+    pts: DevBuf
+    n: DevBuf
+    dt: DevBuf
+    status: DevBuf
+    frame_number: DevBuf
 
 
 class SceneBatch:
@@ -247,8 +258,8 @@ class SceneBatch:
 
     # -- hot path -------------------------------------------------------------
     def step_dev(self, pts_ptr, n_ptr, dt_ptr, assoc_ptr=None, labels_ptr=None, dbn_ptr=None):
-        """TrackBuffer.track for all scenes; every argument is a device pointer (int)."""
-        self._chk(self.L.mmw_step(self.h, pts_ptr, n_ptr, dt_ptr, assoc_ptr, labels_ptr, dbn_ptr))
+        """TrackBuffer.track for all scenes; every argument is a device pointer (int) or a `DevBuf` (what `read_radars` returns)."""
+        self._chk(self.L.mmw_step(self.h, *[getattr(a, "ptr", a) for a in (pts_ptr, n_ptr, dt_ptr, assoc_ptr, labels_ptr, dbn_ptr)]))
 
     def step_dev_f32(self, pts_ptr, n_ptr, dt_ptr, assoc_ptr=None, labels_ptr=None, dbn_ptr=None):
         """mmw_step_f32: the same with the frame's rows as fp32 ([S][max_pts][8] float, device pointer), promoted exactly."""
@@ -266,6 +277,99 @@ class SceneBatch:
         -> pts[S][max_pts][8] fp64, n_out[S] (device).  Nothing outside packets[0 .. packets_bytes) is read; a body that does not
         fit, or announces more than max_pts objects, gives n_out = _lib.BAD_FRAME (the next step raises the scene's bad count)."""
         self._chk(self.L.mmw_normalize_tlv(self.h, packets_ptr, int(packets_bytes), tlv_offset_ptr, C.byref(uart_cfg), pts_ptr, n_out_ptr))
+
+    # -- device-resident radar readers ------------------------------------------
+    def open_radars(self, config_parameters, t0: float = None):
+        """mmw_uart_open: one `ReadIWR14xx` per scene on the device -- a zeroed 2^15-byte byteBuffer, byteBufferLength 0 -- from the
+        reference's `configParameters` dict (one for every scene, or a list of S), with main.py's `t` = t0 (default: now)."""
+        import time
+        from .radar import uart_cfg
+        lst = [config_parameters] if isinstance(config_parameters, dict) else list(config_parameters)
+        if len(lst) not in (1, self.S):
+            raise ValueError(f"open_radars: {len(lst)} configParameters for {self.S} scenes (one, or one per scene)")
+        arr = (_lib.MmwUartCfg * len(lst))(*[uart_cfg(p) for p in lst])
+        self._chk(self.L.mmw_uart_open(self.h, arr, len(lst), float(time.time() if t0 is None else t0)))
+
+    def close_radars(self):
+        self._chk(self.L.mmw_uart_close(self.h))
+
+    def read_radars_dev(self, chunks_ptr, chunk_off_ptr, chunks_bytes, now, pts_ptr, n_out_ptr, dt_ptr, status_ptr, frame_ptr, flags_ptr=None):
+        """mmw_uart_read, the pointer form: ReadIWR14xx.read + Utils.normalize_data for every flagged scene in one kernel.  chunks
+        (device bytes, 4-byte aligned), chunk_off[S + 1] (device int64), flags[S] (device int32 or None = every scene) ->
+        pts[S][max_pts][8] fp64, n_out[S], dt[S] fp64, status[S] (`_lib.UART_*`), frame_number[S] uint32, all on the device and
+        ready for `step_dev`.  Asynchronous; nothing is read back."""
+        self._chk(self.L.mmw_uart_read(self.h, chunks_ptr, chunk_off_ptr, int(chunks_bytes), flags_ptr, float(now), pts_ptr, n_out_ptr, dt_ptr,
+                                       status_ptr, frame_ptr))
+
+    def _radar_staging(self, nbytes: int) -> np.ndarray:
+        """A host block of at least nbytes for read_radars' one upload: pinned when torch can provide it, pageable otherwise."""
+        st = getattr(self, "_radar_host", None)
+        if st is None or st.nbytes < nbytes:
+            size = max(2 * nbytes, 1 << 16)
+            try:
+                import torch
+                self._radar_pin = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+                st = self._radar_pin.numpy()
+            except Exception:
+                st = np.empty(size, dtype=np.uint8)
+            self._radar_host = st
+        return st
+
+    def read_radars(self, chunks, now: float, scenes=None):
+        """One `read()` per scene with `chunks[s]` (bytes-like; b"" is still a read) as what its port delivered at time `now`:
+        offsets, flags and bytes are packed into one host block and uploaded with ONE copy, then `read_radars_dev`.  `scenes`:
+        the scenes that read (default all; `chunks` still has S entries).  Returns `RadarRead(pts, n, dt, status, frame_number)`
+        of `DevBuf`s owned by this object and rewritten by the next call; `step_dev(r.pts, r.n, r.dt)` takes them as they are, and
+        nobody has to download `status` / `frame_number`."""
+        S = self.S
+        if len(chunks) != S:
+            raise ValueError(f"read_radars: {len(chunks)} chunks for {S} scenes")
+        views = [np.frombuffer(c, dtype=np.uint8) for c in chunks]
+        off = np.zeros(S + 1, dtype=np.int64)
+        np.cumsum([len(v) for v in views], out=off[1:])
+        total = int(off[S])
+        head = ((S + 1) * 8 + S * 4 + 15) // 16 * 16          # [S + 1] int64 offsets | [S] int32 flags | pad | the bytes
+        nbytes = head + (total + 15) // 16 * 16 + 16
+        host = self._radar_staging(nbytes)
+        host[: (S + 1) * 8].view(np.int64)[:] = off
+        flags = host[(S + 1) * 8: (S + 1) * 8 + S * 4].view(np.int32)
+        if scenes is None:
+            flags[:] = 1
+        else:
+            flags[:] = 0
+            flags[np.asarray(scenes, dtype=np.int64)] = 1
+        for s, v in enumerate(views):
+            host[head + off[s]: head + off[s + 1]] = v
+        b_in = self.buf("radar_in", nbytes)
+        self._chk(self.L.mmw_memcpy_h2d(self.h, b_in.ptr, host.ctypes.data, head + total))
+        r = RadarRead(self.buf("radar_pts", S * self.max_pts * 64), self.buf("radar_n", S * 4), self.buf("radar_dt", S * 8),
+                      self.buf("radar_status", S * 4), self.buf("radar_frame", S * 4))
+        self.read_radars_dev(b_in.ptr + head, b_in.ptr, total, now, r.pts.ptr, r.n.ptr, r.dt.ptr, r.status.ptr, r.frame_number.ptr,
+                             b_in.ptr + (S + 1) * 8)
+        return r
+
+    def radar_state(self, scene: int):
+        """mmw_uart_get_state: (byteBuffer -- all 2^15 bytes, stale ones included --, byteBufferLength, t_last) of one scene."""
+        buf = np.zeros(_lib.UART_BUFFER, dtype=np.uint8)
+        n, t = C.c_int32(0), C.c_double(0.0)
+        self._chk(self.L.mmw_uart_get_state(self.h, int(scene), buf.ctypes.data, C.byref(n), C.byref(t)))
+        return buf, int(n.value), float(t.value)
+
+    def set_radar_state(self, scene: int, buf, length: int, t_last: float):
+        """mmw_uart_set_state: the other direction (a scene moved in from another context; tests)."""
+        a = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf, dtype=np.uint8)
+        if a.shape != (_lib.UART_BUFFER,):
+            raise ValueError(f"set_radar_state: the buffer has {_lib.UART_BUFFER} bytes, not {a.shape}")
+        self._chk(self.L.mmw_uart_set_state(self.h, int(scene), a.ctypes.data, int(length), float(t_last)))
+
+    def set_radar_time(self, t: float, scenes=None):
+        """mmw_uart_set_time: main.py's `t` restarts at `t` for the given scenes (default all), e.g. after `reset_scenes`."""
+        if scenes is None:
+            self._chk(self.L.mmw_uart_set_time(self.h, None, float(t)))
+            return
+        flags = np.zeros(self.S, dtype=np.int32)
+        flags[np.asarray(scenes, dtype=np.int64)] = 1
+        self._chk(self.L.mmw_uart_set_time(self.h, flags.ctypes.data, float(t)))
 
     def step_host(self, pts: np.ndarray, n: np.ndarray, dt: np.ndarray, raise_nonfinite: bool = True, check: bool = True):
         """Host convenience (H2D + step + D2H).  Returns (assoc[S,NP], labels[S,UM], db_n[S]).  raise_nonfinite=False: a scene

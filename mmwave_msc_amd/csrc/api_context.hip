@@ -393,7 +393,7 @@ int mmw_destroy(mmw_ctx *c)
     prof_fold(c);
     for (auto &ep : c->pool) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
     void *ptrs[] = {c->st.hdr, c->st.order, c->st.trk, c->st.trk_ring, c->st.g_ring, c->d_posture, c->d_row_off, c->st.stats, c->st.db_list, c->st.db_count, c->st.q, c->d_probe, c->st.gate_buf, c->st.perm, c->st.upd_count, c->st.upd_list, c->st.spc_count, c->st.spc_list, c->st.inner_buf, c->d_in, c->d_out, c->d_raw, c->d_pchain,
-                    c->d_export, c->st.huge_scratch, c->d_snap, c->d_sites};
+                    c->d_export, c->st.huge_scratch, c->d_snap, c->d_sites, c->uart.buf};
     for (void *p : ptrs) if (p) hipFree(p);
     void *pinned[] = {c->h_in, c->h_out, c->h_hdr, c->h_q};
     for (void *p : pinned) if (p) hipHostFree(p);

@@ -1,7 +1,8 @@
-// api_uart.hip -- the C-ABI (include/mmw.h): the radar's UART packets, decoded on the host (no context, no HIP call).
+// api_uart.hip -- the C-ABI (include/mmw.h): the radar's UART packets -- decoded on the host (mmw_parse_uart*, mmw_find_tlv: no
+// context, no HIP call), and the device-resident readers (mmw_uart_*: their state, and the launch of k_uart.hip).
 #include <cstring>
 
-#include "mmw_device.hpp"
+#include "mmw_ctx.hpp"
 
 // The packet part of ReadIWR14xx.read (ReadDataIWR1443.py:47-113), shared by mmw_parse_uart and mmw_find_tlv: the LAST magic word
 // that starts in buf[0 .. len-8), more than 16 bytes from there and at least totalPacketLen of them -- whatever totalPacketLen
@@ -99,4 +100,100 @@ int mmw_find_tlv(const uint8_t *buf, size_t len, int64_t *body_offset, int32_t *
     *body_offset = (int64_t)body;
     *n_obj = (int32_t)num;
     return 1;
+}
+
+// ---- the device-resident readers ----
+static_assert((MMW_UART_BUFFER - 48) / 12 == 2726, "the rule behind MMW_E_CAPACITY above, with the packet at the head of the buffer (k_uart.hip)");
+
+int mmw_uart_close(mmw_ctx *c)
+{
+    if (!c) return MMW_E_ARG;
+    if (!c->uart.buf) return MMW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (a read may still be queued on what is freed here)
+    HIPCHK(c, hipFree(c->uart.buf));
+    c->uart = UartState{};
+    return MMW_OK;
+}
+
+int mmw_uart_open(mmw_ctx *c, const mmw_uart_cfg *cfg, int32_t n_cfg, double t0)
+{
+    if (!c || !cfg) return fail(c, MMW_E_ARG, "mmw_uart_open: null argument");
+    const size_t S = c->dc.n_scenes;
+    if (n_cfg != 1 && (size_t)n_cfg != S) return fail(c, MMW_E_ARG, "mmw_uart_open: n_cfg=%d must be 1 or n_scenes=%zu", n_cfg, S);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->uart.buf) {
+        uint8_t *p = nullptr;
+        HIPCHK(c, hipMalloc((void **)&p, S * (MMW_UART_BUFFER + sizeof(UartScene))));
+        c->uart.buf = p;
+        c->uart.scene = reinterpret_cast<UartScene *>(p + S * MMW_UART_BUFFER);
+    }
+    std::vector<UartScene> h(S);
+    for (size_t s = 0; s < S; s++) {
+        const mmw_uart_cfg &u = cfg[n_cfg == 1 ? 0 : s];
+        h[s] = UartScene{t0, u.num_doppler_bins / 2.0 - 1, u.doppler_resolution_mps, 0, 0};
+    }
+    HIPCHK(c, hipMemsetAsync(c->uart.buf, 0, S * MMW_UART_BUFFER, c->stream));   // np.zeros(2**15) (ReadDataIWR1443.py:15)
+    HIPCHK(c, hipMemcpyAsync(c->uart.scene, h.data(), S * sizeof(UartScene), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (h goes out of scope)
+    return MMW_OK;
+}
+
+int mmw_uart_read(mmw_ctx *c, const uint8_t *chunks, const int64_t *chunk_off, size_t chunks_bytes, const int32_t *scene_flags, double now,
+                  double *pts, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number)
+{
+    if (!c || !chunks || !chunk_off || !pts || !n_out || !dt_out || !status || !frame_number) return fail(c, MMW_E_ARG, "mmw_uart_read: null pointer");
+    if (!c->uart.buf) return fail(c, MMW_E_ARG, "mmw_uart_read: the readers are not open (mmw_uart_open)");
+    if (((uintptr_t)pts & 15) != 0 || ((uintptr_t)chunks & 3) != 0) return fail(c, MMW_E_ARG, "mmw_uart_read: pts must be 16-byte aligned, chunks 4-byte aligned");
+    if (chunks_bytes > (size_t)INT64_MAX) return fail(c, MMW_E_ARG, "mmw_uart_read: chunks_bytes out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    static_assert(sizeof(long long) == sizeof(int64_t), "chunk offsets");
+    launch_uart_read(c->dc, sites_or_null(c), c->uart, chunks, reinterpret_cast<const long long *>(chunk_off), (long long)chunks_bytes, scene_flags, now, pts,
+                     n_out, dt_out, status, frame_number, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MMW_OK;
+}
+
+int mmw_uart_get_state(mmw_ctx *c, int32_t scene, uint8_t *buf, int32_t *len, double *t_last)
+{
+    if (!c || !buf || !len || !t_last) return fail(c, MMW_E_ARG, "mmw_uart_get_state: null argument");
+    if (!c->uart.buf) return fail(c, MMW_E_ARG, "mmw_uart_get_state: the readers are not open (mmw_uart_open)");
+    if (scene < 0 || scene >= c->dc.n_scenes) return fail(c, MMW_E_ARG, "mmw_uart_get_state: scene %d out of range", scene);
+    HIPCHK(c, hipSetDevice(c->device));
+    UartScene h;
+    MMW_TRY(d2h_after_kernels(c, buf, c->uart.buf + (size_t)scene * MMW_UART_BUFFER, MMW_UART_BUFFER));
+    MMW_TRY(d2h_after_kernels(c, &h, c->uart.scene + scene, sizeof(h)));
+    *len = h.len;
+    *t_last = h.t_last;
+    return MMW_OK;
+}
+
+int mmw_uart_set_state(mmw_ctx *c, int32_t scene, const uint8_t *buf, int32_t len, double t_last)
+{
+    if (!c || !buf) return fail(c, MMW_E_ARG, "mmw_uart_set_state: null argument");
+    if (!c->uart.buf) return fail(c, MMW_E_ARG, "mmw_uart_set_state: the readers are not open (mmw_uart_open)");
+    if (scene < 0 || scene >= c->dc.n_scenes) return fail(c, MMW_E_ARG, "mmw_uart_set_state: scene %d out of range", scene);
+    if (len < 0 || len >= MMW_UART_BUFFER) return fail(c, MMW_E_ARG, "mmw_uart_set_state: len=%d must be in [0, %d)", len, MMW_UART_BUFFER);
+    HIPCHK(c, hipSetDevice(c->device));
+    UartScene h;
+    MMW_TRY(d2h_after_kernels(c, &h, c->uart.scene + scene, sizeof(h)));   // (the scene keeps its scales)
+    h.t_last = t_last;
+    h.len = len;
+    HIPCHK(c, hipMemcpyAsync(c->uart.buf + (size_t)scene * MMW_UART_BUFFER, buf, MMW_UART_BUFFER, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->uart.scene + scene, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMW_OK;
+}
+
+int mmw_uart_set_time(mmw_ctx *c, const int32_t *scene_flags, double t)
+{
+    if (!c) return MMW_E_ARG;
+    if (!c->uart.buf) return fail(c, MMW_E_ARG, "mmw_uart_set_time: the readers are not open (mmw_uart_open)");
+    HIPCHK(c, hipSetDevice(c->device));
+    // (the flags travel through the context's [S + 1]-word scratch, as those of mmw_reset_scenes do)
+    if (scene_flags) HIPCHK(c, hipMemcpyAsync(c->d_row_off, scene_flags, sizeof(int32_t) * c->dc.n_scenes, hipMemcpyHostToDevice, c->stream));
+    launch_uart_set_time(c->dc, c->uart, scene_flags ? c->d_row_off : nullptr, t, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMW_OK;
 }

@@ -89,6 +89,7 @@ struct mmw_ctx {
     int32_t *pc_owner = nullptr;
     PostureBatch *pb = nullptr;       // mmw_posture_attach (any number of scenes); independent of the one-scene chain above
     ReportCtx *rep = nullptr;         // mmw_report_enable; nullptr = reports are off and nothing of them is launched
+    UartState uart = {};              // mmw_uart_open: the radar readers' state (uart.buf is the allocation, uart.scene lies behind the buffers); nullptr = closed
     // profiling
     unsigned prof_mask = 0;           // bit k: time kernel id k (mmw_profile_enable)
     std::vector<EventPair> pending;

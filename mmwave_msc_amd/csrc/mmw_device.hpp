@@ -100,6 +100,23 @@ __host__ __device__ inline int nf_error_of(int bits) { return (bits & 1) ? ERR_N
 // (ReadDataIWR1443.py:118), which wraps -- 2^q for q <= 62, -2^63 for q = 63, 0 for q >= 64 (then x / 0 = +-inf, 0 / 0 = NaN).
 __host__ __device__ inline double xyz_q_divisor(unsigned q) { return q <= 62 ? (double)(1ull << q) : (q == 63 ? -9223372036854775808.0 : 0.0); }
 
+// The device-resident radar readers (mmw_uart_open; k_uart.hip): per scene what a ReadIWR14xx object keeps between two read()
+// calls -- byteBufferLength, and the 2^15-byte byteBuffer itself in UartState::buf -- with main.py's `t` (the time of the last
+// read that gave points) and the two scales of the scene's configParameters the decode needs.
+constexpr int kUartBuf = MMW_UART_BUFFER;
+struct UartScene {
+    double t_last;
+    double half_bins;      // numDopplerBins / 2 - 1
+    double doppler_res;    // dopplerResolutionMps
+    int32_t len;           // byteBufferLength
+    int32_t reserved;
+};
+static_assert(sizeof(UartScene) == 32, "UartScene");
+struct UartState {
+    uint8_t *buf;          // [S][kUartBuf], 16-byte aligned
+    UartScene *scene;      // [S]
+};
+
 // One ClusterTrack.  187 doubles = 1496 B.
 struct TrackRec {
     double x[9];

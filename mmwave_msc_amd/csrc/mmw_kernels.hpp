@@ -11,6 +11,7 @@ namespace mmw {
 struct DevCfg;     // mmw_device.hpp (the CNN's kernel files do without it)
 struct DevState;
 struct ReportState;
+struct UartState;
 // k_track.hip, k_kalman.hip, k_scene.hip: the step
 size_t track_lds_bytes(const DevCfg &c);
 hipError_t prepare_track(const DevCfg &cfg);
@@ -55,6 +56,9 @@ void launch_set_batch_size(const DevCfg &cfg, const DevState &s, const int32_t *
 void launch_report_baseline(const DevCfg &cfg, const DevState &s, const ReportState &rp, hipStream_t st);
 void launch_report_rebase(const DevCfg &cfg, const ReportState &rp, const int32_t *flags, hipStream_t st);
 void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ReportState &rp, mmw_track_report *rows, int cap_rows, mmw_track_event *events, int cap_events, int scene_base, hipStream_t st);
+// k_uart.hip: the device-resident radar readers
+void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
+void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);
 // k_mars.hip, k_dense.hip, k_dense2.hip: the posture CNN
 void launch_mars_conv(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
 void launch_range_gather(const float *feat, int32_t *list, int n, int per, int cap, float *small, int32_t *range_flag, hipStream_t stream);

@@ -11,6 +11,9 @@ Parity: pinned by a recording of the reference's own read() under numpy 1.26 (te
 oracle/gen_uart_golden.py) -- short and odd totalPacketLen values, objects read from the stale bytes of the 2^15-byte
 buffer, the int64 wrap of `2 ** xyzQFormat` included.  One declared difference: more than `max_obj` objects raise
 `_lib.MmwError` (MMW_E_ARG) where the reference decodes them.
+
+Many radars in one context: `SceneBatch.open_radars / read_radars` keep this same buffer discipline per scene on the device
+(mmw_uart_read, csrc/k_uart.hip) -- there a packet over `max_pts` objects is dropped as the reference drops a decoded one.
 """
 from __future__ import annotations
 
