@@ -25,43 +25,18 @@
 #include "mmw_math.hpp"
 #include "mmw_cloud.hpp"
 #include "mmw_kalman.hpp"
+#ifndef MMW_PROBE_BLOCK
+#define MMW_PROBE_BLOCK 7   // (diagnostic build: the workgroup whose waves PROBE stamps; AHEAD of mmw_assoc.hpp, whose default is k_track's)
+#endif
+#include "mmw_assoc.hpp"
 #include "mmw_launch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
 
-// Diagnostic build only (make STAMPS=1): raw clock of lane 0 of every wave of ONE workgroup (block kProbeBlock), and the
-// start / end of every workgroup -- scripts/probe_timeline.py, scripts/wg_times.py.  Never compiled into the product library.
-#ifdef MMW_STAMPS
-#ifndef MMW_PROBE_BLOCK
-#define MMW_PROBE_BLOCK 7
-#endif
-#define PROBE(id)                                                                             \
-    do {                                                                                      \
-        if (blockIdx.x == MMW_PROBE_BLOCK && (threadIdx.x & 63) == 0)                         \
-            st.stats[kStatSlots * kStatWords + (threadIdx.x >> 6) * 64 + (id)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#define WGTIME(k)                                                                             \
-    do {                                                                                      \
-        if (threadIdx.x == 0 && blockIdx.x < 2048) {                                          \
-            st.stats[kStatSlots * kStatWords + 256 + blockIdx.x * 4 + (k) * 2] = __builtin_amdgcn_s_memrealtime(); \
-            st.stats[kStatSlots * kStatWords + 256 + blockIdx.x * 4 + (k) * 2 + 1] = __builtin_amdgcn_s_memtime(); \
-        }                                                                                     \
-    } while (0)
-#else
-#define PROBE(id)
-#define WGTIME(k)
-#endif
-
 namespace scene {
 
 constexpr int kRes = 16;       // tracks whose record prefix lives in LDS for the whole step
-constexpr int kTilePad = 2;    // columns of the point tile are NP + 2 doubles apart (k_track.hip)
-constexpr int kTrackBytesPerTrack = 352 + 392 + 540;  // as k_track counts them (bench.py prices the Kalman stages itself)
-
-__host__ __device__ inline int split8(int n) { const int h = n / 2; return h - h % 8; }
-__host__ __device__ inline int max_leaves(int np) { return np > 128 ? np / 57 + 1 : 0; }
-__host__ __device__ inline size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 struct Lds {
     double *rec;         // [kRes][kRecStage] record prefix of tracks 0..kRes-1, by effective_tracks position at the start of the frame
@@ -91,11 +66,11 @@ __host__ __device__ __forceinline__ size_t lds_layout(const DevCfg &c, char *bas
     size_t off = 0;
 #define CARVE(field, type, count)                            \
     if constexpr (WRITE) L->field = (type *)(base + off);    \
-    off = al16(off + sizeof(type) * (size_t)(count));
+    off = align16(off + sizeof(type) * (size_t)(count));
     CARVE(rec, double, kRes *kRecStage)
     CARVE(tmp, double, 4 * kRecStage)
     {
-        const size_t tile = (size_t)6 * (NP + kTilePad) + (size_t)max_leaves(NP) * 21;
+        const size_t tile = (size_t)6 * (NP + kTilePad) + (size_t)pw_max_leaves(NP) * 21;
         const size_t kal = (size_t)16 * (kUpdW > kPredW ? kUpdW : kPredW);
         const size_t scr = (4096 + kCloudGrid * 4 + 64) / 8;
         size_t w = tile > kal ? tile : kal;
@@ -111,7 +86,7 @@ __host__ __device__ __forceinline__ size_t lds_layout(const DevCfg &c, char *bas
     CARVE(cnt, unsigned short, NB *CLS)
     CARVE(cls_n, int, CLS)
     CARVE(cls_off, int, CLS + 1)
-    CARVE(ml, int, 2 + 5 * (max_leaves(NP) + 1))
+    CARVE(ml, int, ml_words(NP))
     CARVE(slot, int, c.t_cap)
     CARVE(slot2, int, c.t_cap)
     CARVE(stat, int, c.t_cap)
@@ -119,59 +94,6 @@ __host__ __device__ __forceinline__ size_t lds_layout(const DevCfg &c, char *bas
     CARVE(misc, int, 16)
 #undef CARVE
     return off;
-}
-
-// numpy pairwise_sum_DOUBLE (the 1-D np.mean of ClusterTrack._get_D, Tracking.py:286) -- see k_track.hip for the order.
-template <int D, typename F>
-__device__ __forceinline__ void for_each_leaf(int off, int n, F f)
-{
-    if constexpr (D == 0) f(off, n);
-    else {
-        if (n <= 128) f(off, n);
-        else { const int n2 = split8(n); for_each_leaf<D - 1>(off, n2, f); for_each_leaf<D - 1>(off + n2, n - n2, f); }
-    }
-}
-template <int D>
-__device__ __forceinline__ double combine_leaves(int n, const double *leafsum, int stride, int &idx)
-{
-    if constexpr (D == 0) { const double v = leafsum[idx * stride]; idx++; return v; }
-    else {
-        if (n <= 128) { const double v = leafsum[idx * stride]; idx++; return v; }
-        const int n2 = split8(n);
-        const double l = combine_leaves<D - 1>(n2, leafsum, stride, idx);
-        const double r = combine_leaves<D - 1>(n - n2, leafsum, stride, idx);
-        return l + r;
-    }
-}
-constexpr int kPwDepth = 4;
-
-// one leaf (n <= 128) of sum_r (pa[r]-ca)*(pb[r]-cb): numpy's eight interleaved accumulators, then the n%8 leftovers
-__device__ __forceinline__ double pw_leaf(const double *pa, const double *pb, double ca, double cb, int n)
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; i++) res += (pa[i] - ca) * (pb[i] - cb);
-        return res;
-    }
-    const int lim = n - (n & 7);
-    double r[8], xa[8], xb[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) { xa[u] = pa[u]; xb[u] = pb[u]; }
-#pragma unroll
-    for (int u = 0; u < 8; u++) r[u] = (xa[u] - ca) * (xb[u] - cb);
-    for (int i = 8; i < lim; i += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) { xa[u] = pa[i + u]; xb[u] = pb[i + u]; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) r[u] += (xa[u] - ca) * (xb[u] - cb);
-    }
-    const int left = n - lim;  // the n%8 leftovers, loaded together, added one by one
-#pragma unroll
-    for (int u = 0; u < 7; u++) { xa[u] = (u < left) ? pa[lim + u] : 0.0; xb[u] = (u < left) ? pb[lim + u] : 0.0; }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-#pragma unroll
-    for (int u = 0; u < 7; u++) if (u < left) res += (xa[u] - ca) * (xb[u] - cb);
-    return res;
 }
 
 // a word of track j's record prefix: from the LDS copy (j < kRes) or from global memory
@@ -272,11 +194,7 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
     if (s == 0 && tid < kUpdWords) st.upd_count[(parity ^ 1) * kUpdWords + tid] = 0;
     if (s == 0 && tid == NT - 1) st.spc_count[parity ^ 1] = 0;
     if (!frame_reaches_track(n_raw, NP)) {  // offline_main.py:56: empty frames never reach track()
-        if (tid == 0) {
-            hdr->need_db = 0;
-            hdr->skipped = (hv.skipped & ~255) | 1;   // (the ring's non-finite flags stay)
-            if (n_raw != 0) atomicOr(&hdr->err, ERR_BADCOUNT);
-        }
+        if (tid == 0) frame_skipped(hdr, hv.skipped, n_raw);
         return;
     }
     int T = hv.n_tracks;
@@ -333,25 +251,16 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
     }
 
     PROBE(3);
-    // ---- gate every point against the scene's tracks (Tracking.py:553-572): see k_track.hip ----
+    // ---- gate every point against the scene's tracks (Tracking.py:553-572): the records through the scalar cache, the distance and
+    //      the first-best rule in mmw_assoc.hpp ----
     double bestd[PPT];
     int bestj[PPT];
 #pragma unroll
     for (int q = 0; q < PPT; q++) { bestd[q] = 0.0; bestj[q] = -1; }
     {
-        // One track's record (C^-1, log det, predicted position: 43 doubles) is the same for every point: read through the
-        // scalar cache (constant address space, uniform address -> s_load) it enters the fp64 VALU ops as their SGPR operand.
-        // y' C^-1 y as k-ordered FUSED chains, the arithmetic definition the oracle shares (k_track.hip).
-#ifdef MMW_DIAG_VGATE   // (diagnostic build, scripts/dual_run.py: the records by VECTOR loads -- volatile global -- instead of through the scalar cache)
-        typedef const volatile double *gate_ptr;
-#else
-        typedef const double __attribute__((address_space(4))) *gate_ptr;
-#endif
         const int su = __builtin_amdgcn_readfirstlane(s), Tu = __builtin_amdgcn_readfirstlane(T);
         gate_ptr gb = (gate_ptr)(st.gate_buf + (size_t)su * cfg.t_cap * kGateRec);
-        // (the constant address space promises the compiler memory that does not change: the pointer is made opaque HERE,
-        //  behind the invalidate, so that no load through it can be moved above this statement)
-        asm volatile("; mmw: gate pointer opaque from here" : "+s"(gb) : : "memory");
+        gb = gate_records_opaque(gb);   // (HERE, behind the invalidate: no load through it can be moved above this statement)
 #ifndef MMW_DIAG_VGATE
         {   // warm the scalar cache: one dword of every 64-byte line of the records, all requests in flight together
             typedef const int __attribute__((address_space(4))) *line_ptr;
@@ -376,31 +285,8 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
             for (int q = 0; q < PPT; q++) {
                 const int i = q * NT + tid;
                 if (q * NT < n) {  // wave-uniform
-                    const double y0 = pr[q][0].x - G[37], y1 = pr[q][0].y - G[38], y2 = pr[q][1].x - G[39], y3 = pr[q][1].y - G[40],
-                                 y4 = pr[q][2].x - G[41], y5 = pr[q][2].y - G[42];
-                    double v[6];
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = y0 * G[k];
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y1, G[6 + k], v[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y2, G[12 + k], v[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y3, G[18 + k], v[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y4, G[24 + k], v[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y5, G[30 + k], v[k]);
-                    double quad = v[0] * y0;
-                    quad = __builtin_fma(v[1], y1, quad);
-                    quad = __builtin_fma(v[2], y2, quad);
-                    quad = __builtin_fma(v[3], y3, quad);
-                    quad = __builtin_fma(v[4], y4, quad);
-                    quad = __builtin_fma(v[5], y5, quad);
-                    const double d = G[36] + quad;
-                    if (i < n && d < cfg.tr_gate) {
-                        if (bestj[q] < 0 || d < bestd[q]) { bestj[q] = j; bestd[q] = d; }
-                    }
+                    const double d = gate_distance(G, pr[q][0].x, pr[q][0].y, pr[q][1].x, pr[q][1].y, pr[q][2].x, pr[q][2].y);
+                    gate_first_best(cfg, i < n, d, j, bestj[q], bestd[q]);
                 }
             }
         }
@@ -678,31 +564,22 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
         rec_st(L, rec, j, rCen + m, cen);
         rec->minv[m] = mn;
         rec->maxv[m] = mx;
-        // _estimate_measurement_spread Tracking.py:246-268
-        double spread = mx - mn;
-        const double lim = cfg.kf_spread_lim[m], lim2 = 2 * lim;
-        if (nj != 1) spread = spread * (double)(nj + 1) / (double)(nj - 1);
-        spread = spread < lim2 ? spread : lim2;
-        spread = spread > lim ? spread : lim;
-        rec_st(L, rec, j, rSpr + m, spread > old ? spread : (1.0 - cfg.kf_a_spr) * old + cfg.kf_a_spr * spread);
+        rec_st(L, rec, j, rSpr + m, spread_estimate(cfg, m, nj, mn, mx, old));
         if (m == 0) {
             if (nj > 128) {  // leaves of this cloud's pairwise sums, for the dispersion phase below
                 int cnt = 0;
-                for_each_leaf<kPwDepth>(0, nj, [&](int, int) { cnt++; });
+                pw_for_each_leaf<kPwDepth>(0, nj, [&](int, int) { cnt++; });
                 const int first = atomicAdd(&L.ml[0], cnt), c = atomicAdd(&L.ml[1], 1);
-                int *lf = L.ml + 2 + first * 3, *cl = L.ml + 2 + 3 * max_leaves(NP);
+                int *lf = L.ml + 2 + first * 3, *cl = L.ml + 2 + 3 * pw_max_leaves(NP);
                 cl[c * 2] = j; cl[c * 2 + 1] = first;
                 int k = 0;
-                for_each_leaf<kPwDepth>(0, nj, [&](int o, int len) { lf[k * 3] = j; lf[k * 3 + 1] = o; lf[k * 3 + 2] = len; k++; });
+                pw_for_each_leaf<kPwDepth>(0, nj, [&](int o, int len) { lf[k * 3] = j; lf[k * 3 + 1] = o; lf[k * 3 + 2] = len; k++; });
             }
             rec_st(L, rec, j, rLife, 0.0);
             L.life[j] = 0.0;
             rec->point_num = nj;
             if (j < kRes) reinterpret_cast<int32_t *>(L.rec + (size_t)j * kRecStage + rInts)[0] = nj;
-            // _estimate_point_num Tracking.py:232-244
-            double ne = rec_ld(L, rec, j, rNest);
-            if (cfg.kf_enable_est) ne = ((double)nj > ne) ? (double)nj : (1 - cfg.kf_a_n) * ne + cfg.kf_a_n * (double)nj;
-            else ne = cfg.kf_est_pointnum > (double)nj ? cfg.kf_est_pointnum : (double)nj;
+            const double ne = point_num_estimate(cfg, nj, rec_ld(L, rec, j, rNest));
             rec_st(L, rec, j, rNest, ne);
             L.nest[j] = ne;
         }
@@ -710,15 +587,14 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
     PROBE(13);
     lds_barrier();
     PROBE(14);
-    // status: sqrt(sum(centroid[3:6]^2)) < TR_VEL_THRES (Tracking.py:132-136) and BatchedData.add_frame on the track ring
+    // cluster.status (centroid_is_static) and BatchedData.add_frame on the track ring
     // (Tracking.py:43-51; the rows were written above): the LAST wave's threads, a track each -- the dispersion items below
     // fill the waves from the front
     for (int j = NT - 1 - tid; j < T; j += NT) {
         const int nj = L.cls_n[j + 1];
         if (nj > 0) {
             TrackRec *rec = trk + L.slot[j];
-            const double v3 = L.cen[j * 6 + 3], v4 = L.cen[j * 6 + 4], v5 = L.cen[j * 6 + 5];
-            const int stc = sqrt((v3 * v3 + v4 * v4) + v5 * v5) < cfg.tr_vel_thres ? 1 : 0;
+            const int stc = centroid_is_static(cfg, L.cen[j * 6 + 3], L.cen[j * 6 + 4], L.cen[j * 6 + 5]);
             rec->is_static = stc;
             L.stat[j] = stc;
             int len, rn[MMW_RING_MAX], rs[MMW_RING_MAX];
@@ -756,8 +632,7 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
     {
         double *leafsum = L.work + 6 * NPs;  // [leaf][21]
         const int nleaf = L.ml[0], ncloud = L.ml[1];
-        const int *lf = L.ml + 2, *cl = L.ml + 2 + 3 * max_leaves(NP);
-        auto entry = [](int e, int &a, int &b) { a = 0; while (e >= 6 - a) { e -= 6 - a; a++; } b = a + e; };
+        const int *lf = L.ml + 2, *cl = L.ml + 2 + 3 * pw_max_leaves(NP);
         auto blend = [&](TrackRec *rec, int j, int a, int b, double res, int nj, double g_ab, double g_ba, double ne) {
             const double D = res / (double)nj;
             if (ne == 0.0) { err |= ERR_DIVZERO; return; }
@@ -768,7 +643,7 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
         for (int it = tid; it < (T + nleaf) * 21; it += NT) {
             const int u = it / 21;
             int a, b;
-            entry(it - u * 21, a, b);
+            disp_entry(it - u * 21, a, b);
             const bool direct = u < T;
             const int j = direct ? u : lf[(u - T) * 3];
             const int nj = L.cls_n[j + 1];
@@ -786,12 +661,12 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
             for (int it = tid; it < ncloud * 21; it += NT) {
                 const int c = it / 21, e = it - c * 21;
                 int a, b;
-                entry(e, a, b);
+                disp_entry(e, a, b);
                 const int j = cl[c * 2], nj = L.cls_n[j + 1];
                 TrackRec *rec = trk + L.slot[j];
                 const double g_ab = rec_ld(L, rec, j, rGd + a * 6 + b), g_ba = rec_ld(L, rec, j, rGd + b * 6 + a), ne = L.nest[j];
                 int idx = 0;
-                const double res = combine_leaves<kPwDepth>(nj, leafsum + cl[c * 2 + 1] * 21 + e, 21, idx);
+                const double res = pw_combine<kPwDepth>(nj, leafsum + cl[c * 2 + 1] * 21 + e, 21, idx);
                 blend(rec, j, a, b, res, nj, g_ab, g_ba, ne);
             }
         }
@@ -857,7 +732,7 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
         int phys = gs[0], live = 0;
 #pragma unroll
         for (int k = 1; k < MMW_RING_MAX; k++) if (k == g_len - 1) phys = gs[k];
-        const int nff = nf_flags_with((hv.skipped >> kSkipNfShift) & kSkipNfMask, phys, L.misc[15]);
+        const int nff = nf_ring_flags(hv.skipped, phys, L.misc[15]);
 #pragma unroll
         for (int k = 0; k < MMW_RING_MAX; k++) if (k < g_len) live |= (nff >> (2 * gs[k])) & 3;
         const int nfe = nf_error_of(live);
@@ -926,11 +801,7 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
     if (tid == 0 && st.stats) {
         int ring_rows = 0;
         for (int j = 0; j < Tin; j++) ring_rows += min(L.cls_n[j + 1], cfg.ring_rows);
-        unsigned long long *sl = stats_slot(st, s);
-        atomicAdd(&sl[0], (unsigned long long)((F32 ? 32 : 64) * n + 4 * n + Tin * kTrackBytesPerTrack + 64 * nun + 64 * ring_rows));
-        atomicAdd(&sl[2], 1ULL);
-        atomicAdd(&sl[5], (unsigned long long)Tin);
-        atomicAdd(&sl[6], (unsigned long long)n * (unsigned long long)Tin);
+        step_account(stats_slot(st, s), F32, n, Tin, nun, ring_rows);
     }
     PROBE(22);
     WGTIME(1);

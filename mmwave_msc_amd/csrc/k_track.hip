@@ -15,13 +15,14 @@
 #include "mmw_math.hpp"
 #include "mmw_cloud.hpp"
 #include "mmw_kalman.hpp"
+#include "mmw_assoc.hpp"
 #include "mmw_launch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
 
 // Diagnostic build only (make STAMPS=1 -> libmmw_hip_stamps.so): per-phase cycle sums of wave 0,
-// accumulated into stats[8 + phase].  Never compiled into the product library.
+// accumulated into stats[8 + phase].  Never compiled into the product library.  (PROBE, WGTIME: mmw_assoc.hpp)
 #ifdef MMW_STAMPS
 #define STAMP(k)                                                                              \
     do {                                                                                      \
@@ -31,48 +32,9 @@ namespace mmw {
             t_prev = t_now;                                                                   \
         }                                                                                     \
     } while (0)
-// PROBE(id): raw clock of lane 0 of every wave of ONE workgroup (scene kProbeScene), for timelines
-constexpr int kProbeScene = 460;   // (a block index: st.perm puts the scenes with the most tracks first)
-#define PROBE(id)                                                                             \
-    do {                                                                                      \
-        if (blockIdx.x == kProbeScene && (threadIdx.x & 63) == 0)                             \
-            st.stats[kStatSlots * kStatWords + (threadIdx.x >> 6) * 64 + (id)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-// WGTIME(k): s_memrealtime (100 MHz, chip-wide) and s_memtime of every workgroup's start (k = 0) and end (k = 1)
-// (-DMMW_STAMPS_POST: k_post's workgroups write these words instead, k_dbscan.hip)
-#ifdef MMW_STAMPS_POST
-#define WGTIME(k)
-#else
-// (2048 slots: a launch of more workgroups stamps every second / fourth ... one)
-#define WGTIME(k)                                                                             \
-    do {                                                                                      \
-        int wg_sh = 0;                                                                        \
-        while (((int)gridDim.x >> wg_sh) > 2048) wg_sh++;                                     \
-        if (threadIdx.x == 0 && (blockIdx.x & ((1u << wg_sh) - 1)) == 0) {                    \
-            const unsigned wg_slot = blockIdx.x >> wg_sh;                                     \
-            st.stats[kStatSlots * kStatWords + 256 + wg_slot * 4 + (k) * 2] = __builtin_amdgcn_s_memrealtime(); \
-            st.stats[kStatSlots * kStatWords + 256 + wg_slot * 4 + (k) * 2 + 1] = __builtin_amdgcn_s_memtime(); \
-        }                                                                                     \
-    } while (0)
-#endif
 #else
 #define STAMP(k)
-#define PROBE(id)
-#define WGTIME(k)
 #endif
-
-
-// Columns of the point tile are NP + 2 doubles apart: with a power-of-two stride the same row of all six
-// columns -- what the lanes of one track read together -- would sit in one LDS bank (6-way conflicts).
-constexpr int kTilePad = 2;
-// per track: gate record in (352) + spread, N_est, group dispersion, ring state in (392) + centroid, min, max,
-// spread, group dispersion, N_est, lifetime, counters, ring state out (540)
-constexpr int kTrackBytesPerTrack = 352 + 392 + 540;
-
-// numpy's pairwise split point and the bound on leaves per frame (see pw_* below): a leaf that comes from a
-// split holds at least 57 rows, so a frame has at most max_pts/57 of them.
-__host__ __device__ inline int pw_split(int n) { const int h = n / 2; return h - h % 8; }
-__host__ __device__ inline int pw_max_leaves(int np) { return np > 128 ? np / 57 + 1 : 0; }
 
 struct TrackLds {
     double *p6;      // [6][NP + kTilePad] point columns x,y,z,vx,vy,vz, class-sorted (see the split)
@@ -89,8 +51,6 @@ struct TrackLds {
     int *slot2;      // [t_cap]
     int *misc;       // [16]
 };
-
-__host__ __device__ inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // WRITE=false only sizes the layout.  (No `if (L)` null test: in the private address space a
 // null check on an alloca cannot be folded and would pin the struct in scratch memory.)
@@ -124,7 +84,7 @@ __host__ __device__ __forceinline__ size_t track_lds_layout(const DevCfg &c, cha
     }
     CARVE(cls_n, int, CLS)
     CARVE(cls_off, int, CLS + 1)
-    CARVE(ml, int, 2 + 5 * (pw_max_leaves(NP) + 1))
+    CARVE(ml, int, ml_words(NP))
     CARVE(slot, int, c.t_cap)
     CARVE(misc, int, 16)
 #undef CARVE
@@ -141,68 +101,6 @@ size_t track_lds_bytes(const DevCfg &c)
     if (const char *x = getenv("MMW_DIAG_LDS_EXTRA")) b += (size_t)atoi(x);
 #endif
     return b;
-}
-
-// numpy pairwise_sum_DOUBLE (the summation order of the 1-D np.mean in ClusterTrack._get_D, Tracking.py:286):
-//   n < 8      : one by one
-//   n <= 128   : eight interleaved accumulators r[k] += x[i+k], ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the
-//                n%8 leftovers one by one                                   -- a LEAF
-//   otherwise  : n2 = n/2 - (n/2)%8 ;  pairwise(x, n2) + pairwise(x+n2, n-n2)
-// The leaves of one sum are independent, so they are spread over lanes (pw_leaf) and only the few adds of
-// the recursion (pw_combine) stay serial.  D = recursion depth budget: 4 levels cover n <= 2048.
-
-template <int D, typename F>
-__device__ __forceinline__ void pw_for_each_leaf(int off, int n, F f)
-{
-    if constexpr (D == 0) f(off, n);
-    else {
-        if (n <= 128) f(off, n);
-        else { const int n2 = pw_split(n); pw_for_each_leaf<D - 1>(off, n2, f); pw_for_each_leaf<D - 1>(off + n2, n - n2, f); }
-    }
-}
-
-// sums of the leaves, in leaf order, back into the value numpy returns
-template <int D>
-__device__ __forceinline__ double pw_combine(int n, const double *leafsum, int stride, int &idx)
-{
-    if constexpr (D == 0) { const double v = leafsum[idx * stride]; idx++; return v; }
-    else {
-        if (n <= 128) { const double v = leafsum[idx * stride]; idx++; return v; }
-        const int n2 = pw_split(n);
-        const double l = pw_combine<D - 1>(n2, leafsum, stride, idx);
-        const double r = pw_combine<D - 1>(n - n2, leafsum, stride, idx);
-        return l + r;
-    }
-}
-constexpr int kPwDepth = 4;
-
-// one leaf (n <= 128) of sum_r (pa[r]-ca)*(pb[r]-cb)
-__device__ __forceinline__ double pw_leaf(const double *pa, const double *pb, double ca, double cb, int n)
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; i++) res += (pa[i] - ca) * (pb[i] - cb);
-        return res;
-    }
-    const int lim = n - (n & 7);
-    double r[8], xa[8], xb[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) { xa[u] = pa[u]; xb[u] = pb[u]; }
-#pragma unroll
-    for (int u = 0; u < 8; u++) r[u] = (xa[u] - ca) * (xb[u] - cb);
-    for (int i = 8; i < lim; i += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) { xa[u] = pa[i + u]; xb[u] = pb[i + u]; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) r[u] += (xa[u] - ca) * (xb[u] - cb);
-    }
-    const int left = n - lim;  // the n%8 leftovers, loaded together, added one by one
-#pragma unroll
-    for (int u = 0; u < 7; u++) { xa[u] = (u < left) ? pa[lim + u] : 0.0; xb[u] = (u < left) ? pb[lim + u] : 0.0; }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-#pragma unroll
-    for (int u = 0; u < 7; u++) if (u < left) res += (xa[u] - ca) * (xb[u] - cb);
-    return res;
 }
 
 // PPT = points per thread = ceil(max_pts / 256): a template so that per-point registers are not
@@ -262,12 +160,8 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
     if (s == 0 && tid >= 8 && tid < 11) st.q[kQBig + (parity ^ 1) * 8 + (tid - 8)] = tid - 8 == kQHead ? q_tag(cfg.epoch + 1) : 0;  // ... and those of the large clouds' queue
     if (s == 0 && tid < kUpdWords) st.upd_count[(parity ^ 1) * kUpdWords + tid] = 0;       // ... and the lengths of its update lists
     if (s == 0 && tid == kThreads - 1) st.spc_count[parity ^ 1] = 0;
-    if (!frame_reaches_track(n_raw, NP)) {  // offline_main.py:56: empty frames never reach track()
-        if (tid == 0) {
-            hdr->need_db = 0;
-            hdr->skipped = (hdr->skipped & ~255) | 1;  // not in this frame's update lists: the next k_predict finds its tracks by this flag (the ring's size and non-finite flags stay)
-            if (n_raw != 0) atomicOr(&hdr->err, ERR_BADCOUNT);  // a count the context was not sized for
-        }
+    if (!frame_reaches_track(n_raw, NP)) {
+        if (tid == 0) frame_skipped(hdr, hdr->skipped, n_raw);
         return;
     }
     int32_t *order = st.order + (size_t)s * cfg.t_cap;
@@ -316,26 +210,13 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
 #pragma unroll
     for (int q = 0; q < PPT; q++) { bestd[q] = 0.0; bestj[q] = -1; }
 
-    // ---- gate every point against the scene's tracks (Tracking.py:553-572) ----
-    // The gate record of a track (C^-1, log|det C|, predicted position: 43 doubles, k_predict -> gate_buf) is the same
-    // for every point, i.e. wave-uniform: it is read through the SCALAR cache (constant address space, uniform address
-    // -> s_load) and enters the fp64 VALU ops as their SGPR operand (no LDS staging, no barriers in this phase).
-    // y' C^-1 y as k-ordered FUSED chains, v_k = fma(y_a, Ci[a][k], v_k) row by row over C^-1, then q = fma(v_k, y_k, q):
-    // the arithmetic definition the oracle shares (oracle/c/mmw_oracle.c, _calc_dist_fun); with the operands in SGPRs the
-    // phase is bound by fp64 issue, and the fused form is 49 instead of 84 instructions per (point, track).
+    // ---- gate every point against the scene's tracks (Tracking.py:553-572): the records through the scalar cache (no LDS
+    //      staging, no barriers in this phase), the distance and the first-best rule in mmw_assoc.hpp ----
     {
-#ifdef MMW_DIAG_VGATE   // (diagnostic build, scripts/dual_run.py: the records by VECTOR loads -- volatile global -- instead of through the scalar cache)
-        typedef const volatile double *gate_ptr;
-#else
-        typedef const double __attribute__((address_space(4))) *gate_ptr;
-#endif
         const int su = __builtin_amdgcn_readfirstlane(s), Tu = __builtin_amdgcn_readfirstlane(T);
         gate_ptr gb = (gate_ptr)(st.gate_buf + (size_t)su * cfg.t_cap * kGateRec);
         if constexpr (PRED) {
-            // The records were written by this launch.  The constant address space promises the compiler memory that does not
-            // change, so the pointer itself is made opaque HERE, behind the invalidate: no load through it can be moved above
-            // this statement.
-            asm volatile("; mmw: gate pointer opaque from here" : "+s"(gb) : : "memory");
+            gb = gate_records_opaque(gb);   // (the records were written by this launch: opaque HERE, behind the invalidate)
 #ifndef MMW_DIAG_VGATE
             // Warm the scalar cache: one dword of every 64-byte line of the scene's gate records, all requests in flight
             // together.  The loop below then takes its records (six s_loads per track, waited for as a batch) from the
@@ -365,31 +246,8 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
             for (int q = 0; q < PPT; q++) {
                 const int i = q * kThreads + tid;
                 if (q * kThreads < n) {  // wave-uniform
-                    const double y0 = pr[q][0].x - G[37], y1 = pr[q][0].y - G[38], y2 = pr[q][1].x - G[39], y3 = pr[q][1].y - G[40],
-                                 y4 = pr[q][2].x - G[41], y5 = pr[q][2].y - G[42];
-                    double v[6];
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = y0 * G[k];
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y1, G[6 + k], v[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y2, G[12 + k], v[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y3, G[18 + k], v[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y4, G[24 + k], v[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; k++) v[k] = __builtin_fma(y5, G[30 + k], v[k]);
-                    double quad = v[0] * y0;
-                    quad = __builtin_fma(v[1], y1, quad);
-                    quad = __builtin_fma(v[2], y2, quad);
-                    quad = __builtin_fma(v[3], y3, quad);
-                    quad = __builtin_fma(v[4], y4, quad);
-                    quad = __builtin_fma(v[5], y5, quad);
-                    const double d = G[36] + quad;
-                    if (i < n && d < cfg.tr_gate) {
-                        if (bestj[q] < 0 || d < bestd[q]) { bestj[q] = j; bestd[q] = d; }
-                    }
+                    const double d = gate_distance(G, pr[q][0].x, pr[q][0].y, pr[q][1].x, pr[q][1].y, pr[q][2].x, pr[q][2].y);
+                    gate_first_best(cfg, i < n, d, j, bestj[q], bestd[q]);
                 }
             }
         }
@@ -555,7 +413,7 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
         L.misc[13] = U;
         // the ring's non-finite flags (two bits per physical slot, SceneHdr.skipped): this frame's replace those of the slot it
         // was written to; [15] = the new flags | what the live frames hold together << 8, for the trigger below
-        const int nff = nf_flags_with((gp_skw >> kSkipNfShift) & kSkipNfMask, phys, L.misc[15]);
+        const int nff = nf_ring_flags(gp_skw, phys, L.misc[15]);
         int live = 0;
 #pragma unroll
         for (int k = 0; k < MMW_RING_MAX; k++) if (k < len) live |= (nff >> (2 * gp_s[k])) & 3;
@@ -580,13 +438,7 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
         rec->centroid[m] = cen;
         rec->minv[m] = mn;
         rec->maxv[m] = mx;
-        // _estimate_measurement_spread Tracking.py:246-268
-        double spread = mx - mn;
-        const double lim = cfg.kf_spread_lim[m], lim2 = 2 * lim;
-        if (nj != 1) spread = spread * (double)(nj + 1) / (double)(nj - 1);
-        spread = spread < lim2 ? spread : lim2;
-        spread = spread > lim ? spread : lim;
-        rec->spread[m] = spread > old ? spread : (1.0 - cfg.kf_a_spr) * old + cfg.kf_a_spr * spread;
+        rec->spread[m] = spread_estimate(cfg, m, nj, mn, mx, old);
         if (m == 0) {
             if (nj > 128) {  // leaves of this cloud's pairwise sums, for the dispersion phase below
                 int cnt = 0;
@@ -599,10 +451,7 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
             }
             rec->lifetime = 0.0;
             rec->point_num = nj;
-            // _estimate_point_num Tracking.py:232-244
-            double ne = ne_old;
-            if (cfg.kf_enable_est) ne = ((double)nj > ne) ? (double)nj : (1 - cfg.kf_a_n) * ne + cfg.kf_a_n * (double)nj;
-            else ne = cfg.kf_est_pointnum > (double)nj ? cfg.kf_est_pointnum : (double)nj;
+            const double ne = point_num_estimate(cfg, nj, ne_old);
             rec->n_est = ne;
             L.nest[j] = ne;
         }
@@ -805,8 +654,7 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
         if (nj > 0) {
             TrackRec *rec = trk + L.slot[j];
             const int rsize = INNER ? (rec->inner & 255) : cfg.ring;
-            const double v3 = L.cen[j * 6 + 3], v4 = L.cen[j * 6 + 4], v5 = L.cen[j * 6 + 5];
-            rec->is_static = sqrt((v3 * v3 + v4 * v4) + v5 * v5) < cfg.tr_vel_thres ? 1 : 0;
+            rec->is_static = centroid_is_static(cfg, L.cen[j * 6 + 3], L.cen[j * 6 + 4], L.cen[j * 6 + 5]);
             // BatchedData.add_frame on the track ring (Tracking.py:43-51); the rows were written above.
             // ring_len, ring_n[], ring_slot[] come in together and go back together.
             int len = rec->ring_len;
@@ -838,7 +686,6 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
         double *leafsum = L.work + 6 * NPs;  // [leaf][21]
         const int nleaf = L.ml[0], ncloud = L.ml[1];
         const int *lf = L.ml + 2, *cl = L.ml + 2 + 3 * pw_max_leaves(NP);
-        auto entry = [](int e, int &a, int &b) { a = 0; while (e >= 6 - a) { e -= 6 - a; a++; } b = a + e; };
         auto blend = [&](TrackRec *rec, int a, int b, double res, int nj, double g_ab, double g_ba, double ne) {
             const double D = res / (double)nj;
             if (ne == 0.0) { err |= ERR_DIVZERO; return; }
@@ -849,7 +696,7 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
         for (int it = tid; it < (T + nleaf) * 21; it += kThreads) {
             const int u = it / 21;
             int a, b;
-            entry(it - u * 21, a, b);
+            disp_entry(it - u * 21, a, b);
             const bool direct = u < T;
             const int j = direct ? u : lf[(u - T) * 3];
             const int nj = L.cls_n[j + 1];
@@ -871,7 +718,7 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
             for (int it = tid; it < ncloud * 21; it += kThreads) {
                 const int c = it / 21, e = it - c * 21;
                 int a, b;
-                entry(e, a, b);
+                disp_entry(e, a, b);
                 const int j = cl[c * 2], nj = L.cls_n[j + 1];
                 TrackRec *rec = trk + L.slot[j];
                 const double g_ab = rec->gd[a * 6 + b], g_ba = rec->gd[b * 6 + a], ne = L.nest[j];
@@ -1025,16 +872,9 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
     PROBE(9);
     STAMP(10);  // DBSCAN screens + push
     if (tid == 0 && st.stats) {
-        // algorithmic bytes of this scene-frame: points in, assoc out, per track the gate record
-        // and the record fields this kernel reads and writes, unassigned rows appended to the global ring, rows
-        // appended to track rings
         int ring_rows = 0;
         for (int j = 0; j < Tin; j++) ring_rows += min(L.cls_n[j + 1], cfg.ring_rows);
-        unsigned long long *sl = stats_slot(st, s);
-        atomicAdd(&sl[0], (unsigned long long)((F32 ? 32 : 64) * n + 4 * n + Tin * kTrackBytesPerTrack + 64 * L.cls_n[0] + 64 * ring_rows));
-        atomicAdd(&sl[2], 1ULL);
-        atomicAdd(&sl[5], (unsigned long long)Tin);
-        atomicAdd(&sl[6], (unsigned long long)n * (unsigned long long)Tin);
+        step_account(stats_slot(st, s), F32, n, Tin, L.cls_n[0], ring_rows);
     }
     if (tid < 64) {   // (wave 0: its lane 0 holds the place; T <= 63 entries, one store instruction)
         const int pos = __builtin_amdgcn_readfirstlane(upd_pos);

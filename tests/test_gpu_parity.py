@@ -166,6 +166,59 @@ def test_multi_scene_vs_oracle():
     sb.close()
 
 
+def _one_tight_target(seed, n_frames, max_pts, rows):
+    """pts[F, max_pts, 8]: ONE slowly walking target of `rows` points per frame and nothing else -- tight enough (8 cm, 3 cm/s)
+    that from the second frame on every row falls into the gate of the track the first frame's DBSCAN spawned."""
+    rng = np.random.default_rng(seed)
+    vel = np.array([0.3, 0.2])
+    pts = np.zeros((n_frames, max_pts, 8), np.float32)
+    for f in range(n_frames):
+        p = np.zeros((rows, 8))
+        p[:, 0:2] = np.array([0.5, 3.0]) + vel * 0.1 * f + rng.normal(0.0, 0.08, size=(rows, 2))
+        p[:, 2] = rng.uniform(0.6, 1.2, size=rows)
+        p[:, 3:5] = vel + rng.normal(0.0, 0.03, size=(rows, 2))
+        p[:, 5] = rng.normal(0.0, 0.03, size=rows)
+        p[:, 6] = rng.normal(0.0, 0.3, size=rows)
+        p[:, 7] = rng.gamma(1.0, 30.0, size=rows)
+        pts[f, :rows] = p
+    return pts
+
+
+@pytest.mark.parametrize("max_pts", [256, 512])
+def test_clouds_of_more_than_128_rows_vs_oracle(max_pts):
+    """A (point, track) cloud of more than 128 rows takes the leaf list of the dispersion phase (numpy's pairwise summation
+    splits it: csrc/mmw_assoc.hpp pw_*), in k_track and in k_scene (the layouts), at one and at two points per thread (max_pts).
+    Four scenes of one target: 150 rows (two leaves), 300 rows (a split of depth 2; 256 rows, two leaves, where the frame
+    holds no more), and the switch itself, 128 rows (one leaf) and 129.  The rows per cloud are a condition on the input,
+    checked here through the oracle: from the second frame on the track takes EVERY row.  Everything bit for bit."""
+    from oracle import c_oracle as co
+    S, F = 4, 10
+    rows = [150, min(300, max_pts), 128, 129]
+    kw = dict(tr_max_tracks=4)
+    sb = _mk(S, max_pts, **kw)
+    cfg = co.default_config(**kw)
+    scenes = [co.OracleScene(cfg, max_pts) for _ in range(S)]
+    pts = np.stack([_one_tight_target(8800 + s, F, max_pts, rows[s]) for s in range(S)], axis=1)
+    cnt = np.array(rows, np.int32)
+    dts = np.full(S, 0.1)
+    full = np.zeros(S, int)
+    for f in range(F):
+        assoc, labels, dbn = sb.step_host(pts[f].astype(np.float64), cnt, dts)
+        ntr = sb.num_tracks()
+        trk = sb.tracks(cap=8)
+        for s in range(S):
+            oa, ol = scenes[s].track(pts[f, s, : rows[s]].astype(np.float64), dts[s])
+            full[s] += int(np.all(oa == 0))
+            assert np.array_equal(assoc[s, : rows[s]], oa), (f, s)
+            assert (ol is None) == (dbn[s] < 0), (f, s)
+            if ol is not None:
+                assert np.array_equal(labels[s, : dbn[s]], ol), (f, s)
+            assert ntr[s] == scenes[s].n_tracks
+            assert_tracks_match(trk[s, : ntr[s]], scenes[s].tracks(), ctx=f"f{f} s{s}", exact=True)
+    assert np.all(full >= F // 2), full   # the clouds really had 150 / 300 / 128 / 129 rows on at least half of the frames
+    sb.close()
+
+
 @pytest.mark.parametrize("case", [
     dict(db_min_samples=4, db_eps=0.05),                       # cores appear and vanish inside plain clutter
     dict(db_min_samples=6, db_eps=0.12),
