@@ -479,6 +479,50 @@ int mmw_report_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n_ev
 int mmw_report(mmw_ctx *ctx, mmw_track_report *rows, int32_t cap_rows, mmw_track_event *events, int32_t cap_events,
                int32_t scene_base, int32_t *n_rows, int32_t *n_events);                   /* async + wait */
 
+/* ---- live-track point clouds ----
+ * Where the live tracks' points are: every track's `track.batch.effective_data` (Tracking.py:43-58 -- np.concatenate of the ring's
+ * frames, what Visualizer.update_bb scatters, Visualizer.py:232-260), compacted on the device in ONE call and in the report's order,
+ * so that directory entry i belongs to mmw_report row i of the same state.
+ *
+ * Output: a DIRECTORY of one mmw_cloud_track per entry and the points / rows of all entries, back to back.  Scenes ascend; inside a
+ * scene the entries follow effective_tracks order; with MMW_CLOUD_UNASSIGNED one more entry (slot -1, uid -1) follows each scene's
+ * tracks: its global ring, the unassigned points apply_DBscan clusters.  Inside an entry frames run oldest first and rows keep their
+ * stored order.  The entries partition the output: first of entry i + 1 = first + count of entry i, the last one ends at *n_points.
+ * mode (bits 0): MMW_CLOUD_POINTS writes mmw_cloud_point (columns 0..2 rounded once to fp32 and the index of the point's directory
+ * entry), MMW_CLOUD_ROWS writes the ring rows verbatim (double[8] each: effective_data bit for bit).  Non-finite values pass through.
+ *
+ * `dropped`: a track frame stores min(ring_n[k], ring_rows) rows (mmw_get_dims); what the reference's effective_data holds beyond that
+ * is counted here, the one declared difference.  Contexts with ring_rows = max_pts, or with seek_inner, store whole frames: 0.
+ *
+ * Capacity is decided on the DEVICE, as the report's: more entries than cap_tracks or more points than cap_points (totals formed in
+ * 64 bits; one above INT32_MAX never fits and is reported saturated) -> nothing is written to either buffer and mmw_clouds_wait
+ * returns MMW_E_CAPACITY with both counts needed.  mmw_clouds_async queues its kernels on the context's stream behind whatever was
+ * queued last; the counts follow into pinned memory and mmw_clouds_wait(ticket) waits for THAT copy only.  ticket in [0,4), ticket 3
+ * is mmw_clouds' own.  No enable call: the first call allocates the context's scratch, mmw_destroy frees it; a context that never
+ * calls launches what it did before.  dir: dev pointer, 4-byte aligned; out: dev pointer, 16-byte aligned; scene ids are offset by
+ * scene_base.  MMW_E_ARG, nothing touched: a NULL context, a NULL buffer with a positive cap, a negative cap, a mode outside
+ * {0, 1, 2, 3}, a bad ticket, a misaligned buffer, a wait for a ticket with nothing outstanding. */
+typedef struct mmw_cloud_track {     /* 32 bytes: one directory entry */
+    int32_t scene;    /* global scene id (scene_base + local index) */
+    int32_t slot;     /* position in effective_tracks; -1 = the scene's global ring (unassigned points) */
+    int32_t uid;      /* mmw_track_record.uid; -1 for the global ring */
+    int32_t first;    /* index of this entry's first point / row in the output */
+    int32_t count;    /* points written: sum over the ring's frames of the rows it STORES */
+    int32_t frames;   /* len(track.batch.buffer)  (g_len for the global ring) */
+    int32_t newest;   /* rows of the newest frame among `count` (the last `newest` of the run) */
+    int32_t dropped;  /* rows effective_data has in the reference that this context does not store:
+                         sum of max(0, ring_n[k] - ring_rows); always 0 for the global ring */
+} mmw_cloud_track;
+typedef struct mmw_cloud_point { float x, y, z; int32_t track; } mmw_cloud_point;   /* 16 bytes; track = index of its directory entry */
+#define MMW_CLOUD_POINTS 0      /* out = mmw_cloud_point[]: columns 0..2 rounded once to fp32 */
+#define MMW_CLOUD_ROWS 1        /* out = double[][8]: the ring rows verbatim = effective_data bit for bit */
+#define MMW_CLOUD_UNASSIGNED 2  /* flag bit: after a scene's tracks, one entry (slot -1) for its global ring */
+int mmw_clouds_async(mmw_ctx *ctx, mmw_cloud_track *dir, int32_t cap_tracks, void *out, int32_t cap_points, int32_t mode,
+                     int32_t scene_base, int32_t ticket);
+int mmw_clouds_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_tracks, int32_t *n_points);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_clouds(mmw_ctx *ctx, mmw_cloud_track *dir, int32_t cap_tracks, void *out, int32_t cap_points, int32_t mode,
+               int32_t scene_base, int32_t *n_tracks, int32_t *n_points);                   /* async + wait */
+
 /* Snapshot / restore of scene state (format version 1).
  *
  * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global

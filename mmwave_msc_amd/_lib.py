@@ -46,6 +46,7 @@ EXPORTS = [
     "mmw_set_sites", "mmw_get_sites", "mmw_clear_sites", "mmw_has_sites",
     "mmw_posture_attach", "mmw_estimate_posture", "mmw_posture_range", "mmw_mars_dense2", "mmw_mars_split_weights",
     "mmw_report_enable", "mmw_report_async", "mmw_report_wait", "mmw_report",
+    "mmw_clouds_async", "mmw_clouds_wait", "mmw_clouds",
     "mmw_uart_open", "mmw_uart_close", "mmw_uart_read", "mmw_uart_get_state", "mmw_uart_set_state", "mmw_uart_set_time",
 ]
 
@@ -161,6 +162,25 @@ class MmwTrackReport(C.Structure):
 class MmwTrackEvent(C.Structure):
     """struct mmw_track_event (include/mmw.h): a track that appeared or left, or a scene whose uids restarted."""
     _fields_ = [("scene", C.c_int32), ("uid", C.c_int32), ("kind", C.c_int32), ("slot", C.c_int32)]
+
+
+# struct mmw_cloud_track / mmw_cloud_point (include/mmw.h): the directory entries (32 bytes) and points (16 bytes) of mmw_clouds_*
+CLOUD_TRACK_DTYPE = np.dtype([("scene", "i4"), ("slot", "i4"), ("uid", "i4"), ("first", "i4"), ("count", "i4"), ("frames", "i4"),
+                              ("newest", "i4"), ("dropped", "i4")], align=True)
+CLOUD_POINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("track", "i4")], align=True)
+CLOUD_POINTS, CLOUD_ROWS, CLOUD_UNASSIGNED = 0, 1, 2   # MMW_CLOUD_*: the mode of mmw_clouds_* (UNASSIGNED is a flag bit)
+CLOUD_TICKETS = 4                             # mmw_clouds_async calls that may be outstanding (mmw_clouds itself uses the last ticket)
+
+
+class MmwCloudTrack(C.Structure):
+    """struct mmw_cloud_track (include/mmw.h): one directory entry -- a live track's cloud, or (slot -1) a scene's global ring."""
+    _fields_ = [("scene", C.c_int32), ("slot", C.c_int32), ("uid", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
+                ("frames", C.c_int32), ("newest", C.c_int32), ("dropped", C.c_int32)]
+
+
+class MmwCloudPoint(C.Structure):
+    """struct mmw_cloud_point (include/mmw.h): x, y, z in fp32 and the index of the point's directory entry."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("track", C.c_int32)]
 
 
 _lib = None
@@ -355,6 +375,9 @@ def load():
         "mmw_report_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
         "mmw_report_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_report": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
+        "mmw_clouds_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32]),
+        "mmw_clouds_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_clouds": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32p, i32p]),
         "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
         "mmw_uart_close": (C.c_int, [vp]),
         "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),

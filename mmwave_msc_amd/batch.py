@@ -682,6 +682,56 @@ class SceneBatch:
         events = b_e.download((n_e,), edt) if n_e else np.zeros(0, edt)
         return rows, events
 
+    # -- live-track point clouds ----------------------------------------------
+    def clouds_dev(self, dir_ptr, cap_tracks: int, out_ptr, cap_points: int, mode: int = 0, ticket: int = 0, scene_base: int = 0):
+        """mmw_clouds_async: every live track's `effective_data` into device buffers -- a `_lib.CLOUD_TRACK_DTYPE` directory entry
+        per track in the report's (scene, slot) order and, back to back, their points (`_lib.CLOUD_POINT_DTYPE`, mode
+        `_lib.CLOUD_POINTS`) or ring rows (float64[8], `_lib.CLOUD_ROWS`); `| _lib.CLOUD_UNASSIGNED` adds each scene's global ring as
+        an entry with slot -1.  Queued behind the last step on the context's stream -- no host wait.  Tickets 0 .. 3
+        (`clouds_host` uses 3).  `out_ptr` 16-byte aligned."""
+        self._chk(self.L.mmw_clouds_async(self.h, dir_ptr, int(cap_tracks), out_ptr, int(cap_points), int(mode), int(scene_base), int(ticket)))
+
+    def clouds_wait(self, ticket: int = 0):
+        """(n_tracks, n_points) of the `clouds_dev` call with this ticket: waits for its counts only, not for the stream.  Buffers
+        too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written."""
+        nt, npt = C.c_int32(0), C.c_int32(0)
+        rc = self.L.mmw_clouds_wait(self.h, int(ticket), C.byref(nt), C.byref(npt))
+        if rc == _lib.E_CAPACITY:
+            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
+            err.needed = (int(nt.value), int(npt.value))
+            raise err
+        self._chk(rc)
+        return int(nt.value), int(npt.value)
+
+    def clouds_host(self, rows: bool = False, unassigned: bool = False, scene_base: int = 0):
+        """(dir[n_tracks] CLOUD_TRACK_DTYPE, points[n_points] CLOUD_POINT_DTYPE) -- or, with rows=True, the ring rows
+        float64[n_points, 8]: entry i owns out[first : first + count], frames oldest first (`track.batch.effective_data`), and
+        without `unassigned` entry i is the track of `report_host` row i.  The device buffers are kept and grow to what the
+        device says it needs (one retry)."""
+        mode = (_lib.CLOUD_ROWS if rows else _lib.CLOUD_POINTS) | (_lib.CLOUD_UNASSIGNED if unassigned else 0)
+        ddt, item = _lib.CLOUD_TRACK_DTYPE, 64 if rows else _lib.CLOUD_POINT_DTYPE.itemsize
+        cap_t, cap_p = getattr(self, "_cloud_caps", (64, 4096))
+        for attempt in (0, 1):
+            b_d, b_o = self.buf("cloud_dir", cap_t * ddt.itemsize), self.buf("cloud_out", cap_p * item)
+            self.clouds_dev(b_d.ptr, cap_t, b_o.ptr, cap_p, mode, _lib.CLOUD_TICKETS - 1, scene_base)
+            try:
+                n_t, n_p = self.clouds_wait(_lib.CLOUD_TICKETS - 1)
+                break
+            except MmwError as e:
+                if e.code != _lib.E_CAPACITY or attempt:
+                    raise
+                if max(e.needed) >= 2 ** 31 - 1:   # (saturated: more entries or points than an int32 counts -- no buffer can be offered)
+                    raise MmwError(_lib.E_CAPACITY, "clouds_host: the clouds of this context exceed INT32_MAX entries or points; "
+                                                    "ask for fewer scenes per context") from e
+                cap_t, cap_p = max(cap_t, e.needed[0]), max(cap_p, e.needed[1])
+                self._cloud_caps = (cap_t, cap_p)
+        d = b_d.download((n_t,), ddt) if n_t else np.zeros(0, ddt)
+        if rows:
+            out = b_o.download((n_p, 8), np.float64) if n_p else np.zeros((0, 8))
+        else:
+            out = b_o.download((n_p,), _lib.CLOUD_POINT_DTYPE) if n_p else np.zeros(0, _lib.CLOUD_POINT_DTYPE)
+        return d, out
+
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):
         if scenes is None:

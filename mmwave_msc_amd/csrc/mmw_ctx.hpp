@@ -41,6 +41,15 @@ struct ReportCtx {
     bool issued[kTickets] = {false, false, false, false};
 };
 
+// mmw_clouds_*: the scratch of the live-track point clouds (allocated by the first call), the pinned counts of the outstanding calls
+struct CloudCtx {
+    CloudState cs = {};
+    char *d_block = nullptr;          // one allocation behind cs
+    int32_t *h_counts = nullptr;      // pinned [kTickets][4]: entries, points, fits -- as CloudState::totals
+    hipEvent_t ev[kTickets] = {nullptr, nullptr, nullptr, nullptr};
+    bool issued[kTickets] = {false, false, false, false};
+};
+
 struct mmw_ctx {
     mmw_config cfg;
     DevCfg dc;
@@ -89,6 +98,7 @@ struct mmw_ctx {
     int32_t *pc_owner = nullptr;
     PostureBatch *pb = nullptr;       // mmw_posture_attach (any number of scenes); independent of the one-scene chain above
     ReportCtx *rep = nullptr;         // mmw_report_enable; nullptr = reports are off and nothing of them is launched
+    CloudCtx *cloud = nullptr;        // mmw_clouds_*: allocated by the first call; nullptr = never called, nothing of it exists
     UartState uart = {};              // mmw_uart_open: the radar readers' state (uart.buf is the allocation, uart.scene lies behind the buffers); nullptr = closed
     // profiling
     unsigned prof_mask = 0;           // bit k: time kernel id k (mmw_profile_enable)
@@ -107,6 +117,7 @@ int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q)
 void posture_batch_free(PostureBatch *b);                          // api_posture.hip
 void report_free(ReportCtx *r);                                    // api_report.hip
 int report_rebase(mmw_ctx *c, const int32_t *dev_flags);           // api_report.hip: the scenes' uids restart (no-op while reports are off)
+void cloud_free(CloudCtx *k);                                      // api_cloud.hip
 #pragma GCC visibility pop
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)

@@ -12,6 +12,7 @@ struct DevCfg;     // mmw_device.hpp (the CNN's kernel files do without it)
 struct DevState;
 struct ReportState;
 struct UartState;
+struct CloudState;
 // k_track.hip, k_kalman.hip, k_scene.hip: the step
 size_t track_lds_bytes(const DevCfg &c);
 hipError_t prepare_track(const DevCfg &cfg);
@@ -56,6 +57,8 @@ void launch_set_batch_size(const DevCfg &cfg, const DevState &s, const int32_t *
 void launch_report_baseline(const DevCfg &cfg, const DevState &s, const ReportState &rp, hipStream_t st);
 void launch_report_rebase(const DevCfg &cfg, const ReportState &rp, const int32_t *flags, hipStream_t st);
 void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ReportState &rp, mmw_track_report *rows, int cap_rows, mmw_track_event *events, int cap_events, int scene_base, hipStream_t st);
+// k_cloud.hip: the live tracks' point clouds (mode: MMW_CLOUD_POINTS / MMW_CLOUD_ROWS, | MMW_CLOUD_UNASSIGNED)
+void launch_clouds(const DevCfg &cfg, const DevState &s, const CloudState &cs, mmw_cloud_track *dir, int cap_tracks, void *out, int cap_points, int mode, int scene_base, hipStream_t st);
 // k_uart.hip: the device-resident radar readers
 void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);

@@ -1,0 +1,119 @@
+"""The live tracks' point clouds (mmw_clouds_*, include/mmw.h) as far as a machine without a GPU can check them: the header declares
+the entries and the library exports them, the ctypes and numpy layouts of the directory entries and points are the C structs', and
+the kernels of csrc/k_cloud.hip compile without scratch or spilled registers and move rows and points as 16-byte pieces."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from mmwave_msc_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("mmw_clouds_async", "mmw_clouds_wait", "mmw_clouds")
+FIELDS_T = ["scene", "slot", "uid", "first", "count", "frames", "newest", "dropped"]
+FIELDS_P = ["x", "y", "z", "track"]
+
+
+def test_header_declares_and_library_exports_the_cloud_entries():
+    txt = open(os.path.join(ROOT, "include", "mmw.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    for name in NEW:
+        assert re.search(r"\bint\s+%s\s*\(" % name, code), name
+        assert name in _lib.EXPORTS, name
+    for macro, val in (("MMW_CLOUD_POINTS", 0), ("MMW_CLOUD_ROWS", 1), ("MMW_CLOUD_UNASSIGNED", 2)):
+        assert re.search(r"#define\s+%s\s+%d\b" % (macro, val), code), macro
+    assert (_lib.CLOUD_POINTS, _lib.CLOUD_ROWS, _lib.CLOUD_UNASSIGNED) == (0, 1, 2)
+    assert "typedef struct mmw_cloud_track" in code and "typedef struct mmw_cloud_point" in code
+    L = C.CDLL(_lib.LIB_PATH)
+    for name in NEW:
+        assert hasattr(L, name), f"{name} not exported by {_lib.LIB_PATH}"
+    L = _lib.load()   # (declares every prototype: AttributeError if one is missing)
+    for name in NEW:
+        assert getattr(L, name).argtypes is not None, name
+    # without a context every entry refuses its arguments instead of touching a device
+    assert L.mmw_clouds_async(None, None, 0, None, 0, 0, 0, 0) == _lib.E_ARG
+    assert L.mmw_clouds_wait(None, 0, None, None) == _lib.E_ARG
+    assert L.mmw_clouds(None, None, 0, None, 0, 0, 0, None, None) == _lib.E_ARG
+
+
+def _c_layout():
+    """sizeof / offsetof of the two structs as a C compiler lays out include/mmw.h."""
+    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("no C compiler")
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "mmw.h"\nint main(void){printf("%zu %zu", sizeof(mmw_cloud_track), sizeof(mmw_cloud_point));\n'
+    src += "".join('printf(" %%zu", offsetof(mmw_cloud_track, %s));\n' % f for f in FIELDS_T)
+    src += "".join('printf(" %%zu", offsetof(mmw_cloud_point, %s));\n' % f for f in FIELDS_P)
+    src += "return 0;}\n"
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, "layout.c"), "w") as fh:
+            fh.write(src)
+        exe = os.path.join(d, "layout")
+        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), os.path.join(d, "layout.c"), "-o", exe], check=True, capture_output=True)
+        v = [int(t) for t in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    return v[0], v[1], dict(zip(FIELDS_T, v[2: 2 + len(FIELDS_T)])), dict(zip(FIELDS_P, v[2 + len(FIELDS_T):]))
+
+
+def test_cloud_layouts_match_the_c_structs():
+    size_t, size_p, off_t, off_p = _c_layout()
+    assert (size_t, size_p) == (32, 16)
+    tdt, pdt = _lib.CLOUD_TRACK_DTYPE, _lib.CLOUD_POINT_DTYPE
+    assert tdt.itemsize == C.sizeof(_lib.MmwCloudTrack) == size_t
+    assert pdt.itemsize == C.sizeof(_lib.MmwCloudPoint) == size_p
+    assert list(tdt.names) == FIELDS_T and list(pdt.names) == FIELDS_P
+    for f, o in off_t.items():
+        assert tdt.fields[f][1] == o == getattr(_lib.MmwCloudTrack, f).offset, f
+        assert tdt.fields[f][0] == np.dtype("i4"), f
+    for f, o in off_p.items():
+        assert pdt.fields[f][1] == o == getattr(_lib.MmwCloudPoint, f).offset, f
+        assert pdt.fields[f][0] == np.dtype("i4" if f == "track" else "f4"), f
+    # both sizes are pinned where the kernels and the C-ABI are compiled
+    for name in ("k_cloud.hip", "api_cloud.hip"):
+        txt = open(os.path.join(ROOT, "mmwave_msc_amd", "csrc", name)).read()
+        assert re.search(r"static_assert\(sizeof\(mmw_cloud_track\) == 32", txt), name
+        assert re.search(r"static_assert\(sizeof\(mmw_cloud_point\) == 16", txt), name
+
+
+def test_cloud_launcher_is_declared_once_and_the_files_are_built():
+    csrc = os.path.join(ROOT, "mmwave_msc_amd", "csrc")
+    decl = open(os.path.join(csrc, "mmw_kernels.hpp")).read()
+    assert len(re.findall(r"\bvoid\s+launch_clouds\s*\(", decl)) == 1
+    for name in ("api_cloud.hip", "api_context.hip"):
+        assert not re.search(r"\bvoid\s+launch_clouds\s*\(", open(os.path.join(csrc, name)).read()), name
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    assert "k_cloud.hip" in mk and "api_cloud.hip" in mk
+    # the product build knows nothing of the diagnostic switch that makes k_cloud_write ignore the slot permutation
+    assert "MMW_MUTANT_CLOUD_IDENT_SLOTS" not in mk
+
+
+def test_cloud_kernels_use_no_scratch_and_move_16_byte_pieces():
+    from tests.test_cabi_exports import _device_isa, _kernel_report
+    rep, asm = _device_isa(("k_cloud",))["k_cloud"]
+    rows = _kernel_report(rep)
+    names = [k[0] for k in rows]
+    for k in ("k_cloud_count", "k_cloud_scan"):
+        assert sum(k in n for n in names) == 1, (k, names)
+    assert sum("k_cloud_write" in n for n in names) == 2, names   # MMW_CLOUD_POINTS and MMW_CLOUD_ROWS
+    assert len(names) == 4, names
+    for name, scratch, vspill, vgprs, occ, sspill in rows:
+        assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
+        body = asm[asm.index("\n" + name + ":"):]
+        body = body[: body.index(".Lfunc_end")]   # (the whole kernel: one that returns early has more than one s_endpgm)
+        assert "s_endpgm" in body, name
+        assert "scratch_" not in body, name
+        if "k_cloud_write" in name:
+            # ROWS: a row moves as four 16-byte pieces; POINTS: x, y arrive as one 16-byte load and a point leaves as one 16-byte store
+            assert "global_load_dwordx4" in body and "global_store_dwordx4" in body, name
+            assert occ >= 4, (name, occ)
+
+
+def test_cloud_dtype_arrays_are_plain_bytes():
+    d = np.zeros(3, _lib.CLOUD_TRACK_DTYPE)
+    p = np.zeros(5, _lib.CLOUD_POINT_DTYPE)
+    assert d.nbytes == 3 * 32 and d.view(np.uint8).shape == (3 * 32,)
+    assert p.nbytes == 5 * 16 and p.view(np.uint8).shape == (5 * 16,)
