@@ -523,6 +523,56 @@ int mmw_clouds_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_tracks, int32_t *n_
 int mmw_clouds(mmw_ctx *ctx, mmw_cloud_track *dir, int32_t cap_tracks, void *out, int32_t cap_points, int32_t mode,
                int32_t scene_base, int32_t *n_tracks, int32_t *n_points);                   /* async + wait */
 
+/* ---- live-track skeletons ----
+ * How the live tracks stand: every track's 57 keypoints turned from their track-relative, mirrored form into the room-frame skeleton
+ * that Visualizer.update_posture draws (Visualizer.py:265-307), with its plausibility check, compacted on the device in ONE call and
+ * in the report's order: in MMW_SKEL_ALL entry i belongs to mmw_report row i and mmw_clouds directory entry i (without
+ * MMW_CLOUD_UNASSIGNED) of the same state; `row` carries that index into MMW_SKEL_DRAWN, which leaves out the entries the check drops.
+ *
+ * The keypoints are 57 fp32 values kp[]; the reference views them as reshape(3, 19): row 0 = kp[0..18], row 1 = kp[19..37] (plotted
+ * as height), row 2 = kp[38..56] (plotted as depth).  x is the track's fp64 state (mmw_track_record.x[0], x[1]; the same for dim_x 6
+ * and 9).
+ *   check   g_c = fp32(kp[19c + 1] - kp[19c + 2]) for c = 0, 1, 2 (SpineMid - Neck: one fp32 subtraction each, as numpy's on a float32
+ *           array); s = g_0^2 + g_1^2 + g_2^2 in fp64, in that order (the products of fp32 values are exact there);
+ *           MMW_SKEL_SKIPPED iff s > 0.25; gap = fp32(sqrt(s)).  A NaN makes the comparison false: the track is drawn, as
+ *           `nan > 0.5` is false in the reference.
+ *   joints  joint[j][0] = fp32(-(double)kp[j] + x[0]);  joint[j][1] = fp32((double)kp[38 + j] + x[1]);  joint[j][2] = kp[19 + j]
+ *           ONE rounding each, from fp64: track.state.x[0] is a shape-(1,) fp64 array (state.x is (dim_x, 1), Tracking.py:96), so the
+ *           reference's in-place `+=` on the float32 view is computed in fp64 and cast back.  Non-finite values pass through.
+ * Skipped entries carry their joints all the same in MMW_SKEL_ALL.  The call is a pure function of the state and never writes it
+ * (the reference's reshape is a view: it transforms track.keypoints in place each time it draws; DESIGN.md 8e lists the differences).
+ * Call order: main.py:56 displays BEFORE estimate_posture (line 60) -- last frame's keypoints around this frame's position: call
+ * between mmw_step and mmw_estimate_posture for that, behind mmw_estimate_posture for this frame's keypoints.
+ *
+ * Capacity is decided on the DEVICE, as the clouds': more entries than cap -> nothing is written and mmw_skeletons_wait returns
+ * MMW_E_CAPACITY with both counts: *n_out the entries the mode needs, *n_live the live tracks (= *n_out in MMW_SKEL_ALL).
+ * mmw_skeletons_async queues its kernels on the context's stream behind whatever was queued last; the counts and the fit decision
+ * follow into pinned memory and mmw_skeletons_wait(ticket) waits for THAT copy only.  ticket in [0,4), ticket 3 is mmw_skeletons' own.
+ * No enable call: the first call allocates the context's scratch, mmw_destroy frees it; a context that never calls launches what it
+ * did before.  out: dev pointer, 16-byte aligned; scene ids are offset by scene_base.  MMW_E_ARG, nothing touched: a NULL context,
+ * a negative cap, a NULL out with a positive cap, a misaligned out, a mode outside {0, 1}, a bad ticket, a wait for a ticket with
+ * nothing outstanding. */
+typedef struct mmw_skeleton {          /* 256 bytes, no padding */
+    int32_t scene;      /* global scene id (scene_base + local index) */
+    int32_t slot;       /* position in effective_tracks */
+    int32_t uid;        /* mmw_track_record.uid */
+    int32_t row;        /* rank of this track among ALL live tracks in (scene, slot) order: the index of its mmw_report row */
+    int32_t flags;      /* bit 0 MMW_SKEL_SKIPPED: the reference's check drops this skeleton (Visualizer.py:276-278) */
+    float   gap;        /* |SpineMid - Neck| as defined above */
+    float   joint[19][3]; /* (x, y = depth, z = height) in the room frame: what the reference hands to plot / scatter */
+    int32_t reserved_;  /* 0 */
+} mmw_skeleton;
+#define MMW_SKEL_SKIPPED 1
+#define MMW_SKEL_ALL 0          /* mode: one entry per live track, entry i <-> report row i */
+#define MMW_SKEL_DRAWN 1        /* mode: only the entries the reference draws (flag bit 0 clear), compacted, order kept */
+int mmw_skeletons_async(mmw_ctx *ctx, mmw_skeleton *out, int32_t cap, int32_t mode, int32_t scene_base, int32_t ticket);
+int mmw_skeletons_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_out, int32_t *n_live);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_skeletons(mmw_ctx *ctx, mmw_skeleton *out, int32_t cap, int32_t mode, int32_t scene_base, int32_t *n_out, int32_t *n_live);   /* async + wait */
+/* host only, no context, no GPU: the 18 bones as joint index pairs ([18][2], Visualizer.py:100-119 order) and a class per joint
+ * ([19]: 0 blue, 1 green, 2 red = the head, which the reference draws larger and square; Visualizer.py:122-142, 295-307).  The
+ * tables are static; either pointer may be NULL. */
+int mmw_skeleton_tables(const int32_t **connections, const int32_t **joint_class);
+
 /* Snapshot / restore of scene state (format version 1).
  *
  * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global

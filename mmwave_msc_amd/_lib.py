@@ -47,6 +47,7 @@ EXPORTS = [
     "mmw_posture_attach", "mmw_estimate_posture", "mmw_posture_range", "mmw_mars_dense2", "mmw_mars_split_weights",
     "mmw_report_enable", "mmw_report_async", "mmw_report_wait", "mmw_report",
     "mmw_clouds_async", "mmw_clouds_wait", "mmw_clouds",
+    "mmw_skeletons_async", "mmw_skeletons_wait", "mmw_skeletons", "mmw_skeleton_tables",
     "mmw_uart_open", "mmw_uart_close", "mmw_uart_read", "mmw_uart_get_state", "mmw_uart_set_state", "mmw_uart_set_time",
 ]
 
@@ -181,6 +182,26 @@ class MmwCloudTrack(C.Structure):
 class MmwCloudPoint(C.Structure):
     """struct mmw_cloud_point (include/mmw.h): x, y, z in fp32 and the index of the point's directory entry."""
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("track", C.c_int32)]
+
+
+# struct mmw_skeleton (include/mmw.h): one live track's room-frame skeleton of mmw_skeletons_* (256 bytes, no padding)
+SKEL_JOINTS, SKEL_BONES = 19, 18
+SKELETON_DTYPE = np.dtype([("scene", "i4"), ("slot", "i4"), ("uid", "i4"), ("row", "i4"), ("flags", "i4"), ("gap", "f4"),
+                           ("joint", "f4", (SKEL_JOINTS, 3)), ("reserved_", "i4")], align=True)
+SKEL_SKIPPED = 1                              # MMW_SKEL_SKIPPED: bit 0 of mmw_skeleton.flags
+SKEL_ALL, SKEL_DRAWN = 0, 1                   # MMW_SKEL_*: the mode of mmw_skeletons_*
+SKEL_TICKETS = 4                              # mmw_skeletons_async calls that may be outstanding (mmw_skeletons itself uses the last ticket)
+SKEL_CLASS_NAMES = ("blue", "green", "red")   # mmw_skeleton_tables' joint classes as the reference's colour names
+
+
+def skeleton_tables():
+    """mmw_skeleton_tables (host only, no GPU): (connections int32[18, 2] -- the bones as joint index pairs, in the order the
+    reference draws them --, joint_class int32[19]: 0 blue, 1 green, 2 red = the head)."""
+    conn, cls = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+    rc = load().mmw_skeleton_tables(C.byref(conn), C.byref(cls))
+    if rc:
+        raise MmwError(rc, "mmw_skeleton_tables")
+    return (np.ctypeslib.as_array(conn, (SKEL_BONES, 2)).astype(np.int32), np.ctypeslib.as_array(cls, (SKEL_JOINTS,)).astype(np.int32))
 
 
 _lib = None
@@ -378,6 +399,10 @@ def load():
         "mmw_clouds_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32]),
         "mmw_clouds_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_clouds": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32p, i32p]),
+        "mmw_skeletons_async": (C.c_int, [vp, vp, i32, i32, i32, i32]),
+        "mmw_skeletons_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_skeletons": (C.c_int, [vp, vp, i32, i32, i32, i32p, i32p]),
+        "mmw_skeleton_tables": (C.c_int, [C.POINTER(i32p), C.POINTER(i32p)]),
         "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
         "mmw_uart_close": (C.c_int, [vp]),
         "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),

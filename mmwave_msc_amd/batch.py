@@ -732,6 +732,48 @@ class SceneBatch:
             out = b_o.download((n_p,), _lib.CLOUD_POINT_DTYPE) if n_p else np.zeros(0, _lib.CLOUD_POINT_DTYPE)
         return d, out
 
+    # -- live-track skeletons -------------------------------------------------
+    def skeletons_dev(self, out_ptr, cap: int, mode: int = 0, ticket: int = 0, scene_base: int = 0):
+        """mmw_skeletons_async: every live track's room-frame skeleton (`_lib.SKELETON_DTYPE`: the keypoints mirrored and shifted
+        to the track's position as Visualizer.update_posture does, with its plausibility check in `flags` / `gap`) into a device
+        buffer, in the report's (scene, slot) order.  `_lib.SKEL_ALL`: one entry per live track, entry i is `report_host` row i;
+        `_lib.SKEL_DRAWN`: only the entries the reference draws, `row` keeping the report index.  Queued behind the last step on
+        the context's stream -- no host wait.  Tickets 0 .. 3 (`skeletons_host` uses 3).  `out_ptr` 16-byte aligned.  Called
+        between the step and `estimate_posture` it gives what main.py:56 displays (last frame's keypoints around this frame's
+        position), called after `estimate_posture` this frame's keypoints."""
+        self._chk(self.L.mmw_skeletons_async(self.h, out_ptr, int(cap), int(mode), int(scene_base), int(ticket)))
+
+    def skeletons_wait(self, ticket: int = 0):
+        """(n_out, n_live) of the `skeletons_dev` call with this ticket: waits for its counts only, not for the stream.  Buffer
+        too small: MmwError with code E_CAPACITY and both counts in `.needed` -- nothing was written."""
+        no, nl = C.c_int32(0), C.c_int32(0)
+        rc = self.L.mmw_skeletons_wait(self.h, int(ticket), C.byref(no), C.byref(nl))
+        if rc == _lib.E_CAPACITY:
+            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
+            err.needed = (int(no.value), int(nl.value))
+            raise err
+        self._chk(rc)
+        return int(no.value), int(nl.value)
+
+    def skeletons_host(self, drawn: bool = False, scene_base: int = 0) -> np.ndarray:
+        """The skeletons as a `_lib.SKELETON_DTYPE` array: one per live track (entry i is `report_host` row i), or with
+        drawn=True only those the reference's check lets through.  The device buffer is kept and grows to what the device says
+        it needs (one retry)."""
+        sdt = _lib.SKELETON_DTYPE
+        mode = _lib.SKEL_DRAWN if drawn else _lib.SKEL_ALL
+        cap = getattr(self, "_skel_cap", 64)
+        for attempt in (0, 1):
+            b = self.buf("skeletons", cap * sdt.itemsize)
+            self.skeletons_dev(b.ptr, cap, mode, _lib.SKEL_TICKETS - 1, scene_base)
+            try:
+                n_out, _ = self.skeletons_wait(_lib.SKEL_TICKETS - 1)
+                break
+            except MmwError as e:
+                if e.code != _lib.E_CAPACITY or attempt:
+                    raise
+                cap = self._skel_cap = max(cap, e.needed[0])
+        return b.download((n_out,), sdt) if n_out else np.zeros(0, sdt)
+
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):
         if scenes is None:

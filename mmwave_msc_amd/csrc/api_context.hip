@@ -404,6 +404,7 @@ int mmw_destroy(mmw_ctx *c)
     posture_batch_free(c->pb);
     report_free(c->rep);
     cloud_free(c->cloud);
+    skel_free(c->skel);
     if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->side_gate) hipEventDestroy(c->side_gate);
     if (c->own_stream) hipStreamDestroy(c->own_stream);

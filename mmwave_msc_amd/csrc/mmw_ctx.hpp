@@ -50,6 +50,15 @@ struct CloudCtx {
     bool issued[kTickets] = {false, false, false, false};
 };
 
+// mmw_skeletons_*: the scratch of the live-track skeletons (allocated by the first call), the pinned counts of the outstanding calls
+struct SkelCtx {
+    SkelState ks = {};
+    char *d_block = nullptr;          // one allocation behind ks
+    int32_t *h_counts = nullptr;      // pinned [kTickets][4]: entries, live tracks, fits -- as SkelState::totals
+    hipEvent_t ev[kTickets] = {nullptr, nullptr, nullptr, nullptr};
+    bool issued[kTickets] = {false, false, false, false};
+};
+
 struct mmw_ctx {
     mmw_config cfg;
     DevCfg dc;
@@ -99,6 +108,7 @@ struct mmw_ctx {
     PostureBatch *pb = nullptr;       // mmw_posture_attach (any number of scenes); independent of the one-scene chain above
     ReportCtx *rep = nullptr;         // mmw_report_enable; nullptr = reports are off and nothing of them is launched
     CloudCtx *cloud = nullptr;        // mmw_clouds_*: allocated by the first call; nullptr = never called, nothing of it exists
+    SkelCtx *skel = nullptr;          // mmw_skeletons_*: allocated by the first call; nullptr = never called, nothing of it exists
     UartState uart = {};              // mmw_uart_open: the radar readers' state (uart.buf is the allocation, uart.scene lies behind the buffers); nullptr = closed
     // profiling
     unsigned prof_mask = 0;           // bit k: time kernel id k (mmw_profile_enable)
@@ -118,6 +128,7 @@ void posture_batch_free(PostureBatch *b);                          // api_postur
 void report_free(ReportCtx *r);                                    // api_report.hip
 int report_rebase(mmw_ctx *c, const int32_t *dev_flags);           // api_report.hip: the scenes' uids restart (no-op while reports are off)
 void cloud_free(CloudCtx *k);                                      // api_cloud.hip
+void skel_free(SkelCtx *k);                                        // api_skeleton.hip
 #pragma GCC visibility pop
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)

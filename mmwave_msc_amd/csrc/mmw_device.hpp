@@ -181,6 +181,11 @@ struct CloudState {
     int32_t *off;         // [2][S + 1] directory entries / points per scene of the call in flight, scanned in place; [S] = the total
     int32_t *totals;      // [4] entries, points (saturated at INT32_MAX), 1 = both fit the caller's buffers (the device's capacity decision)
 };
+// mmw_skeletons_*: the scratch of the live-track skeletons (k_skeleton.hip).  All device memory; nothing is kept between two calls.
+struct SkelState {
+    int32_t *off;         // [2][S + 1] live tracks / emitted entries per scene of the call in flight, scanned in place; [S] = the total
+    int32_t *totals;      // [4] entries the mode needs, live tracks, 1 = the entries fit the caller's buffer (the device's capacity decision)
+};
 // The update lists (track-wise Kalman kernels).  A scene's workgroup of k_track appends its T tracks to the list of its SHARD
 // (workgroup index mod shards: eight counters instead of one word that every workgroup of the launch adds to) with one atomicAdd;
 // the consumers' unit w serves shard w mod shards, entries 4 (w / shards) .. + 3, so the list entry and the list's length are ONE

@@ -13,6 +13,7 @@ struct DevState;
 struct ReportState;
 struct UartState;
 struct CloudState;
+struct SkelState;
 // k_track.hip, k_kalman.hip, k_scene.hip: the step
 size_t track_lds_bytes(const DevCfg &c);
 hipError_t prepare_track(const DevCfg &cfg);
@@ -59,6 +60,8 @@ void launch_report_rebase(const DevCfg &cfg, const ReportState &rp, const int32_
 void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ReportState &rp, mmw_track_report *rows, int cap_rows, mmw_track_event *events, int cap_events, int scene_base, hipStream_t st);
 // k_cloud.hip: the live tracks' point clouds (mode: MMW_CLOUD_POINTS / MMW_CLOUD_ROWS, | MMW_CLOUD_UNASSIGNED)
 void launch_clouds(const DevCfg &cfg, const DevState &s, const CloudState &cs, mmw_cloud_track *dir, int cap_tracks, void *out, int cap_points, int mode, int scene_base, hipStream_t st);
+// k_skeleton.hip: the live tracks' room-frame skeletons (mode: MMW_SKEL_ALL / MMW_SKEL_DRAWN)
+void launch_skeletons(const DevCfg &cfg, const DevState &s, const SkelState &ks, mmw_skeleton *out, int cap, int mode, int scene_base, hipStream_t st);
 // k_uart.hip: the device-resident radar readers
 void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);
