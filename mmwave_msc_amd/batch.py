@@ -636,6 +636,17 @@ class SceneBatch:
         self.track_table_dev(b.ptr, slots, scene_base)
         return b.download((self.S, slots), SUMMARY_DTYPE)
 
+    def _export_wait(self, wait, ticket: int):
+        """The two counts of an export's `*_wait` entry; E_CAPACITY becomes an MmwError that carries them in `.needed`."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        rc = wait(self.h, int(ticket), C.byref(a), C.byref(b))
+        if rc == _lib.E_CAPACITY:
+            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
+            err.needed = (int(a.value), int(b.value))
+            raise err
+        self._chk(rc)
+        return int(a.value), int(b.value)
+
     # -- live-track report ----------------------------------------------------
     def enable_report(self, on: bool = True):
         """mmw_report_enable: the tracks live now become the baseline of the next report (they produce no event); on=False
@@ -652,14 +663,7 @@ class SceneBatch:
         """(n_rows, n_events) of the `report_async` call with this ticket: waits for its counts only, not for the stream.
         Buffers too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written and the
         baseline is unchanged, so the same report can be asked for again with room."""
-        nr, ne = C.c_int32(0), C.c_int32(0)
-        rc = self.L.mmw_report_wait(self.h, int(ticket), C.byref(nr), C.byref(ne))
-        if rc == _lib.E_CAPACITY:
-            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
-            err.needed = (int(nr.value), int(ne.value))
-            raise err
-        self._chk(rc)
-        return int(nr.value), int(ne.value)
+        return self._export_wait(self.L.mmw_report_wait, ticket)
 
     def report_host(self, scene_base: int = 0):
         """The report as two structured arrays: (rows[n_rows] TRACK_REPORT_DTYPE, events[n_events] TRACK_EVENT_DTYPE).  A
@@ -694,14 +698,7 @@ class SceneBatch:
     def clouds_wait(self, ticket: int = 0):
         """(n_tracks, n_points) of the `clouds_dev` call with this ticket: waits for its counts only, not for the stream.  Buffers
         too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written."""
-        nt, npt = C.c_int32(0), C.c_int32(0)
-        rc = self.L.mmw_clouds_wait(self.h, int(ticket), C.byref(nt), C.byref(npt))
-        if rc == _lib.E_CAPACITY:
-            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
-            err.needed = (int(nt.value), int(npt.value))
-            raise err
-        self._chk(rc)
-        return int(nt.value), int(npt.value)
+        return self._export_wait(self.L.mmw_clouds_wait, ticket)
 
     def clouds_host(self, rows: bool = False, unassigned: bool = False, scene_base: int = 0):
         """(dir[n_tracks] CLOUD_TRACK_DTYPE, points[n_points] CLOUD_POINT_DTYPE) -- or, with rows=True, the ring rows
@@ -746,14 +743,7 @@ class SceneBatch:
     def skeletons_wait(self, ticket: int = 0):
         """(n_out, n_live) of the `skeletons_dev` call with this ticket: waits for its counts only, not for the stream.  Buffer
         too small: MmwError with code E_CAPACITY and both counts in `.needed` -- nothing was written."""
-        no, nl = C.c_int32(0), C.c_int32(0)
-        rc = self.L.mmw_skeletons_wait(self.h, int(ticket), C.byref(no), C.byref(nl))
-        if rc == _lib.E_CAPACITY:
-            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
-            err.needed = (int(no.value), int(nl.value))
-            raise err
-        self._chk(rc)
-        return int(no.value), int(nl.value)
+        return self._export_wait(self.L.mmw_skeletons_wait, ticket)
 
     def skeletons_host(self, drawn: bool = False, scene_base: int = 0) -> np.ndarray:
         """The skeletons as a `_lib.SKELETON_DTYPE` array: one per live track (entry i is `report_host` row i), or with

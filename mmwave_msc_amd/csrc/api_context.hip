@@ -402,9 +402,9 @@ int mmw_destroy(mmw_ctx *c)
     if (c->handback_ev) hipEventDestroy(c->handback_ev);
     if (c->h_rows) hipHostFree(c->h_rows);
     posture_batch_free(c->pb);
-    report_free(c->rep);
-    cloud_free(c->cloud);
-    skel_free(c->skel);
+    export_free(c->rep);
+    export_free(c->cloud);
+    export_free(c->skel);
     if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->side_gate) hipEventDestroy(c->side_gate);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -431,7 +431,7 @@ int mmw_reset_scenes(mmw_ctx *c, const int32_t *scene_flags)
     HIPCHK(c, hipSetDevice(c->device));
     return with_scene_flags(c, scene_flags, [&](const int32_t *f) {
         launch_reset(c->dc, c->st, f, c->stream);
-        if (c->rep) launch_report_rebase(c->dc, c->rep->rs, f, c->stream);   // (reports enabled: the reset scenes' uids restart)
+        if (c->rep.d_block) launch_report_rebase(c->dc, c->rs, f, c->stream);   // (reports enabled: the reset scenes' uids restart)
     });
 }
 

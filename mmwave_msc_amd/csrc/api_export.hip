@@ -1,0 +1,47 @@
+// api_export.hip -- what mmw_report_*, mmw_clouds_* and mmw_skeletons_* share on the host (not part of the ABI): the device scratch
+// that k_pair_scan works on, and the tickets -- the totals of every call follow its kernels into a pinned slot of their own, and a
+// wait is for that copy only.
+#include "mmw_ctx.hpp"
+
+void export_free(ExportCtx &x)
+{
+    if (x.d_block) hipFree(x.d_block);
+    if (x.h_counts) hipHostFree(x.h_counts);
+    for (int k = 0; k < kTickets; k++) if (x.ev[k]) hipEventDestroy(x.ev[k]);
+    x = ExportCtx();
+}
+
+int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name)
+{
+    const size_t S = c->dc.n_scenes;
+    const size_t words = extra_words + 2 * (S + 1) + 4;
+    if (hipMalloc((void **)&x.d_block, words * sizeof(int32_t)) != hipSuccess) { export_free(x); return fail(c, MMW_E_HIP, "%s: hipMalloc(%zu B) failed", name, words * sizeof(int32_t)); }
+    x.sc.off = reinterpret_cast<int32_t *>(x.d_block) + extra_words;
+    x.sc.totals = x.sc.off + 2 * (S + 1);
+    if (hipHostMalloc((void **)&x.h_counts, kTickets * 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { export_free(x); return fail(c, MMW_E_HIP, "%s: hipHostMalloc failed", name); }
+    memset(x.h_counts, 0, kTickets * 4 * sizeof(int32_t));
+    for (int k = 0; k < kTickets; k++)
+        if (hipEventCreateWithFlags(&x.ev[k], hipEventDisableTiming) != hipSuccess) { export_free(x); return fail(c, MMW_E_HIP, "%s: hipEventCreate failed", name); }
+    return MMW_OK;
+}
+
+int export_issue(mmw_ctx *c, ExportCtx &x, int ticket)
+{
+    HIPCHK(c, hipGetLastError());
+    // the counts and the capacity decision follow the kernels into pinned memory: export_wait(ticket) waits for THIS copy only
+    HIPCHK(c, hipMemcpyAsync(x.h_counts + ticket * 4, x.sc.totals, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(x.ev[ticket], c->stream));
+    x.issued[ticket] = true;
+    return MMW_OK;
+}
+
+int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const char *none, const int32_t **counts)
+{
+    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "%s: ticket %d outside [0, %d)", name, ticket, kTickets);
+    if (!x.issued[ticket]) return fail(c, MMW_E_ARG, "%s: %s outstanding under ticket %d", name, none, ticket);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(x.ev[ticket]));
+    x.issued[ticket] = false;
+    *counts = x.h_counts + ticket * 4;
+    return MMW_OK;
+}

@@ -1,38 +1,9 @@
 // api_skeleton.hip -- the C-ABI (include/mmw.h): the live tracks' room-frame skeletons.  mmw_skeletons_async queues the kernels of
 // k_skeleton.hip and the copy of the two counts, mmw_skeletons_wait waits for that copy.  The first call allocates the context's
 // scratch; mmw_destroy frees it.  mmw_skeleton_tables is host data only.
-#include <new>
-
 #include "mmw_ctx.hpp"
 
 static_assert(sizeof(mmw_skeleton) == 256, "mmw_skeleton: the numpy layout of mmwave_msc_amd/_lib.py");
-
-void skel_free(SkelCtx *k)
-{
-    if (!k) return;
-    if (k->d_block) hipFree(k->d_block);
-    if (k->h_counts) hipHostFree(k->h_counts);
-    for (int t = 0; t < kTickets; t++) if (k->ev[t]) hipEventDestroy(k->ev[t]);
-    delete k;
-}
-
-static int skel_alloc(mmw_ctx *c)
-{
-    SkelCtx *k = new (std::nothrow) SkelCtx();
-    if (!k) return fail(c, MMW_E_ARG, "out of host memory");
-    const size_t S = c->dc.n_scenes;
-    const size_t words = 2 * (S + 1) + 4;
-    if (hipMalloc((void **)&k->d_block, words * sizeof(int32_t)) != hipSuccess) { skel_free(k); return fail(c, MMW_E_HIP, "mmw_skeletons: hipMalloc(%zu B) failed", words * sizeof(int32_t)); }
-    int32_t *p = reinterpret_cast<int32_t *>(k->d_block);
-    k->ks.off = p; p += 2 * (S + 1);
-    k->ks.totals = p;
-    if (hipHostMalloc((void **)&k->h_counts, kTickets * 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { skel_free(k); return fail(c, MMW_E_HIP, "mmw_skeletons: hipHostMalloc failed"); }
-    memset(k->h_counts, 0, kTickets * 4 * sizeof(int32_t));
-    for (int t = 0; t < kTickets; t++)
-        if (hipEventCreateWithFlags(&k->ev[t], hipEventDisableTiming) != hipSuccess) { skel_free(k); return fail(c, MMW_E_HIP, "mmw_skeletons: hipEventCreate failed"); }
-    c->skel = k;
-    return MMW_OK;
-}
 
 int mmw_skeletons_async(mmw_ctx *c, mmw_skeleton *out, int32_t cap, int32_t mode, int32_t scene_base, int32_t ticket)
 {
@@ -42,27 +13,16 @@ int mmw_skeletons_async(mmw_ctx *c, mmw_skeleton *out, int32_t cap, int32_t mode
     if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_skeletons: ticket %d outside [0, %d)", ticket, kTickets);
     if (((uintptr_t)out & 15) != 0) return fail(c, MMW_E_ARG, "mmw_skeletons: out must be 16-byte aligned");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->skel) MMW_TRY(skel_alloc(c));
-    SkelCtx *k = c->skel;
-    launch_skeletons(c->dc, c->st, k->ks, out, cap, mode, scene_base, c->stream);
-    HIPCHK(c, hipGetLastError());
-    // the counts and the capacity decision follow the kernels into pinned memory: mmw_skeletons_wait(ticket) waits for THIS copy only
-    HIPCHK(c, hipMemcpyAsync(k->h_counts + ticket * 4, k->ks.totals, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(k->ev[ticket], c->stream));
-    k->issued[ticket] = true;
-    return MMW_OK;
+    if (!c->skel.d_block) MMW_TRY(export_alloc(c, c->skel, 0, "mmw_skeletons"));
+    launch_skeletons(c->dc, c->st, c->skel.sc, out, cap, mode, scene_base, c->stream);
+    return export_issue(c, c->skel, ticket);
 }
 
 int mmw_skeletons_wait(mmw_ctx *c, int32_t ticket, int32_t *n_out, int32_t *n_live)
 {
     if (!c) return MMW_E_ARG;
-    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_skeletons_wait: ticket %d outside [0, %d)", ticket, kTickets);
-    SkelCtx *k = c->skel;
-    if (!k || !k->issued[ticket]) return fail(c, MMW_E_ARG, "mmw_skeletons_wait: nothing outstanding under ticket %d", ticket);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(k->ev[ticket]));
-    k->issued[ticket] = false;
-    const int32_t *h = k->h_counts + ticket * 4;
+    const int32_t *h;
+    MMW_TRY(export_wait(c, c->skel, ticket, "mmw_skeletons_wait", "nothing", &h));
     if (n_out) *n_out = h[0];
     if (n_live) *n_live = h[1];
     if (!h[2]) return fail(c, MMW_E_CAPACITY, "mmw_skeletons: %d entries (%d live tracks) do not fit the buffer: nothing was written", h[0], h[1]);

@@ -3,7 +3,7 @@
 // order with a directory entry per cloud.  Reads SceneHdr, order, TrackRec and the two rings after the step, the way k_snap_pack
 // does; nothing of the step is touched and nothing is kept between two calls.
 //   k_cloud_count   entries and points per scene: a wave per scene, a lane per track (t_cap <= 64)
-//   k_cloud_scan    one workgroup: the two offset scans, the capacity decision, the totals (formed in 64 bits)
+//   k_pair_scan     (k_scan.hip) one workgroup: the two offset scans, the capacity decision, the totals (formed in 64 bits)
 //   k_cloud_write   a workgroup per scene: the directory and the rows (MMW_CLOUD_ROWS) or points (MMW_CLOUD_POINTS) -- only if everything fits
 //
 // The rings are slot-permuted: logical frame k (k-th oldest) lives in physical slot ring_slot[k] of the track's ring, g_slot[k] of
@@ -75,59 +75,19 @@ __device__ __forceinline__ int newest_rows(const Ring &r)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_cloud_count(DevCfg cfg, DevState st, CloudState cs, int unassigned)
+__global__ __launch_bounds__(256) void k_cloud_count(DevCfg cfg, DevState st, ExportScratch sc, int unassigned)
 {
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
     const SceneHdr *hdr = st.hdr + s;
-    const int T = clampi(hdr->n_tracks, 0, cfg.t_cap);
+    const int T = live_tracks(cfg, st, s);
     int rows = 0;
-    if (lane < T) rows = track_ring(cfg, st.trk + (size_t)s * cfg.t_cap + clampi(st.order[(size_t)s * cfg.t_cap + lane], 0, cfg.t_cap - 1)).stored;
+    if (lane < T) rows = track_ring(cfg, st.trk + (size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane)).stored;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o);
     if (lane == 0) {
-        cs.off[s] = T + (unassigned ? 1 : 0);
-        cs.off[cfg.n_scenes + 1 + s] = rows + (unassigned ? global_ring(cfg, hdr).stored : 0);
-    }
-}
-
-// single workgroup: in-place exclusive scans of the entry and the point counts (k_report_scan's shape), then the capacity decision
-// -- both totals, formed in 64 bits, against the caller's buffers -- which k_cloud_write and the host read.  A total above INT32_MAX
-// fits no buffer (the caps are int32) and is reported saturated; the per-scene offsets are then meaningless and nobody reads them.
-__global__ __launch_bounds__(1024) void k_cloud_scan(DevCfg cfg, CloudState cs, int cap_tracks, int cap_points)
-{
-    __shared__ long long part[2][1024];
-    const int tid = threadIdx.x, S = cfg.n_scenes;
-    const int per = (S + 1023) / 1024;
-    const int s0 = min(S, tid * per), s1 = min(S, s0 + per);
-    int32_t *off_e = cs.off, *off_p = cs.off + S + 1;
-    long long sum_e = 0, sum_p = 0;
-    for (int s = s0; s < s1; s++) { sum_e += off_e[s]; sum_p += off_p[s]; }
-    part[0][tid] = sum_e;
-    part[1][tid] = sum_p;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const long long ve = tid >= o ? part[0][tid - o] : 0, vp = tid >= o ? part[1][tid - o] : 0;
-        __syncthreads();
-        part[0][tid] += ve;
-        part[1][tid] += vp;
-        __syncthreads();
-    }
-    long long run_e = part[0][tid] - sum_e, run_p = part[1][tid] - sum_p;
-    for (int s = s0; s < s1; s++) {
-        const int ce = off_e[s], cp = off_p[s];
-        off_e[s] = (int32_t)run_e; run_e += ce;
-        off_p[s] = (int32_t)run_p; run_p += cp;
-    }
-    if (tid == 1023) {
-        const long long tot_e = part[0][1023], tot_p = part[1][1023], lim = 0x7fffffffLL;
-        const int32_t te = (int32_t)(tot_e < lim ? tot_e : lim), tp = (int32_t)(tot_p < lim ? tot_p : lim);
-        off_e[S] = te;
-        off_p[S] = tp;
-        cs.totals[0] = te;
-        cs.totals[1] = tp;
-        cs.totals[2] = (tot_e <= (long long)cap_tracks && tot_p <= (long long)cap_points) ? 1 : 0;
-        cs.totals[3] = 0;
+        sc.off[s] = T + (unassigned ? 1 : 0);
+        sc.off[cfg.n_scenes + 1 + s] = rows + (unassigned ? global_ring(cfg, hdr).stored : 0);
     }
 }
 
@@ -167,15 +127,15 @@ __device__ __forceinline__ void move_rows(const double *__restrict__ src, int n,
 // walk its frames oldest first through the slot permutation.  The global ring (up to ring x max_pts rows, many times a track's)
 // is moved by all four waves together.
 template <int MODE>
-__global__ __launch_bounds__(256) void k_cloud_write(DevCfg cfg, DevState st, CloudState cs, mmw_cloud_track *__restrict__ dir, void *__restrict__ out,
+__global__ __launch_bounds__(256) void k_cloud_write(DevCfg cfg, DevState st, ExportScratch sc, mmw_cloud_track *__restrict__ dir, void *__restrict__ out,
                                                      int unassigned, int scene_base)
 {
-    if (!cs.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer is written
+    if (!sc.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer is written
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int s = blockIdx.x, S = cfg.n_scenes;
     const SceneHdr *hdr = st.hdr + s;
-    const int T = clampi(hdr->n_tracks, 0, cfg.t_cap);
-    const int e0 = cs.off[s], p0 = cs.off[S + 1 + s];
+    const int T = live_tracks(cfg, st, s);
+    const int e0 = sc.off[s], p0 = sc.off[S + 1 + s];
 
     Ring r;
     r.len = r.stored = r.dropped = 0;
@@ -183,7 +143,7 @@ __global__ __launch_bounds__(256) void k_cloud_write(DevCfg cfg, DevState st, Cl
     for (int k = 0; k < MMW_RING_MAX; k++) r.n[k] = r.phys[k] = 0;
     int rslot = 0, uid = -1;
     if (lane < T) {
-        rslot = clampi(st.order[(size_t)s * cfg.t_cap + lane], 0, cfg.t_cap - 1);
+        rslot = live_slot(cfg, st, s, lane);
         const TrackRec *rec = st.trk + (size_t)s * cfg.t_cap + rslot;
         r = track_ring(cfg, rec);
         uid = rec->uid;
@@ -223,14 +183,14 @@ __global__ __launch_bounds__(256) void k_cloud_write(DevCfg cfg, DevState st, Cl
     }
 }
 
-void launch_clouds(const DevCfg &cfg, const DevState &s, const CloudState &cs, mmw_cloud_track *dir, int cap_tracks, void *out, int cap_points, int mode,
+void launch_clouds(const DevCfg &cfg, const DevState &s, const ExportScratch &sc, mmw_cloud_track *dir, int cap_tracks, void *out, int cap_points, int mode,
                    int scene_base, hipStream_t st)
 {
     const int unassigned = (mode & MMW_CLOUD_UNASSIGNED) ? 1 : 0;
-    hipLaunchKernelGGL(k_cloud_count, dim3((cfg.n_scenes + 3) / 4), dim3(256), 0, st, cfg, s, cs, unassigned);
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, cfg, cs, cap_tracks, cap_points);
-    if (mode & MMW_CLOUD_ROWS) hipLaunchKernelGGL(k_cloud_write<MMW_CLOUD_ROWS>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, cs, dir, out, unassigned, scene_base);
-    else hipLaunchKernelGGL(k_cloud_write<MMW_CLOUD_POINTS>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, cs, dir, out, unassigned, scene_base);
+    hipLaunchKernelGGL(k_cloud_count, dim3((cfg.n_scenes + 3) / 4), dim3(256), 0, st, cfg, s, sc, unassigned);
+    launch_pair_scan(cfg.n_scenes, sc.off, sc.totals, cap_tracks, cap_points, st);
+    if (mode & MMW_CLOUD_ROWS) hipLaunchKernelGGL(k_cloud_write<MMW_CLOUD_ROWS>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, sc, dir, out, unassigned, scene_base);
+    else hipLaunchKernelGGL(k_cloud_write<MMW_CLOUD_POINTS>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, sc, dir, out, unassigned, scene_base);
 }
 
 }  // namespace mmw

@@ -12,6 +12,7 @@
 #include "mmw_device.hpp"
 #include "mmw_math.hpp"
 #include "mmw_normalize.hpp"
+#include "mmw_scan.hpp"
 #include "mmw_summary.hpp"
 #include "mmw_launch.hpp"
 #include "mmw_kernels.hpp"
@@ -140,12 +141,9 @@ __global__ __launch_bounds__(256) void k_feat_count(DevCfg cfg, DevState st, int
 {
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
-    const SceneHdr *hdr = st.hdr + s;
-    const int32_t *order = st.order + (size_t)s * cfg.t_cap;
-    const TrackRec *trk = st.trk + (size_t)s * cfg.t_cap;
     bool elig = false;
-    if (lane < hdr->n_tracks) {
-        const TrackRec *rec = trk + order[lane];
+    if (lane < live_tracks(cfg, st, s)) {
+        const TrackRec *rec = st.trk + (size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane);
         const int rl = rec->ring_len;
         int total = 0;
 #pragma unroll
@@ -166,13 +164,7 @@ __global__ __launch_bounds__(1024) void k_feat_scan(DevCfg cfg, int32_t *__restr
     int sum = 0;
     for (int s = s0; s < s1; s++) sum += row_off[s];
     part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
+    workgroup_scan_1024(tid, scan_lane<ScanAdd>(part));
     int run = part[tid] - sum;
     for (int s = s0; s < s1; s++) { const int c = row_off[s]; row_off[s] = run; run += c; }
     if (tid == 1023) row_off[S] = part[1023];

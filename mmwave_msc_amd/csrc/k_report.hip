@@ -4,7 +4,7 @@
 //   k_report_baseline  the baseline of mmw_report_enable: the uids live now
 //   k_report_rebase    mmw_reset / mmw_reset_scenes / mmw_restore: the touched scenes' generation word
 //   k_report_count     rows and events per scene: a wave per scene, a lane per track (t_cap <= 64)
-//   k_report_scan      one workgroup: the two offset scans, the capacity decision, the totals
+//   k_pair_scan        (k_scan.hip) one workgroup: the two offset scans, the capacity decision, the totals
 //   k_report_write     rows (staged in LDS, stored as contiguous 16-byte pieces), events, the new baseline -- only if everything fits
 #include <cstddef>
 #include "mmw_device.hpp"
@@ -36,10 +36,10 @@ struct SceneDiff {
 __device__ __forceinline__ SceneDiff scene_diff(const DevCfg &cfg, const DevState &st, const ReportState &rp, int s, int lane)
 {
     SceneDiff d;
-    d.T = min(st.hdr[s].n_tracks, cfg.t_cap);
+    d.T = live_tracks(cfg, st, s);
     d.Tb = min(rp.base_len[s], cfg.t_cap);
     d.rebased = rp.gen[s] != rp.seen[s];
-    d.cuid = lane < d.T ? st.trk[(size_t)s * cfg.t_cap + st.order[(size_t)s * cfg.t_cap + lane]].uid : -1;
+    d.cuid = lane < d.T ? st.trk[(size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane)].uid : -1;
     d.buid = lane < d.Tb ? rp.base_uid[(size_t)s * cfg.t_cap + lane] : -1;
     bool in_base = false, in_cur = false;
     const int n = max(d.T, d.Tb);
@@ -58,8 +58,8 @@ __global__ __launch_bounds__(256) void k_report_baseline(DevCfg cfg, DevState st
 {
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
-    const int T = min(st.hdr[s].n_tracks, cfg.t_cap);
-    if (lane < T) rp.base_uid[(size_t)s * cfg.t_cap + lane] = st.trk[(size_t)s * cfg.t_cap + st.order[(size_t)s * cfg.t_cap + lane]].uid;
+    const int T = live_tracks(cfg, st, s);
+    if (lane < T) rp.base_uid[(size_t)s * cfg.t_cap + lane] = st.trk[(size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane)].uid;
     if (lane == 0) { rp.base_len[s] = T; rp.gen[s] = 0; rp.seen[s] = 0; }
 }
 
@@ -76,46 +76,8 @@ __global__ __launch_bounds__(256) void k_report_count(DevCfg cfg, DevState st, R
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
     const SceneDiff d = scene_diff(cfg, st, rp, s, lane);
     if (lane == 0) {
-        rp.off[s] = d.T;
-        rp.off[cfg.n_scenes + 1 + s] = d.rebased ? 1 : __popcll(d.born) + __popcll(d.gone);
-    }
-}
-
-// single workgroup: in-place exclusive scans of the row and the event counts (k_feat_scan's shape, twice), then the capacity
-// decision -- both totals against the caller's buffers -- which k_report_write and the host read
-__global__ __launch_bounds__(1024) void k_report_scan(DevCfg cfg, ReportState rp, int cap_rows, int cap_events)
-{
-    __shared__ int part[2][1024];
-    const int tid = threadIdx.x, S = cfg.n_scenes;
-    const int per = (S + 1023) / 1024;
-    const int s0 = tid * per, s1 = min(S, s0 + per);
-    int32_t *off_r = rp.off, *off_e = rp.off + S + 1;
-    int sum_r = 0, sum_e = 0;
-    for (int s = s0; s < s1; s++) { sum_r += off_r[s]; sum_e += off_e[s]; }
-    part[0][tid] = sum_r;
-    part[1][tid] = sum_e;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int vr = tid >= o ? part[0][tid - o] : 0, ve = tid >= o ? part[1][tid - o] : 0;
-        __syncthreads();
-        part[0][tid] += vr;
-        part[1][tid] += ve;
-        __syncthreads();
-    }
-    int run_r = part[0][tid] - sum_r, run_e = part[1][tid] - sum_e;
-    for (int s = s0; s < s1; s++) {
-        const int cr = off_r[s], ce = off_e[s];
-        off_r[s] = run_r; run_r += cr;
-        off_e[s] = run_e; run_e += ce;
-    }
-    if (tid == 1023) {
-        const int tot_r = part[0][1023], tot_e = part[1][1023];
-        off_r[S] = tot_r;
-        off_e[S] = tot_e;
-        rp.totals[0] = tot_r;
-        rp.totals[1] = tot_e;
-        rp.totals[2] = (tot_r <= cap_rows && tot_e <= cap_events) ? 1 : 0;
-        rp.totals[3] = 0;
+        rp.sc.off[s] = d.T;
+        rp.sc.off[cfg.n_scenes + 1 + s] = d.rebased ? 1 : __popcll(d.born) + __popcll(d.gone);
     }
 }
 
@@ -129,12 +91,12 @@ __global__ __launch_bounds__(256) void k_report_write(DevCfg cfg, const mmw_scen
                                                       mmw_track_report *__restrict__ rows, mmw_track_event *__restrict__ events, int scene_base)
 {
     __shared__ __attribute__((aligned(16))) uint32_t stage[4][kStageWords];
-    if (!rp.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer, the baseline nor a generation is written
+    if (!rp.sc.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer, the baseline nor a generation is written
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int s = blockIdx.x * 4 + wave, S = cfg.n_scenes;
     if (s >= S) return;          // (wave-uniform)
     const SceneDiff d = scene_diff(cfg, st, rp, s, lane);
-    const int row0 = rp.off[s], ev0 = rp.off[S + 1 + s];
+    const int row0 = rp.sc.off[s], ev0 = rp.sc.off[S + 1 + s];
     const unsigned long long lt = lanemask_lt();
 
     // events: GONE in baseline order, then BORN in current order; a rebased scene's single event instead
@@ -159,7 +121,7 @@ __global__ __launch_bounds__(256) void k_report_write(DevCfg cfg, const mmw_scen
         const int sh = (int)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3);   // words past a 16-byte boundary
         if (lane >= c && lane < c + n) {
             mmw_track_report *o = reinterpret_cast<mmw_track_report *>(lds + sh + (lane - c) * kRowWords);
-            const TrackRec *rec = st.trk + (size_t)s * cfg.t_cap + st.order[(size_t)s * cfg.t_cap + lane];
+            const TrackRec *rec = st.trk + (size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane);
             o->scene = scene_base + s;
             o->slot = lane;
             o->uid = d.cuid;
@@ -194,7 +156,9 @@ void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevStat
 {
     const dim3 grid((cfg.n_scenes + 3) / 4);
     hipLaunchKernelGGL(k_report_count, grid, dim3(256), 0, st, cfg, s, rp);
-    hipLaunchKernelGGL(k_report_scan, dim3(1), dim3(1024), 0, st, cfg, rp, cap_rows, cap_events);
+    // (rows <= S * t_cap, events <= 2 * S * t_cap: below 2^31, so the scan's saturation at INT32_MAX never fires for a report)
+    static_assert(2LL * kUpdMaxScenes * MMW_TRACK_CAP_LIMIT < (1LL << 31), "a report's totals fit an int32");
+    launch_pair_scan(cfg.n_scenes, rp.sc.off, rp.sc.totals, cap_rows, cap_events, st);
     if (sites) hipLaunchKernelGGL(k_report_write<true>, grid, dim3(256), 0, st, cfg, sites, s, rp, rows, events, scene_base);
     else hipLaunchKernelGGL(k_report_write<false>, grid, dim3(256), 0, st, cfg, sites, s, rp, rows, events, scene_base);
 }

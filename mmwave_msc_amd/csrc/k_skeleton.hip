@@ -2,9 +2,9 @@
 // track's position, with the plausibility check of Visualizer.update_posture (Visualizer.py:265-307), compacted into one output in
 // the report's (scene, slot) order.  Reads SceneHdr, order and TrackRec after the step, the way k_report and k_cloud do; nothing of
 // the step is touched, nothing is written to the state and nothing is kept between two calls.
-//   k_skel_count   live tracks and emitted entries per scene: a wave per scene, a lane per track (t_cap <= 64)
-//   k_skel_scan    one workgroup: the two offset scans (all live tracks -> `row`, emitted entries -> the position), the capacity
-//                  decision, the totals
+//   k_skel_count   emitted entries and live tracks per scene: a wave per scene, a lane per track (t_cap <= 64)
+//   k_pair_scan    (k_scan.hip) one workgroup: the two offset scans (emitted entries -> the position, all live tracks -> `row`),
+//                  the capacity decision on the emitted total, the totals
 //   k_skel_write   a wave per scene: 16 lanes own one entry's sixteen 16-byte pieces -- only if everything fits
 //
 // The arithmetic (include/mmw.h): kp viewed as reshape(3, 19), row 1 the height, row 2 the depth.
@@ -46,57 +46,18 @@ __device__ __forceinline__ SkelCheck skel_check(const TrackRec *rec)
 __device__ __forceinline__ const TrackRec *skel_track(const DevCfg &cfg, const DevState &st, int s, int lane, int T)
 {
     if (lane >= T) return nullptr;
-    const int slot = min(max(st.order[(size_t)s * cfg.t_cap + lane], 0), cfg.t_cap - 1);
-    return st.trk + (size_t)s * cfg.t_cap + slot;
+    return st.trk + (size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane);
 }
 
-__global__ __launch_bounds__(256) void k_skel_count(DevCfg cfg, DevState st, SkelState ks, int mode)
+__global__ __launch_bounds__(256) void k_skel_count(DevCfg cfg, DevState st, ExportScratch sc, int mode)
 {
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
-    const int T = min(max(st.hdr[s].n_tracks, 0), cfg.t_cap);
+    const int T = live_tracks(cfg, st, s);
     const unsigned long long skipped = __ballot(skel_check(skel_track(cfg, st, s, lane, T)).skipped);
     if (lane == 0) {
-        ks.off[s] = T;
-        ks.off[cfg.n_scenes + 1 + s] = mode == MMW_SKEL_DRAWN ? T - __popcll(skipped) : T;
-    }
-}
-
-// single workgroup: in-place exclusive scans of the live and the emitted counts (k_report_scan's shape), then the capacity decision
-// -- the emitted total against the caller's buffer -- which k_skel_write and the host read
-__global__ __launch_bounds__(1024) void k_skel_scan(DevCfg cfg, SkelState ks, int cap)
-{
-    __shared__ int part[2][1024];
-    const int tid = threadIdx.x, S = cfg.n_scenes;
-    const int per = (S + 1023) / 1024;
-    const int s0 = min(S, tid * per), s1 = min(S, s0 + per);
-    int32_t *off_l = ks.off, *off_e = ks.off + S + 1;
-    int sum_l = 0, sum_e = 0;
-    for (int s = s0; s < s1; s++) { sum_l += off_l[s]; sum_e += off_e[s]; }
-    part[0][tid] = sum_l;
-    part[1][tid] = sum_e;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int vl = tid >= o ? part[0][tid - o] : 0, ve = tid >= o ? part[1][tid - o] : 0;
-        __syncthreads();
-        part[0][tid] += vl;
-        part[1][tid] += ve;
-        __syncthreads();
-    }
-    int run_l = part[0][tid] - sum_l, run_e = part[1][tid] - sum_e;
-    for (int s = s0; s < s1; s++) {
-        const int cl = off_l[s], ce = off_e[s];
-        off_l[s] = run_l; run_l += cl;
-        off_e[s] = run_e; run_e += ce;
-    }
-    if (tid == 1023) {
-        const int tot_l = part[0][1023], tot_e = part[1][1023];
-        off_l[S] = tot_l;
-        off_e[S] = tot_e;
-        ks.totals[0] = tot_e;
-        ks.totals[1] = tot_l;
-        ks.totals[2] = tot_e <= cap ? 1 : 0;
-        ks.totals[3] = 0;
+        sc.off[s] = mode == MMW_SKEL_DRAWN ? T - __popcll(skipped) : T;
+        sc.off[cfg.n_scenes + 1 + s] = T;
     }
 }
 
@@ -122,13 +83,13 @@ __device__ __forceinline__ uint32_t skel_word(int w, int c, float k, double x0, 
 // the scene's emitted entries).  Then the wave takes four tracks at a time: 16 lanes own one entry's 16 pieces, each lane loads the
 // four keypoints its words are formed from, forms the words without a branch and stores them as ONE 16-byte piece -- the 16 lanes of an entry write its 256
 // bytes contiguously, the wave 1 KiB per instruction in MMW_SKEL_ALL.  A skipped track's lanes store nothing in MMW_SKEL_DRAWN.
-__global__ __launch_bounds__(256) void k_skel_write(DevCfg cfg, DevState st, SkelState ks, mmw_skeleton *__restrict__ out, int mode, int scene_base)
+__global__ __launch_bounds__(256) void k_skel_write(DevCfg cfg, DevState st, ExportScratch sc, mmw_skeleton *__restrict__ out, int mode, int scene_base)
 {
-    if (!ks.totals[2]) return;   // (uniform over the launch) the entries do not fit: nothing is written
+    if (!sc.totals[2]) return;   // (uniform over the launch) the entries do not fit: nothing is written
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, S = cfg.n_scenes;
     if (s >= S) return;          // (wave-uniform)
-    const int T = min(max(st.hdr[s].n_tracks, 0), cfg.t_cap);
-    const int row0 = ks.off[s], e0 = ks.off[S + 1 + s];
+    const int T = live_tracks(cfg, st, s);
+    const int row0 = sc.off[S + 1 + s], e0 = sc.off[s];
 
     const TrackRec *mine = skel_track(cfg, st, s, lane, T);
     const SkelCheck chk = skel_check(mine);
@@ -160,12 +121,12 @@ __global__ __launch_bounds__(256) void k_skel_write(DevCfg cfg, DevState st, Ske
     }
 }
 
-void launch_skeletons(const DevCfg &cfg, const DevState &s, const SkelState &ks, mmw_skeleton *out, int cap, int mode, int scene_base, hipStream_t st)
+void launch_skeletons(const DevCfg &cfg, const DevState &s, const ExportScratch &sc, mmw_skeleton *out, int cap, int mode, int scene_base, hipStream_t st)
 {
     const dim3 grid((cfg.n_scenes + 3) / 4);
-    hipLaunchKernelGGL(k_skel_count, grid, dim3(256), 0, st, cfg, s, ks, mode);
-    hipLaunchKernelGGL(k_skel_scan, dim3(1), dim3(1024), 0, st, cfg, ks, cap);
-    hipLaunchKernelGGL(k_skel_write, grid, dim3(256), 0, st, cfg, s, ks, out, mode, scene_base);
+    hipLaunchKernelGGL(k_skel_count, grid, dim3(256), 0, st, cfg, s, sc, mode);
+    launch_pair_scan(cfg.n_scenes, sc.off, sc.totals, cap, INT32_MAX, st);   // (emitted, live: only the emitted entries need room)
+    hipLaunchKernelGGL(k_skel_write, grid, dim3(256), 0, st, cfg, s, sc, out, mode, scene_base);
 }
 
 }  // namespace mmw

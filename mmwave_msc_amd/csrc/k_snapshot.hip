@@ -24,6 +24,7 @@
 // perm[] is a schedule, any permutation gives the same results.
 #include "mmw_device.hpp"
 #include "mmw_kalman.hpp"
+#include "mmw_scan.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -140,15 +141,7 @@ __global__ __launch_bounds__(1024) void k_snap_scan(int n, unsigned long long ba
     for (int i = i0; i < i1; i++) { sum += bytes[i]; mt = max(mt, dir[i].n_tracks); }
     part[tid] = sum;
     tmax[tid] = mt;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const unsigned long long v = tid >= o ? part[tid - o] : 0ULL;
-        const int m = tid >= o ? tmax[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        tmax[tid] = max(tmax[tid], m);
-        __syncthreads();
-    }
+    workgroup_scan_1024(tid, scan_lane<ScanAdd>(part), scan_lane<ScanMax>(tmax));
     unsigned long long run = base + part[tid] - sum;
     for (int i = i0; i < i1; i++) { dir[i].offset = run; run += bytes[i]; }
     if (tid == 1023) { bytes[n] = base + part[1023]; bytes[n + 1] = (unsigned long long)tmax[1023]; }

@@ -32,29 +32,12 @@ struct PostureBatch {
     hipEvent_t total_ev = nullptr;
 };
 
-// mmw_report_enable: the baseline and scratch of the live-track report, the pinned counts of the outstanding reports
-struct ReportCtx {
-    ReportState rs = {};
-    char *d_block = nullptr;          // one allocation behind rs
-    int32_t *h_counts = nullptr;      // pinned [kTickets][4]: rows, events, fits -- as ReportState::totals
-    hipEvent_t ev[kTickets] = {nullptr, nullptr, nullptr, nullptr};
-    bool issued[kTickets] = {false, false, false, false};
-};
-
-// mmw_clouds_*: the scratch of the live-track point clouds (allocated by the first call), the pinned counts of the outstanding calls
-struct CloudCtx {
-    CloudState cs = {};
-    char *d_block = nullptr;          // one allocation behind cs
-    int32_t *h_counts = nullptr;      // pinned [kTickets][4]: entries, points, fits -- as CloudState::totals
-    hipEvent_t ev[kTickets] = {nullptr, nullptr, nullptr, nullptr};
-    bool issued[kTickets] = {false, false, false, false};
-};
-
-// mmw_skeletons_*: the scratch of the live-track skeletons (allocated by the first call), the pinned counts of the outstanding calls
-struct SkelCtx {
-    SkelState ks = {};
-    char *d_block = nullptr;          // one allocation behind ks
-    int32_t *h_counts = nullptr;      // pinned [kTickets][4]: entries, live tracks, fits -- as SkelState::totals
+// What the three live-track exports (mmw_report_*, mmw_clouds_*, mmw_skeletons_*) keep on the host: the device scratch of the call
+// in flight and the pinned counts of the outstanding calls, one slot per ticket (api_export.hip).  d_block == nullptr: not allocated.
+struct ExportCtx {
+    ExportScratch sc = {};
+    char *d_block = nullptr;          // one allocation: [extra words of the owner | sc.off | sc.totals]
+    int32_t *h_counts = nullptr;      // pinned [kTickets][4]: as ExportScratch::totals
     hipEvent_t ev[kTickets] = {nullptr, nullptr, nullptr, nullptr};
     bool issued[kTickets] = {false, false, false, false};
 };
@@ -106,9 +89,10 @@ struct mmw_ctx {
     float *pc_feat = nullptr, *pc_act = nullptr, *pc_hidden = nullptr, *pc_kp = nullptr;
     int32_t *pc_owner = nullptr;
     PostureBatch *pb = nullptr;       // mmw_posture_attach (any number of scenes); independent of the one-scene chain above
-    ReportCtx *rep = nullptr;         // mmw_report_enable; nullptr = reports are off and nothing of them is launched
-    CloudCtx *cloud = nullptr;        // mmw_clouds_*: allocated by the first call; nullptr = never called, nothing of it exists
-    SkelCtx *skel = nullptr;          // mmw_skeletons_*: allocated by the first call; nullptr = never called, nothing of it exists
+    ExportCtx rep;                    // mmw_report_enable; not allocated = reports are off and nothing of them is launched
+    ReportState rs = {};              // ... the report's baseline, in front of rep's scratch in rep.d_block (rs.sc = rep.sc)
+    ExportCtx cloud;                  // mmw_clouds_*: allocated by the first call; not allocated = never called, nothing of it exists
+    ExportCtx skel;                   // mmw_skeletons_*: allocated by the first call; not allocated = never called, nothing of it exists
     UartState uart = {};              // mmw_uart_open: the radar readers' state (uart.buf is the allocation, uart.scene lies behind the buffers); nullptr = closed
     // profiling
     unsigned prof_mask = 0;           // bit k: time kernel id k (mmw_profile_enable)
@@ -125,10 +109,12 @@ int probe_side_streams(mmw_ctx *c);                                // api_contex
 int read_headers(mmw_ctx *c, std::vector<SceneHdr> &h);            // api_query.hip
 int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q);   // api_query.hip
 void posture_batch_free(PostureBatch *b);                          // api_posture.hip
-void report_free(ReportCtx *r);                                    // api_report.hip
 int report_rebase(mmw_ctx *c, const int32_t *dev_flags);           // api_report.hip: the scenes' uids restart (no-op while reports are off)
-void cloud_free(CloudCtx *k);                                      // api_cloud.hip
-void skel_free(SkelCtx *k);                                        // api_skeleton.hip
+// api_export.hip: the ticketed counts of the three live-track exports (`name`: the entry the messages speak for)
+int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name);   // extra_words int32 in front of the scratch, at x.d_block
+void export_free(ExportCtx &x);                                    // ... and x is as never allocated
+int export_issue(mmw_ctx *c, ExportCtx &x, int ticket);           // behind the launch: its error, the totals into the ticket's pinned slot, the event
+int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const char *none, const int32_t **counts);   // -> the ticket's four words
 #pragma GCC visibility pop
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)

@@ -167,25 +167,29 @@ struct DevState {
     char *huge_scratch;            // [workers][huge_stride] BallTree carve-ups of the clouds of more than kBigCloudMax points (k_dbscan_huge); null when no ring of the context can hold one
     size_t huge_stride;
 };
+// The scratch of one live-track export's call in flight (k_report.hip, k_cloud.hip, k_skeleton.hip; scanned by k_scan.hip).  All
+// device memory; nothing is kept between two calls.  What the two counts are:
+//   report     rows, events          clouds     directory entries, points          skeletons  emitted entries, live tracks
+struct ExportScratch {
+    int32_t *off;         // [2][S + 1] the two counts per scene, scanned in place into offsets; [S] = the total
+    int32_t *totals;      // [4] the two totals (saturated at INT32_MAX), 1 = both fit the caller's capacities (the device's decision), 0
+};
 // mmw_report_enable: what the live-track report keeps between two reports (k_report.hip).  All device memory.
 struct ReportState {
     int32_t *base_uid;    // [S][t_cap] the uids live at the previous report, in effective_tracks order as it was then (the BASELINE)
     int32_t *base_len;    // [S] ... and how many
     int32_t *gen;         // [S] generation of the scene's uids: bumped by mmw_reset / mmw_reset_scenes / mmw_restore (uids restart there)
     int32_t *seen;        // [S] the generation the baseline was taken in
-    int32_t *off;         // [2][S + 1] rows / events per scene of the report in flight, scanned in place; [S] = the total
-    int32_t *totals;      // [4] rows, events, 1 = both fit the caller's buffers (the device's capacity decision)
+    ExportScratch sc;     // rows / events of the report in flight
 };
-// mmw_clouds_*: the scratch of the live-track point clouds (k_cloud.hip).  All device memory; nothing is kept between two calls.
-struct CloudState {
-    int32_t *off;         // [2][S + 1] directory entries / points per scene of the call in flight, scanned in place; [S] = the total
-    int32_t *totals;      // [4] entries, points (saturated at INT32_MAX), 1 = both fit the caller's buffers (the device's capacity decision)
-};
-// mmw_skeletons_*: the scratch of the live-track skeletons (k_skeleton.hip).  All device memory; nothing is kept between two calls.
-struct SkelState {
-    int32_t *off;         // [2][S + 1] live tracks / emitted entries per scene of the call in flight, scanned in place; [S] = the total
-    int32_t *totals;      // [4] entries the mode needs, live tracks, 1 = the entries fit the caller's buffer (the device's capacity decision)
-};
+
+// The live list of scene s, as every export walks it: T = live_tracks lanes, lane -> live_slot -> the scene's TrackRec.  Both are
+// clamped into range, so a damaged state gives the same list -- report row i, cloud entry i, skeleton i -- in every export.
+__device__ __forceinline__ int live_tracks(const DevCfg &cfg, const DevState &st, int s) { return min(max(st.hdr[s].n_tracks, 0), cfg.t_cap); }
+__device__ __forceinline__ int live_slot(const DevCfg &cfg, const DevState &st, int s, int lane)
+{
+    return min(max(st.order[(size_t)s * cfg.t_cap + lane], 0), cfg.t_cap - 1);
+}
 // The update lists (track-wise Kalman kernels).  A scene's workgroup of k_track appends its T tracks to the list of its SHARD
 // (workgroup index mod shards: eight counters instead of one word that every workgroup of the launch adds to) with one atomicAdd;
 // the consumers' unit w serves shard w mod shards, entries 4 (w / shards) .. + 3, so the list entry and the list's length are ONE

@@ -12,8 +12,7 @@ struct DevCfg;     // mmw_device.hpp (the CNN's kernel files do without it)
 struct DevState;
 struct ReportState;
 struct UartState;
-struct CloudState;
-struct SkelState;
+struct ExportScratch;
 // k_track.hip, k_kalman.hip, k_scene.hip: the step
 size_t track_lds_bytes(const DevCfg &c);
 hipError_t prepare_track(const DevCfg &cfg);
@@ -54,14 +53,16 @@ void launch_probe_set(int32_t *w, hipStream_t st);
 void launch_pop_frame(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st);
 void launch_clear_errors(const DevCfg &cfg, const DevState &s, const int32_t *flags, int bits, hipStream_t st);
 void launch_set_batch_size(const DevCfg &cfg, const DevState &s, const int32_t *flags, int new_size, hipStream_t st);
+// k_scan.hip: the scan step of the three live-track exports below -- two count arrays to offsets, totals and the capacity decision
+void launch_pair_scan(int S, int32_t *off, int32_t *totals, int cap0, int cap1, hipStream_t st);
 // k_report.hip: the live-track report
 void launch_report_baseline(const DevCfg &cfg, const DevState &s, const ReportState &rp, hipStream_t st);
 void launch_report_rebase(const DevCfg &cfg, const ReportState &rp, const int32_t *flags, hipStream_t st);
 void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ReportState &rp, mmw_track_report *rows, int cap_rows, mmw_track_event *events, int cap_events, int scene_base, hipStream_t st);
 // k_cloud.hip: the live tracks' point clouds (mode: MMW_CLOUD_POINTS / MMW_CLOUD_ROWS, | MMW_CLOUD_UNASSIGNED)
-void launch_clouds(const DevCfg &cfg, const DevState &s, const CloudState &cs, mmw_cloud_track *dir, int cap_tracks, void *out, int cap_points, int mode, int scene_base, hipStream_t st);
+void launch_clouds(const DevCfg &cfg, const DevState &s, const ExportScratch &sc, mmw_cloud_track *dir, int cap_tracks, void *out, int cap_points, int mode, int scene_base, hipStream_t st);
 // k_skeleton.hip: the live tracks' room-frame skeletons (mode: MMW_SKEL_ALL / MMW_SKEL_DRAWN)
-void launch_skeletons(const DevCfg &cfg, const DevState &s, const SkelState &ks, mmw_skeleton *out, int cap, int mode, int scene_base, hipStream_t st);
+void launch_skeletons(const DevCfg &cfg, const DevState &s, const ExportScratch &sc, mmw_skeleton *out, int cap, int mode, int scene_base, hipStream_t st);
 // k_uart.hip: the device-resident radar readers
 void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);

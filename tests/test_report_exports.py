@@ -83,9 +83,10 @@ def test_report_kernels_use_no_scratch_and_store_rows_in_16_byte_pieces():
     rep, asm = _device_isa(("k_report",))["k_report"]
     rows = _kernel_report(rep)
     names = [k[0] for k in rows]
-    for k in ("k_report_baseline", "k_report_rebase", "k_report_count", "k_report_scan"):
+    for k in ("k_report_baseline", "k_report_rebase", "k_report_count"):
         assert sum(k in n for n in names) == 1, (k, names)
     assert sum("k_report_write" in n for n in names) == 2, names   # the context's window, and each scene's own site
+    assert len(names) == 5, names                                   # (the scan is k_pair_scan of k_scan.hip)
     for name, scratch, vspill, vgprs, occ, sspill in rows:
         assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
         body = asm[asm.index("\n" + name + ":"):]
@@ -95,6 +96,38 @@ def test_report_kernels_use_no_scratch_and_store_rows_in_16_byte_pieces():
             # the image goes LDS -> global in 16-byte pieces (ds_read_b128 + global_store_dwordx4), not a lane per row
             assert "ds_read_b128" in body and "global_store_dwordx4" in body, name
             assert occ >= 4, (name, occ)
+
+
+def test_the_exports_share_one_scan_kernel_without_scratch():
+    """k_scan.hip holds the one two-array offset scan of the library, k_pair_scan: no scratch, no spilled register.  The three
+    kernels it replaced are in no export's device code, and its launcher is declared once and defined once."""
+    from tests.test_cabi_exports import _device_isa, _kernel_report
+    isa = _device_isa(("k_scan", "k_report", "k_cloud", "k_skeleton"))
+    rep, asm = isa["k_scan"]
+    rows = _kernel_report(rep)
+    assert len(rows) == 1 and "k_pair_scan" in rows[0][0], rows
+    name, scratch, vspill, vgprs, occ, sspill = rows[0]
+    assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
+    body = asm[asm.index("\n" + name + ":"):]
+    body = body[: body.index(".Lfunc_end")]
+    assert "s_endpgm" in body and "scratch_" not in body, name
+    for f, (_, a) in isa.items():
+        for old in ("k_%s_scan" % e for e in ("report", "cloud", "skel")):   # (the three copies this kernel replaced)
+            assert old not in a, (f, old)
+        assert ("k_pair_scan" in a) == (f == "k_scan"), f
+    csrc = os.path.join(ROOT, "mmwave_msc_amd", "csrc")
+    pat = r"\bvoid\s+launch_pair_scan\s*\("
+    assert len(re.findall(pat, open(os.path.join(csrc, "mmw_kernels.hpp")).read())) == 1
+    assert len(re.findall(pat, open(os.path.join(csrc, "k_scan.hip")).read())) == 1
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".hpp")) and fn not in ("mmw_kernels.hpp", "k_scan.hip"):
+            assert not re.search(pat, open(os.path.join(csrc, fn)).read()), fn
+    # the 1024-thread scan loop is written once, in the primitive all five scans use
+    loop = "for (int o = 1; o < 1024; o <<= 1)"
+    holders = [fn for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".hpp")) and loop in open(os.path.join(csrc, fn)).read()]
+    assert holders == ["mmw_scan.hpp"] and open(os.path.join(csrc, "mmw_scan.hpp")).read().count(loop) == 1, holders
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    assert "k_scan.hip" in mk and "mmw_scan.hpp" in mk and "api_export.hip" in mk
 
 
 def test_table_kernels_still_compile_without_scratch_after_sharing_their_body():

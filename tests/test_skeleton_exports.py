@@ -108,9 +108,12 @@ def test_skeleton_launcher_is_declared_once_and_the_files_are_built():
     for name in ("api_skeleton.hip", "api_context.hip", "mmw_ctx.hpp"):
         assert not re.search(r"\bvoid\s+launch_skeletons\s*\(", open(os.path.join(csrc, name)).read()), name
     assert len(re.findall(r"\bvoid\s+launch_skeletons\s*\(", open(os.path.join(csrc, "k_skeleton.hip")).read())) == 1
+    assert len(re.findall(r"\bvoid\s+launch_pair_scan\s*\(", decl)) == 1
+    assert len(re.findall(r"\bvoid\s+launch_pair_scan\s*\(", open(os.path.join(csrc, "k_scan.hip")).read())) == 1
+    assert not re.search(r"\bvoid\s+launch_pair_scan\s*\(", open(os.path.join(csrc, "k_skeleton.hip")).read())
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "k_skeleton.hip" in mk and "api_skeleton.hip" in mk
-    assert "skel_free(c->skel)" in open(os.path.join(csrc, "api_context.hip")).read()
+    assert "export_free(c->skel)" in open(os.path.join(csrc, "api_context.hip")).read()
 
 
 def test_skeleton_kernels_use_no_scratch_and_store_16_byte_pieces():
@@ -118,9 +121,9 @@ def test_skeleton_kernels_use_no_scratch_and_store_16_byte_pieces():
     rep, asm = _device_isa(("k_skeleton",))["k_skeleton"]
     rows = _kernel_report(rep)
     names = [k[0] for k in rows]
-    for k in ("k_skel_count", "k_skel_scan", "k_skel_write"):
+    for k in ("k_skel_count", "k_skel_write"):
         assert sum(k in n for n in names) == 1, (k, names)
-    assert len(names) == 3, names
+    assert len(names) == 2, names                                 # (the scan is k_pair_scan of k_scan.hip)
     for name, scratch, vspill, vgprs, occ, sspill in rows:
         assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
         body = asm[asm.index("\n" + name + ":"):]
