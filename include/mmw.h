@@ -837,6 +837,51 @@ int mmw_uart_get_state(mmw_ctx *ctx, int32_t scene, uint8_t *buf /*[MMW_UART_BUF
 int mmw_uart_set_state(mmw_ctx *ctx, int32_t scene, const uint8_t *buf /*[MMW_UART_BUFFER]*/, int32_t len, double t_last);
 int mmw_uart_set_time(mmw_ctx *ctx, const int32_t *scene_flags, double t);
 
+/* ---- radar log ----
+ * What the readers decoded, as it came off the wire: the recorder's `dataOk, frameNumber, detObj = IWR1443.read()`
+ * (DataLogging.py:30-38) for every scene in ONE call, taken from the SAME read that fed the tracker -- not from a second
+ * parser on the host.  mmw_uart_log_enable(on != 0), after mmw_uart_open (before it: MMW_E_ARG): from then on mmw_uart_read
+ * launches the logging twins of its kernels, which also keep each scene's last decoded frame (MMW_UART_POINTS) on the device:
+ * its wire objects, frameNumber, the Q format and the `now` of that read.  Every other status leaves the scene's staged frame
+ * alone; MMW_UART_OVERFLOW and MMW_UART_RAISED log nothing (the readers' declared difference).  A second read before the
+ * export OVERWRITES the first frame: call mmw_uart_log after every mmw_uart_read.  on = 0 frees the log, and the context
+ * launches exactly what it launched before; a context that never enables it never launches anything else.
+ *
+ * Output: a DIRECTORY of one mmw_uart_frame per emitted scene, scenes ascending, and their objects back to back -- entry i
+ * owns rows[first .. first + count); the entries partition rows, as in mmw_clouds.  A scene is ASKED when scene_flags (dev [S])
+ * is NULL or its flag is non-zero; an asked scene with a frame not exported yet and frame_number % frame_select == 0 (unsigned;
+ * read_thread's FB_FRAMES_SKIP + 1; frame_select < 1 is MMW_E_ARG) is EMITTED.  count = 0 is a valid entry (dataOK with
+ * tlv_numObj = 0).  A row is the reference's detObj bit for bit: x, y, z = int16 / 2 ** xyzQFormat (numpy's int64 power: inf
+ * and NaN for Q >= 63 pass through), doppler and peak_val as mmw_parse_uart_cap gives them, range = rangeIdx * the scene's
+ * range_idx_to_meters.  t is the `now` of the read that decoded the frame; the reference's detObj["timestamp"] is
+ * round(t * 1000), which the host forms.
+ * Consumed once: a successful call marks the frame of every ASKED scene exported, emitted or filtered out by frame_select;
+ * scenes not asked keep theirs for a later call.
+ * Capacity is decided on the DEVICE, as the clouds': more entries than cap_frames or more objects than cap_rows -> nothing is
+ * written, no frame is consumed, and mmw_uart_log_wait returns MMW_E_CAPACITY with both counts needed: a retry loses nothing.
+ * Tickets as mmw_clouds_* (ticket in [0,4); ticket 3 is mmw_uart_log's own).  dir: dev pointer, 8-byte aligned; rows: dev
+ * pointer, 16-byte aligned; scene ids are offset by scene_base.  MMW_E_ARG, nothing touched: a NULL context, the log not
+ * enabled, a NULL buffer with a positive cap, a negative cap, frame_select < 1, a bad ticket, a misaligned buffer, a wait for
+ * a ticket with nothing outstanding.
+ * Life cycle: mmw_uart_open called again marks every staged frame exported; mmw_uart_close and mmw_destroy free the log;
+ * mmw_reset*, mmw_restore, mmw_uart_set_state and mmw_uart_set_time do not touch it. */
+typedef struct mmw_uart_frame {      /* 32 bytes: one directory entry */
+    int32_t scene;          /* global scene id (scene_base + local index) */
+    uint32_t frame_number;  /* the packet header's frameNumber */
+    int32_t first, count;   /* this frame's objects are rows[first .. first + count) */
+    double t;               /* `now` of the mmw_uart_read that decoded it */
+    int32_t q_format;       /* xyzQFormat as sent (u16) */
+    int32_t reserved_;
+} mmw_uart_frame;
+typedef struct mmw_uart_object { double x, y, z, doppler, peak_val, range; } mmw_uart_object;   /* 48 bytes: one detObj row */
+int mmw_uart_log_enable(mmw_ctx *ctx, int32_t on);
+int mmw_uart_log_async(mmw_ctx *ctx, mmw_uart_frame *dir, int32_t cap_frames, mmw_uart_object *rows, int32_t cap_rows,
+                       const int32_t *scene_flags /*dev [S] or NULL*/, int32_t frame_select, int32_t scene_base, int32_t ticket);
+int mmw_uart_log_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_frames, int32_t *n_rows);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_uart_log(mmw_ctx *ctx, mmw_uart_frame *dir, int32_t cap_frames, mmw_uart_object *rows, int32_t cap_rows,
+                 const int32_t *scene_flags /*dev [S] or NULL*/, int32_t frame_select, int32_t scene_base, int32_t *n_frames,
+                 int32_t *n_rows);                                                          /* async + wait */
+
 /* Work counters accumulated by the kernels since the last reset (sync):
  * [0] k_track algorithmic bytes  [1] k_dbscan algorithmic bytes  [2] scene-frames stepped
  * [3] apply_DBscan calls  [4] sum of U over those calls  [5] sum of tracks entering track()

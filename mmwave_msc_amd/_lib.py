@@ -49,6 +49,7 @@ EXPORTS = [
     "mmw_clouds_async", "mmw_clouds_wait", "mmw_clouds",
     "mmw_skeletons_async", "mmw_skeletons_wait", "mmw_skeletons", "mmw_skeleton_tables",
     "mmw_uart_open", "mmw_uart_close", "mmw_uart_read", "mmw_uart_get_state", "mmw_uart_set_state", "mmw_uart_set_time",
+    "mmw_uart_log_enable", "mmw_uart_log_async", "mmw_uart_log_wait", "mmw_uart_log",
 ]
 
 
@@ -183,6 +184,12 @@ class MmwCloudPoint(C.Structure):
     """struct mmw_cloud_point (include/mmw.h): x, y, z in fp32 and the index of the point's directory entry."""
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("track", C.c_int32)]
 
+
+# struct mmw_uart_frame / mmw_uart_object (include/mmw.h): the directory entries (32 bytes) and detObj rows (48 bytes) of mmw_uart_log_*
+UART_FRAME_DTYPE = np.dtype([("scene", "i4"), ("frame_number", "u4"), ("first", "i4"), ("count", "i4"), ("t", "f8"), ("q_format", "i4"),
+                             ("reserved_", "i4")], align=True)
+UART_OBJECT_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("z", "f8"), ("doppler", "f8"), ("peak_val", "f8"), ("range", "f8")], align=True)
+UART_LOG_TICKETS = 4                          # mmw_uart_log_async calls that may be outstanding (mmw_uart_log itself uses the last ticket)
 
 # struct mmw_skeleton (include/mmw.h): one live track's room-frame skeleton of mmw_skeletons_* (256 bytes, no padding)
 SKEL_JOINTS, SKEL_BONES = 19, 18
@@ -409,6 +416,10 @@ def load():
         "mmw_uart_get_state": (C.c_int, [vp, i32, vp, i32p, f64p]),
         "mmw_uart_set_state": (C.c_int, [vp, i32, vp, i32, C.c_double]),
         "mmw_uart_set_time": (C.c_int, [vp, vp, C.c_double]),
+        "mmw_uart_log_enable": (C.c_int, [vp, i32]),
+        "mmw_uart_log_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32]),
+        "mmw_uart_log_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_uart_log": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32p, i32p]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

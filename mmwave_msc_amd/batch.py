@@ -371,6 +371,54 @@ class SceneBatch:
         flags[np.asarray(scenes, dtype=np.int64)] = 1
         self._chk(self.L.mmw_uart_set_time(self.h, flags.ctypes.data, float(t)))
 
+    # -- radar log ----------------------------------------------------------------
+    def enable_radar_log(self, on: bool = True):
+        """mmw_uart_log_enable (after `open_radars`): from now on every `read_radars` also keeps each scene's decoded frame as it
+        came off the wire -- the recorder's `dataOk, frameNumber, detObj` (DataLogging.py:36) -- for `radar_log_*`; on=False frees
+        it.  Until enabled, the log calls are refused (E_ARG) and the context launches nothing of them."""
+        self._chk(self.L.mmw_uart_log_enable(self.h, 1 if on else 0))
+
+    def radar_log_dev(self, dir_ptr, cap_frames: int, rows_ptr, cap_rows: int, frame_select: int = 1, flags_ptr=None, ticket: int = 0,
+                      scene_base: int = 0):
+        """mmw_uart_log_async: the frame each asked scene decoded at the last `read_radars` into device buffers -- a
+        `_lib.UART_FRAME_DTYPE` directory entry per scene whose frame number is a multiple of `frame_select`, scenes ascending,
+        and their objects back to back (`_lib.UART_OBJECT_DTYPE`: the reference's detObj bit for bit).  `flags_ptr`: device
+        int32[S], the scenes asked (None = all).  A frame is handed out once; call after every read.  Queued on the context's
+        stream -- no host wait.  Tickets 0 .. 3 (`radar_log_host` uses 3).  `rows_ptr` 16-byte aligned."""
+        self._chk(self.L.mmw_uart_log_async(self.h, dir_ptr, int(cap_frames), rows_ptr, int(cap_rows), flags_ptr, int(frame_select),
+                                            int(scene_base), int(ticket)))
+
+    def radar_log_wait(self, ticket: int = 0):
+        """(n_frames, n_rows) of the `radar_log_dev` call with this ticket: waits for its counts only, not for the stream.  Buffers
+        too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written, no frame consumed."""
+        return self._export_wait(self.L.mmw_uart_log_wait, ticket)
+
+    def radar_log_host(self, frame_select: int = 1, scenes=None, scene_base: int = 0):
+        """(dir[n_frames] UART_FRAME_DTYPE, rows[n_rows] UART_OBJECT_DTYPE): entry i owns rows[first : first + count].  `scenes`:
+        the scenes asked (default all); the others keep their frame for a later call.  The device buffers are kept and grow to
+        what the device says it needs (one retry; a refused export loses nothing)."""
+        fdt, odt = _lib.UART_FRAME_DTYPE, _lib.UART_OBJECT_DTYPE
+        flags_ptr = None
+        if scenes is not None:
+            flags = np.zeros(self.S, dtype=np.int32)
+            flags[np.asarray(scenes, dtype=np.int64)] = 1
+            flags_ptr = self.buf("radar_log_flags", self.S * 4).upload(flags).ptr
+        cap_f, cap_r = getattr(self, "_radar_log_caps", (64, 4096))
+        for attempt in (0, 1):
+            b_d, b_r = self.buf("radar_log_dir", cap_f * fdt.itemsize), self.buf("radar_log_rows", cap_r * odt.itemsize)
+            self.radar_log_dev(b_d.ptr, cap_f, b_r.ptr, cap_r, frame_select, flags_ptr, _lib.UART_LOG_TICKETS - 1, scene_base)
+            try:
+                n_f, n_r = self.radar_log_wait(_lib.UART_LOG_TICKETS - 1)
+                break
+            except MmwError as e:
+                if e.code != _lib.E_CAPACITY or attempt:
+                    raise
+                cap_f, cap_r = max(cap_f, e.needed[0]), max(cap_r, e.needed[1])
+                self._radar_log_caps = (cap_f, cap_r)
+        d = b_d.download((n_f,), fdt) if n_f else np.zeros(0, fdt)
+        rows = b_r.download((n_r,), odt) if n_r else np.zeros(0, odt)
+        return d, rows
+
     def step_host(self, pts: np.ndarray, n: np.ndarray, dt: np.ndarray, raise_nonfinite: bool = True, check: bool = True):
         """Host convenience (H2D + step + D2H).  Returns (assoc[S,NP], labels[S,UM], db_n[S]).  raise_nonfinite=False: a scene
         whose apply_DBscan call raised sklearn's ValueError (a NaN / infinite row in its ring) does not raise here -- its db_n is

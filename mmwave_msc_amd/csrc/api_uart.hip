@@ -1,5 +1,6 @@
 // api_uart.hip -- the C-ABI (include/mmw.h): the radar's UART packets -- decoded on the host (mmw_parse_uart*, mmw_find_tlv: no
-// context, no HIP call), and the device-resident readers (mmw_uart_*: their state, and the launch of k_uart.hip).
+// context, no HIP call), and the device-resident readers (mmw_uart_*: their state, and the launch of k_uart.hip; the radar log
+// they feed is api_uart_log.hip's).
 #include <cstring>
 
 #include "mmw_ctx.hpp"
@@ -111,8 +112,10 @@ int mmw_uart_close(mmw_ctx *c)
     if (!c->uart.buf) return MMW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (a read may still be queued on what is freed here)
+    uart_log_free(c);
     HIPCHK(c, hipFree(c->uart.buf));
     c->uart = UartState{};
+    c->uart_range.clear();
     return MMW_OK;
 }
 
@@ -129,14 +132,16 @@ int mmw_uart_open(mmw_ctx *c, const mmw_uart_cfg *cfg, int32_t n_cfg, double t0)
         c->uart.scene = reinterpret_cast<UartScene *>(p + S * MMW_UART_BUFFER);
     }
     std::vector<UartScene> h(S);
+    c->uart_range.resize(S);
     for (size_t s = 0; s < S; s++) {
         const mmw_uart_cfg &u = cfg[n_cfg == 1 ? 0 : s];
         h[s] = UartScene{t0, u.num_doppler_bins / 2.0 - 1, u.doppler_resolution_mps, 0, 0};
+        c->uart_range[s] = u.range_idx_to_meters;
     }
     HIPCHK(c, hipMemsetAsync(c->uart.buf, 0, S * MMW_UART_BUFFER, c->stream));   // np.zeros(2**15) (ReadDataIWR1443.py:15)
     HIPCHK(c, hipMemcpyAsync(c->uart.scene, h.data(), S * sizeof(UartScene), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (h goes out of scope)
-    return MMW_OK;
+    return uart_log_rearm(c);   // (a log that is on starts again: no staged frame survives the new readers)
 }
 
 int mmw_uart_read(mmw_ctx *c, const uint8_t *chunks, const int64_t *chunk_off, size_t chunks_bytes, const int32_t *scene_flags, double now,
@@ -148,7 +153,7 @@ int mmw_uart_read(mmw_ctx *c, const uint8_t *chunks, const int64_t *chunk_off, s
     if (chunks_bytes > (size_t)INT64_MAX) return fail(c, MMW_E_ARG, "mmw_uart_read: chunks_bytes out of range");
     HIPCHK(c, hipSetDevice(c->device));
     static_assert(sizeof(long long) == sizeof(int64_t), "chunk offsets");
-    launch_uart_read(c->dc, sites_or_null(c), c->uart, chunks, reinterpret_cast<const long long *>(chunk_off), (long long)chunks_bytes, scene_flags, now, pts,
+    launch_uart_read(c->dc, sites_or_null(c), c->uart, c->ulog.word ? &c->ulog : nullptr, chunks, reinterpret_cast<const long long *>(chunk_off), (long long)chunks_bytes, scene_flags, now, pts,
                      n_out, dt_out, status, frame_number, c->stream);
     HIPCHK(c, hipGetLastError());
     return MMW_OK;

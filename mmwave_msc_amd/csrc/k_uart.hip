@@ -3,6 +3,8 @@
 //                    scene keeps that scene's 2^15-byte byteBuffer in global memory, appends the bytes that arrived, cuts to
 //                    the last magic word, decodes one packet into registers, drops it and normalises the rows
 //   k_uart_read_site the same body with each scene's own mounting (mmw_set_sites)
+//   k_uart_read_log, k_uart_read_site_log   the same body again, which also leaves the decoded frame as it came off the wire in
+//                    the scene's radar log (mmw_uart_log_enable; exported by k_uart_log.hip).  Launched only while the log is on.
 //   k_uart_set_time  main.py's `t` restarted
 // The buffer discipline is the reference's to the byte: its two slice assignments (66-69, 191-195) are moves of the buffer
 // onto itself, and what they leave behind past byteBufferLength is read again by a later packet whose objects reach past the
@@ -125,12 +127,13 @@ __device__ __forceinline__ int find_last_magic(const uint8_t *buf, int limit, in
 __device__ __forceinline__ uint32_t ld32(const uint8_t *p) { return *reinterpret_cast<const uint32_t *>(p); }
 
 // One read() of scene blockIdx.x, then normalize_data on what it decoded.  R = rows per thread, as in k_normalize_tlv.
-template <int R>
+// LOG: a read that gives MMW_UART_POINTS also stores its wire objects and the scene's log word (UartLog, mmw_device.hpp).
+template <int R, bool LOG = false>
 __device__ __forceinline__ void uart_read_scene(const DevCfg &cfg, const UartState &us, const uint8_t *__restrict__ chunks,
                                                 const long long *__restrict__ chunk_off, long long chunks_bytes, const int32_t *__restrict__ flags,
                                                 double now, double *__restrict__ out, int32_t *__restrict__ n_out, double *__restrict__ dt_out,
                                                 int32_t *__restrict__ status, uint32_t *__restrict__ frame_number, int *wcnt /* LDS [R * 4] */,
-                                                int *red /* LDS [4] */)
+                                                int *red /* LDS [4] */, const UartLog &log = UartLog{})
 {
     const int s = blockIdx.x, tid = threadIdx.x;
     UartScene *sc = us.scene + s;
@@ -174,7 +177,7 @@ __device__ __forceinline__ void uart_read_scene(const DevCfg &cfg, const UartSta
     }
     // 5. header, TLV head, objects (85-150): idx is the reference's idX when it reaches "remove already processed data"
     int st = MMW_UART_NONE, idx = 36, n = 0;
-    uint32_t frame = 0;
+    uint32_t frame = 0, head_word = 0;
     double q = 1.0;
     if (complete) {
         st = MMW_UART_PACKET;
@@ -190,7 +193,7 @@ __device__ __forceinline__ void uart_read_scene(const DevCfg &cfg, const UartSta
                 } else {
                     idx = 48 + 12 * num;
                     if (num > cfg.max_pts) st = MMW_UART_OVERFLOW;
-                    else { st = MMW_UART_POINTS; n = num; q = xyz_q_divisor(head >> 16); }
+                    else { st = MMW_UART_POINTS; n = num; q = xyz_q_divisor(head >> 16); head_word = head; }
                 }
             }
         }
@@ -202,6 +205,7 @@ __device__ __forceinline__ void uart_read_scene(const DevCfg &cfg, const UartSta
         unsigned short w[6] = {0, 0, 0, 0, 0, 0};
         if (i < n) {   // (48 + 12 i + 12 <= kUartBuf: num was checked) -- bytes past len are the buffer's stale bytes
             const U3A o = *reinterpret_cast<const U3A *>(buf + 48 + 12 * i);
+            if constexpr (LOG) *reinterpret_cast<U3A *>(log.obj + ((size_t)s * cfg.max_pts + i) * 12) = o;   // (n <= max_pts; contiguous across lanes)
             w[0] = (unsigned short)o.x; w[1] = (unsigned short)(o.x >> 16);
             w[2] = (unsigned short)o.y; w[3] = (unsigned short)(o.y >> 16);
             w[4] = (unsigned short)o.z; w[5] = (unsigned short)(o.z >> 16);
@@ -227,6 +231,13 @@ __device__ __forceinline__ void uart_read_scene(const DevCfg &cfg, const UartSta
         status[s] = st | dropped;
         frame_number[s] = frame;
         sc->len = len;
+        if constexpr (LOG) {
+            if (st == MMW_UART_POINTS) {             // (every other status leaves the log alone: OVERFLOW and RAISED log nothing)
+                UartLogWord *lw = log.word + s;
+                lw->t = now;
+                *reinterpret_cast<uint4 *>(&lw->frame) = uint4{frame, (uint32_t)n, head_word, 1u};   // frame, count, head, fresh
+            }
+        }
     }
 }
 
@@ -252,23 +263,55 @@ __global__ __launch_bounds__(256) void k_uart_read_site(DevCfg cfg, const mmw_sc
                        wcnt, red);
 }
 
+template <int R>
+__global__ __launch_bounds__(256) void k_uart_read_log(DevCfg cfg, UartState us, UartLog log, const uint8_t *__restrict__ chunks, const long long *__restrict__ chunk_off,
+                                                       long long chunks_bytes, const int32_t *__restrict__ flags, double now, double *__restrict__ out,
+                                                       int32_t *__restrict__ n_out, double *__restrict__ dt_out, int32_t *__restrict__ status,
+                                                       uint32_t *__restrict__ frame_number)
+{
+    __shared__ int wcnt[R * 4];
+    __shared__ int red[4];
+    uart_read_scene<R, true>(cfg, us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number, wcnt, red, log);
+}
+template <int R>
+__global__ __launch_bounds__(256) void k_uart_read_site_log(DevCfg cfg, const mmw_scene_site *__restrict__ sites, UartState us, UartLog log,
+                                                            const uint8_t *__restrict__ chunks, const long long *__restrict__ chunk_off, long long chunks_bytes,
+                                                            const int32_t *__restrict__ flags, double now, double *__restrict__ out, int32_t *__restrict__ n_out,
+                                                            double *__restrict__ dt_out, int32_t *__restrict__ status, uint32_t *__restrict__ frame_number)
+{
+    __shared__ int wcnt[R * 4];
+    __shared__ int red[4];
+    uart_read_scene<R, true>(cfg_with_mounting(cfg, sites + blockIdx.x), us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status,
+                             frame_number, wcnt, red, log);
+}
+
 __global__ __launch_bounds__(256) void k_uart_set_time(UartState us, const int32_t *__restrict__ flags, double t, int n_scenes)
 {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s < n_scenes && (!flags || flags[s] != 0)) us.scene[s].t_last = t;
 }
 
-void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const uint8_t *chunks, const long long *chunk_off,
+void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const UartLog *log, const uint8_t *chunks, const long long *chunk_off,
                       long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status,
                       uint32_t *frame_number, hipStream_t st)
 {
     const int r = (cfg.max_pts + 255) / 256;   // rows per thread, as launch_normalize_tlv
-#define MMW_UART_READ(R) mmw_launch(k_uart_read<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number)
-#define MMW_UART_READ_SITE(R) mmw_launch(k_uart_read_site<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number)
-    if (sites) { if (r <= 1) MMW_UART_READ_SITE(1); else if (r == 2) MMW_UART_READ_SITE(2); else MMW_UART_READ_SITE(4); }
+#define MMW_UART_ARGS chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number
+#define MMW_UART_READ(R) mmw_launch(k_uart_read<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, us, MMW_UART_ARGS)
+#define MMW_UART_READ_SITE(R) mmw_launch(k_uart_read_site<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, us, MMW_UART_ARGS)
+#define MMW_UART_READ_LOG(R) mmw_launch(k_uart_read_log<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, us, *log, MMW_UART_ARGS)
+#define MMW_UART_READ_SITE_LOG(R) mmw_launch(k_uart_read_site_log<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, us, *log, MMW_UART_ARGS)
+    if (log) {   // the twins, only while the radar log is enabled
+        if (sites) { if (r <= 1) MMW_UART_READ_SITE_LOG(1); else if (r == 2) MMW_UART_READ_SITE_LOG(2); else MMW_UART_READ_SITE_LOG(4); }
+        else if (r <= 1) MMW_UART_READ_LOG(1); else if (r == 2) MMW_UART_READ_LOG(2); else MMW_UART_READ_LOG(4);
+    }
+    else if (sites) { if (r <= 1) MMW_UART_READ_SITE(1); else if (r == 2) MMW_UART_READ_SITE(2); else MMW_UART_READ_SITE(4); }
     else if (r <= 1) MMW_UART_READ(1); else if (r == 2) MMW_UART_READ(2); else MMW_UART_READ(4);
 #undef MMW_UART_READ
 #undef MMW_UART_READ_SITE
+#undef MMW_UART_READ_LOG
+#undef MMW_UART_READ_SITE_LOG
+#undef MMW_UART_ARGS
 }
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st)
 {

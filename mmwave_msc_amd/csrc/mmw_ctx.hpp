@@ -32,7 +32,7 @@ struct PostureBatch {
     hipEvent_t total_ev = nullptr;
 };
 
-// What the three live-track exports (mmw_report_*, mmw_clouds_*, mmw_skeletons_*) keep on the host: the device scratch of the call
+// What the three live-track exports (mmw_report_*, mmw_clouds_*, mmw_skeletons_*) and the radar log (mmw_uart_log_*) keep on the host: the device scratch of the call
 // in flight and the pinned counts of the outstanding calls, one slot per ticket (api_export.hip).  d_block == nullptr: not allocated.
 struct ExportCtx {
     ExportScratch sc = {};
@@ -93,6 +93,9 @@ struct mmw_ctx {
     ReportState rs = {};              // ... the report's baseline, in front of rep's scratch in rep.d_block (rs.sc = rep.sc)
     ExportCtx cloud;                  // mmw_clouds_*: allocated by the first call; not allocated = never called, nothing of it exists
     ExportCtx skel;                   // mmw_skeletons_*: allocated by the first call; not allocated = never called, nothing of it exists
+    ExportCtx ulog_x;                 // mmw_uart_log_enable; not allocated = the radar log is off and mmw_uart_read launches what it always did
+    UartLog ulog = {};                // ... the staged frames, in front of ulog_x's scratch in ulog_x.d_block
+    std::vector<double> uart_range;   // [S] rangeIdxToMeters of the open readers (the log's range column)
     UartState uart = {};              // mmw_uart_open: the radar readers' state (uart.buf is the allocation, uart.scene lies behind the buffers); nullptr = closed
     // profiling
     unsigned prof_mask = 0;           // bit k: time kernel id k (mmw_profile_enable)
@@ -110,6 +113,8 @@ int read_headers(mmw_ctx *c, std::vector<SceneHdr> &h);            // api_query.
 int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q);   // api_query.hip
 void posture_batch_free(PostureBatch *b);                          // api_posture.hip
 int report_rebase(mmw_ctx *c, const int32_t *dev_flags);           // api_report.hip: the scenes' uids restart (no-op while reports are off)
+int uart_log_rearm(mmw_ctx *c);                                    // api_uart_log.hip: every scene's log word as new, with its range scale (no-op while the log is off)
+void uart_log_free(mmw_ctx *c);                                    // api_uart_log.hip: ... and the log is off (the caller has waited for the stream)
 // api_export.hip: the ticketed counts of the three live-track exports (`name`: the entry the messages speak for)
 int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name);   // extra_words int32 in front of the scratch, at x.d_block
 void export_free(ExportCtx &x);                                    // ... and x is as never allocated

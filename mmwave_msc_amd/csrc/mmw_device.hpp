@@ -116,6 +116,23 @@ struct UartState {
     uint8_t *buf;          // [S][kUartBuf], 16-byte aligned
     UartScene *scene;      // [S]
 };
+// The radar log (mmw_uart_log_enable; k_uart_read_log stages, k_uart_log.hip exports): per scene the frame its last read()
+// decoded, as it came off the wire -- the DataLogging.py recorder's `dataOk, frameNumber, detObj`.  A read that gives
+// MMW_UART_POINTS rewrites the scene's word (all of it but `range_scale`, which the host sets) and its first `count` objects;
+// every other status leaves both alone.
+struct UartLogWord {
+    double t;              // `now` of the read that decoded the frame
+    double range_scale;    // rangeIdxToMeters (mmw_uart_log_enable / mmw_uart_open; no kernel writes it)
+    uint32_t frame;        // frameNumber
+    int32_t count;         // tlv_numObj (<= max_pts)
+    uint32_t head;         // the TLV head word: numObj | xyzQFormat << 16
+    int32_t fresh;         // 1 = not exported yet
+};
+static_assert(sizeof(UartLogWord) == 32, "UartLogWord");
+struct UartLog {
+    UartLogWord *word;     // [S], 16-byte aligned
+    uint8_t *obj;          // [S][max_pts][12] the wire objects (rangeIdx, dopplerIdx, peakVal, x, y, z: six little-endian u16)
+};
 
 // One ClusterTrack.  187 doubles = 1496 B.
 struct TrackRec {

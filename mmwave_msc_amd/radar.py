@@ -14,10 +14,14 @@ buffer, the int64 wrap of `2 ** xyzQFormat` included.  One declared difference: 
 
 Many radars in one context: `SceneBatch.open_radars / read_radars` keep this same buffer discipline per scene on the device
 (mmw_uart_read, csrc/k_uart.hip) -- there a packet over `max_pts` objects is dropped as the reference drops a decoded one.
+
+Recording: `ExperimentLogger` is DataLogging.py's `write_thread` (50-89) per scene, fed by `SceneBatch.radar_log_host` -- the
+frames the device readers decoded, so the log is what the tracker saw.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 import time
 
 import numpy as np
@@ -196,3 +200,55 @@ class UartFrameParser:
     def _num_detected(self) -> int:
         b = self.byteBuffer
         return int(b[28]) | int(b[29]) << 8 | int(b[30]) << 16 | int(b[31]) << 24
+
+
+class ExperimentLogger:
+    """DataLogging.py's `write_thread` (50-89) for many scenes: `paths` maps a scene id (as `radar_log_host` reports it, scene_base
+    included) to the directory of its experiment, which must exist; frames of other scenes are ignored.  Per scene a pandas buffer
+    of `Frame, X, Y, Z, Doppler, Intensity, Timestamp` rows is appended to `<dir>/<k>.csv` (k = 1, 2, ...; no header, no index)
+    whenever it holds FB_WRITE_BUFFER_SIZE rows or the shard has FB_EXPERIMENT_FILE_SIZE frames, which starts the next shard --
+    the files `utils.OfflineManager`, `dataset.preprocess_experiment` and `train` start from.  A frame with zero objects adds no
+    row but counts as a frame, as there.  Declared difference: `close()` writes what is still buffered; the reference loses its
+    unflushed rows at KeyboardInterrupt."""
+
+    COLUMNS = ("Frame", "X", "Y", "Z", "Doppler", "Intensity", "Timestamp")
+
+    def __init__(self, paths: dict):
+        import pandas as pd
+        self._pd = pd
+        self.paths = {int(s): str(p) for s, p in paths.items()}
+        # per scene: [data_buffer, cur_file_index, frames_in_cur_file]
+        self._state = {s: [pd.DataFrame(), 1, 0] for s in self.paths}
+        self.frames_written = {s: 0 for s in self.paths}
+
+    def _flush(self, scene: int):
+        st = self._state[scene]
+        st[0].to_csv(os.path.join(self.paths[scene], f"{st[1]}.csv"), mode="a", index=False, header=False)
+        st[0].drop(st[0].index, inplace=True)
+
+    def write(self, dir, rows):
+        """One export of `SceneBatch.radar_log_host`: every directory entry of a scene in `paths` is one `queue.get()` of the
+        reference's writer."""
+        from . import constants as const
+        pd = self._pd
+        for e in dir:
+            scene = int(e["scene"])
+            st = self._state.get(scene)
+            if st is None:
+                continue
+            r = rows[int(e["first"]): int(e["first"]) + int(e["count"])]
+            data = {"Frame": int(e["frame_number"]), "X": r["x"], "Y": r["y"], "Z": r["z"], "Doppler": r["doppler"],
+                    "Intensity": r["peak_val"].astype(np.int16), "Timestamp": round(float(e["t"]) * 1000)}
+            st[0] = pd.concat([st[0], pd.DataFrame(data)], ignore_index=True)
+            st[2] += 1
+            self.frames_written[scene] += 1
+            if len(st[0]) >= const.FB_WRITE_BUFFER_SIZE or st[2] >= const.FB_EXPERIMENT_FILE_SIZE:
+                self._flush(scene)
+                if st[2] >= const.FB_EXPERIMENT_FILE_SIZE:
+                    st[2] = 0
+                    st[1] += 1
+
+    def close(self):
+        for scene, st in self._state.items():
+            if len(st[0]):
+                self._flush(scene)
