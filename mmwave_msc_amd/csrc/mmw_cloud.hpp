@@ -140,7 +140,7 @@ __device__ __forceinline__ void cloud_finish_empty(const DevState &st, SceneHdr 
 // Both stages return true (uniformly over the 256 calling threads) only when NO point can be a core point of
 // sklearn's BallTree DBSCAN, i.e. every label is -1 (Utils.py:268-275 then returns no clusters).
 //
-// Bound (proof in dbscan_core, k_dbscan.hip): every BallTree neighbour q of p has
+// Bound (proof in dbscan_core, mmw_balltree.hpp): every BallTree neighbour q of p has
 //   E(p,q)^2 = dx^2 + dy^2 + z_w dz^2 <= 2 eps / wmin =: R^2,   wmin = min over the cloud of 1 - range_w * y.
 // Counting the points inside that ellipsoid is a SUPERSET count, so it may be formed in fp32 as long as the
 // radius is widened by everything fp32 can lose: coordinates (z pre-scaled by sqrt(z_w)) are rounded once,

@@ -57,7 +57,7 @@ struct mmw_ctx {
     int side_trusted = 0;                // mmw_config.chain_side_stream == 2: the side stream is used without the concurrency check
     int side_probed = 0;                 // the side streams have been checked against the current context stream (probe_side_streams)
     int32_t *d_probe = nullptr;          // [4] flag + results of that check
-    int epoch = 0;                       // step number (queue protocol of list 3, k_dbscan.hip)
+    int epoch = 0;                       // step number (queue protocol of the DBSCAN workers, mmw_dbqueue.hpp)
     std::string err;
     // internal scratch
     int32_t *d_row_off = nullptr;     // [S+1]

@@ -562,7 +562,7 @@ def test_dbscan_of_at_most_13_points_through_the_step(ms):
 
 def test_dbscan_pairs_at_the_threshold_vs_oracle():
     """query_radius decides most leaf tests from an fp32 value of the metric and only the pairs within its error bound of eps in
-    fp64 (k_dbscan.hip, leaf_screen).  Clouds built so that MANY pairs sit within 1e-7 .. 1e-3 of eps (lattices at the
+    fp64 (mmw_balltree.hpp, leaf_screen).  Clouds built so that MANY pairs sit within 1e-7 .. 1e-3 of eps (lattices at the
     threshold spacing, jittered), the same far from the origin (a wider bound), and at coordinates where fp32 resolves nothing
     (1e9: the screen must switch itself off): labels equal the fp64 oracle's (Utils.py:250-291 through sklearn's BallTree)."""
     from oracle import c_oracle as co
@@ -1025,7 +1025,7 @@ def test_two_side_worker_contexts_in_one_process():
         torch.cuda.synchronize()
         if f >= 3:   # (the first frames hold the start-up DBSCAN and the stream probe)
             times.append(time.perf_counter() - t0)
-    # a worker that holds a stream back costs its bounded wait: 0.2 s and more (k_dbscan.hip: kMustWaitTicks) -- or, for idle
+    # a worker that holds a stream back costs its bounded wait: 0.2 s and more (mmw_dbqueue.hpp: kMustWaitTicks) -- or, for idle
     # workers on a crosswise-shared queue, a few ms per step.  Wall-clock on a shared box: the typical step is judged at 20 ms,
     # a single one at 150 ms (one hiccup of the host must not fail the suite); give-ups are checked below (mmw_check)
     times.sort()
