@@ -271,6 +271,32 @@ def gen_normalize_nonfinite():
     print("  normalize_nonfinite: " + ", ".join(f"{out[f'raw_{i}'].shape[0]} -> {out[f'out_{i}'].shape[0]}" for i in range(4)))
 
 
+def gen_normalize_edges(out_path=None):
+    """normalize_data on the rows ON the scene filter's comparisons (tests/_rows_ref.py: edge_rows, the fp64 list and the fp32
+    one), each on its own, followed by one seam frame of 513 rows -- under S_TILT = 0 / S_HEIGHT = 1.0, where every transformed
+    value is exact, and under the default mounting: tests/test_oracle_golden.py.  peakVal = row index, so `out_*`[:, 7] says
+    which rows the reference kept."""
+    from tests._rows_ref import edge_rows, seam_frame
+    const, utils, _ = load_reference()
+    edges = edge_rows(False) + [e for e in edge_rows(True) if e.row not in [d.row for d in edge_rows(False)]]
+    raw = np.vstack([np.array([e.row + (0.0,) for e in edges]), seam_frame(513, 513000)[0]])
+    raw[:, 4] = np.arange(len(raw))
+    det = {"x": list(raw[:, 0]), "y": list(raw[:, 1]), "z": list(raw[:, 2]), "doppler": list(raw[:, 3]), "peakVal": list(raw[:, 4])}
+    saved = (const.S_HEIGHT, const.S_TILT)
+    out = {}
+    try:
+        for name, (h, tilt) in (("exact", (1.0, 0)), ("default", saved)):
+            const.S_HEIGHT, const.S_TILT = h, tilt
+            with np.errstate(all="ignore"):
+                out[f"out_{name}"] = np.asarray(utils.normalize_data(det), dtype=np.float64).reshape(-1, 8)
+            out[f"mount_{name}"] = np.array([h, tilt], dtype=np.float64)
+    finally:
+        const.S_HEIGHT, const.S_TILT = saved
+    np.savez_compressed(out_path or os.path.join(GOLDEN_DIR, "normalize_edges.npz"), raw=raw, n_edges=len(edges),
+                        names=np.array([e.name for e in edges]), meta=_meta(), **out)
+    print(f"  normalize_edges: {len(edges)} edge rows + 513 -> " + ", ".join(f"{k}: {len(v)}" for k, v in out.items() if k.startswith("out_")))
+
+
 def gen_dbscan():
     const, utils, _ = load_reference()
     from sklearn.cluster import DBSCAN
@@ -798,6 +824,7 @@ def gen_splitsets():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
+    ap.add_argument("--out", default=None, help="with --only normalize_edges: write there instead of tests/golden/")
     args = ap.parse_args()
     if not have_reference():
         print("reference not present: nothing generated")
@@ -813,6 +840,8 @@ def main():
         gen_constants()
     if not args.only or args.only == "normalize_nonfinite":
         gen_normalize_nonfinite()
+    if not args.only or args.only == "normalize_edges":
+        gen_normalize_edges(args.out)
     if not args.only or args.only == "dbscan":
         gen_dbscan()
     if not args.only or args.only == "dbscan_huge":

@@ -156,3 +156,55 @@ def test_pop_frame_matches_reference_recording():
         assert np.array_equal(a.astype(np.int16), g["assoc"][f, :c]), f
         assert sc.n_tracks == int(g["n_tracks"][f]), f
         assert sc.batch_ring().tolist() == [int(v) for v in g["ring_n"][f, : int(g["ring_len"][f])]], f
+
+
+EDGES = os.path.join(GOLDEN, "normalize_edges.npz")
+
+
+def test_normalize_edge_rows_match_reference_golden():
+    """tests/golden/normalize_edges.npz (oracle/gen_golden.py gen_normalize_edges): the reference's normalize_data on the rows ON
+    the scene filter's comparisons, r == 0 by underflow, r == inf, NaN / inf coordinates and dopplers (tests/_rows_ref.py) and
+    on one seam frame, under tilt 0 / height 1.0 and under the default mounting.  The C oracle keeps exactly the rows the
+    reference kept, with its values (NaN where it has NaN); under tilt 0 / height 1.0 those are the rows _rows_ref lists as kept,
+    with the velocities it lists."""
+    from tests._rows_ref import edge_rows, expected_rows
+    z = np.load(EDGES)
+    raw, n_edges = z["raw"], int(z["n_edges"])
+    assert np.array_equal(raw[:, 4], np.arange(len(raw))) and len(raw) == n_edges + 513
+    for name in ("exact", "default"):
+        h, tilt = z[f"mount_{name}"]
+        want = z[f"out_{name}"]
+        got = expected_rows({"s_height": float(h), "s_tilt": float(tilt)}, raw, len(raw))
+        assert np.array_equal(got[:, 7], want[:, 7]), (name, sorted(set(got[:, 7]) ^ set(want[:, 7])))   # the kept row set, in order
+        assert np.array_equal(np.isnan(got), np.isnan(want)), name
+        assert np.allclose(got, want, rtol=0, atol=1e-12, equal_nan=True), name
+        assert np.array_equal(got[:, [0, 6, 7]], want[:, [0, 6, 7]], equal_nan=True), name                # pass-through columns
+        assert 0 < (want[:, 7] >= n_edges).sum() < 513                                                    # the seam frame keeps and drops
+    h, tilt = z["mount_exact"]
+    assert (h, tilt) == (1.0, 0.0) and tuple(z["mount_default"]) != (1.0, 0.0)
+    edges = edge_rows(False) + [e for e in edge_rows(True) if e.row not in [d.row for d in edge_rows(False)]]
+    assert [e.name for e in edges] == [str(s) for s in z["names"]] and len(edges) == n_edges
+    want = z["out_exact"]
+    for i, e in enumerate(edges):
+        assert np.array_equal(raw[i, :4], np.array(e.row), equal_nan=True), e.name
+        hit = want[want[:, 7] == i]
+        assert len(hit) == int(e.kept), (e.name, hit)                    # the reference keeps / drops the row as listed
+        if e.kept:
+            assert hit[0, 1] == e.row[1] and hit[0, 2] == e.row[2] + 1.0, (e.name, hit)   # exact under this mounting
+            if e.vel is not None:
+                assert np.array_equal(hit[0, 3:6], np.array(e.vel), equal_nan=True), (e.name, hit[0, 3:6])
+
+
+@pytest.mark.reference
+def test_normalize_edges_recording_is_what_the_generator_writes(tmp_path):
+    import subprocess
+    import sys
+    out = str(tmp_path / "normalize_edges.npz")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.run([sys.executable, "-m", "oracle.gen_golden", "--only", "normalize_edges", "--out", out], check=True, cwd=root,
+                   capture_output=True, timeout=600)
+    a, b = np.load(out), np.load(EDGES)
+    assert sorted(a.files) == sorted(b.files)
+    for k in a.files:
+        if k != "meta":
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
