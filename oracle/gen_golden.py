@@ -821,6 +821,54 @@ def gen_splitsets():
     print(f"  splitsets: {len(after_split)} files after split_sets, {len(after_noise)} after add_noise")
 
 
+def gen_decision_edges():
+    """tests/golden/decision_edges.npz: the reference on the equality scenes and the exact tie of tests/_edge_inputs.py (inputs,
+    configuration, and per frame the association, DBSCAN labels, track list, global ring and feature owners).  The reference is
+    driven the way tests/test_reference_fuzz.py drives it: DB_EPS / DB_MIN_SAMPLES_MIN are default arguments of Utils.apply_DBscan,
+    bound at import -- re-bound here and restored --, MOTION_MODEL is the constants module's own object."""
+    from tests import _edge_inputs as ei
+    from tests._fuzz import reference_overrides
+    const, utils, _ = load_reference()
+    out = {}
+    for name, eq in ei.equality_scenes().items():
+        sc = eq.scene
+        kw = {k: v for k, v in sc.cfg.items() if k not in ("ring_rows", "track_cap")}     # (not constants of the reference)
+        over = reference_overrides(kw)
+        if "MOTION_MODEL" in over:
+            over["MOTION_MODEL"] = getattr(const, over["MOTION_MODEL"])
+        saved = utils.apply_DBscan.__defaults__
+        utils.apply_DBscan.__defaults__ = (float(kw.get("db_eps", const.DB_EPS)), int(kw["db_min_samples"]))
+        ref = RefScene(dict(over))
+        try:
+            f, n = sc.pts.shape[0], sc.max_pts
+            ring = ref.const.FB_FRAMES_BATCH + 1
+            rec = dict(assoc=np.full((f, n), -2, np.int16), db_n=np.full(f, -1, np.int32), labels=np.full((f, ring * n), -2, np.int16),
+                       n_tracks=np.zeros(f, np.int32), ring_len=np.zeros(f, np.int32), ring_n=np.zeros((f, 4), np.int32),
+                       n_feat=np.zeros(f, np.int32), owner=np.full((f, 8), -1, np.int32), tracks=np.zeros((f, 8), dtype=TRACK_DTYPE))
+            for i in range(f):
+                c = int(sc.cnt[i])
+                a, lab = ref.track(sc.pts[i, :c], float(sc.dt[i]))
+                rec["assoc"][i, :c] = a
+                if lab is not None:
+                    rec["db_n"][i] = len(lab)
+                    rec["labels"][i, : len(lab)] = lab
+                rec["n_tracks"][i] = ref.n_tracks
+                rec["tracks"][i, : ref.n_tracks] = ref.tracks()
+                br = ref.batch_ring()
+                rec["ring_len"][i] = len(br)
+                rec["ring_n"][i, : len(br)] = br
+                ow = ref.features()[1]
+                rec["n_feat"][i] = len(ow)
+                rec["owner"][i, : len(ow)] = ow
+        finally:
+            ref.close()
+            utils.apply_DBscan.__defaults__ = saved
+        rec.update(pts=sc.pts, cnt=sc.cnt, dt=sc.dt, cfg=json.dumps(sc.cfg, sort_keys=True))
+        out.update({f"{name}__{k}": v for k, v in rec.items()})
+        print(f"  decision_edges {name}: F={f} tracks per frame {rec['n_tracks'].tolist()} dbscan frames {(rec['db_n'] >= 0).sum()}")
+    np.savez_compressed(os.path.join(GOLDEN_DIR, "decision_edges.npz"), meta=_meta(), **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -834,6 +882,8 @@ def main():
         if args.only and args.only != name:
             continue
         gen_scenario(name, sc)
+    if not args.only or args.only == "decision_edges":
+        gen_decision_edges()
     if not args.only or args.only == "normalize":
         gen_normalize()
     if not args.only or args.only == "constants":
