@@ -882,6 +882,51 @@ int mmw_uart_log(mmw_ctx *ctx, mmw_uart_frame *dir, int32_t cap_frames, mmw_uart
                  const int32_t *scene_flags /*dev [S] or NULL*/, int32_t frame_select, int32_t scene_base, int32_t *n_frames,
                  int32_t *n_rows);                                                          /* async + wait */
 
+/* ---- training samples ----
+ * The dataset side: what preprocessing.py:192-220 saves of a scene after its track(), for every scene in ONE call.  A scene gives
+ * a SAMPLE when effective_tracks is not empty, effective_tracks[0].lifetime == 0 (the frame updated it) and its
+ * batch.effective_data is not empty.  The sample is that track's ring, `frames = list(track.batch.buffer)`, made relative with
+ * relative_coordinates(frames, track.cluster.centroid) (Utils.py:437-465: centroid[0], centroid[1] subtracted from columns 0, 1 in
+ * fp64) and laid out by format_batched_frames (Utils.py:523-548): frames NEWEST first, of each its columns [0, 1, 2, 6, 7], cut to
+ * its first 64 rows or padded to 64 with true zero rows (pad rows are not shifted); a frame the ring does not hold yet is 64 zero rows.
+ *
+ * Output: a DIRECTORY of one mmw_sample_entry per sample, scenes ascending, and out[i] = the block of entry i.
+ * mode: MMW_SAMPLE_BLOCK writes double[192][5], the block bit for bit.  MMW_SAMPLE_INPUT writes float[8][8][5], what
+ * format_mmwave_to_npy makes of it -- format_single_frame_mode(np.float32(block), mean, std, 1, fuse=True), Utils.py:551-572 --:
+ * rows 0..63 (the newest frame), every value rounded once to fp32, intensity (I - f32(mean)) / f32(std) as two fp32 operations,
+ * rows that are all zero AFTER that moved behind the others as true zero rows, then sorted by fp32 x.  np.argsort leaves ties
+ * undefined; here they are ordered by (is-all-zero, row position), a stable sort of the reference's array.  mean / std: the
+ * scene's site while a site table is in use (mmw_set_sites), else the context's.  | MMW_SAMPLE_ABSOLUTE: no centroid
+ * subtraction, in either form (the reference's RELATIVE_ENABLED = False); the entry's centroid is filled in all the same.
+ *
+ * A scene is ASKED when scene_flags (dev [S]) is NULL or its flag is non-zero: pass the scenes that ran track() this frame -- the
+ * library keeps nothing between calls, and a skipped scene whose position-0 track still has lifetime 0 gives its sample again
+ * when asked.  A context whose ring holds more than 3 frames (fb_frames_batch > 2) is refused with MMW_E_ARG: the reference
+ * raises there, frame 3 does not fit the 3 x 64 block.
+ * Capacity is decided on the DEVICE, as the clouds': more samples than cap_samples -> neither buffer is written and
+ * mmw_samples_wait returns MMW_E_CAPACITY with the count needed.  Tickets as mmw_clouds_* (ticket in [0,4); ticket 3 is
+ * mmw_samples' own).  No enable call: the first call allocates the context's scratch, mmw_destroy frees it.  dir: dev pointer,
+ * 8-byte aligned; out: dev pointer, 16-byte aligned, cap_samples blocks; scene ids are offset by scene_base.  MMW_E_ARG, nothing
+ * touched: a NULL context, a NULL buffer with a positive cap, a negative cap, a mode outside {0, 1, 2, 3}, a bad ticket, a
+ * misaligned buffer, a ring of more than 3 frames, a wait for a ticket with nothing outstanding. */
+typedef struct mmw_sample_entry {    /* 48 bytes, no padding: one directory entry */
+    int32_t scene;          /* global scene id (scene_base + local index) */
+    int32_t uid;            /* mmw_track_record.uid of effective_tracks[0] */
+    int32_t frames;         /* len(track.batch.buffer): 1..3 */
+    int32_t reserved;       /* 0 */
+    int32_t rows[3];        /* rows the reference holds in each frame, newest first (0 = absent) */
+    int32_t cut;            /* rows beyond 64, summed over the frames: what the block leaves out */
+    double centroid[2];     /* track.cluster.centroid[:2] */
+} mmw_sample_entry;
+#define MMW_SAMPLE_BLOCK 0      /* out = double[n][192][5] */
+#define MMW_SAMPLE_INPUT 1      /* out = float[n][8][8][5] */
+#define MMW_SAMPLE_ABSOLUTE 2   /* flag bit: no centroid subtraction */
+int mmw_samples_async(mmw_ctx *ctx, mmw_sample_entry *dir, int32_t cap_samples, void *out, int32_t mode,
+                      const int32_t *scene_flags /*dev [S] or NULL*/, int32_t scene_base, int32_t ticket);
+int mmw_samples_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_samples);   /* waits for that ticket's count only; n_samples may be NULL */
+int mmw_samples(mmw_ctx *ctx, mmw_sample_entry *dir, int32_t cap_samples, void *out, int32_t mode,
+                const int32_t *scene_flags /*dev [S] or NULL*/, int32_t scene_base, int32_t *n_samples);   /* async + wait */
+
 /* Work counters accumulated by the kernels since the last reset (sync):
  * [0] k_track algorithmic bytes  [1] k_dbscan algorithmic bytes  [2] scene-frames stepped
  * [3] apply_DBscan calls  [4] sum of U over those calls  [5] sum of tracks entering track()

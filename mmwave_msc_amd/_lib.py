@@ -50,6 +50,7 @@ EXPORTS = [
     "mmw_skeletons_async", "mmw_skeletons_wait", "mmw_skeletons", "mmw_skeleton_tables",
     "mmw_uart_open", "mmw_uart_close", "mmw_uart_read", "mmw_uart_get_state", "mmw_uart_set_state", "mmw_uart_set_time",
     "mmw_uart_log_enable", "mmw_uart_log_async", "mmw_uart_log_wait", "mmw_uart_log",
+    "mmw_samples_async", "mmw_samples_wait", "mmw_samples",
 ]
 
 
@@ -190,6 +191,13 @@ UART_FRAME_DTYPE = np.dtype([("scene", "i4"), ("frame_number", "u4"), ("first", 
                              ("reserved_", "i4")], align=True)
 UART_OBJECT_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("z", "f8"), ("doppler", "f8"), ("peak_val", "f8"), ("range", "f8")], align=True)
 UART_LOG_TICKETS = 4                          # mmw_uart_log_async calls that may be outstanding (mmw_uart_log itself uses the last ticket)
+
+# struct mmw_sample_entry (include/mmw.h): the directory entries (48 bytes, no padding) of mmw_samples_*
+SAMPLE_ENTRY_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("frames", "i4"), ("reserved", "i4"), ("rows", "i4", (3,)), ("cut", "i4"),
+                               ("centroid", "f8", (2,))], align=True)
+SAMPLE_BLOCK, SAMPLE_INPUT, SAMPLE_ABSOLUTE = 0, 1, 2   # MMW_SAMPLE_*: the mode of mmw_samples_* (ABSOLUTE is a flag bit)
+SAMPLE_BLOCK_SHAPE, SAMPLE_INPUT_SHAPE = (192, 5), (8, 8, 5)   # float64 / float32 per sample
+SAMPLE_TICKETS = 4                            # mmw_samples_async calls that may be outstanding (mmw_samples itself uses the last ticket)
 
 # struct mmw_skeleton (include/mmw.h): one live track's room-frame skeleton of mmw_skeletons_* (256 bytes, no padding)
 SKEL_JOINTS, SKEL_BONES = 19, 18
@@ -420,6 +428,9 @@ def load():
         "mmw_uart_log_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32]),
         "mmw_uart_log_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_uart_log": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32p, i32p]),
+        "mmw_samples_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32]),
+        "mmw_samples_wait": (C.c_int, [vp, i32, i32p]),
+        "mmw_samples": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32p]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

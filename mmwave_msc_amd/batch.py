@@ -777,6 +777,48 @@ class SceneBatch:
             out = b_o.download((n_p,), _lib.CLOUD_POINT_DTYPE) if n_p else np.zeros(0, _lib.CLOUD_POINT_DTYPE)
         return d, out
 
+    # -- training samples -----------------------------------------------------
+    def samples_dev(self, dir_ptr, cap_samples: int, out_ptr, mode: int = 0, flags_ptr=None, ticket: int = 0, scene_base: int = 0):
+        """mmw_samples_async: what preprocessing.py:192-220 saves of every asked scene whose `effective_tracks[0]` was updated by
+        the last step (lifetime 0) -- a `_lib.SAMPLE_ENTRY_DTYPE` directory entry per sample, scenes ascending, and per entry the
+        (192, 5) float64 block of `relative_coordinates` + `format_batched_frames` (`_lib.SAMPLE_BLOCK`) or the (8, 8, 5) float32
+        CNN input `format_mmwave_to_npy` makes of it (`_lib.SAMPLE_INPUT`); `| _lib.SAMPLE_ABSOLUTE` leaves the centroid in.
+        `flags_ptr`: device int32[S], the scenes that ran track() this frame (None = all).  Queued behind the last step on the
+        context's stream -- no host wait.  Tickets 0 .. 3 (`samples_host` uses 3).  `out_ptr` 16-byte aligned."""
+        self._chk(self.L.mmw_samples_async(self.h, dir_ptr, int(cap_samples), out_ptr, int(mode), flags_ptr, int(scene_base), int(ticket)))
+
+    def samples_wait(self, ticket: int = 0) -> int:
+        """Samples of the `samples_dev` call with this ticket: waits for its count only, not for the stream.  Buffers too small:
+        MmwError with code E_CAPACITY and the count needed in `.needed` -- nothing was written."""
+        n = C.c_int32(0)
+        rc = self.L.mmw_samples_wait(self.h, int(ticket), C.byref(n))
+        if rc == _lib.E_CAPACITY:
+            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
+            err.needed = int(n.value)
+            raise err
+        self._chk(rc)
+        return int(n.value)
+
+    def samples_host(self, inputs: bool = False, absolute: bool = False, scenes=None, scene_base: int = 0):
+        """(dir[n] SAMPLE_ENTRY_DTYPE, blocks): blocks float64[n, 192, 5], or with inputs=True float32[n, 8, 8, 5].  `scenes`:
+        the scenes that ran track() this frame (default all).  At most one sample per scene, so the buffers are sized by the
+        context's scene count and never grow."""
+        mode = (_lib.SAMPLE_INPUT if inputs else _lib.SAMPLE_BLOCK) | (_lib.SAMPLE_ABSOLUTE if absolute else 0)
+        edt = _lib.SAMPLE_ENTRY_DTYPE
+        shape, dt = (_lib.SAMPLE_INPUT_SHAPE, np.float32) if inputs else (_lib.SAMPLE_BLOCK_SHAPE, np.float64)
+        item = int(np.prod(shape)) * np.dtype(dt).itemsize
+        flags_ptr = None
+        if scenes is not None:
+            flags = np.zeros(self.S, dtype=np.int32)
+            flags[np.asarray(scenes, dtype=np.int64)] = 1
+            flags_ptr = self.buf("sample_flags", self.S * 4).upload(flags).ptr
+        b_d, b_o = self.buf("sample_dir", self.S * edt.itemsize), self.buf("sample_out", self.S * item)
+        self.samples_dev(b_d.ptr, self.S, b_o.ptr, mode, flags_ptr, _lib.SAMPLE_TICKETS - 1, scene_base)
+        n = self.samples_wait(_lib.SAMPLE_TICKETS - 1)
+        d = b_d.download((n,), edt) if n else np.zeros(0, edt)
+        out = b_o.download((n,) + shape, dt) if n else np.zeros((0,) + shape, dt)
+        return d, out
+
     # -- live-track skeletons -------------------------------------------------
     def skeletons_dev(self, out_ptr, cap: int, mode: int = 0, ticket: int = 0, scene_base: int = 0):
         """mmw_skeletons_async: every live track's room-frame skeleton (`_lib.SKELETON_DTYPE`: the keypoints mirrored and shifted

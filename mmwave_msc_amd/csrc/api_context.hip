@@ -405,6 +405,7 @@ int mmw_destroy(mmw_ctx *c)
     export_free(c->rep);
     export_free(c->cloud);
     export_free(c->skel);
+    export_free(c->sample);
     uart_log_free(c);
     if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->side_gate) hipEventDestroy(c->side_gate);

@@ -32,7 +32,7 @@ struct PostureBatch {
     hipEvent_t total_ev = nullptr;
 };
 
-// What the three live-track exports (mmw_report_*, mmw_clouds_*, mmw_skeletons_*) and the radar log (mmw_uart_log_*) keep on the host: the device scratch of the call
+// What the three live-track exports (mmw_report_*, mmw_clouds_*, mmw_skeletons_*), the radar log (mmw_uart_log_*) and the training samples (mmw_samples_*) keep on the host: the device scratch of the call
 // in flight and the pinned counts of the outstanding calls, one slot per ticket (api_export.hip).  d_block == nullptr: not allocated.
 struct ExportCtx {
     ExportScratch sc = {};
@@ -93,6 +93,7 @@ struct mmw_ctx {
     ReportState rs = {};              // ... the report's baseline, in front of rep's scratch in rep.d_block (rs.sc = rep.sc)
     ExportCtx cloud;                  // mmw_clouds_*: allocated by the first call; not allocated = never called, nothing of it exists
     ExportCtx skel;                   // mmw_skeletons_*: allocated by the first call; not allocated = never called, nothing of it exists
+    ExportCtx sample;                 // mmw_samples_*: allocated by the first call; not allocated = never called, nothing of it exists
     ExportCtx ulog_x;                 // mmw_uart_log_enable; not allocated = the radar log is off and mmw_uart_read launches what it always did
     UartLog ulog = {};                // ... the staged frames, in front of ulog_x's scratch in ulog_x.d_block
     std::vector<double> uart_range;   // [S] rangeIdxToMeters of the open readers (the log's range column)

@@ -69,6 +69,8 @@ void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const Uart
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);
 // k_uart_log.hip: the radar log's export (scene_flags: dev [S] or nullptr = every scene)
 void launch_uart_log(const DevCfg &cfg, const UartState &us, const UartLog &log, const ExportScratch &sc, mmw_uart_frame *dir, int cap_frames, mmw_uart_object *rows, int cap_rows, const int32_t *scene_flags, int frame_select, int scene_base, hipStream_t st);
+// k_sample.hip: the training samples (mode: MMW_SAMPLE_BLOCK / MMW_SAMPLE_INPUT, | MMW_SAMPLE_ABSOLUTE; sites as k_features'; scene_flags: dev [S] or nullptr)
+void launch_samples(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ExportScratch &sc, mmw_sample_entry *dir, int cap_samples, void *out, int mode, const int32_t *scene_flags, int scene_base, hipStream_t st);
 // k_mars.hip, k_dense.hip, k_dense2.hip: the posture CNN
 void launch_mars_conv(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
 void launch_range_gather(const float *feat, int32_t *list, int n, int per, int cap, float *small, int32_t *range_flag, hipStream_t stream);

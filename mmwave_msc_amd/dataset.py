@@ -9,6 +9,7 @@ tracker inside `preprocess_experiment` is the GPU `TrackBuffer`.
   static_kinect            skeleton rows into the radar's frame / relative to the track    preprocessing.py:90-145
   filter_kinect_frames     the Kinect rows that have a valid mmWave frame                  preprocessing.py:52-87
   preprocess_experiment    one pass of preprocess_dataset()'s loop body                    preprocessing.py:148-275
+  preprocess_experiments   ... for many experiments at once, one scene each of one context   (mmw_samples, include/mmw.h)
   format_mmwave_to_npy,
   format_kinect_to_npy     pre-processed CSVs -> `<mode>_mmWave.npy` / `<mode>_labels.npy`  preprocessing.py:298-384
   split_sets               experiments into training / validate / testing by name prefix    preprocessing.py:406-468
@@ -27,6 +28,7 @@ import shutil
 import numpy as np
 import pandas as pd
 
+from . import _lib
 from . import constants as const
 from .utils import (OfflineManager, format_batched_frames, format_single_frame_mode, normalize_data,
                     relative_coordinates)
@@ -186,6 +188,123 @@ def preprocess_experiment(mmwave_dir: str, kinect_csv: str, out_dir: str, out_ki
         np.save(centroid_npy, cen)
     filter_kinect_frames(pairs, invalid, kinect_csv, out_kinect_csv)
     return pairs, invalid, cen
+
+
+class _Experiment:
+    """The host books of one experiment inside `preprocess_experiments`: what `preprocess_experiment` keeps in its locals."""
+
+    def __init__(self, mmwave_dir, kinect_csv, out_dir, out_kinect_csv, centroid_npy):
+        self.kinect_csv, self.out_dir, self.out_kinect_csv, self.centroid_npy = kinect_csv, out_dir, out_kinect_csv, centroid_npy
+        self.pairs = pair(kinect_csv, mmwave_dir)
+        self.paired = {p[0] for p in self.pairs}
+        if os.path.exists(out_dir):
+            shutil.rmtree(out_dir)
+        os.makedirs(out_dir)
+        self.pending = pd.DataFrame()
+        self.in_file, self.file_no = 0, 1
+        self.cur = os.path.join(out_dir, f"{self.file_no}.csv")
+        self.centroids, self.invalid, self.inputs = [], [], []
+        self.man = OfflineManager(mmwave_dir)
+        self.first, self.t = True, 0.0
+        self.frame, self.valid = None, False
+
+    def save(self, block, centroid):
+        self.valid = True
+        if RELATIVE_ENABLED:
+            self.centroids.append(centroid)
+        self.pending = pd.concat([self.pending, pd.DataFrame({
+            "Frame": self.frame, "X": block[:, 0], "Y": block[:, 1], "Z": block[:, 2], "Doppler": block[:, 3],
+            "Intensity": block[:, 4]})], ignore_index=True)
+        self.in_file += 1
+        if len(self.pending) >= const.FB_WRITE_BUFFER_SIZE or self.in_file >= const.FB_EXPERIMENT_FILE_SIZE:
+            self.pending.to_csv(self.cur, mode="a", index=False, header=False)
+            self.pending = self.pending.iloc[0:0]
+            if self.in_file >= const.FB_EXPERIMENT_FILE_SIZE:
+                self.in_file = 0
+                self.file_no += 1
+                self.cur = os.path.join(self.out_dir, f"{self.file_no}.csv")
+
+    def finish(self):
+        pd.DataFrame(self.pending).to_csv(self.cur, mode="a", index=False, header=False)
+        cen = np.array(self.centroids)
+        if self.centroid_npy is not None:
+            np.save(self.centroid_npy, cen)
+        filter_kinect_frames(self.pairs, self.invalid, self.kinect_csv, self.out_kinect_csv)
+        return cen
+
+
+def preprocess_experiments(jobs, device: int = 0, max_pts: int = 512, inputs: bool = False):
+    """`preprocess_experiment` for many experiments at once: `jobs` = [(mmwave_dir, kinect_csv, out_dir, out_kinect_csv,
+    centroid_npy)], every experiment one scene of ONE `SceneBatch` with its own OfflineManager, pairing, `dt` / `t` and first-frame
+    `dt = 0.1`.  Per iteration every unfinished experiment takes its next frame and does nothing (unpaired, or the normalised
+    cloud is empty), pops the global ring's oldest frame (paired, no data) or steps; one `samples_host` call whose flags are the
+    scenes that stepped then brings every saved block (`mmw_samples`, include/mmw.h) -- no per-frame getter, no host formatting.
+    The files are written as `preprocess_experiment` writes them.  Returns per experiment (pairs, invalid frame numbers,
+    centroids); with `inputs` also the (n_valid, 8, 8, 5) float32 stack `format_mmwave_to_npy` would make of the saved blocks
+    (MMW_SAMPLE_INPUT; rows of equal x ordered by position, where np.argsort leaves the order open)."""
+    from .batch import SceneBatch
+    exps = [_Experiment(*job) for job in jobs]
+    if not exps:
+        return []
+    ring = const.FB_FRAMES_BATCH + 1
+    sb = SceneBatch(const.to_config(ring_rows=max(64, ring * max_pts)), len(exps), max_pts, device)
+    raw = np.zeros((sb.S, max_pts, 5))
+    n, dt = np.zeros(sb.S, np.int32), np.zeros(sb.S)
+    try:
+        while True:
+            took, asked, pops = [], [], []
+            n[:] = 0
+            for s, e in enumerate(exps):
+                if e.man.is_finished():
+                    continue
+                ok, e.frame, det = e.man.get_data()
+                e.valid = False
+                took.append(s)
+                if e.frame not in e.paired:
+                    continue
+                if not ok:
+                    pops.append(s)
+                    continue
+                dt[s] = 0.1 if e.first else det["posix"][0] / 1000 - e.t
+                e.first = False
+                e.t = det["posix"][0] / 1000
+                m = len(det["x"])
+                if m > max_pts:
+                    raise ValueError(f"frame {e.frame} of {e.man.experiment_path} has {m} points; preprocess_experiments(max_pts={max_pts})")
+                for i, k in enumerate(("x", "y", "z", "doppler", "peakVal")):
+                    raw[s, :m, i] = det[k]
+                n[s] = m
+                asked.append(s)
+            if not took:
+                break
+            stepped = []
+            if asked:
+                r = sb.frame_host(n, dt, raw=raw, want_labels=False)
+                stepped = [s for s in asked if r["n_out"][s] > 0]   # (an empty normalised cloud never reaches track())
+            if pops:
+                sb.pop_frame(pops)
+            if stepped:
+                d, blocks = sb.samples_host(absolute=not RELATIVE_ENABLED, scenes=stepped)
+                if inputs:
+                    d_in, feats = sb.samples_host(inputs=True, absolute=not RELATIVE_ENABLED, scenes=stepped)
+                    assert d_in.tobytes() == d.tobytes()
+                for i, ent in enumerate(d):
+                    e = exps[int(ent["scene"])]
+                    e.save(blocks[i], ent["centroid"].copy())
+                    if inputs:
+                        e.inputs.append(feats[i])
+            for s in took:
+                if not exps[s].valid:
+                    exps[s].invalid.append(exps[s].frame)
+    finally:
+        sb.close()
+    out = []
+    for e in exps:
+        res = (e.pairs, e.invalid, e.finish())
+        if inputs:
+            res += (np.array(e.inputs, dtype=np.float32).reshape((-1,) + _lib.SAMPLE_INPUT_SHAPE),)
+        out.append(res)
+    return out
 
 
 def extract_parts(filename):

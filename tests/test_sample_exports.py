@@ -1,0 +1,167 @@
+"""The training samples (mmw_samples_*, include/mmw.h; SceneBatch.samples_*; dataset.preprocess_experiments) as far as a machine
+without a GPU can check them: the numpy restatement the GPU tests compare with (tests/_sample_ref.py) equals the repository's
+own relative_coordinates + format_batched_frames and format_single_frame_mode bit for bit, the header declares the entries and
+the library exports them, the numpy layout is the C struct's, and the kernels of csrc/k_sample.hip compile without scratch,
+with at most 8 KB of LDS, and store their blocks as 16-byte pieces."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from mmwave_msc_amd import _lib
+from tests import _sample_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("mmw_samples_async", "mmw_samples_wait", "mmw_samples")
+FIELDS = ["scene", "uid", "frames", "reserved", "rows", "cut", "centroid"]
+MEAN, STD = 27.0187, 70.351
+
+
+def _ring(rng, sizes):
+    """Frames of the given row counts, oldest first: coordinates that need all 53 bits, integer intensities as the radar's."""
+    out = []
+    for n in sizes:
+        fr = rng.normal(size=(n, 8))
+        fr[:, 1] += 3.0
+        fr[:, 7] = rng.integers(0, 400, n)
+        out.append(fr)
+    return out
+
+
+def _rings():
+    rng = np.random.default_rng(20)
+    rings = []
+    for n_frames in (1, 2, 3):
+        for rows in (1, 63, 64, 65, 200):
+            sizes = [rows] + [int(rng.choice([1, 63, 64, 65, 200])) for _ in range(n_frames - 1)]
+            rings.append((_ring(rng, sizes[::-1]), rng.normal(size=6) + 1.5))
+    # rows with x equal after fp32 rounding (distinct in fp64), in several groups and next to an exact copy
+    fr = _ring(rng, [40])[0]
+    fr[5:9, 0] = 0.75 + np.arange(4) * 2.0 ** -40
+    fr[20:23, 0] = fr[5, 0]
+    fr[30, 0] = fr[31, 0] = -1.25
+    rings.append(([fr], np.zeros(6)))
+    # a row that normalises to all zero: it sits ON the centroid at height 0 with no doppler and the mean intensity (mean 27: exact)
+    fr = _ring(rng, [10])[0]
+    cen = np.array([0.5, 2.0, 0, 0, 0, 0])
+    fr[3] = [0.5, 2.0, 0, 9.0, 9.0, 9.0, 0, 27.0]
+    fr[6, 0] = 0.5                                       # relative x = 0 with the rest non-zero: ties with the zero rows, and goes first
+    rings.append(([fr], cen))
+    return rings
+
+
+@pytest.mark.parametrize("mean,std", [(MEAN, STD), (27.0, 70.351), (0.0, 3.5)])
+def test_the_restatement_is_the_repositorys_own_formatters_bit_for_bit(monkeypatch, mean, std):
+    from mmwave_msc_amd import utils
+    stable = np.argsort
+    monkeypatch.setattr(utils.np, "argsort", lambda a, *k, **kw: stable(a, kind="stable"))   # the tie order the export declares
+    zero_rows = ties = 0
+    for frames, cen in _rings():
+        want = utils.format_batched_frames(utils.relative_coordinates(frames, cen))
+        got = ref.block_of(frames, cen)
+        assert got.shape == (192, 5) and got.dtype == np.float64 and got.tobytes() == want.tobytes()
+        assert ref.block_of(frames, None).tobytes() == utils.format_batched_frames(frames).tobytes()
+        want_in = utils.format_single_frame_mode(np.float32(want), mean, std, 1, fuse=True)
+        got_in = ref.input_of(got, mean, std)
+        assert got_in.shape == (8, 8, 5) and got_in.dtype == np.float32
+        assert np.array_equal(want_in.astype(np.float32).astype(want_in.dtype), want_in)   # (float64 only by numpy's concatenate)
+        assert got_in.tobytes() == want_in.astype(np.float32).tobytes()
+        b = np.float32(got[:64])
+        b[:, 4] = (b[:, 4] - np.float32(mean)) / np.float32(std)
+        nz = b[np.any(b != 0, axis=1)]
+        zero_rows += int(len(nz) < 64)   # (with a non-zero mean the pad rows are NOT zero rows: only a real row can go missing)
+        ties += int(len(np.unique(nz[:, 0])) < len(nz))
+    if mean == 27.0:
+        assert zero_rows >= 1      # the row on the centroid did normalise to all zero
+    assert ties >= 1               # rows with x equal after the rounding were sorted
+    with pytest.raises(ValueError):
+        ref.block_of(_ring(np.random.default_rng(1), [2, 2, 2, 2]))
+
+
+def test_header_binding_and_library_agree_on_the_sample_entries():
+    txt = open(os.path.join(ROOT, "include", "mmw.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    for name in NEW:
+        assert re.search(r"\bint\s+%s\s*\(" % name, code), name
+        assert name in _lib.EXPORTS, name
+    assert "typedef struct mmw_sample_entry" in code
+    for name, val in (("MMW_SAMPLE_BLOCK", _lib.SAMPLE_BLOCK), ("MMW_SAMPLE_INPUT", _lib.SAMPLE_INPUT), ("MMW_SAMPLE_ABSOLUTE", _lib.SAMPLE_ABSOLUTE)):
+        assert re.search(r"#define\s+%s\s+%d\b" % (name, val), code), name
+    L = C.CDLL(_lib.LIB_PATH)
+    for name in NEW:
+        assert hasattr(L, name), f"{name} not exported by {_lib.LIB_PATH}"
+    csrc = os.path.join(ROOT, "mmwave_msc_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    assert re.search(r"^SRCS\s*=.*\bk_sample\.hip\b", mk, flags=re.M) and "api_sample.hip" in mk and "mmw_sort.hpp" in mk and "mmw_ring.hpp" in mk
+    decl = open(os.path.join(csrc, "mmw_kernels.hpp")).read()
+    assert len(re.findall(r"\bvoid\s+launch_samples\s*\(", decl)) == 1
+    # the export scans with the shared kernel, reads the ring as the clouds do and sorts with k_features' network: called, not restated
+    src = open(os.path.join(csrc, "k_sample.hip")).read()
+    for fn in ("launch_pair_scan(", "track_ring(", "bitonic_sort64(", "live_slot("):
+        assert fn in src, fn
+    assert "atomic" not in src
+    misc = open(os.path.join(csrc, "k_misc.hip")).read()
+    assert "bitonic_step" not in misc and '#include "mmw_sort.hpp"' in misc and "sort_rows_store(" in misc
+    assert "export_free(c->sample)" in open(os.path.join(csrc, "api_context.hip")).read()   # (mmw_destroy releases the scratch)
+
+
+def test_every_sample_entry_refuses_a_null_context():
+    L = _lib.load()   # (declares every prototype: AttributeError if one is missing)
+    n = C.c_int32(7)
+    assert L.mmw_samples_async(None, None, 0, None, 0, None, 0, 0) == _lib.E_ARG
+    assert L.mmw_samples_wait(None, 0, C.byref(n)) == _lib.E_ARG
+    assert L.mmw_samples(None, None, 0, None, 0, None, 0, C.byref(n)) == _lib.E_ARG
+    assert n.value == 7
+
+
+def test_sample_entry_layout_matches_the_c_struct():
+    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("no C compiler")
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "mmw.h"\nint main(void){printf("%zu", sizeof(mmw_sample_entry));\n'
+    src += "".join('printf(" %%zu", offsetof(mmw_sample_entry, %s));\n' % f for f in FIELDS)
+    src += "return 0;}\n"
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, "layout.c"), "w") as fh:
+            fh.write(src)
+        exe = os.path.join(d, "layout")
+        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), os.path.join(d, "layout.c"), "-o", exe], check=True, capture_output=True)
+        v = [int(t) for t in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    dt = _lib.SAMPLE_ENTRY_DTYPE
+    assert v[0] == dt.itemsize == 48 and list(dt.names) == FIELDS
+    for f, o in zip(FIELDS, v[1:]):
+        assert dt.fields[f][1] == o, f
+    assert dt.fields["rows"][0] == np.dtype(("i4", (3,))) and dt.fields["centroid"][0] == np.dtype(("f8", (2,)))
+    assert v[1:] == [0, 4, 8, 12, 16, 28, 32]   # no padding
+    assert _lib.SAMPLE_BLOCK_SHAPE == (192, 5) and _lib.SAMPLE_INPUT_SHAPE == (8, 8, 5)
+    for name in ("k_sample.hip", "api_sample.hip"):
+        assert re.search(r"static_assert\(sizeof\(mmw_sample_entry\) == 48", open(os.path.join(ROOT, "mmwave_msc_amd", "csrc", name)).read()), name
+
+
+def test_sample_kernels_use_no_scratch_little_lds_and_store_16_byte_pieces():
+    from tests.test_cabi_exports import _device_isa, _kernel_report
+    rep, asm = _device_isa(("k_sample",))["k_sample"]
+    rows = _kernel_report(rep)
+    names = [k[0] for k in rows]
+    # the count kernel and three writers: the block, the CNN input, and the input's site twin
+    assert sum("k_sample_count" in n for n in names) == 1 and sum("k_sample_write" in n for n in names) == 3 and len(names) == 4, names
+    lds = dict(zip(names, [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", rep)]))
+    for name, scratch, vspill, vgprs, occ, sspill in rows:
+        assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
+        body = asm[asm.index("\n" + name + ":"):]
+        body = body[: body.index(".Lfunc_end")]
+        assert "scratch_" not in body and "atomic" not in body, name
+        if "k_sample_count" in name:
+            assert lds[name] == 0 and "ds_" not in body, (name, lds)
+            continue
+        assert 0 < lds[name] <= 8192, (name, lds)
+        assert occ >= 4, (name, occ)
+        stores = re.findall(r"\b(global_store_\w+|flat_store_\w+|buffer_store_\w+)", body)
+        # the block / the input leave as 16-byte pieces; the one narrower store is the 48-byte directory entry, six lanes x 8 bytes
+        assert stores.count("global_store_dwordx4") >= 2, stores
+        assert sorted(set(stores)) == ["global_store_dwordx2", "global_store_dwordx4"] and stores.count("global_store_dwordx2") == 1, stores
