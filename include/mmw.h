@@ -324,7 +324,12 @@ int mmw_frame_host(mmw_ctx *ctx, const double *raw, const double *pts, const int
  * TrackBuffer.estimate_posture (Tracking.py:705-734): the feature tensors of the tracks with more than MODEL_MIN_INPUT ring
  * points, the CNN in Keras' own fp32 arithmetic (mmw_mars_conv3d's kernel, mmw_mars_head_small's kernels, with a row count
  * only the device knows) and track.keypoints = its rows.  *posture_rows (host, may be NULL) = the tracks estimated.  Still ONE
- * wait for the stream. */
+ * wait for the stream.
+ * mmw_attach_posture_frames is the same entry for either model: frames = 3 IS mmw_attach_posture; frames = 1 takes the
+ * single-frame model define_CNN (train.py:33-68) in the same struct -- conv kernels (kh,kw,in,out) = 720 and 4608 floats,
+ * dense1_w[512][dense1_ld] with dense1_ld >= 2048, dense2_w[57][512] -- on a one-scene context with FB_FRAMES_BATCH == 0 and
+ * track_cap <= 64; mmw_frame_posture_host then runs mmw_mars_conv2d's kernel in place of mmw_mars_conv3d's.  frames must be 3 or 1
+ * and the context's FB_FRAMES_BATCH + 1: anything else is MMW_E_ARG with a message and nothing changed. */
 typedef struct mmw_posture_model {
     const float *conv1_w, *conv1_b, *conv2_w, *conv2_b;
     const float *dense1_w;
@@ -332,6 +337,7 @@ typedef struct mmw_posture_model {
     const float *dense1_b, *dense2_w, *dense2_b;
 } mmw_posture_model;
 int mmw_attach_posture(mmw_ctx *ctx, const mmw_posture_model *model);
+int mmw_attach_posture_frames(mmw_ctx *ctx, const mmw_posture_model *model, int32_t frames);
 int mmw_frame_posture_host(mmw_ctx *ctx, const double *raw, const double *pts, const int32_t *n, const double *dt, double *pts_out,
                            int32_t *n_out, int32_t *assoc, int32_t *db_labels, int32_t *db_n, int32_t *n_tracks, int32_t *posture_rows);
 
@@ -344,7 +350,7 @@ int mmw_frame_posture_host(mmw_ctx *ctx, const double *raw, const double *pts, c
  * uids, the split activation (2 * 6144 + 256 fp16 per row), hidden, keypoints, the fix-up list and MMW_RANGE_FIXUP_SCRATCH; the
  * split-fp16 Dense-1 operand (1536 x 12288 fp16) is built once on the device (mmw_mars_split_weights).  Refused with MMW_E_ARG, a
  * message and nothing changed (an earlier model stays attached): FB_FRAMES_BATCH != 2 (the single-frame model define_CNN is not
- * served here), cap_rows < 1, a null pointer, Dense-1 / Dense-2 not 16-byte aligned, dense1_ld < 6144 or not a multiple of 4, and a
+ * served here: mmw_posture_attach_frames), cap_rows < 1, a null pointer, Dense-1 / Dense-2 not 16-byte aligned, dense1_ld < 6144 or not a multiple of 4, and a
  * conv or Dense-1 weight (conv biases included) that is not finite or of magnitude >= 65 504 -- the split arithmetic is exact inside
  * fp16's range only, and there is no silent fp32 fallback.  model == NULL detaches and frees.  Independent of mmw_attach_posture: a
  * one-scene context may hold both.  Sync.
@@ -359,8 +365,18 @@ int mmw_frame_posture_host(mmw_ctx *ctx, const double *raw, const double *pts, c
  * (mmw_get_tracks, mmw_track_table, the next mmw_step), as with the other asynchronous entries.
  * mmw_posture_range reads and clears this path's sticky range word -- MarsCNN.range_overflow() --: bit 0 = a sample's input or
  * activation left fp16's range and its keypoints were recomputed in fp32 (valid), bit 1 = more than MMW_RANGE_FIXUP_CAP such
- * samples in one call, the surplus keeps meaningless keypoints.  Sync. */
+ * samples in one call, the surplus keeps meaningless keypoints.  Sync.
+ * mmw_posture_attach_frames is mmw_posture_attach for either model: frames = 3 IS mmw_posture_attach (same buffers, same launches,
+ * same bits); frames = 1 takes the single-frame model define_CNN (train.py:33-68) on a context with FB_FRAMES_BATCH == 0, in the same
+ * struct: conv kernels (kh,kw,in,out) = 720 and 4608 floats, dense1_w[512][dense1_ld] with dense1_ld >= 2048, dense2_w[57][512].  The
+ * chain's buffers are sized by the model (320 floats per feature row, split activation 2 * 2048 + 256 fp16 per row, hidden 512, the
+ * split Dense-1 operand 512 x 4096 fp16; MMW_RANGE_FIXUP_SCRATCH as it is), the conv weights range-checked over their 2-D sizes.
+ * frames must be 3 or 1 and the context's FB_FRAMES_BATCH + 1: anything else is MMW_E_ARG with a message and nothing changed.
+ * mmw_estimate_posture and mmw_posture_range run whichever model is attached: for frames = 1 mmw_mars_conv_split(frames = 1) ->
+ * mmw_mars_dense1_split (k = 2048, n = 512) -> mmw_mars_dense2 (k = 512) -> mmw_mars_range_fixup_frames(frames = 1) ->
+ * track.keypoints; row count, capacity, detach, sites and the range word as for the 3-frame model. */
 int mmw_posture_attach(mmw_ctx *ctx, const mmw_posture_model *model, int32_t cap_rows);
+int mmw_posture_attach_frames(mmw_ctx *ctx, const mmw_posture_model *model, int32_t frames, int32_t cap_rows);
 int mmw_estimate_posture(mmw_ctx *ctx, int32_t *n_rows);
 int mmw_posture_range(mmw_ctx *ctx, int32_t *word);
 
@@ -669,6 +685,14 @@ int mmw_snapshot_inspect(const void *host_blob, size_t bytes, mmw_snapshot_info 
  *   out[n][3][8][8][32]   = Keras Flatten order (d,h,w,c): feed Dense-1 with Keras' weight rows. */
 int mmw_mars_conv3d(void *hip_stream, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2,
                     float *out, int32_t n);
+/* The two Conv2D(3x3, same, relu) layers of the single-frame model define_CNN (train.py:35-44) the same way (k_mars2d.hip: fp32
+ * matrix cores, fp32 throughout, the intermediate activation never leaves LDS; NaN stays NaN through the ReLUs, as Keras'):
+ *   feat[n][8][8][5]   channels-last input (what mmw_features writes when FB_FRAMES_BATCH == 0)
+ *   w1[3][3][5][16], b1[16], w2[3][3][16][32], b2[32]   Keras kernel layout (kh,kw,in,out)
+ *   out[n][8][8][32]   = Keras Flatten order (h,w,c): feed Dense-1 with Keras' weight rows.
+ * A sample only feeds its own rows of out, in an arithmetic that does not depend on n; rows past n are not written. */
+int mmw_mars_conv2d(void *hip_stream, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2,
+                    float *out, int32_t n);
 
 /* The two convolution layers on the fp16 matrix cores, fp32-exact by operand splitting: every fp32 value a (inputs,
  * weights, activations) is carried as hi = fp16(a), lo' = fp16((a - hi) * 2^11) and a product a.w accumulates in fp32 as
@@ -693,12 +717,18 @@ int mmw_mars_conv_split(void *hip_stream, int32_t frames, const float *feat, con
  * the list is emptied for the next call ([1] = the number taken).  More than MMW_RANGE_FIXUP_CAP flagged samples in one call:
  * bit 1 of *range_flag is raised and the surplus keeps its meaningless rows.
  * define_CNN_3D only (feat[n][3][8][8][5]); cw1 / cb1 / cw2 / cb2 = the conv kernels in Keras layout (fp32), w1[1536][ldw] /
- * bias1 / w2[57][1536] / bias2 as for mmw_mars_head_small; scratch = MMW_RANGE_FIXUP_SCRATCH bytes of device memory. */
+ * bias1 / w2[57][1536] / bias2 as for mmw_mars_head_small; scratch = MMW_RANGE_FIXUP_SCRATCH bytes of device memory.
+ * mmw_mars_range_fixup_frames is the same for either model: frames = 3 IS mmw_mars_range_fixup; frames = 1 repairs define_CNN's
+ * samples (feat[n][8][8][5], the list of mmw_mars_conv_split(frames = 1)) with mmw_mars_conv2d's kernel, conv kernels (kh,kw,in,out),
+ * w1[512][ldw] with ldw >= 2048, w2[57][512]; the same scratch size (the single-frame chain fits inside it).  Other frames: MMW_E_ARG. */
 #define MMW_RANGE_FIXUP_CAP 64
 #define MMW_RANGE_FIXUP_SCRATCH (512 + 64 * (960 + 6144 + 1536 + 57) * 4)
 int mmw_mars_range_fixup(void *hip_stream, const float *feat, int32_t *sample_flags, int32_t n, const float *cw1, const float *cb1,
                          const float *cw2, const float *cb2, const float *w1, int64_t ldw, const float *bias1, const float *w2, const float *bias2,
                          void *scratch, float *kp, int32_t *range_flag);
+int mmw_mars_range_fixup_frames(void *hip_stream, int32_t frames, const float *feat, int32_t *sample_flags, int32_t n, const float *cw1,
+                                const float *cb1, const float *cw2, const float *cb2, const float *w1, int64_t ldw, const float *bias1,
+                                const float *w2, const float *bias2, void *scratch, float *kp, int32_t *range_flag);
 /* Dense-1 of the MARS CNN (train.py:49,87: Dense(512 k, relu); BatchNormalization folded in) on split-fp16 operands, one
  * kernel: out = relu(bias + hi . W_hi + 2^-11 (hi . W_lo' + lo' . W_hi)), fp32 accumulation and output (k_dense.hip).
  * a2 [rows_padded][lda] fp16 as mmw_mars_conv_split writes it; w2 [n][ldw] fp16 = the transposed weights (K contiguous)
@@ -711,7 +741,7 @@ int mmw_mars_dense1_split(void *hip_stream, const void *a2, int64_t lda, const v
  * cores: kp[n_rows][57] = bias2 + hidden[n_rows][ldh] . w2[57][k]^T, fp32 fused multiply-adds in a summation order that is fixed per
  * output (the same for every row, batch size and run), fp32 out.  `hidden` is read once with 16-byte loads; rows past n_rows are
  * neither read nor written; a row only feeds its own output row.  All dev pointers; hidden and w2 16-byte aligned, k and ldh
- * multiples of 4, ldh >= k (k = 1536 for the 3-frame model).  hip_stream as above. */
+ * multiples of 4, ldh >= k (k = 1536 for the 3-frame model, 512 for the single-frame one).  hip_stream as above. */
 int mmw_mars_dense2(void *hip_stream, const float *hidden, int64_t ldh, const float *w2, const float *bias2, float *kp, int32_t n_rows,
                     int32_t k);
 /* The split-fp16 operand of mmw_mars_dense1_split from fp32 weights, on the device (what mars.interleave_split builds with torch,
@@ -725,7 +755,7 @@ int mmw_mars_split_weights(void *hip_stream, const float *w, int64_t ldw, void *
  * loop): Dense-1 + ReLU (train.py:49,87) and Dense-2 (train.py:54,92), both with their BatchNormalization folded in, in fp32
  * fused multiply-adds -- Keras' own arithmetic.  The weight matrix is cut along the features over the whole chip (a tile kernel
  * would stream it through one band of eight workgroups).  act[n_rows][lda] fp32 = the conv pair's output in Keras' Flatten
- * order (mmw_mars_conv3d); w1[n1][ldw] fp32 = Dense-1's weights transposed (K contiguous), bias1[n1]; w2[57][n1], bias2[57];
+ * order (mmw_mars_conv3d, mmw_mars_conv2d); w1[n1][ldw] fp32 = Dense-1's weights transposed (K contiguous), bias1[n1]; w2[57][n1], bias2[57];
  * hidden[n_rows][n1] scratch; kp[n_rows][57].  All dev pointers, 16-byte aligned; k, lda, ldw multiples of 4. */
 int mmw_mars_head_small(void *hip_stream, const float *act, int64_t lda, const float *w1, int64_t ldw, const float *bias1, const float *w2,
                         const float *bias2, float *hidden, float *kp, int32_t n_rows, int32_t k, int32_t n1);

@@ -51,11 +51,13 @@ EXPORTS = [
     "mmw_uart_open", "mmw_uart_close", "mmw_uart_read", "mmw_uart_get_state", "mmw_uart_set_state", "mmw_uart_set_time",
     "mmw_uart_log_enable", "mmw_uart_log_async", "mmw_uart_log_wait", "mmw_uart_log",
     "mmw_samples_async", "mmw_samples_wait", "mmw_samples",
+    "mmw_mars_conv2d", "mmw_mars_range_fixup_frames", "mmw_posture_attach_frames", "mmw_attach_posture_frames",
 ]
 
 
 class MmwPostureModel(C.Structure):
-    """struct mmw_posture_model (include/mmw.h): device pointers of define_CNN_3D's weights, BatchNormalization folded."""
+    """struct mmw_posture_model (include/mmw.h): device pointers of define_CNN_3D's (or, for the *_frames entries with frames = 1,
+    define_CNN's) weights, BatchNormalization folded."""
     _fields_ = [("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("conv2_w", C.c_void_p), ("conv2_b", C.c_void_p),
                 ("dense1_w", C.c_void_p), ("dense1_ld", C.c_int64), ("dense1_b", C.c_void_p), ("dense2_w", C.c_void_p),
                 ("dense2_b", C.c_void_p)]
@@ -431,6 +433,10 @@ def load():
         "mmw_samples_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32]),
         "mmw_samples_wait": (C.c_int, [vp, i32, i32p]),
         "mmw_samples": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32p]),
+        "mmw_mars_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32]),
+        "mmw_mars_range_fixup_frames": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]),
+        "mmw_posture_attach_frames": (C.c_int, [vp, vp, i32, i32]),
+        "mmw_attach_posture_frames": (C.c_int, [vp, vp, i32]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

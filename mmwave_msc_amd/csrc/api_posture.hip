@@ -1,11 +1,12 @@
 // api_posture.hip -- the C-ABI (include/mmw.h): posture.  Feature tensors and keypoints of the tracks, the one-scene fp32 chain's
-// model (mmw_attach_posture; mmw_frame_posture_host runs it), the batched chain (mmw_posture_attach / mmw_estimate_posture) and
-// the stateless mmw_mars_* entries over the CNN kernels.
+// model (mmw_attach_posture / _frames; mmw_frame_posture_host runs it), the batched chain (mmw_posture_attach / _frames,
+// mmw_estimate_posture) and the stateless mmw_mars_* entries over the CNN kernels.  Both chains serve the 3-frame model
+// (define_CNN_3D) and the single-frame one (define_CNN): CnnDims has what differs between them.
 #include <new>
 
 #include "mmw_ctx.hpp"
 
-constexpr long long kPbActLd = 2 * kCnnFlat + 256;   // the batched chain's activation row stride: mars.MarsCNN.ROW_PAD
+static long long pb_act_ld(const CnnDims &d) { return 2LL * d.flat + 256; }   // the batched chain's activation row stride: mars.MarsCNN.ROW_PAD
 constexpr int kPbWordRange = 0, kPbWordWeights = 1, kPbWordList = 2;
 
 void posture_batch_free(PostureBatch *b)
@@ -18,12 +19,12 @@ void posture_batch_free(PostureBatch *b)
     delete b;
 }
 
-// what both chains ask of a model: every weight present, Dense-1 16-byte aligned with a leading dimension >= kCnnFlat that is a
-// multiple of 4; the batched chain's Dense-2 kernel reads its weights 16 bytes at a time as well
-static bool posture_model_ok(const mmw_posture_model *m, bool dense2_aligned)
+// what both chains ask of a model: every weight present, Dense-1 16-byte aligned with a leading dimension >= the model's flat
+// size that is a multiple of 4; the batched chain's Dense-2 kernel reads its weights 16 bytes at a time as well
+static bool posture_model_ok(const mmw_posture_model *m, const CnnDims &d, bool dense2_aligned)
 {
     return m->conv1_w && m->conv1_b && m->conv2_w && m->conv2_b && m->dense1_w && m->dense1_b && m->dense2_w && m->dense2_b &&
-           m->dense1_ld >= kCnnFlat && (m->dense1_ld & 3) == 0 && ((uintptr_t)m->dense1_w & 15) == 0 &&
+           m->dense1_ld >= d.flat && (m->dense1_ld & 3) == 0 && ((uintptr_t)m->dense1_w & 15) == 0 &&
            (!dense2_aligned || ((uintptr_t)m->dense2_w & 15) == 0);
 }
 
@@ -105,27 +106,54 @@ int mmw_set_keypoints_uid(mmw_ctx *c, const float *kp, const int32_t *owner, con
 }
 
 // ---- the one-scene fp32 chain (mmw_frame_posture_host, api_step.hip, runs it behind the step) ----
+// (a context's ring never changes, so neither does the model it can hold: the buffers are sized once)
+static int attach_posture_impl(mmw_ctx *c, const mmw_posture_model *m, int frames, const char *who)
+{
+    const CnnDims d = cnn_dims(frames);
+    if (!posture_model_ok(m, d, false))
+        return fail(c, MMW_E_ARG, "%s: null weight pointer, or Dense-1 not 16-byte aligned with a leading dimension >= %d that is a multiple of 4", who, d.flat);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_pchain) {
+        const size_t cap = (size_t)c->dc.t_cap, per = d.per + d.flat + d.hidden + kCnnKpPad;   // floats per row
+        HIPCHK(c, hipMalloc((void **)&c->d_pchain, cap * (per * sizeof(float) + 2 * sizeof(int32_t))));
+        c->pc_feat = reinterpret_cast<float *>(c->d_pchain);
+        c->pc_act = c->pc_feat + cap * d.per;
+        c->pc_hidden = c->pc_act + cap * d.flat;
+        c->pc_kp = c->pc_hidden + cap * d.hidden;
+        c->pc_owner = reinterpret_cast<int32_t *>(c->pc_kp + cap * kCnnKpPad);
+    }
+    c->model = *m;
+    c->model_frames = frames;
+    c->has_model = true;
+    return MMW_OK;
+}
+
 int mmw_attach_posture(mmw_ctx *c, const mmw_posture_model *m)
 {
     if (!c) return fail(c, MMW_E_ARG, "mmw_attach_posture: null context");
     if (!m) { c->has_model = false; return MMW_OK; }
     if (c->dc.n_scenes != 1 || c->dc.ring != 3 || c->dc.t_cap > 64)
         return fail(c, MMW_E_ARG, "mmw_attach_posture: a one-scene context of the 3-frame model (FB_FRAMES_BATCH = 2) with track_cap <= 64");
-    if (!posture_model_ok(m, false))
-        return fail(c, MMW_E_ARG, "mmw_attach_posture: null weight pointer, or Dense-1 not 16-byte aligned with a leading dimension >= 6144 that is a multiple of 4");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_pchain) {
-        const size_t cap = (size_t)c->dc.t_cap, per = kCnnPer + kCnnFlat + kCnnHidden + kCnnKpPad;   // floats per row
-        HIPCHK(c, hipMalloc((void **)&c->d_pchain, cap * (per * sizeof(float) + 2 * sizeof(int32_t))));
-        c->pc_feat = reinterpret_cast<float *>(c->d_pchain);
-        c->pc_act = c->pc_feat + cap * kCnnPer;
-        c->pc_hidden = c->pc_act + cap * kCnnFlat;
-        c->pc_kp = c->pc_hidden + cap * kCnnHidden;
-        c->pc_owner = reinterpret_cast<int32_t *>(c->pc_kp + cap * kCnnKpPad);
-    }
-    c->model = *m;
-    c->has_model = true;
+    return attach_posture_impl(c, m, 3, "mmw_attach_posture");
+}
+
+// the `frames` argument of the _frames entries: 3 or 1, and the context's ring
+static int frames_ok(mmw_ctx *c, int32_t frames, const char *who)
+{
+    if ((frames != 3 && frames != 1) || c->dc.ring != frames)
+        return fail(c, MMW_E_ARG, "%s: frames = %d must be 3 (define_CNN_3D) or 1 (define_CNN) and the context's FB_FRAMES_BATCH + 1, this context has FB_FRAMES_BATCH = %d",
+                    who, frames, c->dc.ring - 1);
     return MMW_OK;
+}
+
+int mmw_attach_posture_frames(mmw_ctx *c, const mmw_posture_model *m, int32_t frames)
+{
+    if (!c) return fail(c, MMW_E_ARG, "mmw_attach_posture_frames: null context");
+    if (!m) { c->has_model = false; return MMW_OK; }
+    MMW_TRY(frames_ok(c, frames, "mmw_attach_posture_frames"));
+    if (c->dc.n_scenes != 1 || c->dc.t_cap > 64)
+        return fail(c, MMW_E_ARG, "mmw_attach_posture_frames: a one-scene context with track_cap <= 64");
+    return attach_posture_impl(c, m, frames, "mmw_attach_posture_frames");
 }
 
 // ---- the stateless entries over the CNN kernels ----
@@ -135,6 +163,15 @@ int mmw_mars_conv3d(void *hip_stream, const float *feat, const float *w1, const 
     if (n < 0 || (n > 0 && (!feat || !w1 || !b1 || !w2 || !b2 || !out))) return fail(nullptr, MMW_E_ARG, "mmw_mars_conv3d: bad argument");
     launch_mars_conv(feat, w1, b1, w2, b2, out, n, (hipStream_t)hip_stream);
     return launches_done("mmw_mars_conv3d");
+}
+
+int mmw_mars_conv2d(void *hip_stream, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2,
+                    float *out, int32_t n)
+{
+    if (n < 0 || (n > 0 && (!feat || !w1 || !b1 || !w2 || !b2 || !out))) return fail(nullptr, MMW_E_ARG, "mmw_mars_conv2d: bad argument");
+    if (n == 0) return MMW_OK;
+    launch_mars_conv2d(feat, w1, b1, w2, b2, out, n, (hipStream_t)hip_stream);
+    return launches_done("mmw_mars_conv2d");
 }
 
 int mmw_mars_conv_split(void *hip_stream, int32_t frames, const float *feat, const float *w1, const float *b1, const float *w2,
@@ -171,26 +208,45 @@ int mmw_mars_head_small(void *hip_stream, const float *act, int64_t lda, const f
     return launches_done("mmw_mars_head_small");
 }
 
+static int range_fixup_impl(const char *who, void *hip_stream, int frames, const float *feat, int32_t *sample_flags, int32_t n, const float *cw1,
+                            const float *cb1, const float *cw2, const float *cb2, const float *w1, int64_t ldw, const float *bias1, const float *w2,
+                            const float *bias2, void *scratch, float *kp, int32_t *range_flag)
+{
+    constexpr int kCap = MMW_RANGE_FIXUP_CAP;
+    const CnnDims d = cnn_dims(frames);
+    if (n < 0 || (n > 0 && (!feat || !sample_flags || !cw1 || !cb1 || !cw2 || !cb2 || !w1 || !bias1 || !w2 || !bias2 || !scratch || !kp)) ||
+        ldw < d.flat || (ldw & 3) != 0 || (((uintptr_t)scratch | (uintptr_t)w1) & 15) != 0)
+        return fail(nullptr, MMW_E_ARG, "%s: bad argument", who);
+    if (n == 0) return MMW_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    // scratch: small_feat[64][per], act[64][flat], hidden[64][hidden], kp_small[64][57] floats (behind 512 spare bytes; the 3-frame
+    // model's 960 / 6144 / 1536 are what MMW_RANGE_FIXUP_SCRATCH holds, the single-frame model's 320 / 2048 / 512 fit inside);
+    // sample_flags = the fix-up list k_mars_conv16 appended to: [0] running count, [1] taken by this call, [2 ..] sample indices
+    float *small = reinterpret_cast<float *>(reinterpret_cast<char *>(scratch) + 512);
+    float *act = small + (size_t)kCap * d.per, *hidden = act + (size_t)kCap * d.flat, *kps = hidden + (size_t)kCap * d.hidden;
+    const int32_t *taken = sample_flags + 1;
+    launch_range_gather(feat, sample_flags, n, d.per, kCap, small, range_flag, st);
+    if (frames == 3) launch_mars_conv(small, cw1, cb1, cw2, cb2, act, kCap, st, taken);
+    else launch_mars_conv2d(small, cw1, cb1, cw2, cb2, act, kCap, st, taken);
+    launch_mars_head_small(act, d.flat, w1, ldw, bias1, w2, bias2, hidden, kps, kCap, d.flat, d.hidden, MMW_NKP, st, taken);
+    launch_range_scatter(kps, sample_flags, kp, kCap, MMW_NKP, n, st);
+    return launches_done(who);
+}
+
 int mmw_mars_range_fixup(void *hip_stream, const float *feat, int32_t *sample_flags, int32_t n, const float *cw1, const float *cb1,
                          const float *cw2, const float *cb2, const float *w1, int64_t ldw, const float *bias1, const float *w2, const float *bias2,
                          void *scratch, float *kp, int32_t *range_flag)
 {
-    constexpr int kCap = MMW_RANGE_FIXUP_CAP;
-    if (n < 0 || (n > 0 && (!feat || !sample_flags || !cw1 || !cb1 || !cw2 || !cb2 || !w1 || !bias1 || !w2 || !bias2 || !scratch || !kp)) ||
-        ldw < kCnnFlat || (ldw & 3) != 0 || (((uintptr_t)scratch | (uintptr_t)w1) & 15) != 0)
-        return fail(nullptr, MMW_E_ARG, "mmw_mars_range_fixup: bad argument");
-    if (n == 0) return MMW_OK;
-    hipStream_t st = (hipStream_t)hip_stream;
-    // scratch: small_feat[64][960], act[64][6144], hidden[64][1536], kp_small[64][57] floats (behind 512 spare bytes);
-    // sample_flags = the fix-up list k_mars_conv16 appended to: [0] running count, [1] taken by this call, [2 ..] sample indices
-    float *small = reinterpret_cast<float *>(reinterpret_cast<char *>(scratch) + 512);
-    float *act = small + (size_t)kCap * kCnnPer, *hidden = act + (size_t)kCap * kCnnFlat, *kps = hidden + (size_t)kCap * kCnnHidden;
-    const int32_t *taken = sample_flags + 1;
-    launch_range_gather(feat, sample_flags, n, kCnnPer, kCap, small, range_flag, st);
-    launch_mars_conv(small, cw1, cb1, cw2, cb2, act, kCap, st, taken);
-    launch_mars_head_small(act, kCnnFlat, w1, ldw, bias1, w2, bias2, hidden, kps, kCap, kCnnFlat, kCnnHidden, MMW_NKP, st, taken);
-    launch_range_scatter(kps, sample_flags, kp, kCap, MMW_NKP, n, st);
-    return launches_done("mmw_mars_range_fixup");
+    return range_fixup_impl("mmw_mars_range_fixup", hip_stream, 3, feat, sample_flags, n, cw1, cb1, cw2, cb2, w1, ldw, bias1, w2, bias2, scratch, kp, range_flag);
+}
+
+int mmw_mars_range_fixup_frames(void *hip_stream, int32_t frames, const float *feat, int32_t *sample_flags, int32_t n, const float *cw1,
+                                const float *cb1, const float *cw2, const float *cb2, const float *w1, int64_t ldw, const float *bias1,
+                                const float *w2, const float *bias2, void *scratch, float *kp, int32_t *range_flag)
+{
+    if (frames != 3 && frames != 1) return fail(nullptr, MMW_E_ARG, "mmw_mars_range_fixup_frames: frames = %d must be 3 or 1 (FB_FRAMES_BATCH + 1)", frames);
+    return range_fixup_impl("mmw_mars_range_fixup_frames", hip_stream, frames, feat, sample_flags, n, cw1, cb1, cw2, cb2, w1, ldw, bias1, w2, bias2, scratch,
+                            kp, range_flag);
 }
 
 int mmw_mars_dense2(void *hip_stream, const float *hidden, int64_t ldh, const float *w2, const float *bias2, float *kp, int32_t n_rows, int32_t k)
@@ -214,41 +270,44 @@ int mmw_mars_split_weights(void *hip_stream, const float *w, int64_t ldw, void *
 }
 
 // ---- the batched TrackBuffer.estimate_posture (Tracking.py:705-734) behind the C-ABI: any number of scenes, no torch ----
-int mmw_posture_attach(mmw_ctx *c, const mmw_posture_model *m, int32_t cap_rows)
+static int posture_detach(mmw_ctx *c)
 {
-    if (!c) return fail(c, MMW_E_ARG, "mmw_posture_attach: null context");
-    if (!m) {
-        if (c->pb) {
-            HIPCHK(c, hipSetDevice(c->device));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            posture_batch_free(c->pb);
-            c->pb = nullptr;
-        }
-        return MMW_OK;
+    if (c->pb) {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        posture_batch_free(c->pb);
+        c->pb = nullptr;
     }
-    if (c->dc.ring != 3) return fail(c, MMW_E_ARG, "mmw_posture_attach: the 3-frame model only (FB_FRAMES_BATCH = 2), this context has FB_FRAMES_BATCH = %d", c->dc.ring - 1);
-    if (cap_rows < 1) return fail(c, MMW_E_ARG, "mmw_posture_attach: cap_rows = %d must be >= 1", cap_rows);
-    if (cap_rows > INT32_MAX - 255) return fail(c, MMW_E_ARG, "mmw_posture_attach: cap_rows = %d is too large", cap_rows);
-    if (!posture_model_ok(m, true))
-        return fail(c, MMW_E_ARG, "mmw_posture_attach: null weight pointer, or Dense-1 / Dense-2 not 16-byte aligned, or Dense-1's leading dimension not a multiple of 4 that is >= 6144");
+    return MMW_OK;
+}
+
+static int posture_attach_impl(mmw_ctx *c, const mmw_posture_model *m, int frames, int32_t cap_rows, const char *who)
+{
+    const CnnDims d = cnn_dims(frames);
+    const int taps = frames == 3 ? 27 : 9;
+    if (cap_rows < 1) return fail(c, MMW_E_ARG, "%s: cap_rows = %d must be >= 1", who, cap_rows);
+    if (cap_rows > INT32_MAX - 255) return fail(c, MMW_E_ARG, "%s: cap_rows = %d is too large", who, cap_rows);
+    if (!posture_model_ok(m, d, true))
+        return fail(c, MMW_E_ARG, "%s: null weight pointer, or Dense-1 / Dense-2 not 16-byte aligned, or Dense-1's leading dimension not a multiple of 4 that is >= %d", who, d.flat);
     HIPCHK(c, hipSetDevice(c->device));
     PostureBatch *b = new (std::nothrow) PostureBatch();
-    if (!b) return fail(c, MMW_E_HIP, "mmw_posture_attach: out of host memory");
+    if (!b) return fail(c, MMW_E_HIP, "%s: out of host memory", who);
     const size_t cap = ((size_t)cap_rows + 255) & ~(size_t)255;
     b->model = *m;
+    b->frames = frames;
     b->cap = cap_rows;
     const size_t n_words = kPbWordList + 2 + MMW_RANGE_FIXUP_CAP;
     hipError_t e = hipSuccess;
     auto grab = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    grab((void **)&b->feat, cap * kCnnPer * sizeof(float));
+    grab((void **)&b->feat, cap * d.per * sizeof(float));
     grab((void **)&b->owner, cap * 2 * sizeof(int32_t));
     grab((void **)&b->uid, cap * sizeof(int32_t));
-    grab(&b->act16, cap * (size_t)kPbActLd * 2);
-    grab((void **)&b->hidden, cap * kCnnHidden * sizeof(float));
+    grab(&b->act16, cap * (size_t)pb_act_ld(d) * 2);
+    grab((void **)&b->hidden, cap * d.hidden * sizeof(float));
     grab((void **)&b->kp, cap * MMW_NKP * sizeof(float));
     grab((void **)&b->words, n_words * sizeof(int32_t));
     grab(&b->fix_scratch, MMW_RANGE_FIXUP_SCRATCH);
-    grab(&b->w16, (size_t)kCnnHidden * 2 * kCnnFlat * 2);
+    grab(&b->w16, (size_t)d.hidden * 2 * d.flat * 2);
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_total, sizeof(int32_t));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&b->total_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMemsetAsync(b->words, 0, n_words * sizeof(int32_t), c->stream);
@@ -256,10 +315,10 @@ int mmw_posture_attach(mmw_ctx *c, const mmw_posture_model *m, int32_t cap_rows)
     if (e == hipSuccess) {
         // the split Dense-1 operand, once; every weight that meets the split arithmetic must lie inside fp16's range
         int32_t *flag = b->words + kPbWordWeights;
-        launch_split_weights(m->dense1_w, m->dense1_ld, b->w16, 2 * kCnnFlat, kCnnHidden, kCnnFlat, flag, c->stream);
-        launch_range_check(m->conv1_w, 27 * 5 * 16, flag, c->stream);
+        launch_split_weights(m->dense1_w, m->dense1_ld, b->w16, 2 * d.flat, d.hidden, d.flat, flag, c->stream);
+        launch_range_check(m->conv1_w, taps * 5 * 16, flag, c->stream);
         launch_range_check(m->conv1_b, 16, flag, c->stream);
-        launch_range_check(m->conv2_w, 27 * 16 * 32, flag, c->stream);
+        launch_range_check(m->conv2_w, taps * 16 * 32, flag, c->stream);
         launch_range_check(m->conv2_b, 32, flag, c->stream);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
@@ -267,15 +326,31 @@ int mmw_posture_attach(mmw_ctx *c, const mmw_posture_model *m, int32_t cap_rows)
     }
     if (e != hipSuccess) {
         posture_batch_free(b);
-        return fail(c, MMW_E_HIP, "mmw_posture_attach: %s (cap_rows = %d)", hipGetErrorString(e), cap_rows);
+        return fail(c, MMW_E_HIP, "%s: %s (cap_rows = %d)", who, hipGetErrorString(e), cap_rows);
     }
     if (bad) {
         posture_batch_free(b);
-        return fail(c, MMW_E_ARG, "mmw_posture_attach: a conv or Dense-1 weight is not finite or has a magnitude >= 65504: outside fp16's range, where the split arithmetic of this path is not exact (use a one-scene context's fp32 path, mmw_attach_posture, for such a model)");
+        return fail(c, MMW_E_ARG, "%s: a conv or Dense-1 weight is not finite or has a magnitude >= 65504: outside fp16's range, where the split arithmetic of this path is not exact (use a one-scene context's fp32 path, mmw_attach_posture, for such a model)", who);
     }
     if (c->pb) posture_batch_free(c->pb);   // (the stream was waited for above: nothing of the old chain is running)
     c->pb = b;
     return MMW_OK;
+}
+
+int mmw_posture_attach(mmw_ctx *c, const mmw_posture_model *m, int32_t cap_rows)
+{
+    if (!c) return fail(c, MMW_E_ARG, "mmw_posture_attach: null context");
+    if (!m) return posture_detach(c);
+    if (c->dc.ring != 3) return fail(c, MMW_E_ARG, "mmw_posture_attach: the 3-frame model only (FB_FRAMES_BATCH = 2), this context has FB_FRAMES_BATCH = %d", c->dc.ring - 1);
+    return posture_attach_impl(c, m, 3, cap_rows, "mmw_posture_attach");
+}
+
+int mmw_posture_attach_frames(mmw_ctx *c, const mmw_posture_model *m, int32_t frames, int32_t cap_rows)
+{
+    if (!c) return fail(c, MMW_E_ARG, "mmw_posture_attach_frames: null context");
+    if (!m) return posture_detach(c);
+    MMW_TRY(frames_ok(c, frames, "mmw_posture_attach_frames"));
+    return posture_attach_impl(c, m, frames, cap_rows, "mmw_posture_attach_frames");
 }
 
 int mmw_estimate_posture(mmw_ctx *c, int32_t *n_rows)
@@ -286,6 +361,8 @@ int mmw_estimate_posture(mmw_ctx *c, int32_t *n_rows)
     if (!b) return fail(c, MMW_E_ARG, "mmw_estimate_posture: no model attached (mmw_posture_attach)");
     HIPCHK(c, hipSetDevice(c->device));
     const mmw_posture_model &m = b->model;
+    const CnnDims d = cnn_dims(b->frames);
+    const long long act_ld = pb_act_ld(d);
     // the matrix kernels need their exact batch size: the host waits for the total (not for the stream)
     MMW_TRY(features_and_total(c, b->feat, b->owner, b->uid, b->cap, b->h_total, b->total_ev));
     HIPCHK(c, hipEventSynchronize(b->total_ev));
@@ -294,12 +371,12 @@ int mmw_estimate_posture(mmw_ctx *c, int32_t *n_rows)
     if (total <= 0) return MMW_OK;
     const int rows_padded = (total + 255) & ~255;
     int32_t *range = b->words + kPbWordRange, *list = b->words + kPbWordList;
-    if (launch_mars_conv16(3, b->feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, b->act16, kPbActLd, total, range, list, c->stream) != 0 ||
-        launch_mars_dense1(b->act16, kPbActLd, b->w16, 2 * kCnnFlat, m.dense1_b, b->hidden, rows_padded, kCnnFlat, kCnnHidden, c->stream) != 0)
+    if (launch_mars_conv16(b->frames, b->feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, b->act16, act_ld, total, range, list, c->stream) != 0 ||
+        launch_mars_dense1(b->act16, act_ld, b->w16, 2 * d.flat, m.dense1_b, b->hidden, rows_padded, d.flat, d.hidden, c->stream) != 0)
         return fail(c, MMW_E_HIP, "mmw_estimate_posture: hipFuncSetAttribute(max dynamic LDS) failed on this device");
-    launch_mars_dense2(b->hidden, kCnnHidden, m.dense2_w, m.dense2_b, b->kp, total, kCnnHidden, c->stream);
+    launch_mars_dense2(b->hidden, d.hidden, m.dense2_w, m.dense2_b, b->kp, total, d.hidden, c->stream);
     HIPCHK(c, hipGetLastError());
-    const int rc = mmw_mars_range_fixup(c->stream, b->feat, list, total, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, m.dense1_w, m.dense1_ld, m.dense1_b,
+    const int rc = range_fixup_impl("mmw_mars_range_fixup", c->stream, b->frames, b->feat, list, total, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, m.dense1_w, m.dense1_ld, m.dense1_b,
                                         m.dense2_w, m.dense2_b, b->fix_scratch, b->kp, range);
     if (rc) return fail(c, rc, "mmw_estimate_posture: %s", mmw_last_error(nullptr));
     launch_set_kp(c->dc, c->st, b->kp, b->owner, total, c->stream);

@@ -14,8 +14,11 @@ using namespace mmw;
 
 struct EventPair { hipEvent_t a, b; int kid; };
 
-// the posture CNN's shapes, floats per row: feature tensor, conv output, hidden layer, keypoints (MMW_NKP = 57, padded)
-constexpr int kCnnPer = 3 * 8 * 8 * 5, kCnnFlat = 3 * 64 * 32, kCnnHidden = 1536, kCnnKpPad = 64;
+// the posture CNN's shapes, floats per row: feature tensor, conv output, hidden layer -- by model: frames = 3 (define_CNN_3D,
+// train.py:71-106: 960, 6144, 1536) or 1 (define_CNN, train.py:33-68: 320, 2048, 512) -- and keypoints (MMW_NKP = 57, padded)
+constexpr int kCnnKpPad = 64;
+struct CnnDims { int per, flat, hidden; };
+static inline CnnDims cnn_dims(int frames) { return CnnDims{frames * 8 * 8 * 5, frames * 64 * 32, frames * 512}; }
 constexpr int kTickets = 4;
 // the counters of mmw_stats_get in st.stats (the probe words of the diagnostic build lie behind them)
 constexpr size_t kStatBytes = (size_t)kStatSlots * kStatWords * sizeof(unsigned long long);
@@ -23,6 +26,7 @@ constexpr size_t kStatBytes = (size_t)kStatSlots * kStatWords * sizeof(unsigned 
 // mmw_posture_attach: the model, its split Dense-1 operand and the buffers of the batched CNN chain ([cap] rows, cap a multiple of 256)
 struct PostureBatch {
     mmw_posture_model model = {};
+    int frames = 3;                   // the model: 3 = define_CNN_3D, 1 = define_CNN (= the context's ring)
     int32_t cap = 0;
     float *feat = nullptr, *hidden = nullptr, *kp = nullptr;
     int32_t *owner = nullptr, *uid = nullptr;
@@ -84,6 +88,7 @@ struct mmw_ctx {
     char *d_snap = nullptr;           // mmw_snapshot / mmw_restore scratch (lazy): [S] scene list | [S] flags | [4] check word | [S + 2] u64 sizes | [S] directory
     // mmw_attach_posture: the model and the chain's buffers ([cap] rows: feature tensors, owners, conv output, hidden, keypoints)
     bool has_model = false;
+    int model_frames = 3;             // ... 3 = define_CNN_3D, 1 = define_CNN (= the context's ring)
     mmw_posture_model model = {};
     char *d_pchain = nullptr;
     float *pc_feat = nullptr, *pc_act = nullptr, *pc_hidden = nullptr, *pc_kp = nullptr;

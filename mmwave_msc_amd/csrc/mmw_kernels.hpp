@@ -73,6 +73,8 @@ void launch_uart_log(const DevCfg &cfg, const UartState &us, const UartLog &log,
 void launch_samples(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ExportScratch &sc, mmw_sample_entry *dir, int cap_samples, void *out, int mode, const int32_t *scene_flags, int scene_base, hipStream_t st);
 // k_mars.hip, k_dense.hip, k_dense2.hip: the posture CNN
 void launch_mars_conv(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
+// k_mars2d.hip: the Conv2D pair of the single-frame model (define_CNN) in fp32; dev_rows as launch_mars_conv's
+void launch_mars_conv2d(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
 void launch_range_gather(const float *feat, int32_t *list, int n, int per, int cap, float *small, int32_t *range_flag, hipStream_t stream);
 void launch_range_scatter(const float *kp_small, const int32_t *list, float *kp, int cap, int nout, int n, hipStream_t stream);
 int launch_mars_dense1(const void *a2, long long lda, const void *w2, long long ldw, const float *bias, float *out, int rows_padded, int K, int N, hipStream_t stream);

@@ -192,7 +192,8 @@ class TrackBuffer:
             self._sb.restore(blob)
 
     def attach_posture_model(self, model):
-        """The loop body of offline_main.py:53-60 as ONE round trip: with a `mars.MarsCNN` (3-frame model, on this GPU) attached,
+        """The loop body of offline_main.py:53-60 as ONE round trip: with a `mars.MarsCNN` (on this GPU: the 3-frame model, or the
+        single-frame one under FB_FRAMES_BATCH = 0) attached,
         `track()` / `track_raw()` queue `estimate_posture(model)` behind the step -- feature tensors, CNN (Keras' fp32 arithmetic)
         and the keypoint assignment on the device -- before they wait for the frame's results, and the loop's own
         `estimate_posture(model)` call finds the work done.  A caller that does NOT estimate the posture after every tracked
@@ -203,6 +204,8 @@ class TrackBuffer:
             self._fused_model = None
             return False
         ok = getattr(model, "has_small_path", lambda: False)() and sb.ring == 3 and sb.track_cap <= 64
+        if not ok and sb.ring == 1 and sb.track_cap <= 64:   # the single-frame model: the context runs it from the model's tensors alone
+            ok = getattr(model, "frames", None) == 1 and all(hasattr(model, a) for a in ("k_w1", "k_b1", "k_w2", "k_b2", "dense1_dhwc", "dense2"))
         if ok:
             p0 = next(model.parameters(), None)
             ok = p0 is not None and p0.is_cuda and p0.device.index == self._device
