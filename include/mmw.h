@@ -737,6 +737,13 @@ int mmw_mars_range_fixup_frames(void *hip_stream, int32_t frames, const float *f
 int mmw_mars_dense1_split(void *hip_stream, const void *a2, int64_t lda, const void *w2, int64_t ldw, const float *bias, float *out,
                           int32_t rows_padded, int32_t k, int32_t n);
 
+/* The tile plan mmw_mars_dense1_split runs for (rows_padded, n) on the current device, host queries only (no GPU work):
+ * out[0] = bands of 256 rows computed as 256 x 192 tiles (n a multiple of 192), out[1] = bands as 256 x 128 tiles, out[2] = bands
+ * as 128 x 128 half tiles (the tail of the tile list: rows from (out[0] + out[1]) * 256 on), out[3] = the CU count behind the
+ * split.  out[0] + out[1] + out[2] = rows_padded / 256 and one of out[0], out[1] is 0; the grids are out[0] * (n / 192),
+ * out[1] * (n / 128) and 2 * out[2] * (n / 128) workgroups.  The results of mmw_mars_dense1_split do not depend on the plan. */
+int mmw_mars_dense1_plan(int32_t rows_padded, int32_t n, int32_t out[4]);
+
 /* Dense-2 of the MARS CNN at any batch size (train.py:92: Dense(57); BatchNormalization folded in), one kernel on the fp32 matrix
  * cores: kp[n_rows][57] = bias2 + hidden[n_rows][ldh] . w2[57][k]^T, fp32 fused multiply-adds in a summation order that is fixed per
  * output (the same for every row, batch size and run), fp32 out.  `hidden` is read once with 16-byte loads; rows past n_rows are

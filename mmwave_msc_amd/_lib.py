@@ -52,6 +52,7 @@ EXPORTS = [
     "mmw_uart_log_enable", "mmw_uart_log_async", "mmw_uart_log_wait", "mmw_uart_log",
     "mmw_samples_async", "mmw_samples_wait", "mmw_samples",
     "mmw_mars_conv2d", "mmw_mars_range_fixup_frames", "mmw_posture_attach_frames", "mmw_attach_posture_frames",
+    "mmw_mars_dense1_plan",
 ]
 
 
@@ -390,6 +391,7 @@ def load():
         "mmw_mars_conv_split": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, C.c_int64, i32, vp, vp]),
         "mmw_mars_range_fixup": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]),
         "mmw_mars_dense1_split": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, i32, i32, i32]),
+        "mmw_mars_dense1_plan": (C.c_int, [i32, i32, vp]),
         "mmw_mars_head_small": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, i32, i32, i32]),
         "mmw_parse_uart": (C.c_int, [vp, C.c_size_t, vp, vp, vp, i32, vp, vp, vp, vp]),
         "mmw_parse_uart_cap": (C.c_int, [vp, C.c_size_t, C.c_size_t, vp, vp, vp, i32, vp, vp, vp, vp]),

@@ -197,6 +197,18 @@ int mmw_mars_dense1_split(void *hip_stream, const void *a2, int64_t lda, const v
     return launches_done("mmw_mars_dense1_split");
 }
 
+int mmw_mars_dense1_plan(int32_t rows_padded, int32_t n, int32_t out[4])
+{
+    if (!out || rows_padded < 0 || (rows_padded & 255) != 0 || n < 128 || (n & 127) != 0)
+        return fail(nullptr, MMW_E_ARG, "mmw_mars_dense1_plan: rows_padded must be a multiple of 256, n of 128");
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fail(nullptr, MMW_E_NODEVICE, "mmw_mars_dense1_plan: no current HIP device");
+    const int n_cu = mars_dense1_cus(dev);
+    const Dense1Plan p = mars_dense1_plan(rows_padded, n, n_cu);
+    out[0] = p.bands192; out[1] = p.bands128; out[2] = p.bands_half; out[3] = n_cu;
+    return MMW_OK;
+}
+
 int mmw_mars_head_small(void *hip_stream, const float *act, int64_t lda, const float *w1, int64_t ldw, const float *bias1, const float *w2,
                         const float *bias2, float *hidden, float *kp, int32_t n_rows, int32_t k, int32_t n1)
 {

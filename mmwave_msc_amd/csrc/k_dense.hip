@@ -314,6 +314,45 @@ __global__ __launch_bounds__(kThreads, 1) void k_mars_dense1_t(const _Float16 *_
 constexpr int kLds192 = 3 * 256 * kRowBytes + 2 * 192 * kRowBytes;   // 144 KB: three A slots, two W slots
 constexpr int kLds256 = 3 * (256 + 128) * kRowBytes;                  // 144 KB
 constexpr int kLds128 = 3 * (128 + 128) * kRowBytes;                  // 96 KB
+// The tile plan as ONE pure function of (rows_padded, N, n_cu): how many 256-row bands go to which instantiation.  The launcher
+// below runs exactly this plan and mmw_mars_dense1_plan (include/mmw.h) reports it, so a test can choose row counts that reach
+// every instantiation on whatever chip it runs on.
+Dense1Plan mars_dense1_plan(int rows_padded, int N, int n_cu)
+{
+    Dense1Plan p{0, 0, 0};
+    const int bands = rows_padded / BM, tiles_n = N / BN;
+    if (N % 192 == 0) {   // 256 x 192 tiles for the whole waves of workgroups, the rest as 128 x 128 half tiles
+        const int tn2 = N / 192;
+        const long long total2 = (long long)bands * tn2, rem2 = total2 % n_cu;
+        int bm2 = bands;
+        if (rem2 != 0 && 2 * rem2 <= n_cu) {   // the last wave of workgroups would fill less than half the chip: cut it off at a band boundary
+            bm2 = (int)(((total2 / n_cu) * n_cu) / tn2);
+            if (2LL * (bands - bm2) * tiles_n > n_cu) bm2 = bands;   // (... unless the rest is more than one wave of 128 x 128 half tiles)
+        }
+        p.bands192 = bm2;
+        p.bands_half = bands - bm2;
+        return p;
+    }
+    const long long total = (long long)bands * tiles_n;
+    int bands_main = bands;
+    const long long rem = total % n_cu;
+    if (rem != 0 && 2 * rem <= n_cu) {
+        // whole waves of workgroups as 256-row tiles (cut at a band boundary), the remainder as 128-row tiles
+        bands_main = (int)(((total / n_cu) * n_cu) / tiles_n);
+        if (2LL * (bands - bands_main) * tiles_n > n_cu) bands_main = bands;   // (the remainder would be more than one wave of half tiles)
+    }
+    p.bands128 = bands_main;
+    p.bands_half = bands - bands_main;
+    return p;
+}
+
+// the CU count behind the plan: the current device's, 256 where the query fails (host query only)
+int mars_dense1_cus(int dev)
+{
+    hipDeviceProp_t prop;
+    return hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+}
+
 int launch_mars_dense1(const void *a2, long long lda, const void *w2, long long ldw, const float *bias, float *out, int rows_padded, int K, int N,
                        hipStream_t stream)
 {
@@ -328,43 +367,22 @@ int launch_mars_dense1(const void *a2, long long lda, const void *w2, long long 
         if (hipFuncSetAttribute((const void *)k_mars_dense1_t<256, 2, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds192) != hipSuccess) return;
         if (hipFuncSetAttribute((const void *)k_mars_dense1_t<256, 2, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds256) != hipSuccess) return;
         if (hipFuncSetAttribute((const void *)k_mars_dense1_t<128, 4, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds128) != hipSuccess) return;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) P.n_cu = prop.multiProcessorCount;
+        P.n_cu = mars_dense1_cus(dev);
         P.ok = true;
     });
     if (!P.ok) return -1;
-    const int n_cu = P.n_cu;
-    const int bands = rows_padded / BM, tiles_n = N / BN;
-    const long long total = (long long)bands * tiles_n;
-    int bands_main = bands;
-    const long long rem = total % n_cu;
-    if (rem != 0 && 2 * rem <= n_cu) {
-        // whole waves of workgroups as 256-row tiles (cut at a band boundary), the remainder as 128-row tiles
-        bands_main = (int)(((total / n_cu) * n_cu) / tiles_n);
-        if (2LL * (bands - bands_main) * tiles_n > n_cu) bands_main = bands;   // (the remainder would be more than one wave of half tiles)
-    }
+    const Dense1Plan plan = mars_dense1_plan(rows_padded, N, P.n_cu);
+    const int tiles_n = N / BN, bands_main = plan.bands192 + plan.bands128;   // (one of the two: N picks the main instantiation)
     const _Float16 *A = reinterpret_cast<const _Float16 *>(a2), *W = reinterpret_cast<const _Float16 *>(w2);
-    if (N % 192 == 0) {   // 256 x 192 tiles for the whole waves of workgroups, the rest as below
-        const int tn2 = N / 192;
-        const long long total2 = (long long)bands * tn2, rem2 = total2 % n_cu;
-        int bm2 = bands;
-        if (rem2 != 0 && 2 * rem2 <= n_cu) {   // the last wave of workgroups would fill less than half the chip: cut it off at a band boundary
-            bm2 = (int)(((total2 / n_cu) * n_cu) / tn2);
-            if (2LL * (bands - bm2) * tiles_n > n_cu) bm2 = bands;   // (... unless the rest is more than one wave of 128 x 128 half tiles)
-        }
-        if (bm2 > 0)
-            hipLaunchKernelGGL((k_mars_dense1_t<256, 2, 3, 2>), dim3(bm2 * tn2), dim3(kThreads), kLds192, stream, A, lda, W, ldw, bias, out, K, N, 0LL, tn2);
-        if (bm2 < bands)
-            hipLaunchKernelGGL((k_mars_dense1_t<128, 4, 1, 3>), dim3(2 * (bands - bm2) * tiles_n), dim3(kThreads), kLds128, stream, A, lda, W, ldw, bias, out, K,
-                               N, (long long)bm2 * BM, tiles_n);
-        return 0;
-    }
-    if (bands_main > 0)
-        hipLaunchKernelGGL((k_mars_dense1_t<256, 2, 2, 3>), dim3(bands_main * tiles_n), dim3(kThreads), kLds256, stream, A, lda, W, ldw, bias, out, K, N, 0LL,
+    if (plan.bands192 > 0)
+        hipLaunchKernelGGL((k_mars_dense1_t<256, 2, 3, 2>), dim3(plan.bands192 * (N / 192)), dim3(kThreads), kLds192, stream, A, lda, W, ldw, bias, out, K, N, 0LL,
+                           N / 192);
+    if (plan.bands128 > 0)
+        hipLaunchKernelGGL((k_mars_dense1_t<256, 2, 2, 3>), dim3(plan.bands128 * tiles_n), dim3(kThreads), kLds256, stream, A, lda, W, ldw, bias, out, K, N, 0LL,
                            tiles_n);
-    if (bands_main < bands)
-        hipLaunchKernelGGL((k_mars_dense1_t<128, 4, 1, 3>), dim3(2 * (bands - bands_main) * tiles_n), dim3(kThreads), kLds128, stream, A, lda, W, ldw, bias,
-                           out, K, N, (long long)bands_main * BM, tiles_n);
+    if (plan.bands_half > 0)
+        hipLaunchKernelGGL((k_mars_dense1_t<128, 4, 1, 3>), dim3(2 * plan.bands_half * tiles_n), dim3(kThreads), kLds128, stream, A, lda, W, ldw, bias, out, K,
+                           N, (long long)bands_main * BM, tiles_n);
     return 0;
 }
 

@@ -77,6 +77,10 @@ void launch_mars_conv(const float *feat, const float *w1, const float *b1, const
 void launch_mars_conv2d(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
 void launch_range_gather(const float *feat, int32_t *list, int n, int per, int cap, float *small, int32_t *range_flag, hipStream_t stream);
 void launch_range_scatter(const float *kp_small, const int32_t *list, float *kp, int cap, int nout, int n, hipStream_t stream);
+// Dense-1's tile plan (k_dense.hip): bands of 256 rows per instantiation -- 256 x 192 tiles, 256 x 128 tiles, 128 x 128 half tiles
+struct Dense1Plan { int bands192, bands128, bands_half; };
+Dense1Plan mars_dense1_plan(int rows_padded, int N, int n_cu);
+int mars_dense1_cus(int dev);
 int launch_mars_dense1(const void *a2, long long lda, const void *w2, long long ldw, const float *bias, float *out, int rows_padded, int K, int N, hipStream_t stream);
 int launch_mars_head_small(const float *act, long long lda, const float *w1, long long ldw, const float *bias1, const float *w2, const float *bias2, float *hidden, float *kp, int n_rows, int K, int N1, int NOUT, hipStream_t stream, const int32_t *dev_rows = nullptr);
 int launch_mars_conv16(int nz, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, void *out16, long long ld_out, int B, int32_t *range_flag, int32_t *sample_flags, hipStream_t stream);
