@@ -3,6 +3,13 @@
 There is deliberately no fallback: if the HIP library is missing or cannot be
 loaded, importing the compute path raises.  `build()` compiles it in-tree with
 hipcc for gfx950 (no GPU needed to compile).
+
+This module is the one Python mirror of the header, in three tables that tests/test_abi.py holds to it:
+  constants    every integer `#define MMW_X` is the module attribute `X` -- the `MMW_` prefix dropped (`MMW_OK` alone keeps it);
+  ABI_STRUCTS  C struct name -> its one Python definition: a numpy dtype for the structs the library fills arrays of, a
+               ctypes.Structure for those Python builds one value of and passes by pointer;
+  sig          entry name -> (restype, argtypes); `EXPORTS` is its key list.
+A new entry family adds its rows to all three.
 """
 from __future__ import annotations
 
@@ -17,12 +24,18 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("MMW_LIB_NAME", "libmmw_hip.so")) 
 CSRC = os.path.join(_HERE, "csrc")
 RING_MAX = 4
 NKP = 57
+MAX_PTS_LIMIT, TRACK_CAP_LIMIT = 1024, 64   # the largest max_pts / track_cap of mmw_create
 
 MMW_OK = 0
 E_ARG, E_SINGULAR, E_DIVZERO, E_CAPACITY, E_HIP, E_NODEVICE, E_NONFINITE = -1, -2, -3, -4, -5, -6, -7
 DB_RAISED = -2     # MMW_DB_RAISED: db_n of a scene whose apply_DBscan call of the frame raised (E_NONFINITE)
 ERRBIT_SINGULAR, ERRBIT_DIVZERO, ERRBIT_CAPACITY, ERRBIT_BADCOUNT, ERRBIT_NONFINITE_NAN, ERRBIT_NONFINITE_INF = 1, 2, 4, 8, 16, 32
-K_TRACK, K_DBSCAN, K_FEATURES, K_NORMALIZE, K_TABLE, K_PREDICT, K_POST = range(7)
+K_TRACK, K_DBSCAN, K_FEATURES, K_NORMALIZE, K_TABLE, K_PREDICT, K_POST, K_COUNT = range(8)
+RANGE_FIXUP_CAP = 64               # out-of-range samples one call of the posture chain repairs in fp32
+RANGE_FIXUP_SCRATCH = 2226944      # bytes of device scratch mmw_mars_range_fixup* takes (the header's expression, evaluated)
+EXPORT_TICKETS = 4                 # kTickets (csrc/mmw_ctx.hpp): `*_async` calls of one export that may be outstanding; the
+                                   # one-call form of each export (mmw_report, mmw_clouds, ...) uses the last ticket itself
+REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
 
 EMPTY_FRAME = -1   # MMW_EMPTY_FRAME (include/mmw.h)
 BAD_FRAME = -3     # MMW_BAD_FRAME: n_out of mmw_normalize_tlv for a TLV body it refused to decode
@@ -30,30 +43,6 @@ UART_NONE, UART_POINTS, UART_PACKET = 0, 1, 2   # MMW_UART_*: what mmw_parse_uar
 UART_OVERFLOW, UART_RAISED, UART_SKIPPED, UART_BADCHUNK = 3, 4, 5, 6   # ... and the other outcomes of mmw_uart_read (status, low byte)
 UART_CHUNK_DROPPED = 256                        # MMW_UART_CHUNK_DROPPED: bit 8 of that status
 UART_BUFFER = 32768                             # MMW_UART_BUFFER: the reference's maxBufferSize
-
-EXPORTS = [
-    "mmw_config_default", "mmw_create", "mmw_destroy", "mmw_last_error", "mmw_reset", "mmw_pop_frame", "mmw_set_stream",
-    "mmw_synchronize", "mmw_get_dims", "mmw_dev_alloc", "mmw_dev_free", "mmw_memcpy_h2d", "mmw_memcpy_d2h",
-    "mmw_normalize", "mmw_step", "mmw_step_host", "mmw_dbscan", "mmw_features", "mmw_set_keypoints", "mmw_check",
-    "mmw_get_num_tracks", "mmw_get_tracks", "mmw_get_batch_ring", "mmw_get_track_ring_frame",
-    "mmw_get_batch_ring_frame", "mmw_track_table", "mmw_profile_enable", "mmw_profile_reset", "mmw_profile_get",
-    "mmw_kernel_name", "mmw_version", "mmw_stats_get", "mmw_stats_reset", "mmw_format_frames", "mmw_stats_get_ext", "mmw_mars_conv3d",
-    "mmw_parse_uart", "mmw_parse_uart_cap", "mmw_features_async", "mmw_features_wait", "mmw_set_keypoints_uid", "mmw_get_inner",
-    "mmw_set_batch_size", "mmw_set_batch_frame", "mmw_mars_conv_split", "mmw_mars_dense1_split", "mmw_diag_queue", "mmw_set_chain_side_stream", "mmw_side_workers", "mmw_step_kind", "mmw_streams_concurrent", "mmw_reset_scenes", "mmw_get_errors",
-    "mmw_kalman_layout", "mmw_step_f32", "mmw_normalize_f32", "mmw_frame_host", "mmw_mars_head_small", "mmw_mars_range_fixup",
-    "mmw_attach_posture", "mmw_frame_posture_host", "mmw_clear_errors", "mmw_stream_wait", "mmw_wait_stream", "mmw_find_tlv", "mmw_normalize_tlv",
-    "mmw_snapshot_size", "mmw_snapshot", "mmw_restore", "mmw_snapshot_inspect",
-    "mmw_set_sites", "mmw_get_sites", "mmw_clear_sites", "mmw_has_sites",
-    "mmw_posture_attach", "mmw_estimate_posture", "mmw_posture_range", "mmw_mars_dense2", "mmw_mars_split_weights",
-    "mmw_report_enable", "mmw_report_async", "mmw_report_wait", "mmw_report",
-    "mmw_clouds_async", "mmw_clouds_wait", "mmw_clouds",
-    "mmw_skeletons_async", "mmw_skeletons_wait", "mmw_skeletons", "mmw_skeleton_tables",
-    "mmw_uart_open", "mmw_uart_close", "mmw_uart_read", "mmw_uart_get_state", "mmw_uart_set_state", "mmw_uart_set_time",
-    "mmw_uart_log_enable", "mmw_uart_log_async", "mmw_uart_log_wait", "mmw_uart_log",
-    "mmw_samples_async", "mmw_samples_wait", "mmw_samples",
-    "mmw_mars_conv2d", "mmw_mars_range_fixup_frames", "mmw_posture_attach_frames", "mmw_attach_posture_frames",
-    "mmw_mars_dense1_plan",
-]
 
 
 class MmwPostureModel(C.Structure):
@@ -94,15 +83,9 @@ class MmwConfig(C.Structure):
 
 SITE_FIELDS = ("s_height", "tilt_cos", "tilt_sin", "intensity_mu", "intensity_std", "m_x", "m_y", "m_z",
                "v_screen_fade_size_max", "v_screen_fade_size_min", "v_screen_fade_weight")
-
-
-class MmwSceneSite(C.Structure):
-    """struct mmw_scene_site (include/mmw.h): the eleven values of mmw_config that describe a scene's installation --
-    sensor mounting, intensity scale, window / monitoring point -- and one reserved double that must be 0."""
-    _fields_ = [(f, C.c_double) for f in SITE_FIELDS] + [("reserved_", C.c_double)]
-
-
-SITE_DTYPE = np.dtype([(f, "f8") for f in SITE_FIELDS] + [("reserved_", "f8")])   # 12 x f8 = 96 bytes, the struct's layout
+# struct mmw_scene_site (include/mmw.h): the eleven values of mmw_config that describe a scene's installation -- sensor mounting,
+# intensity scale, window / monitoring point -- and one reserved double that must be 0
+SITE_DTYPE = np.dtype([(f, "f8") for f in SITE_FIELDS] + [("reserved_", "f8")], align=True)   # 12 x f8 = 96 bytes
 
 SNAP_MAGIC = b"MMWSNAP"   # MMW_SNAP_MAGIC (8 bytes with the terminating 0)
 SNAP_VERSION = 1
@@ -155,52 +138,23 @@ TRACK_REPORT_DTYPE = np.dtype(
 TRACK_EVENT_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("kind", "i4"), ("slot", "i4")], align=True)
 REPORT_STATIC, REPORT_BORN = 1, 2             # MMW_REPORT_*: bits of mmw_track_report.flags
 EV_BORN, EV_GONE, EV_REBASED = 1, 2, 3        # MMW_EV_*: mmw_track_event.kind
-REPORT_TICKETS = 4                            # reports that may be outstanding (mmw_report itself uses the last ticket)
-
-
-class MmwTrackReport(C.Structure):
-    """struct mmw_track_report (include/mmw.h): one live track of a report."""
-    _fields_ = [("scene", C.c_int32), ("slot", C.c_int32), ("uid", C.c_int32), ("flags", C.c_int32), ("point_num", C.c_int32),
-                ("lifetime", C.c_float), ("x", C.c_float * 9), ("centroid", C.c_float * 6), ("fade_x", C.c_float),
-                ("fade_z", C.c_float), ("fade_size", C.c_float), ("keypoints", C.c_float * NKP)]
-
-
-class MmwTrackEvent(C.Structure):
-    """struct mmw_track_event (include/mmw.h): a track that appeared or left, or a scene whose uids restarted."""
-    _fields_ = [("scene", C.c_int32), ("uid", C.c_int32), ("kind", C.c_int32), ("slot", C.c_int32)]
-
 
 # struct mmw_cloud_track / mmw_cloud_point (include/mmw.h): the directory entries (32 bytes) and points (16 bytes) of mmw_clouds_*
 CLOUD_TRACK_DTYPE = np.dtype([("scene", "i4"), ("slot", "i4"), ("uid", "i4"), ("first", "i4"), ("count", "i4"), ("frames", "i4"),
                               ("newest", "i4"), ("dropped", "i4")], align=True)
 CLOUD_POINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("track", "i4")], align=True)
 CLOUD_POINTS, CLOUD_ROWS, CLOUD_UNASSIGNED = 0, 1, 2   # MMW_CLOUD_*: the mode of mmw_clouds_* (UNASSIGNED is a flag bit)
-CLOUD_TICKETS = 4                             # mmw_clouds_async calls that may be outstanding (mmw_clouds itself uses the last ticket)
-
-
-class MmwCloudTrack(C.Structure):
-    """struct mmw_cloud_track (include/mmw.h): one directory entry -- a live track's cloud, or (slot -1) a scene's global ring."""
-    _fields_ = [("scene", C.c_int32), ("slot", C.c_int32), ("uid", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
-                ("frames", C.c_int32), ("newest", C.c_int32), ("dropped", C.c_int32)]
-
-
-class MmwCloudPoint(C.Structure):
-    """struct mmw_cloud_point (include/mmw.h): x, y, z in fp32 and the index of the point's directory entry."""
-    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("track", C.c_int32)]
-
 
 # struct mmw_uart_frame / mmw_uart_object (include/mmw.h): the directory entries (32 bytes) and detObj rows (48 bytes) of mmw_uart_log_*
 UART_FRAME_DTYPE = np.dtype([("scene", "i4"), ("frame_number", "u4"), ("first", "i4"), ("count", "i4"), ("t", "f8"), ("q_format", "i4"),
                              ("reserved_", "i4")], align=True)
 UART_OBJECT_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("z", "f8"), ("doppler", "f8"), ("peak_val", "f8"), ("range", "f8")], align=True)
-UART_LOG_TICKETS = 4                          # mmw_uart_log_async calls that may be outstanding (mmw_uart_log itself uses the last ticket)
 
 # struct mmw_sample_entry (include/mmw.h): the directory entries (48 bytes, no padding) of mmw_samples_*
 SAMPLE_ENTRY_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("frames", "i4"), ("reserved", "i4"), ("rows", "i4", (3,)), ("cut", "i4"),
                                ("centroid", "f8", (2,))], align=True)
 SAMPLE_BLOCK, SAMPLE_INPUT, SAMPLE_ABSOLUTE = 0, 1, 2   # MMW_SAMPLE_*: the mode of mmw_samples_* (ABSOLUTE is a flag bit)
 SAMPLE_BLOCK_SHAPE, SAMPLE_INPUT_SHAPE = (192, 5), (8, 8, 5)   # float64 / float32 per sample
-SAMPLE_TICKETS = 4                            # mmw_samples_async calls that may be outstanding (mmw_samples itself uses the last ticket)
 
 # struct mmw_skeleton (include/mmw.h): one live track's room-frame skeleton of mmw_skeletons_* (256 bytes, no padding)
 SKEL_JOINTS, SKEL_BONES = 19, 18
@@ -208,8 +162,141 @@ SKELETON_DTYPE = np.dtype([("scene", "i4"), ("slot", "i4"), ("uid", "i4"), ("row
                            ("joint", "f4", (SKEL_JOINTS, 3)), ("reserved_", "i4")], align=True)
 SKEL_SKIPPED = 1                              # MMW_SKEL_SKIPPED: bit 0 of mmw_skeleton.flags
 SKEL_ALL, SKEL_DRAWN = 0, 1                   # MMW_SKEL_*: the mode of mmw_skeletons_*
-SKEL_TICKETS = 4                              # mmw_skeletons_async calls that may be outstanding (mmw_skeletons itself uses the last ticket)
 SKEL_CLASS_NAMES = ("blue", "green", "red")   # mmw_skeleton_tables' joint classes as the reference's colour names
+
+
+# C struct name in include/mmw.h -> its Python mirror; every `typedef struct mmw_*` but the opaque mmw_ctx.  Field names are the
+# header's own throughout, so a mirror needs no second spelling beside it.
+ABI_STRUCTS = {
+    "mmw_config": MmwConfig, "mmw_track_record": TRACK_DTYPE, "mmw_track_summary": SUMMARY_DTYPE, "mmw_scene_site": SITE_DTYPE,
+    "mmw_posture_model": MmwPostureModel, "mmw_track_report": TRACK_REPORT_DTYPE, "mmw_track_event": TRACK_EVENT_DTYPE,
+    "mmw_cloud_track": CLOUD_TRACK_DTYPE, "mmw_cloud_point": CLOUD_POINT_DTYPE, "mmw_skeleton": SKELETON_DTYPE,
+    "mmw_snapshot_header": MmwSnapshotHeader, "mmw_snapshot_entry": MmwSnapshotEntry, "mmw_snapshot_info": MmwSnapshotInfo,
+    "mmw_uart_cfg": MmwUartCfg, "mmw_uart_frame": UART_FRAME_DTYPE, "mmw_uart_object": UART_OBJECT_DTYPE,
+    "mmw_sample_entry": SAMPLE_ENTRY_DTYPE,
+}
+
+
+def _signatures():
+    """Entry name -> (restype, argtypes) of every function include/mmw.h declares."""
+    vp, vpp = C.c_void_p, C.POINTER(C.c_void_p)
+    i32, i32p, i64p = C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    f64p = C.POINTER(C.c_double)
+    cfgp = C.POINTER(MmwConfig)
+    return {
+        "mmw_config_default": (C.c_int, [cfgp]),
+        "mmw_create": (C.c_int, [cfgp, i32, i32, i32, vpp]),
+        "mmw_destroy": (C.c_int, [vp]),
+        "mmw_last_error": (C.c_char_p, [vp]),
+        "mmw_reset": (C.c_int, [vp]),
+        "mmw_set_stream": (C.c_int, [vp, vp]),
+        "mmw_pop_frame": (C.c_int, [vp, vp]),
+        "mmw_synchronize": (C.c_int, [vp]),
+        "mmw_stream_wait": (C.c_int, [vp, vp]),
+        "mmw_wait_stream": (C.c_int, [vp, vp]),
+        "mmw_get_dims": (C.c_int, [vp, i32p, i32p, i32p, i32p, i32p]),
+        "mmw_dev_alloc": (C.c_int, [vp, C.c_size_t, vpp]),
+        "mmw_dev_free": (C.c_int, [vp, vp]),
+        "mmw_memcpy_h2d": (C.c_int, [vp, vp, vp, C.c_size_t]),
+        "mmw_memcpy_d2h": (C.c_int, [vp, vp, vp, C.c_size_t]),
+        "mmw_normalize": (C.c_int, [vp, vp, vp, vp, vp]),
+        "mmw_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "mmw_step_host": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "mmw_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "mmw_frame_host": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mmw_frame_posture_host": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mmw_attach_posture": (C.c_int, [vp, vp]),
+        "mmw_normalize_f32": (C.c_int, [vp, vp, vp, vp, vp]),
+        "mmw_dbscan": (C.c_int, [vp, vp, vp, i32, C.c_double, i32, vp, vp]),
+        "mmw_features": (C.c_int, [vp, vp, vp, i32, i32p]),
+        "mmw_set_keypoints": (C.c_int, [vp, vp, vp, i32]),
+        "mmw_features_async": (C.c_int, [vp, vp, vp, vp, i32, i32]),
+        "mmw_features_wait": (C.c_int, [vp, i32, i32p]),
+        "mmw_set_keypoints_uid": (C.c_int, [vp, vp, vp, vp, i32]),
+        "mmw_get_inner": (C.c_int, [vp, vp, vp, vp, i32]),
+        "mmw_set_batch_size": (C.c_int, [vp, vp, i32]),
+        "mmw_set_batch_frame": (C.c_int, [vp, i32, vp, i32]),
+        "mmw_check": (C.c_int, [vp]),
+        "mmw_get_num_tracks": (C.c_int, [vp, vp]),
+        "mmw_get_tracks": (C.c_int, [vp, vp, i32]),
+        "mmw_get_batch_ring": (C.c_int, [vp, vp, vp]),
+        "mmw_get_track_ring_frame": (C.c_int, [vp, i32, i32, i32, vp, i32p]),
+        "mmw_get_batch_ring_frame": (C.c_int, [vp, i32, i32, vp, i32p]),
+        "mmw_track_table": (C.c_int, [vp, vp, i32, i32]),
+        "mmw_profile_enable": (C.c_int, [vp, i32]),
+        "mmw_profile_reset": (C.c_int, [vp]),
+        "mmw_profile_get": (C.c_int, [vp, i32, f64p, i64p]),
+        "mmw_kernel_name": (C.c_char_p, [i32]),
+        "mmw_version": (C.c_char_p, []),
+        "mmw_stats_get": (C.c_int, [vp, vp]),
+        "mmw_stats_reset": (C.c_int, [vp]),
+        "mmw_diag_queue": (C.c_int, [vp, vp]),
+        "mmw_side_workers": (C.c_int, [vp]),
+        "mmw_step_kind": (C.c_int, [vp]),
+        "mmw_kalman_layout": (C.c_int, [vp]),
+        "mmw_streams_concurrent": (C.c_int, [vp, vp, vp]),
+        "mmw_reset_scenes": (C.c_int, [vp, vp]),
+        "mmw_get_errors": (C.c_int, [vp, vp]),
+        "mmw_clear_errors": (C.c_int, [vp, vp, i32]),
+        "mmw_set_chain_side_stream": (C.c_int, [vp, i32]),
+        "mmw_stats_get_ext": (C.c_int, [vp, vp]),
+        "mmw_mars_conv3d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32]),
+        "mmw_mars_conv_split": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, C.c_int64, i32, vp, vp]),
+        "mmw_mars_range_fixup": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]),
+        "mmw_mars_dense1_split": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, i32, i32, i32]),
+        "mmw_mars_dense1_plan": (C.c_int, [i32, i32, vp]),
+        "mmw_mars_head_small": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, i32, i32, i32]),
+        "mmw_parse_uart": (C.c_int, [vp, C.c_size_t, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "mmw_parse_uart_cap": (C.c_int, [vp, C.c_size_t, C.c_size_t, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "mmw_find_tlv": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
+        "mmw_normalize_tlv": (C.c_int, [vp, vp, C.c_size_t, vp, vp, vp, vp]),
+        "mmw_format_frames": (C.c_int, [vp, vp, vp, vp, vp, i32]),
+        "mmw_snapshot_size": (C.c_int, [vp, vp, i32, C.POINTER(C.c_size_t)]),
+        "mmw_snapshot": (C.c_int, [vp, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "mmw_restore": (C.c_int, [vp, vp, C.c_size_t, vp, i32]),
+        "mmw_snapshot_inspect": (C.c_int, [vp, C.c_size_t, C.POINTER(MmwSnapshotInfo)]),
+        "mmw_set_sites": (C.c_int, [vp, vp, i32, vp]),
+        "mmw_get_sites": (C.c_int, [vp, vp]),
+        "mmw_clear_sites": (C.c_int, [vp]),
+        "mmw_has_sites": (C.c_int, [vp]),
+        "mmw_posture_attach": (C.c_int, [vp, vp, i32]),
+        "mmw_estimate_posture": (C.c_int, [vp, i32p]),
+        "mmw_posture_range": (C.c_int, [vp, i32p]),
+        "mmw_mars_dense2": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, i32, i32]),
+        "mmw_mars_split_weights": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp]),
+        "mmw_report_enable": (C.c_int, [vp, i32]),
+        "mmw_report_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
+        "mmw_report_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_report": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
+        "mmw_clouds_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32]),
+        "mmw_clouds_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_clouds": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32p, i32p]),
+        "mmw_skeletons_async": (C.c_int, [vp, vp, i32, i32, i32, i32]),
+        "mmw_skeletons_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_skeletons": (C.c_int, [vp, vp, i32, i32, i32, i32p, i32p]),
+        "mmw_skeleton_tables": (C.c_int, [C.POINTER(i32p), C.POINTER(i32p)]),
+        "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
+        "mmw_uart_close": (C.c_int, [vp]),
+        "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),
+        "mmw_uart_get_state": (C.c_int, [vp, i32, vp, i32p, f64p]),
+        "mmw_uart_set_state": (C.c_int, [vp, i32, vp, i32, C.c_double]),
+        "mmw_uart_set_time": (C.c_int, [vp, vp, C.c_double]),
+        "mmw_uart_log_enable": (C.c_int, [vp, i32]),
+        "mmw_uart_log_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32]),
+        "mmw_uart_log_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_uart_log": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32p, i32p]),
+        "mmw_samples_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32]),
+        "mmw_samples_wait": (C.c_int, [vp, i32, i32p]),
+        "mmw_samples": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32p]),
+        "mmw_mars_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32]),
+        "mmw_mars_range_fixup_frames": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]),
+        "mmw_posture_attach_frames": (C.c_int, [vp, vp, i32, i32]),
+        "mmw_attach_posture_frames": (C.c_int, [vp, vp, i32]),
+    }
+
+
+sig = _signatures()
+EXPORTS = list(sig)
 
 
 def skeleton_tables():
@@ -326,121 +413,6 @@ def load():
         raise ImportError(
             f"{LIB_PATH} reports {ver!r} but the sources beside it hash to {source_hash()}: it was built from other "
             "sources.  Rebuild it: `python -c 'import __graft_entry__ as g; g.build()'`.")
-    vp, vpp = C.c_void_p, C.POINTER(C.c_void_p)
-    i32, i32p, i64p = C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-    f64p = C.POINTER(C.c_double)
-    cfgp = C.POINTER(MmwConfig)
-    sig = {
-        "mmw_config_default": (C.c_int, [cfgp]),
-        "mmw_create": (C.c_int, [cfgp, i32, i32, i32, vpp]),
-        "mmw_destroy": (C.c_int, [vp]),
-        "mmw_last_error": (C.c_char_p, [vp]),
-        "mmw_reset": (C.c_int, [vp]),
-        "mmw_set_stream": (C.c_int, [vp, vp]),
-        "mmw_pop_frame": (C.c_int, [vp, vp]),
-        "mmw_synchronize": (C.c_int, [vp]),
-        "mmw_stream_wait": (C.c_int, [vp, vp]),
-        "mmw_wait_stream": (C.c_int, [vp, vp]),
-        "mmw_get_dims": (C.c_int, [vp, i32p, i32p, i32p, i32p, i32p]),
-        "mmw_dev_alloc": (C.c_int, [vp, C.c_size_t, vpp]),
-        "mmw_dev_free": (C.c_int, [vp, vp]),
-        "mmw_memcpy_h2d": (C.c_int, [vp, vp, vp, C.c_size_t]),
-        "mmw_memcpy_d2h": (C.c_int, [vp, vp, vp, C.c_size_t]),
-        "mmw_normalize": (C.c_int, [vp, vp, vp, vp, vp]),
-        "mmw_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
-        "mmw_step_host": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
-        "mmw_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
-        "mmw_frame_host": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "mmw_frame_posture_host": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "mmw_attach_posture": (C.c_int, [vp, vp]),
-        "mmw_normalize_f32": (C.c_int, [vp, vp, vp, vp, vp]),
-        "mmw_dbscan": (C.c_int, [vp, vp, vp, i32, C.c_double, i32, vp, vp]),
-        "mmw_features": (C.c_int, [vp, vp, vp, i32, i32p]),
-        "mmw_set_keypoints": (C.c_int, [vp, vp, vp, i32]),
-        "mmw_features_async": (C.c_int, [vp, vp, vp, vp, i32, i32]),
-        "mmw_features_wait": (C.c_int, [vp, i32, i32p]),
-        "mmw_set_keypoints_uid": (C.c_int, [vp, vp, vp, vp, i32]),
-        "mmw_get_inner": (C.c_int, [vp, vp, vp, vp, i32]),
-        "mmw_set_batch_size": (C.c_int, [vp, vp, i32]),
-        "mmw_set_batch_frame": (C.c_int, [vp, i32, vp, i32]),
-        "mmw_check": (C.c_int, [vp]),
-        "mmw_get_num_tracks": (C.c_int, [vp, vp]),
-        "mmw_get_tracks": (C.c_int, [vp, vp, i32]),
-        "mmw_get_batch_ring": (C.c_int, [vp, vp, vp]),
-        "mmw_get_track_ring_frame": (C.c_int, [vp, i32, i32, i32, vp, i32p]),
-        "mmw_get_batch_ring_frame": (C.c_int, [vp, i32, i32, vp, i32p]),
-        "mmw_track_table": (C.c_int, [vp, vp, i32, i32]),
-        "mmw_profile_enable": (C.c_int, [vp, i32]),
-        "mmw_profile_reset": (C.c_int, [vp]),
-        "mmw_profile_get": (C.c_int, [vp, i32, f64p, i64p]),
-        "mmw_kernel_name": (C.c_char_p, [i32]),
-        "mmw_version": (C.c_char_p, []),
-        "mmw_stats_get": (C.c_int, [vp, vp]),
-        "mmw_stats_reset": (C.c_int, [vp]),
-        "mmw_diag_queue": (C.c_int, [vp, vp]),
-        "mmw_side_workers": (C.c_int, [vp]),
-        "mmw_step_kind": (C.c_int, [vp]),
-        "mmw_kalman_layout": (C.c_int, [vp]),
-        "mmw_streams_concurrent": (C.c_int, [vp, vp, vp]),
-        "mmw_reset_scenes": (C.c_int, [vp, vp]),
-        "mmw_get_errors": (C.c_int, [vp, vp]),
-        "mmw_clear_errors": (C.c_int, [vp, vp, i32]),
-        "mmw_set_chain_side_stream": (C.c_int, [vp, i32]),
-        "mmw_stats_get_ext": (C.c_int, [vp, vp]),
-        "mmw_mars_conv3d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32]),
-        "mmw_mars_conv_split": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, C.c_int64, i32, vp, vp]),
-        "mmw_mars_range_fixup": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]),
-        "mmw_mars_dense1_split": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, i32, i32, i32]),
-        "mmw_mars_dense1_plan": (C.c_int, [i32, i32, vp]),
-        "mmw_mars_head_small": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, i32, i32, i32]),
-        "mmw_parse_uart": (C.c_int, [vp, C.c_size_t, vp, vp, vp, i32, vp, vp, vp, vp]),
-        "mmw_parse_uart_cap": (C.c_int, [vp, C.c_size_t, C.c_size_t, vp, vp, vp, i32, vp, vp, vp, vp]),
-        "mmw_find_tlv": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
-        "mmw_normalize_tlv": (C.c_int, [vp, vp, C.c_size_t, vp, vp, vp, vp]),
-        "mmw_format_frames": (C.c_int, [vp, vp, vp, vp, vp, i32]),
-        "mmw_snapshot_size": (C.c_int, [vp, vp, i32, C.POINTER(C.c_size_t)]),
-        "mmw_snapshot": (C.c_int, [vp, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
-        "mmw_restore": (C.c_int, [vp, vp, C.c_size_t, vp, i32]),
-        "mmw_snapshot_inspect": (C.c_int, [vp, C.c_size_t, C.POINTER(MmwSnapshotInfo)]),
-        "mmw_set_sites": (C.c_int, [vp, vp, i32, vp]),
-        "mmw_get_sites": (C.c_int, [vp, vp]),
-        "mmw_clear_sites": (C.c_int, [vp]),
-        "mmw_has_sites": (C.c_int, [vp]),
-        "mmw_posture_attach": (C.c_int, [vp, vp, i32]),
-        "mmw_estimate_posture": (C.c_int, [vp, i32p]),
-        "mmw_posture_range": (C.c_int, [vp, i32p]),
-        "mmw_mars_dense2": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, i32, i32]),
-        "mmw_mars_split_weights": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, i32, i32, vp]),
-        "mmw_report_enable": (C.c_int, [vp, i32]),
-        "mmw_report_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
-        "mmw_report_wait": (C.c_int, [vp, i32, i32p, i32p]),
-        "mmw_report": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
-        "mmw_clouds_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32]),
-        "mmw_clouds_wait": (C.c_int, [vp, i32, i32p, i32p]),
-        "mmw_clouds": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32p, i32p]),
-        "mmw_skeletons_async": (C.c_int, [vp, vp, i32, i32, i32, i32]),
-        "mmw_skeletons_wait": (C.c_int, [vp, i32, i32p, i32p]),
-        "mmw_skeletons": (C.c_int, [vp, vp, i32, i32, i32, i32p, i32p]),
-        "mmw_skeleton_tables": (C.c_int, [C.POINTER(i32p), C.POINTER(i32p)]),
-        "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
-        "mmw_uart_close": (C.c_int, [vp]),
-        "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),
-        "mmw_uart_get_state": (C.c_int, [vp, i32, vp, i32p, f64p]),
-        "mmw_uart_set_state": (C.c_int, [vp, i32, vp, i32, C.c_double]),
-        "mmw_uart_set_time": (C.c_int, [vp, vp, C.c_double]),
-        "mmw_uart_log_enable": (C.c_int, [vp, i32]),
-        "mmw_uart_log_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32]),
-        "mmw_uart_log_wait": (C.c_int, [vp, i32, i32p, i32p]),
-        "mmw_uart_log": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32p, i32p]),
-        "mmw_samples_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32]),
-        "mmw_samples_wait": (C.c_int, [vp, i32, i32p]),
-        "mmw_samples": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32p]),
-        "mmw_mars_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32]),
-        "mmw_mars_range_fixup_frames": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]),
-        "mmw_posture_attach_frames": (C.c_int, [vp, vp, i32, i32]),
-        "mmw_attach_posture_frames": (C.c_int, [vp, vp, i32]),
-    }
-    assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the symbol is missing
         fn.restype, fn.argtypes = res, args

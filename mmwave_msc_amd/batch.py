@@ -77,6 +77,8 @@ class SceneBatch:
         self._frame_out = None      # frame_host(reuse_out=True): the result arrays of the last call
         self._posture_model = None
         self._posture_batch = None   # attach_posture_batch: the weights' device buffers
+        # entries / rows / points the `*_host` exports' device buffers hold; they grow to what the device says it needs
+        self._export_caps = {"report": (64, 64), "clouds": (64, 4096), "skeletons": (64,), "radar_log": (64, 4096)}
 
     # -- plumbing -------------------------------------------------------------
     def _chk(self, rc):
@@ -173,23 +175,26 @@ class SceneBatch:
     def synchronize(self):
         self._chk(self.L.mmw_synchronize(self.h))
 
-    def pop_frame(self, scenes=None):
-        """BatchedData.pop_frame() on the global ring of the given scenes (default: all)."""
+    def _scene_flags(self, scenes, upload_to: str = None):
+        """The scene mask the C-ABI takes: None for scenes=None (every scene), else int32[S] with 1 at `scenes` -- or, with
+        `upload_to`, the device pointer of the buffer of that name, holding it."""
         if scenes is None:
-            self._chk(self.L.mmw_pop_frame(self.h, None))
-            return
+            return None
         flags = np.zeros(self.S, dtype=np.int32)
         flags[np.asarray(scenes, dtype=np.int64)] = 1
-        self._chk(self.L.mmw_pop_frame(self.h, flags.ctypes.data))
+        return self.buf(upload_to, self.S * 4).upload(flags).ptr if upload_to else flags
+
+    @staticmethod
+    def _host_ptr(a):
+        return None if a is None else a.ctypes.data
+
+    def pop_frame(self, scenes=None):
+        """BatchedData.pop_frame() on the global ring of the given scenes (default: all)."""
+        self._chk(self.L.mmw_pop_frame(self.h, self._host_ptr(self._scene_flags(scenes))))
 
     def set_batch_size(self, new_size: int, scenes=None):
         """BatchedData.change_buffer_size(new_size) on the global ring of the given scenes (default: all)."""
-        if scenes is None:
-            self._chk(self.L.mmw_set_batch_size(self.h, None, int(new_size)))
-            return
-        flags = np.zeros(self.S, dtype=np.int32)
-        flags[np.asarray(scenes, dtype=np.int64)] = 1
-        self._chk(self.L.mmw_set_batch_size(self.h, flags.ctypes.data, int(new_size)))
+        self._chk(self.L.mmw_set_batch_size(self.h, self._host_ptr(self._scene_flags(scenes)), int(new_size)))
 
     def set_batch_frame(self, scene: int, rows: np.ndarray):
         """BatchedData(init_data): the scene's global ring becomes one frame holding `rows` (n, 8)."""
@@ -246,12 +251,7 @@ class SceneBatch:
     def clear_errors(self, bits: int, scenes=None):
         """mmw_clear_errors: clears the given sticky bits (of the given scenes; default all) and nothing else -- for a caller that
         catches the reference's ValueError (non-finite rows: the scene's state is what the reference's is) and carries on."""
-        if scenes is None:
-            self._chk(self.L.mmw_clear_errors(self.h, None, int(bits)))
-            return
-        flags = np.zeros(self.S, dtype=np.int32)
-        flags[np.asarray(scenes, dtype=np.int64)] = 1
-        self._chk(self.L.mmw_clear_errors(self.h, flags.ctypes.data, int(bits)))
+        self._chk(self.L.mmw_clear_errors(self.h, self._host_ptr(self._scene_flags(scenes)), int(bits)))
 
     def check(self):
         self._chk(self.L.mmw_check(self.h))
@@ -333,11 +333,7 @@ class SceneBatch:
         host = self._radar_staging(nbytes)
         host[: (S + 1) * 8].view(np.int64)[:] = off
         flags = host[(S + 1) * 8: (S + 1) * 8 + S * 4].view(np.int32)
-        if scenes is None:
-            flags[:] = 1
-        else:
-            flags[:] = 0
-            flags[np.asarray(scenes, dtype=np.int64)] = 1
+        flags[:] = 1 if scenes is None else self._scene_flags(scenes)
         for s, v in enumerate(views):
             host[head + off[s]: head + off[s + 1]] = v
         b_in = self.buf("radar_in", nbytes)
@@ -364,12 +360,7 @@ class SceneBatch:
 
     def set_radar_time(self, t: float, scenes=None):
         """mmw_uart_set_time: main.py's `t` restarts at `t` for the given scenes (default all), e.g. after `reset_scenes`."""
-        if scenes is None:
-            self._chk(self.L.mmw_uart_set_time(self.h, None, float(t)))
-            return
-        flags = np.zeros(self.S, dtype=np.int32)
-        flags[np.asarray(scenes, dtype=np.int64)] = 1
-        self._chk(self.L.mmw_uart_set_time(self.h, flags.ctypes.data, float(t)))
+        self._chk(self.L.mmw_uart_set_time(self.h, self._host_ptr(self._scene_flags(scenes)), float(t)))
 
     # -- radar log ----------------------------------------------------------------
     def enable_radar_log(self, on: bool = True):
@@ -397,27 +388,9 @@ class SceneBatch:
         """(dir[n_frames] UART_FRAME_DTYPE, rows[n_rows] UART_OBJECT_DTYPE): entry i owns rows[first : first + count].  `scenes`:
         the scenes asked (default all); the others keep their frame for a later call.  The device buffers are kept and grow to
         what the device says it needs (one retry; a refused export loses nothing)."""
-        fdt, odt = _lib.UART_FRAME_DTYPE, _lib.UART_OBJECT_DTYPE
-        flags_ptr = None
-        if scenes is not None:
-            flags = np.zeros(self.S, dtype=np.int32)
-            flags[np.asarray(scenes, dtype=np.int64)] = 1
-            flags_ptr = self.buf("radar_log_flags", self.S * 4).upload(flags).ptr
-        cap_f, cap_r = getattr(self, "_radar_log_caps", (64, 4096))
-        for attempt in (0, 1):
-            b_d, b_r = self.buf("radar_log_dir", cap_f * fdt.itemsize), self.buf("radar_log_rows", cap_r * odt.itemsize)
-            self.radar_log_dev(b_d.ptr, cap_f, b_r.ptr, cap_r, frame_select, flags_ptr, _lib.UART_LOG_TICKETS - 1, scene_base)
-            try:
-                n_f, n_r = self.radar_log_wait(_lib.UART_LOG_TICKETS - 1)
-                break
-            except MmwError as e:
-                if e.code != _lib.E_CAPACITY or attempt:
-                    raise
-                cap_f, cap_r = max(cap_f, e.needed[0]), max(cap_r, e.needed[1])
-                self._radar_log_caps = (cap_f, cap_r)
-        d = b_d.download((n_f,), fdt) if n_f else np.zeros(0, fdt)
-        rows = b_r.download((n_r,), odt) if n_r else np.zeros(0, odt)
-        return d, rows
+        flags_ptr = self._scene_flags(scenes, "radar_log_flags")
+        return self._export_host("radar_log", lambda *a: self.radar_log_dev(*a[:4], frame_select, flags_ptr, a[4], scene_base),
+                                 self.L.mmw_uart_log_wait, ("radar_log_dir", _lib.UART_FRAME_DTYPE), ("radar_log_rows", _lib.UART_OBJECT_DTYPE))
 
     def step_host(self, pts: np.ndarray, n: np.ndarray, dt: np.ndarray, raise_nonfinite: bool = True, check: bool = True):
         """Host convenience (H2D + step + D2H).  Returns (assoc[S,NP], labels[S,UM], db_n[S]).  raise_nonfinite=False: a scene
@@ -693,16 +666,41 @@ class SceneBatch:
         self.track_table_dev(b.ptr, slots, scene_base)
         return b.download((self.S, slots), SUMMARY_DTYPE)
 
-    def _export_wait(self, wait, ticket: int):
-        """The two counts of an export's `*_wait` entry; E_CAPACITY becomes an MmwError that carries them in `.needed`."""
-        a, b = C.c_int32(0), C.c_int32(0)
-        rc = wait(self.h, int(ticket), C.byref(a), C.byref(b))
+    def _export_wait(self, wait, ticket: int, counts: int = 2):
+        """The counts of an export's `*_wait` entry -- a pair, or with counts=1 one int; E_CAPACITY becomes an MmwError that
+        carries them in `.needed`."""
+        n = [C.c_int32(0) for _ in range(counts)]
+        rc = wait(self.h, int(ticket), *[C.byref(v) for v in n])
+        got = tuple(int(v.value) for v in n) if counts > 1 else int(n[0].value)
         if rc == _lib.E_CAPACITY:
             err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
-            err.needed = (int(a.value), int(b.value))
+            err.needed = got
             raise err
         self._chk(rc)
-        return int(a.value), int(b.value)
+        return got
+
+    def _export_host(self, name: str, issue, wait, *outs):
+        """What the `*_host` exports share: issue under the last ticket, wait for the counts, on E_CAPACITY grow to what the
+        device says it needs and ask once more, download.  `outs`: a (buffer name, dtype) per output array, sized by
+        `_export_caps[name]`; `issue(ptr, cap, [ptr, cap,] ticket)` queues the export; `wait` is its `*_wait` entry.  One retry is
+        enough: a refused export writes and consumes nothing, and nothing else runs on the context's stream in between, so the
+        counts it reported are the counts the second call finds.  Returns one array per output."""
+        ticket = _lib.EXPORT_TICKETS - 1
+        for attempt in (0, 1):
+            caps = self._export_caps[name]
+            bufs = [self.buf(bn, cap * np.dtype(dt).itemsize) for (bn, dt), cap in zip(outs, caps)]
+            issue(*[v for b, cap in zip(bufs, caps) for v in (b.ptr, cap)], ticket)
+            try:
+                counts = self._export_wait(wait, ticket)
+                break
+            except MmwError as e:
+                if e.code != _lib.E_CAPACITY or attempt:
+                    raise
+                if max(e.needed) >= 2 ** 31 - 1:   # (saturated: more than an int32 counts -- no buffer can be offered)
+                    raise MmwError(_lib.E_CAPACITY, f"{name}_host: what this context holds exceeds INT32_MAX entries, rows or points; "
+                                                    "ask for fewer scenes per context") from e
+                self._export_caps[name] = tuple(max(cap, need) for cap, need in zip(caps, e.needed))
+        return tuple(b.download((n,), dt) if n else np.zeros(0, dt) for b, (_, dt), n in zip(bufs, outs, counts))
 
     # -- live-track report ----------------------------------------------------
     def enable_report(self, on: bool = True):
@@ -726,22 +724,8 @@ class SceneBatch:
         """The report as two structured arrays: (rows[n_rows] TRACK_REPORT_DTYPE, events[n_events] TRACK_EVENT_DTYPE).  A
         difference of states, not a log: a track born and gone between two reports appears in neither.  The buffers grow to
         what the device says it needs (a refused report loses nothing)."""
-        rdt, edt = _lib.TRACK_REPORT_DTYPE, _lib.TRACK_EVENT_DTYPE
-        cap_r, cap_e = getattr(self, "_report_caps", (64, 64))
-        while True:
-            b_r, b_e = self.buf("report_rows", cap_r * rdt.itemsize), self.buf("report_events", cap_e * edt.itemsize)
-            self.report_async(b_r.ptr, cap_r, b_e.ptr, cap_e, scene_base, _lib.REPORT_TICKETS - 1)
-            try:
-                n_r, n_e = self.report_wait(_lib.REPORT_TICKETS - 1)
-                break
-            except MmwError as e:
-                if e.code != _lib.E_CAPACITY:
-                    raise
-                cap_r, cap_e = max(cap_r, e.needed[0]), max(cap_e, e.needed[1])
-                self._report_caps = (cap_r, cap_e)
-        rows = b_r.download((n_r,), rdt) if n_r else np.zeros(0, rdt)
-        events = b_e.download((n_e,), edt) if n_e else np.zeros(0, edt)
-        return rows, events
+        return self._export_host("report", lambda *a: self.report_async(*a[:4], scene_base, a[4]), self.L.mmw_report_wait,
+                                 ("report_rows", _lib.TRACK_REPORT_DTYPE), ("report_events", _lib.TRACK_EVENT_DTYPE))
 
     # -- live-track point clouds ----------------------------------------------
     def clouds_dev(self, dir_ptr, cap_tracks: int, out_ptr, cap_points: int, mode: int = 0, ticket: int = 0, scene_base: int = 0):
@@ -763,28 +747,9 @@ class SceneBatch:
         without `unassigned` entry i is the track of `report_host` row i.  The device buffers are kept and grow to what the
         device says it needs (one retry)."""
         mode = (_lib.CLOUD_ROWS if rows else _lib.CLOUD_POINTS) | (_lib.CLOUD_UNASSIGNED if unassigned else 0)
-        ddt, item = _lib.CLOUD_TRACK_DTYPE, 64 if rows else _lib.CLOUD_POINT_DTYPE.itemsize
-        cap_t, cap_p = getattr(self, "_cloud_caps", (64, 4096))
-        for attempt in (0, 1):
-            b_d, b_o = self.buf("cloud_dir", cap_t * ddt.itemsize), self.buf("cloud_out", cap_p * item)
-            self.clouds_dev(b_d.ptr, cap_t, b_o.ptr, cap_p, mode, _lib.CLOUD_TICKETS - 1, scene_base)
-            try:
-                n_t, n_p = self.clouds_wait(_lib.CLOUD_TICKETS - 1)
-                break
-            except MmwError as e:
-                if e.code != _lib.E_CAPACITY or attempt:
-                    raise
-                if max(e.needed) >= 2 ** 31 - 1:   # (saturated: more entries or points than an int32 counts -- no buffer can be offered)
-                    raise MmwError(_lib.E_CAPACITY, "clouds_host: the clouds of this context exceed INT32_MAX entries or points; "
-                                                    "ask for fewer scenes per context") from e
-                cap_t, cap_p = max(cap_t, e.needed[0]), max(cap_p, e.needed[1])
-                self._cloud_caps = (cap_t, cap_p)
-        d = b_d.download((n_t,), ddt) if n_t else np.zeros(0, ddt)
-        if rows:
-            out = b_o.download((n_p, 8), np.float64) if n_p else np.zeros((0, 8))
-        else:
-            out = b_o.download((n_p,), _lib.CLOUD_POINT_DTYPE) if n_p else np.zeros(0, _lib.CLOUD_POINT_DTYPE)
-        return d, out
+        odt = np.dtype((np.float64, (8,))) if rows else _lib.CLOUD_POINT_DTYPE
+        return self._export_host("clouds", lambda *a: self.clouds_dev(*a[:4], mode, a[4], scene_base), self.L.mmw_clouds_wait,
+                                 ("cloud_dir", _lib.CLOUD_TRACK_DTYPE), ("cloud_out", odt))
 
     # -- training samples -----------------------------------------------------
     def samples_dev(self, dir_ptr, cap_samples: int, out_ptr, mode: int = 0, flags_ptr=None, ticket: int = 0, scene_base: int = 0):
@@ -799,14 +764,7 @@ class SceneBatch:
     def samples_wait(self, ticket: int = 0) -> int:
         """Samples of the `samples_dev` call with this ticket: waits for its count only, not for the stream.  Buffers too small:
         MmwError with code E_CAPACITY and the count needed in `.needed` -- nothing was written."""
-        n = C.c_int32(0)
-        rc = self.L.mmw_samples_wait(self.h, int(ticket), C.byref(n))
-        if rc == _lib.E_CAPACITY:
-            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
-            err.needed = int(n.value)
-            raise err
-        self._chk(rc)
-        return int(n.value)
+        return self._export_wait(self.L.mmw_samples_wait, ticket, counts=1)
 
     def samples_host(self, inputs: bool = False, absolute: bool = False, scenes=None, scene_base: int = 0):
         """(dir[n] SAMPLE_ENTRY_DTYPE, blocks): blocks float64[n, 192, 5], or with inputs=True float32[n, 8, 8, 5].  `scenes`:
@@ -816,14 +774,10 @@ class SceneBatch:
         edt = _lib.SAMPLE_ENTRY_DTYPE
         shape, dt = (_lib.SAMPLE_INPUT_SHAPE, np.float32) if inputs else (_lib.SAMPLE_BLOCK_SHAPE, np.float64)
         item = int(np.prod(shape)) * np.dtype(dt).itemsize
-        flags_ptr = None
-        if scenes is not None:
-            flags = np.zeros(self.S, dtype=np.int32)
-            flags[np.asarray(scenes, dtype=np.int64)] = 1
-            flags_ptr = self.buf("sample_flags", self.S * 4).upload(flags).ptr
+        flags_ptr = self._scene_flags(scenes, "sample_flags")
         b_d, b_o = self.buf("sample_dir", self.S * edt.itemsize), self.buf("sample_out", self.S * item)
-        self.samples_dev(b_d.ptr, self.S, b_o.ptr, mode, flags_ptr, _lib.SAMPLE_TICKETS - 1, scene_base)
-        n = self.samples_wait(_lib.SAMPLE_TICKETS - 1)
+        self.samples_dev(b_d.ptr, self.S, b_o.ptr, mode, flags_ptr, _lib.EXPORT_TICKETS - 1, scene_base)
+        n = self.samples_wait(_lib.EXPORT_TICKETS - 1)
         d = b_d.download((n,), edt) if n else np.zeros(0, edt)
         out = b_o.download((n,) + shape, dt) if n else np.zeros((0,) + shape, dt)
         return d, out
@@ -848,20 +802,9 @@ class SceneBatch:
         """The skeletons as a `_lib.SKELETON_DTYPE` array: one per live track (entry i is `report_host` row i), or with
         drawn=True only those the reference's check lets through.  The device buffer is kept and grows to what the device says
         it needs (one retry)."""
-        sdt = _lib.SKELETON_DTYPE
         mode = _lib.SKEL_DRAWN if drawn else _lib.SKEL_ALL
-        cap = getattr(self, "_skel_cap", 64)
-        for attempt in (0, 1):
-            b = self.buf("skeletons", cap * sdt.itemsize)
-            self.skeletons_dev(b.ptr, cap, mode, _lib.SKEL_TICKETS - 1, scene_base)
-            try:
-                n_out, _ = self.skeletons_wait(_lib.SKEL_TICKETS - 1)
-                break
-            except MmwError as e:
-                if e.code != _lib.E_CAPACITY or attempt:
-                    raise
-                cap = self._skel_cap = max(cap, e.needed[0])
-        return b.download((n_out,), sdt) if n_out else np.zeros(0, sdt)
+        return self._export_host("skeletons", lambda ptr, cap, ticket: self.skeletons_dev(ptr, cap, mode, ticket, scene_base),
+                                 self.L.mmw_skeletons_wait, ("skeletons", _lib.SKELETON_DTYPE))[0]
 
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):

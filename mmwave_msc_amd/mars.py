@@ -46,6 +46,7 @@ def deinterleave_split(a2: torch.Tensor):
     return v[:, :, 0, :].reshape(r, -1), v[:, :, 1, :].reshape(r, -1)
 
 
+from ._lib import RANGE_FIXUP_CAP, RANGE_FIXUP_SCRATCH  # noqa: E402  (constants only: the library itself is loaded on first use)
 from .marsweights import random_keras_weights  # noqa: E402,F401  (torch-free module: CPU-side tools import it without torch)
 
 
@@ -193,7 +194,7 @@ class MarsCNN(nn.Module):
             sflags = sflags.data_ptr()
         elif self.has_range_fixup():
             if self._sflags is None or self._sflags.device != x.device:
-                self._sflags = torch.zeros((2 + 64,), dtype=torch.int32, device=x.device)
+                self._sflags = torch.zeros((2 + RANGE_FIXUP_CAP,), dtype=torch.int32, device=x.device)
             sflags = self._sflags.data_ptr()
         rc = L.mmw_mars_conv_split(torch.cuda.current_stream(x.device).cuda_stream, self.frames, x.data_ptr(), self.k_w1.data_ptr(),
                                    self.k_b1.data_ptr(), self.k_w2.data_ptr(), self.k_b2.data_ptr(), out.data_ptr(), ld, x.shape[0],
@@ -229,7 +230,7 @@ class MarsCNN(nn.Module):
     def new_fixup_list(self, device) -> torch.Tensor:
         """A fix-up list of its own for a caller that keeps several frames in flight (forward(..., fixup=False, sflags=...) then
         range_fixup(..., sflags=...) for the same frame, on any stream ordered behind that forward)."""
-        return torch.zeros((2 + 64,), dtype=torch.int32, device=device)
+        return torch.zeros((2 + RANGE_FIXUP_CAP,), dtype=torch.int32, device=device)
 
     def range_fixup(self, x: torch.Tensor, kp: torch.Tensor, sflags: torch.Tensor):
         """The repair forward(..., fixup=False, sflags=sflags) left out, on torch's current stream: rows of kp[n][57] whose samples
@@ -243,7 +244,7 @@ class MarsCNN(nn.Module):
         from . import _lib
         L = _lib.load()
         if self._fix_scratch is None or self._fix_scratch.device != x.device:
-            self._fix_scratch = torch.empty((512 + 64 * (960 + 6144 + 1536 + 57) * 4,), dtype=torch.uint8, device=x.device)   # MMW_RANGE_FIXUP_SCRATCH
+            self._fix_scratch = torch.empty((RANGE_FIXUP_SCRATCH,), dtype=torch.uint8, device=x.device)
         w1 = self.dense1_dhwc.weight
         rc = L.mmw_mars_range_fixup(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), (sflags if sflags is not None else self._sflags).data_ptr(), x.shape[0],
                                     self.k_w1.data_ptr(), self.k_b1.data_ptr(), self.k_w2.data_ptr(), self.k_b2.data_ptr(), w1.data_ptr(), w1.stride(0),

@@ -26,7 +26,7 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import NKP
+from ._lib import NKP, RANGE_FIXUP_CAP
 
 
 class PostureRangeError(RuntimeError):
@@ -164,12 +164,12 @@ class PosturePipeline:
         self.A.synchronize()
         self.B.synchronize()
         # The asynchronous path cannot recompute a frame that is long scattered.  Keypoints that are MEANINGLESS -- samples outside
-        # fp16's range that were not repaired: more than MMW_RANGE_FIXUP_CAP (64) of them in one batch of the 3-frame model, any
+        # fp16's range that were not repaired: more than RANGE_FIXUP_CAP of them in one batch of the 3-frame model, any
         # at all in the single-frame model (no fp32 kernel) -- are an error, not a warning: Keras' fp32 would have been finite.
         if getattr(self.model, "arith", None) == "f16x3" and hasattr(self.model, "range_overflow") and self.model.range_overflow():
             self.range_overflowed = True
             raise PostureRangeError("MarsCNN (split-fp16 arithmetic): inputs or activations left fp16's range during this run and were NOT repaired "
-                                    "(the 3-frame model repairs up to 64 samples per batch on the device, the single-frame model none): the keypoints "
+                                    f"(the 3-frame model repairs up to {RANGE_FIXUP_CAP} samples per batch on the device, the single-frame model none): the keypoints "
                                     "of the samples concerned are meaningless -- use MarsCNN(arith='f32' / 'torch') for such data")
 
     def close(self):

@@ -18,9 +18,10 @@ from collections import deque
 import numpy as np
 
 from . import constants as const
+from ._lib import MAX_PTS_LIMIT
 from .batch import SceneBatch
 
-_UTIL_MAX_PTS = 1024  # MMW_MAX_PTS_LIMIT; with ring 2: DBSCAN clouds up to 2048 points, ring 4 (dbscan_labels on larger ones): 4096
+_UTIL_MAX_PTS = MAX_PTS_LIMIT  # with ring 2: DBSCAN clouds up to 2048 points, ring 4 (dbscan_labels on larger ones): 4096
 _ctx_cache = {}
 
 

@@ -1,28 +1,10 @@
-"""The C-ABI library loads on a machine without a GPU and exports every symbol
-include/mmw.h declares (no compute call is made here)."""
+"""The C-ABI library loads on a machine without a GPU (no compute call is made here; that it exports every symbol
+include/mmw.h declares, with the header's prototypes and layouts, is tests/test_abi.py), and the step kernels compile as their
+launch geometry needs them."""
 import ctypes as C
-import os
-import re
 
 from mmwave_msc_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared_symbols():
-    txt = open(os.path.join(ROOT, "include", "mmw.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mmw_[a-z0-9_]+)\s*\(", txt)))
-
-
-def test_library_is_built_and_exports_every_declared_symbol():
-    assert os.path.isfile(_lib.LIB_PATH), "libmmw_hip.so missing: run __graft_entry__.build()"
-    L = C.CDLL(_lib.LIB_PATH)
-    declared = _declared_symbols()
-    assert len(declared) >= 30
-    for name in declared:
-        assert hasattr(L, name), f"{name} declared in include/mmw.h but not exported"
-    assert sorted(declared) == sorted(_lib.EXPORTS), "python binding and header disagree"
+from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
 
 
 def test_config_struct_matches_header_layout():
@@ -62,48 +44,6 @@ def test_track_record_dtype_matches_c_struct():
     assert _lib.SUMMARY_DTYPE.itemsize == 5 * 4 + 4 + (9 + 6 + 57) * 4 + 3 * 4
 
 
-_ISA_CACHE = {}
-
-
-def _device_isa(names):
-    """(resource report, ISA text) of csrc/<name>.hip for gfx950 with the product's flags: ONE device-only compile per file gives
-    both (the remarks on stderr, the assembly on stdout); files compile side by side and are cached for the session."""
-    import os
-    import shutil
-    import subprocess
-    from concurrent.futures import ThreadPoolExecutor
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        import pytest
-        pytest.skip("hipcc not available")
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mmwave_msc_amd", "csrc")
-
-    def one(name):
-        out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "--cuda-device-only",
-                              "-Rpass-analysis=kernel-resource-usage", "-S", "-c", os.path.join(root, name + ".hip"), "-o", "-"],
-                             capture_output=True, text=True, timeout=900)
-        assert out.returncode == 0, out.stderr[-2000:]
-        return out.stderr, out.stdout
-
-    todo = [n for n in names if n not in _ISA_CACHE]
-    with ThreadPoolExecutor(max_workers=4) as ex:
-        for n, r in zip(todo, ex.map(one, todo)):
-            _ISA_CACHE[n] = r
-    return {n: _ISA_CACHE[n] for n in names}
-
-
-def _kernel_report(rep):
-    """[(mangled name, scratch bytes per lane, spilled VGPRs, VGPRs, waves per SIMD, spilled SGPRs)] from -Rpass-analysis=kernel-resource-usage."""
-    import re
-    out = []
-    for blk in re.split(r"remark: Function Name: ", rep)[1:]:
-        name = blk.split()[0]
-        f = lambda pat: int(re.search(pat, blk).group(1))
-        out.append((name, f(r"ScratchSize \[bytes/lane\]: (\d+)"), f(r"VGPRs Spill: (\d+)"), f(r" VGPRs: (\d+)"), f(r"Occupancy \[waves/SIMD\]: (\d+)"),
-                    f(r"SGPRs Spill: (\d+)")))
-    return out
-
-
 # The one kernel that is ALLOWED to spill, with the ceiling it must stay under: k_dbscan_startup (frame 0 after a reset: every scene
 # clusters its whole first frame) takes two 512-thread workgroups per CU, i.e. 128 registers per lane, for a BallTree chain that wants
 # ~180 -- measured 3.0 ms per 4096 clouds that way against 4.0 ms unspilled at one workgroup per CU (k_dbscan.hip: launch_dbscan_big).
@@ -139,8 +79,7 @@ def test_step_kernels_compile_without_scratch():
                 continue
             assert vspill == 0, (name, vspill, vgprs, occ)
             if scratch:
-                body = asm[asm.index("\n" + name + ":"):]
-                body = body[: body.index("s_endpgm")]
+                body = kernel_body(asm, name)
                 assert not re.search(r"\bscratch_|buffer_(load|store)\S* .*offen", body), (name, scratch)
     for k in ("k_track", "k_scene", "k_predict", "k_post", "k_chain", "k_dbscan_big", "k_dbscan_huge", "k_inner", "k_dbscan_startup"):
         assert k in seen, (k, sorted(seen))
@@ -164,8 +103,7 @@ def test_gate_records_are_not_read_before_the_scalar_cache_invalidate():
         names = re.findall(pat, asm, flags=re.M)
         assert len(names) >= 6, (src, names)
         for n in names:
-            body = asm[asm.index("\n" + n + ":"):]
-            body = body[: body.index("s_endpgm")]
+            body = kernel_body(asm, n)
             inv, mark = body.find("s_dcache_inv"), body.find("; mmw: gate pointer opaque from here")
             assert 0 < inv < mark, (n, inv, mark)
             kern = re.search(r"s_load_dword\S* \S+ (s\[\d+:\d+\]), 0x", body).group(1)   # first scalar load: the kernel arguments
@@ -190,9 +128,9 @@ def test_dense1_tile_kernel_keeps_its_pipeline():
     assert len(rows) == 3, list(rows)
     for name, (_, scratch, vspill, vgprs, occ, sspill) in rows.items():
         n_mfma, n_dma, vm = next(v for k, v in shapes.items() if k in name)
-        assert scratch == 0 and vspill == 0 and sspill == 0 and vgprs <= 256 and occ >= 2, rows[name]
-        body = asm[asm.index("\n" + name + ":"):]
-        body = body[: body.index("s_endpgm")]
+        assert_clean([rows[name]])
+        assert vgprs <= 256 and occ >= 2, rows[name]
+        body = kernel_body(asm, name)
         assert "scratch_" not in body
         # the steady-state loop: the basic block with the back edge that holds a K-step's MFMAs and one barrier
         blocks = re.split(r"\n\.LBB\d+_\d+:", body)

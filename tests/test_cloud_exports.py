@@ -1,76 +1,35 @@
-"""The live tracks' point clouds (mmw_clouds_*, include/mmw.h) as far as a machine without a GPU can check them: the header declares
-the entries and the library exports them, the ctypes and numpy layouts of the directory entries and points are the C structs', and
-the kernels of csrc/k_cloud.hip compile without scratch or spilled registers and move rows and points as 16-byte pieces."""
-import ctypes as C
+"""The live tracks' point clouds (mmw_clouds_*, include/mmw.h) as far as a machine without a GPU can check them: the entries refuse
+a missing context, the directory entries and points have the sizes and field types the kernels pin (tests/test_abi.py holds every
+layout and prototype to the header), and the kernels of csrc/k_cloud.hip compile without scratch or spilled registers and move rows and points as 16-byte pieces."""
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
-import pytest
 
 from mmwave_msc_amd import _lib
+from tests import _abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("mmw_clouds_async", "mmw_clouds_wait", "mmw_clouds")
 FIELDS_T = ["scene", "slot", "uid", "first", "count", "frames", "newest", "dropped"]
 FIELDS_P = ["x", "y", "z", "track"]
 
 
 def test_header_declares_and_library_exports_the_cloud_entries():
-    txt = open(os.path.join(ROOT, "include", "mmw.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, code), name
-        assert name in _lib.EXPORTS, name
-    for macro, val in (("MMW_CLOUD_POINTS", 0), ("MMW_CLOUD_ROWS", 1), ("MMW_CLOUD_UNASSIGNED", 2)):
-        assert re.search(r"#define\s+%s\s+%d\b" % (macro, val), code), macro
-    assert (_lib.CLOUD_POINTS, _lib.CLOUD_ROWS, _lib.CLOUD_UNASSIGNED) == (0, 1, 2)
-    assert "typedef struct mmw_cloud_track" in code and "typedef struct mmw_cloud_point" in code
-    L = C.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert hasattr(L, name), f"{name} not exported by {_lib.LIB_PATH}"
     L = _lib.load()   # (declares every prototype: AttributeError if one is missing)
-    for name in NEW:
-        assert getattr(L, name).argtypes is not None, name
     # without a context every entry refuses its arguments instead of touching a device
     assert L.mmw_clouds_async(None, None, 0, None, 0, 0, 0, 0) == _lib.E_ARG
     assert L.mmw_clouds_wait(None, 0, None, None) == _lib.E_ARG
     assert L.mmw_clouds(None, None, 0, None, 0, 0, 0, None, None) == _lib.E_ARG
 
 
-def _c_layout():
-    """sizeof / offsetof of the two structs as a C compiler lays out include/mmw.h."""
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang")
-    if cc is None:
-        pytest.skip("no C compiler")
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "mmw.h"\nint main(void){printf("%zu %zu", sizeof(mmw_cloud_track), sizeof(mmw_cloud_point));\n'
-    src += "".join('printf(" %%zu", offsetof(mmw_cloud_track, %s));\n' % f for f in FIELDS_T)
-    src += "".join('printf(" %%zu", offsetof(mmw_cloud_point, %s));\n' % f for f in FIELDS_P)
-    src += "return 0;}\n"
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "layout.c"), "w") as fh:
-            fh.write(src)
-        exe = os.path.join(d, "layout")
-        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), os.path.join(d, "layout.c"), "-o", exe], check=True, capture_output=True)
-        v = [int(t) for t in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    return v[0], v[1], dict(zip(FIELDS_T, v[2: 2 + len(FIELDS_T)])), dict(zip(FIELDS_P, v[2 + len(FIELDS_T):]))
-
-
 def test_cloud_layouts_match_the_c_structs():
-    size_t, size_p, off_t, off_p = _c_layout()
-    assert (size_t, size_p) == (32, 16)
+    lay = _abi.c_layout()
     tdt, pdt = _lib.CLOUD_TRACK_DTYPE, _lib.CLOUD_POINT_DTYPE
-    assert tdt.itemsize == C.sizeof(_lib.MmwCloudTrack) == size_t
-    assert pdt.itemsize == C.sizeof(_lib.MmwCloudPoint) == size_p
+    assert (lay["mmw_cloud_track"]["size"], lay["mmw_cloud_point"]["size"]) == (32, 16) == (tdt.itemsize, pdt.itemsize)
     assert list(tdt.names) == FIELDS_T and list(pdt.names) == FIELDS_P
-    for f, o in off_t.items():
-        assert tdt.fields[f][1] == o == getattr(_lib.MmwCloudTrack, f).offset, f
+    for f in FIELDS_T:
         assert tdt.fields[f][0] == np.dtype("i4"), f
-    for f, o in off_p.items():
-        assert pdt.fields[f][1] == o == getattr(_lib.MmwCloudPoint, f).offset, f
+    for f in FIELDS_P:
         assert pdt.fields[f][0] == np.dtype("i4" if f == "track" else "f4"), f
     # both sizes are pinned where the kernels and the C-ABI are compiled
     for name in ("k_cloud.hip", "api_cloud.hip"):
@@ -96,17 +55,16 @@ def test_cloud_launcher_is_declared_once_and_the_files_are_built():
 
 
 def test_cloud_kernels_use_no_scratch_and_move_16_byte_pieces():
-    from tests.test_cabi_exports import _device_isa, _kernel_report
+    from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
     rep, asm = _device_isa(("k_cloud",))["k_cloud"]
     rows = _kernel_report(rep)
     names = [k[0] for k in rows]
     assert sum("k_cloud_count" in n for n in names) == 1, names
     assert sum("k_cloud_write" in n for n in names) == 2, names   # MMW_CLOUD_POINTS and MMW_CLOUD_ROWS
     assert len(names) == 3, names                                 # (the scan is k_pair_scan of k_scan.hip)
+    assert_clean(rows)
     for name, scratch, vspill, vgprs, occ, sspill in rows:
-        assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
-        body = asm[asm.index("\n" + name + ":"):]
-        body = body[: body.index(".Lfunc_end")]   # (the whole kernel: one that returns early has more than one s_endpgm)
+        body = kernel_body(asm, name, ".Lfunc_end")   # (the whole kernel: one that returns early has more than one s_endpgm)
         assert "s_endpgm" in body, name
         assert "scratch_" not in body, name
         if "k_cloud_write" in name:

@@ -172,3 +172,48 @@ def test_one_scene_through_all_three_exports(tracks):
         for b in bufs:
             b.free()
     sb.close()
+
+
+# ---- the host wrappers' growth path ------------------------------------------------------------------------------------
+def test_every_host_export_grows_once_and_returns_what_an_unrefused_twin_returns():
+    """report_host, clouds_host, skeletons_host and radar_log_host share one issue / wait / grow / retry helper.  Context A starts
+    with room for ONE entry in every buffer, so each export is refused once (E_CAPACITY with the counts needed) and asked again;
+    its twin B, fed the same frames and the same radar bytes, has ample room and is never refused.  A returns B's arrays byte for
+    byte -- the refused call wrote, consumed and rebased nothing --, A's capacities end up as the counts returned, B's never moved."""
+    from mmwave_msc_amd import radar
+    from tests import _rows_ref as rr
+    from tests._report_scenes import scenario
+    S, N, F = 4, 96, 6
+    pts, cnt, dts = scenario(n_scenes=S, n_pts=N)   # (its 12 frames: the third target's arrival needs 9; the first six are stepped)
+    rng = np.random.default_rng(61)
+    objects = (5, 1, 17, 9)
+    chunks = []
+    for s in range(S):
+        raw = np.column_stack([rng.uniform(-3, 3, N), rng.uniform(0.2, 7, N), rng.uniform(-1.5, 0.8, N),
+                               rng.integers(-12, 13, N) * rr.CFGP["dopplerResolutionMps"], rng.integers(0, 4000, N)])
+        body = radar.encode_tlv_bodies(raw, objects[s], 9, rr.CFGP["dopplerResolutionMps"])
+        chunks.append(rr.uart_packet(s + 1, body.tobytes(), objects[s]))
+    a, b = _batch(S, N), _batch(S, N)
+    for sb in (a, b):
+        sb.enable_report()
+        sb.open_radars(rr.CFGP, t0=0.0)
+        sb.enable_radar_log()
+        for f in range(F):
+            sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
+        sb.read_radars(chunks, now=1.0)
+    ample = {"report": (256, 512), "clouds": (256, 16384), "skeletons": (256,), "radar_log": (64, 4096)}
+    assert sorted(a._export_caps) == sorted(ample)
+    a._export_caps = {k: (1,) * len(v) for k, v in ample.items()}
+    b._export_caps = dict(ample)
+    calls = {"report": lambda sb: sb.report_host(), "clouds": lambda sb: sb.clouds_host(unassigned=True),
+             "skeletons": lambda sb: (sb.skeletons_host(),), "radar_log": lambda sb: sb.radar_log_host()}
+    for name, call in calls.items():
+        got, want = call(a), call(b)
+        print(name, [len(w) for w in want])
+        assert len(got) == len(want) == len(ample[name]), name
+        for g, w in zip(got, want):
+            assert len(w) > 0 and g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes(), name
+        assert max(len(w) for w in want) > 1, name                       # (room for one entry was too little: A was refused)
+        assert a._export_caps[name] == tuple(len(g) for g in got), (name, a._export_caps[name])
+        assert b._export_caps[name] == ample[name], (name, b._export_caps[name])
+    a.close(); b.close()

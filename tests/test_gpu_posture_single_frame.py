@@ -175,7 +175,7 @@ def test_range_fixup_single_frame_rewrites_exactly_the_flagged_rows(hot):
     assert set(listed[2:2 + min(len(hot), 64)]) <= set(hot) and len(set(listed[2:2 + min(len(hot), 64)])) == min(len(hot), 64)
     word.zero_()
     kp = torch.full((n, 57), CANARY, dtype=torch.float32, device="cuda")
-    scratch = torch.zeros(512 + 64 * (960 + 6144 + 1536 + 57) * 4, dtype=torch.uint8, device="cuda")   # MMW_RANGE_FIXUP_SCRATCH
+    scratch = torch.zeros(_lib.RANGE_FIXUP_SCRATCH, dtype=torch.uint8, device="cuda")
     rc = L.mmw_mars_range_fixup_frames(_stream(), 1, x.data_ptr(), flags.data_ptr(), n, d["conv1_w"].data_ptr(), d["conv1_b"].data_ptr(),
                                        d["conv2_w"].data_ptr(), d["conv2_b"].data_ptr(), d["dense1_w"].data_ptr(), 2048, d["dense1_b"].data_ptr(),
                                        d["dense2_w"].data_ptr(), d["dense2_b"].data_ptr(), scratch.data_ptr(), kp.data_ptr(), word.data_ptr())

@@ -127,7 +127,7 @@ def test_capacity_is_decided_on_the_device_and_a_retry_loses_nothing():
         sb.enable_report()
         for f in range(6):
             _step(sb, f)
-    b._report_caps = (S * b.track_cap, 2 * S * b.track_cap)   # (the twin is never refused)
+    b._export_caps["report"] = (S * b.track_cap, 2 * S * b.track_cap)   # (the twin is never refused)
     want_rows, want_events = b.report_host()
     n_r, n_e = len(want_rows), len(want_events)
     assert n_r > 0 and n_e > 0

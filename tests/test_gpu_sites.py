@@ -499,8 +499,8 @@ def test_site_struct_is_96_bytes_everywhere():
     import os
     import re
     from mmwave_msc_amd import _lib
-    assert C.sizeof(_lib.MmwSceneSite) == 96 and _lib.SITE_DTYPE.itemsize == 96
-    assert [f for f, _ in _lib.MmwSceneSite._fields_] == list(_lib.SITE_DTYPE.names)
+    assert _lib.SITE_DTYPE.itemsize == 96 and _lib.ABI_STRUCTS["mmw_scene_site"] is _lib.SITE_DTYPE
+    assert list(_lib.SITE_DTYPE.names) == list(_lib.SITE_FIELDS) + ["reserved_"]
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     txt = open(os.path.join(root, "include", "mmw.h")).read()
     body = re.search(r"typedef struct mmw_scene_site \{(.*?)\} mmw_scene_site;", txt, flags=re.S).group(1)

@@ -124,16 +124,15 @@ def test_gpu_scenario_moves_its_track_lists(S):
 def test_new_kernels_compile_without_scratch():
     """k_mars_dense2 and k_split_weights (csrc/k_dense2.hip), from the compiler's own resource report: no scratch, no spilled
     register; Dense-2 (eight 32x32 accumulators = 128 registers per lane, one workgroup per CU by design) stays inside the file."""
-    from tests.test_cabi_exports import _device_isa, _kernel_report
+    from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
     rep, asm = _device_isa(("k_dense2",))["k_dense2"]
     rows = {k[0]: k for k in _kernel_report(rep)}
     for short in ("k_mars_dense2", "k_split_weights"):
         hit = [v for k, v in rows.items() if short in k]
         assert len(hit) == 1, (short, list(rows))
         name, scratch, vspill, vgprs, occ, sspill = hit[0]
-        assert scratch == 0 and vspill == 0 and sspill == 0, hit[0]
-        body = asm[asm.index("\n" + name + ":"):]
-        body = body[: body.index("s_endpgm")]
+        assert_clean(hit)
+        body = kernel_body(asm, name)
         assert "scratch_" not in body
         if short == "k_mars_dense2":
             assert vgprs <= 256 and occ >= 1, hit[0]

@@ -79,16 +79,15 @@ def test_gpu_scenario_at_one_frame_per_track():
 def test_conv2d_kernel_compiles_without_scratch():
     """k_mars_conv2d from the compiler's own resource report: no scratch, no spilled register, both fp32 matrix instructions in the
     body, conv2's 72 weights resident beside a 32x32 accumulator, the padded planes and conv1's weights in under 12 KB of LDS."""
-    from tests.test_cabi_exports import _device_isa, _kernel_report
+    from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
     rep, asm = _device_isa(("k_mars2d",))["k_mars2d"]
     rows = _kernel_report(rep)
     assert len(rows) == 1 and "k_mars_conv2d" in rows[0][0], rows
     name, scratch, vspill, vgprs, occ, sspill = rows[0]
     lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", rep).group(1))
     print(f"k_mars_conv2d: {vgprs} VGPRs, {lds} bytes of LDS per workgroup, {occ} waves per SIMD")
-    assert scratch == 0 and vspill == 0 and sspill == 0, rows[0]
-    body = asm[asm.index("\n" + name + ":"):]
-    body = body[: body.index("s_endpgm")]
+    assert_clean(rows)
+    body = kernel_body(asm, name)
     assert "scratch_" not in body
     assert body.count("v_mfma_f32_32x32x2_f32") == 72 and body.count("v_mfma_f32_16x16x4_f32") == 24
     assert 72 + 16 <= vgprs <= 256 and occ >= 1

@@ -1,34 +1,18 @@
-"""The live-track report (mmw_report_*, include/mmw.h) as far as a machine without a GPU can check it: the header declares
-the entries and the library exports them, the ctypes and numpy layouts of the rows and events are the C structs', and the
-kernels of csrc/k_report.hip compile without scratch or spilled registers and store the rows in 16-byte pieces."""
-import ctypes as C
+"""The live-track report (mmw_report_*, include/mmw.h) as far as a machine without a GPU can check it: the entries refuse
+a missing context, the rows and events have the sizes the kernels pin (tests/test_abi.py holds every layout and prototype to
+the header), and the kernels of csrc/k_report.hip compile without scratch or spilled registers and store the rows in 16-byte pieces."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
 from mmwave_msc_amd import _lib
+from tests import _abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("mmw_report_enable", "mmw_report_async", "mmw_report_wait", "mmw_report")
 
 
 def test_header_declares_and_library_exports_the_report_entries():
-    txt = open(os.path.join(ROOT, "include", "mmw.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, code), name
-        assert name in _lib.EXPORTS, name
-    for macro, val in (("MMW_EV_BORN", 1), ("MMW_EV_GONE", 2), ("MMW_EV_REBASED", 3), ("MMW_REPORT_STATIC", 1), ("MMW_REPORT_BORN", 2)):
-        assert re.search(r"#define\s+%s\s+%d\b" % (macro, val), code), macro
-    assert (_lib.EV_BORN, _lib.EV_GONE, _lib.EV_REBASED, _lib.REPORT_STATIC, _lib.REPORT_BORN) == (1, 2, 3, 1, 2)
-    assert "typedef struct mmw_track_report" in code and "typedef struct mmw_track_event" in code
-    L = C.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert hasattr(L, name), f"{name} not exported by {_lib.LIB_PATH}"
     L = _lib.load()   # (declares every prototype: AttributeError if one is missing)
     # without a context every entry refuses its arguments instead of touching a device
     assert L.mmw_report_enable(None, 1) == _lib.E_ARG
@@ -37,37 +21,10 @@ def test_header_declares_and_library_exports_the_report_entries():
     assert L.mmw_report(None, None, 0, None, 0, 0, None, None) == _lib.E_ARG
 
 
-def _c_layout():
-    """sizeof / offsetof of the two structs as a C compiler lays out include/mmw.h."""
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang")
-    if cc is None:
-        pytest.skip("no C compiler")
-    fields_r = ["scene", "slot", "uid", "flags", "point_num", "lifetime", "x", "centroid", "fade_x", "fade_z", "fade_size", "keypoints"]
-    fields_e = ["scene", "uid", "kind", "slot"]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "mmw.h"\nint main(void){printf("%zu %zu", sizeof(mmw_track_report), sizeof(mmw_track_event));\n'
-    src += "".join('printf(" %%zu", offsetof(mmw_track_report, %s));\n' % f for f in fields_r)
-    src += "".join('printf(" %%zu", offsetof(mmw_track_event, %s));\n' % f for f in fields_e)
-    src += "return 0;}\n"
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "layout.c"), "w") as fh:
-            fh.write(src)
-        exe = os.path.join(d, "layout")
-        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), os.path.join(d, "layout.c"), "-o", exe], check=True, capture_output=True)
-        v = [int(t) for t in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    return v[0], v[1], dict(zip(fields_r, v[2: 2 + len(fields_r)])), dict(zip(fields_e, v[2 + len(fields_r):]))
-
-
 def test_report_layouts_match_the_c_structs():
-    size_r, size_e, off_r, off_e = _c_layout()
-    assert (size_r, size_e) == (324, 16)
+    lay = _abi.c_layout()
     rdt, edt = _lib.TRACK_REPORT_DTYPE, _lib.TRACK_EVENT_DTYPE
-    assert rdt.itemsize == C.sizeof(_lib.MmwTrackReport) == size_r
-    assert edt.itemsize == C.sizeof(_lib.MmwTrackEvent) == size_e
-    for f, o in off_r.items():
-        assert rdt.fields[f][1] == o == getattr(_lib.MmwTrackReport, f).offset, f
-    for f, o in off_e.items():
-        assert edt.fields[f][1] == o == getattr(_lib.MmwTrackEvent, f).offset, f
+    assert (lay["mmw_track_report"]["size"], lay["mmw_track_event"]["size"]) == (324, 16) == (rdt.itemsize, edt.itemsize)
     # every field a row shares with the track table has the table's type and shape
     for f in ("scene", "slot", "point_num", "lifetime", "x", "centroid", "keypoints", "fade_x", "fade_z", "fade_size"):
         assert rdt.fields[f][0] == _lib.SUMMARY_DTYPE.fields[f][0], f
@@ -79,7 +36,7 @@ def test_report_layouts_match_the_c_structs():
 
 
 def test_report_kernels_use_no_scratch_and_store_rows_in_16_byte_pieces():
-    from tests.test_cabi_exports import _device_isa, _kernel_report
+    from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
     rep, asm = _device_isa(("k_report",))["k_report"]
     rows = _kernel_report(rep)
     names = [k[0] for k in rows]
@@ -87,10 +44,9 @@ def test_report_kernels_use_no_scratch_and_store_rows_in_16_byte_pieces():
         assert sum(k in n for n in names) == 1, (k, names)
     assert sum("k_report_write" in n for n in names) == 2, names   # the context's window, and each scene's own site
     assert len(names) == 5, names                                   # (the scan is k_pair_scan of k_scan.hip)
+    assert_clean(rows)
     for name, scratch, vspill, vgprs, occ, sspill in rows:
-        assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
-        body = asm[asm.index("\n" + name + ":"):]
-        body = body[: body.index("s_endpgm")]
+        body = kernel_body(asm, name)
         assert "scratch_" not in body, name
         if "k_report_write" in name:
             # the image goes LDS -> global in 16-byte pieces (ds_read_b128 + global_store_dwordx4), not a lane per row
@@ -101,15 +57,14 @@ def test_report_kernels_use_no_scratch_and_store_rows_in_16_byte_pieces():
 def test_the_exports_share_one_scan_kernel_without_scratch():
     """k_scan.hip holds the one two-array offset scan of the library, k_pair_scan: no scratch, no spilled register.  The three
     kernels it replaced are in no export's device code, and its launcher is declared once and defined once."""
-    from tests.test_cabi_exports import _device_isa, _kernel_report
+    from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
     isa = _device_isa(("k_scan", "k_report", "k_cloud", "k_skeleton"))
     rep, asm = isa["k_scan"]
     rows = _kernel_report(rep)
     assert len(rows) == 1 and "k_pair_scan" in rows[0][0], rows
     name, scratch, vspill, vgprs, occ, sspill = rows[0]
-    assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
-    body = asm[asm.index("\n" + name + ":"):]
-    body = body[: body.index(".Lfunc_end")]
+    assert_clean(rows)
+    body = kernel_body(asm, name, ".Lfunc_end")
     assert "s_endpgm" in body and "scratch_" not in body, name
     for f, (_, a) in isa.items():
         for old in ("k_%s_scan" % e for e in ("report", "cloud", "skel")):   # (the three copies this kernel replaced)
@@ -132,12 +87,11 @@ def test_the_exports_share_one_scan_kernel_without_scratch():
 
 def test_table_kernels_still_compile_without_scratch_after_sharing_their_body():
     """k_table / k_table_site call the function the report rows come from (mmw_summary.hpp)."""
-    from tests.test_cabi_exports import _device_isa, _kernel_report
+    from tests._isa import _device_isa, _kernel_report, assert_clean
     rep, _ = _device_isa(("k_misc",))["k_misc"]
     rows = [k for k in _kernel_report(rep) if "k_table" in k[0]]
     assert len(rows) == 2, rows
-    for name, scratch, vspill, vgprs, occ, sspill in rows:
-        assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
+    assert_clean(rows)
     src = open(os.path.join(ROOT, "mmwave_msc_amd", "csrc", "k_misc.hip")).read()
     assert "summary_fields(" in src and "summary_fields(" in open(os.path.join(ROOT, "mmwave_msc_amd", "csrc", "k_report.hip")).read()
 

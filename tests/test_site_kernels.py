@@ -4,7 +4,7 @@ VGPR, no scratch; and the mounting of k_normalize_site / k_normalize_tlv_site ar
 one scene), not as a per-lane load."""
 import re
 
-from tests.test_cabi_exports import _device_isa, _kernel_report
+from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
 
 
 def test_site_kernels_use_no_scratch_and_read_the_mounting_through_the_scalar_cache():
@@ -14,10 +14,9 @@ def test_site_kernels_use_no_scratch_and_read_the_mounting_through_the_scalar_ca
     assert sum("k_normalize_siteI" in n for n in names) == 6      # fp64 / fp32 raw rows x 1, 2, 4 rows per thread
     assert sum("k_normalize_tlv_siteI" in n for n in names) == 3
     assert sum("k_features_site" in n for n in names) == 1 and sum("k_table_site" in n for n in names) == 1
+    assert_clean(rows)
     for name, scratch, vspill, vgprs, occ, sspill in rows:
-        assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
-        body = asm[asm.index("\n" + name + ":"):]
-        body = body[: body.index("s_endpgm")]
+        body = kernel_body(asm, name)
         assert "scratch_" not in body, name
         if "k_normalize" in name:
             # the site variant adds no vector load to its plain twin's: the three doubles of the mounting come by s_load from the
@@ -29,8 +28,7 @@ def test_site_kernels_use_no_scratch_and_read_the_mounting_through_the_scalar_ca
             twins = [k[0] for k in _kernel_report(rep) if k[0].startswith("_ZN3mmw%d%sI%sEEv" % (len(plain), plain, m.group(2)))]
             assert len(twins) == 1, (name, twins)
             twin = twins[0]
-            tb = asm[asm.index("\n" + twin + ":"):]
-            tb = tb[: tb.index("s_endpgm")]
+            tb = kernel_body(asm, twin)
             vload = lambda b: len(re.findall(r"\b(global|flat|buffer)_load_", b))
             sload = lambda b: sum({"": 1, "x2": 2, "x4": 4, "x8": 8, "x16": 16}[m] for m in re.findall(r"\bs_load_dword(x\d+)?\b", b))
             assert vload(body) == vload(tb), (name, vload(body), vload(tb))

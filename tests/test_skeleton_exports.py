@@ -1,5 +1,6 @@
-"""The live tracks' skeletons (mmw_skeletons_*, include/mmw.h) as far as a machine without a GPU can check them: the header declares
-the entries and the library exports them, the numpy layout is the C struct's, mmw_skeleton_tables gives the reference's bones and
+"""The live tracks' skeletons (mmw_skeletons_*, include/mmw.h) as far as a machine without a GPU can check them: the entries refuse a
+missing context, the numpy layout has the offsets pinned here (tests/test_abi.py holds every layout and prototype to the header),
+mmw_skeleton_tables gives the reference's bones and
 joint colours (tests/golden/skeleton_tables.json: Visualizer.py:100-142 as plain data), the kernels of csrc/k_skeleton.hip compile
 without scratch or spilled registers and store 16-byte pieces, and the numpy restatement the GPU tests compare with
 (tests/_skeleton_ref.py) reproduces three entries computed by hand.
@@ -10,63 +11,30 @@ import ctypes as C
 import json
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
-import pytest
 
 from mmwave_msc_amd import _lib
+from tests import _abi
 from tests import _skeleton_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("mmw_skeletons_async", "mmw_skeletons_wait", "mmw_skeletons", "mmw_skeleton_tables")
 FIELDS = ["scene", "slot", "uid", "row", "flags", "gap", "joint", "reserved_"]
 
 
 def test_header_declares_and_library_exports_the_skeleton_entries():
-    txt = open(os.path.join(ROOT, "include", "mmw.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, code), name
-        assert name in _lib.EXPORTS, name
-    for macro, val in (("MMW_SKEL_SKIPPED", 1), ("MMW_SKEL_ALL", 0), ("MMW_SKEL_DRAWN", 1)):
-        assert re.search(r"#define\s+%s\s+%d\b" % (macro, val), code), macro
-    assert (_lib.SKEL_SKIPPED, _lib.SKEL_ALL, _lib.SKEL_DRAWN) == (1, 0, 1)
-    assert "typedef struct mmw_skeleton" in code
+    code = _abi.header_code()
     assert code.index("mmw_clouds(") < code.index("typedef struct mmw_skeleton") < code.index("mmw_snapshot_header")   # after the clouds
-    L = C.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert hasattr(L, name), f"{name} not exported by {_lib.LIB_PATH}"
     L = _lib.load()   # (declares every prototype: AttributeError if one is missing)
-    for name in NEW:
-        assert getattr(L, name).argtypes is not None, name
     # without a context every entry refuses its arguments instead of touching a device
     assert L.mmw_skeletons_async(None, None, 0, 0, 0, 0) == _lib.E_ARG
     assert L.mmw_skeletons_wait(None, 0, None, None) == _lib.E_ARG
     assert L.mmw_skeletons(None, None, 0, 0, 0, None, None) == _lib.E_ARG
 
 
-def _c_layout():
-    """sizeof / offsetof of mmw_skeleton as a C compiler lays out include/mmw.h."""
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang")
-    if cc is None:
-        pytest.skip("no C compiler")
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "mmw.h"\nint main(void){printf("%zu", sizeof(mmw_skeleton));\n'
-    src += "".join('printf(" %%zu", offsetof(mmw_skeleton, %s));\n' % f for f in FIELDS)
-    src += 'printf(" %zu", sizeof(((mmw_skeleton *)0)->joint));\nreturn 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "layout.c"), "w") as fh:
-            fh.write(src)
-        exe = os.path.join(d, "layout")
-        subprocess.run([cc, "-I", os.path.join(ROOT, "include"), os.path.join(d, "layout.c"), "-o", exe], check=True, capture_output=True)
-        v = [int(t) for t in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    return v[0], dict(zip(FIELDS, v[1: 1 + len(FIELDS)])), v[-1]
-
-
 def test_skeleton_layout_matches_the_c_struct():
-    size, off, joint_bytes = _c_layout()
+    lay = _abi.c_layout()["mmw_skeleton"]
+    size, off, joint_bytes = lay["size"], {f: lay["fields"][f][0] for f in FIELDS}, lay["fields"]["joint"][1]
     sdt = _lib.SKELETON_DTYPE
     assert size == 256 == sdt.itemsize
     assert list(sdt.names) == FIELDS
@@ -117,17 +85,16 @@ def test_skeleton_launcher_is_declared_once_and_the_files_are_built():
 
 
 def test_skeleton_kernels_use_no_scratch_and_store_16_byte_pieces():
-    from tests.test_cabi_exports import _device_isa, _kernel_report
+    from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
     rep, asm = _device_isa(("k_skeleton",))["k_skeleton"]
     rows = _kernel_report(rep)
     names = [k[0] for k in rows]
     for k in ("k_skel_count", "k_skel_write"):
         assert sum(k in n for n in names) == 1, (k, names)
     assert len(names) == 2, names                                 # (the scan is k_pair_scan of k_scan.hip)
+    assert_clean(rows)
     for name, scratch, vspill, vgprs, occ, sspill in rows:
-        assert scratch == 0 and vspill == 0 and sspill == 0, (name, scratch, vspill, sspill)
-        body = asm[asm.index("\n" + name + ":"):]
-        body = body[: body.index(".Lfunc_end")]   # (the whole kernel: one that returns early has more than one s_endpgm)
+        body = kernel_body(asm, name, ".Lfunc_end")   # (the whole kernel: one that returns early has more than one s_endpgm)
         assert "s_endpgm" in body, name
         assert "scratch_" not in body, name
         if "k_skel_write" in name:
