@@ -52,6 +52,11 @@ class MmwPostureModel(C.Structure):
                 ("dense1_w", C.c_void_p), ("dense1_ld", C.c_int64), ("dense1_b", C.c_void_p), ("dense2_w", C.c_void_p),
                 ("dense2_b", C.c_void_p)]
 
+    @classmethod
+    def of(cls, conv1_w, conv1_b, conv2_w, conv2_b, dense1_w, dense1_b, dense2_w, dense2_b, dense1_ld):
+        """From the eight device pointers (weight, bias of each layer in turn) and Dense-1's leading dimension in floats."""
+        return cls(conv1_w, conv1_b, conv2_w, conv2_b, dense1_w, dense1_ld, dense1_b, dense2_w, dense2_b)
+
 
 class MmwUartCfg(C.Structure):
     """struct mmw_uart_cfg (include/mmw.h): the scales ReadIWR14xx.__parseConfigFile derives from the radar .cfg."""
@@ -338,6 +343,17 @@ class MmwDivZero(MmwError, ZeroDivisionError):
 def error_for(code, msg) -> MmwError:
     cls = {E_NONFINITE: MmwNonFinite, E_SINGULAR: MmwSingular, E_DIVZERO: MmwDivZero}.get(code, MmwError)
     return cls(code, msg)
+
+
+def last_error(ctx=None) -> str:
+    """mmw_last_error: the message of the last failed call on `ctx`, or (None) of the last failed call that had no context."""
+    return (load().mmw_last_error(ctx) or b"").decode()
+
+
+def check(rc, ctx=None):
+    """The one way a C-ABI status becomes an exception."""
+    if rc != 0:
+        raise error_for(rc, last_error(ctx))
 
 
 def source_hash() -> str:

@@ -65,8 +65,7 @@ class SceneBatch:
         self.h = None
         h = C.c_void_p()
         rc = self.L.mmw_create(C.byref(self.cfg), int(n_scenes), int(max_pts), int(device), C.byref(h))
-        if rc != 0:
-            raise MmwError(rc, (self.L.mmw_last_error(None) or b"").decode())
+        _lib.check(rc)
         self.h = h
         self.S, self.max_pts, self.device = int(n_scenes), int(max_pts), int(device)
         dims = [C.c_int32() for _ in range(5)]
@@ -82,8 +81,7 @@ class SceneBatch:
 
     # -- plumbing -------------------------------------------------------------
     def _chk(self, rc):
-        if rc != 0:
-            raise error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
+        _lib.check(rc, self.h)
 
     def close(self):
         if self.h:
@@ -412,28 +410,24 @@ class SceneBatch:
         return assoc, labels, dbn
 
     def attach_posture(self, model=None):
-        """mmw_attach_posture / mmw_attach_posture_frames: hands the context a `mars.MarsCNN` (on this GPU; the 3-frame model, or the
-        single-frame one on a context with FB_FRAMES_BATCH = 0) so that `frame_host(posture=True)` runs TrackBuffer.estimate_posture
-        behind the step in the same round trip; None detaches.  Only the model's tensors are read (k_w1 .. k_b2, dense1_dhwc,
-        dense2).  The context keeps the weights' device pointers: the model must stay where it is (in-place updates are fine) until
-        detached."""
+        """mmw_attach_posture_frames (with frames = 3: mmw_attach_posture): hands the context a `mars.MarsCNN` (on this GPU; the
+        3-frame model, or the single-frame one on a context with FB_FRAMES_BATCH = 0) so that `frame_host(posture=True)` runs
+        TrackBuffer.estimate_posture behind the step in the same round trip; None detaches.  Only the model's tensors are read
+        (k_w1 .. k_b2, dense1_dhwc, dense2).  The context keeps the weights' device pointers: the model must stay where it is
+        (in-place updates are fine) until detached."""
         if model is None:
-            self._chk(self.L.mmw_attach_posture(self.h, None))
+            self._chk(self.L.mmw_attach_posture_frames(self.h, None, self.ring))
             self._posture_model = None
             return
-        w1 = model.dense1_dhwc.weight
-        m = _lib.MmwPostureModel(model.k_w1.data_ptr(), model.k_b1.data_ptr(), model.k_w2.data_ptr(), model.k_b2.data_ptr(),
-                                 w1.data_ptr(), w1.stride(0), model.dense1_dhwc.bias.data_ptr(), model.dense2.weight.data_ptr(),
-                                 model.dense2.bias.data_ptr())
-        if w1.shape[1] == 2048:   # define_CNN's Dense-1 (8 x 8 x 32 inputs): the single-frame model
-            self._chk(self.L.mmw_attach_posture_frames(self.h, C.byref(m), 1))
-        else:
-            self._chk(self.L.mmw_attach_posture(self.h, C.byref(m)))
+        d1, d2 = model.dense1_dhwc, model.dense2
+        m = _lib.MmwPostureModel.of(*(t.data_ptr() for t in (model.k_w1, model.k_b1, model.k_w2, model.k_b2, d1.weight, d1.bias, d2.weight, d2.bias)),
+                                    dense1_ld=d1.weight.stride(0))
+        self._chk(self.L.mmw_attach_posture_frames(self.h, C.byref(m), model.frames))
         self._posture_model = model   # (keeps the tensors alive)
 
     def attach_posture_batch(self, weights=None, cap_rows: int = None):
-        """mmw_posture_attach / mmw_posture_attach_frames: the batched `TrackBuffer.estimate_posture` for every scene of this context,
-        no torch on the path.
+        """mmw_posture_attach_frames (with frames = 3: mmw_posture_attach): the batched `TrackBuffer.estimate_posture` for every
+        scene of this context, no torch on the path.
         `weights`: Keras-convention tensors of the context's model -- define_CNN_3D when FB_FRAMES_BATCH = 2, the single-frame
         define_CNN when FB_FRAMES_BATCH = 0 -- as a dict, an `.npz` or a Keras `.h5` path (what
         `MarsCNN.from_keras_weights` / `MarsCNN.load` take); both BatchNorms are folded on the host in fp64
@@ -442,20 +436,18 @@ class SceneBatch:
         Refused: a model whose frame count is not the context's FB_FRAMES_BATCH + 1 (ValueError); with MmwError, E_ARG:
         FB_FRAMES_BATCH + 1 not 3 or 1, cap_rows < 1, a weight outside fp16's range."""
         if weights is None:
-            self._chk(self.L.mmw_posture_attach(self.h, None, 0))
+            self._chk(self.L.mmw_posture_attach_frames(self.h, None, self.ring, 0))
             self._free_posture_batch()
             return
-        from .marsweights import fold_keras_weights, load_keras_weights
+        from .marsweights import FOLDED_KEYS, fold_keras_weights, load_keras_weights
         f = fold_keras_weights(load_keras_weights(weights))
         if f["frames"] != self.ring:
             raise ValueError(f"attach_posture_batch: these weights are the {f['frames']}-frame model's, this context holds {self.ring} "
                              f"frame(s) per track (FB_FRAMES_BATCH = {self.ring - 1})")
         cap = int(cap_rows if cap_rows is not None else self.S * self.track_cap)
-        keys = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "dense1_w", "dense1_b", "dense2_w", "dense2_b")
-        bufs = {k: DevBuf(self, f[k].nbytes).upload(f[k]) for k in keys}
-        m = _lib.MmwPostureModel(bufs["conv1_w"].ptr, bufs["conv1_b"].ptr, bufs["conv2_w"].ptr, bufs["conv2_b"].ptr, bufs["dense1_w"].ptr,
-                                 f["dense1_w"].shape[1], bufs["dense1_b"].ptr, bufs["dense2_w"].ptr, bufs["dense2_b"].ptr)
-        rc = self.L.mmw_posture_attach(self.h, C.byref(m), cap) if self.ring == 3 else self.L.mmw_posture_attach_frames(self.h, C.byref(m), self.ring, cap)
+        bufs = {k: DevBuf(self, f[k].nbytes).upload(f[k]) for k in FOLDED_KEYS}
+        m = _lib.MmwPostureModel.of(*(bufs[k].ptr for k in FOLDED_KEYS), dense1_ld=f["dense1_w"].shape[1])
+        rc = self.L.mmw_posture_attach_frames(self.h, C.byref(m), self.ring, cap)
         if rc != 0:   # (refused atomically: an earlier model stays attached, with its own buffers)
             for b in bufs.values():
                 b.free()
@@ -673,7 +665,7 @@ class SceneBatch:
         rc = wait(self.h, int(ticket), *[C.byref(v) for v in n])
         got = tuple(int(v.value) for v in n) if counts > 1 else int(n[0].value)
         if rc == _lib.E_CAPACITY:
-            err = error_for(rc, (self.L.mmw_last_error(self.h) or b"").decode())
+            err = error_for(rc, _lib.last_error(self.h))
             err.needed = got
             raise err
         self._chk(rc)

@@ -220,14 +220,15 @@ int mmw_mars_head_small(void *hip_stream, const float *act, int64_t lda, const f
     return launches_done("mmw_mars_head_small");
 }
 
-static int range_fixup_impl(const char *who, void *hip_stream, int frames, const float *feat, int32_t *sample_flags, int32_t n, const float *cw1,
-                            const float *cb1, const float *cw2, const float *cb2, const float *w1, int64_t ldw, const float *bias1, const float *w2,
-                            const float *bias2, void *scratch, float *kp, int32_t *range_flag)
+// (the model's weights as the struct of the attach entries: dense1_ld is the entries' ldw)
+static int range_fixup_impl(const char *who, void *hip_stream, int frames, const float *feat, int32_t *sample_flags, int32_t n, const mmw_posture_model &m,
+                            void *scratch, float *kp, int32_t *range_flag)
 {
     constexpr int kCap = MMW_RANGE_FIXUP_CAP;
     const CnnDims d = cnn_dims(frames);
-    if (n < 0 || (n > 0 && (!feat || !sample_flags || !cw1 || !cb1 || !cw2 || !cb2 || !w1 || !bias1 || !w2 || !bias2 || !scratch || !kp)) ||
-        ldw < d.flat || (ldw & 3) != 0 || (((uintptr_t)scratch | (uintptr_t)w1) & 15) != 0)
+    if (n < 0 || (n > 0 && (!feat || !sample_flags || !m.conv1_w || !m.conv1_b || !m.conv2_w || !m.conv2_b || !m.dense1_w || !m.dense1_b || !m.dense2_w ||
+                            !m.dense2_b || !scratch || !kp)) ||
+        m.dense1_ld < d.flat || (m.dense1_ld & 3) != 0 || (((uintptr_t)scratch | (uintptr_t)m.dense1_w) & 15) != 0)
         return fail(nullptr, MMW_E_ARG, "%s: bad argument", who);
     if (n == 0) return MMW_OK;
     hipStream_t st = (hipStream_t)hip_stream;
@@ -236,11 +237,8 @@ static int range_fixup_impl(const char *who, void *hip_stream, int frames, const
     // sample_flags = the fix-up list k_mars_conv16 appended to: [0] running count, [1] taken by this call, [2 ..] sample indices
     float *small = reinterpret_cast<float *>(reinterpret_cast<char *>(scratch) + 512);
     float *act = small + (size_t)kCap * d.per, *hidden = act + (size_t)kCap * d.flat, *kps = hidden + (size_t)kCap * d.hidden;
-    const int32_t *taken = sample_flags + 1;
     launch_range_gather(feat, sample_flags, n, d.per, kCap, small, range_flag, st);
-    if (frames == 3) launch_mars_conv(small, cw1, cb1, cw2, cb2, act, kCap, st, taken);
-    else launch_mars_conv2d(small, cw1, cb1, cw2, cb2, act, kCap, st, taken);
-    launch_mars_head_small(act, d.flat, w1, ldw, bias1, w2, bias2, hidden, kps, kCap, d.flat, d.hidden, MMW_NKP, st, taken);
+    launch_mars_small_f32(frames, small, m, act, hidden, kps, kCap, st, sample_flags + 1);
     launch_range_scatter(kps, sample_flags, kp, kCap, MMW_NKP, n, st);
     return launches_done(who);
 }
@@ -249,7 +247,7 @@ int mmw_mars_range_fixup(void *hip_stream, const float *feat, int32_t *sample_fl
                          const float *cw2, const float *cb2, const float *w1, int64_t ldw, const float *bias1, const float *w2, const float *bias2,
                          void *scratch, float *kp, int32_t *range_flag)
 {
-    return range_fixup_impl("mmw_mars_range_fixup", hip_stream, 3, feat, sample_flags, n, cw1, cb1, cw2, cb2, w1, ldw, bias1, w2, bias2, scratch, kp, range_flag);
+    return range_fixup_impl("mmw_mars_range_fixup", hip_stream, 3, feat, sample_flags, n, {cw1, cb1, cw2, cb2, w1, ldw, bias1, w2, bias2}, scratch, kp, range_flag);
 }
 
 int mmw_mars_range_fixup_frames(void *hip_stream, int32_t frames, const float *feat, int32_t *sample_flags, int32_t n, const float *cw1,
@@ -257,7 +255,7 @@ int mmw_mars_range_fixup_frames(void *hip_stream, int32_t frames, const float *f
                                 const float *w2, const float *bias2, void *scratch, float *kp, int32_t *range_flag)
 {
     if (frames != 3 && frames != 1) return fail(nullptr, MMW_E_ARG, "mmw_mars_range_fixup_frames: frames = %d must be 3 or 1 (FB_FRAMES_BATCH + 1)", frames);
-    return range_fixup_impl("mmw_mars_range_fixup_frames", hip_stream, frames, feat, sample_flags, n, cw1, cb1, cw2, cb2, w1, ldw, bias1, w2, bias2, scratch,
+    return range_fixup_impl("mmw_mars_range_fixup_frames", hip_stream, frames, feat, sample_flags, n, {cw1, cb1, cw2, cb2, w1, ldw, bias1, w2, bias2}, scratch,
                             kp, range_flag);
 }
 
@@ -296,7 +294,6 @@ static int posture_detach(mmw_ctx *c)
 static int posture_attach_impl(mmw_ctx *c, const mmw_posture_model *m, int frames, int32_t cap_rows, const char *who)
 {
     const CnnDims d = cnn_dims(frames);
-    const int taps = frames == 3 ? 27 : 9;
     if (cap_rows < 1) return fail(c, MMW_E_ARG, "%s: cap_rows = %d must be >= 1", who, cap_rows);
     if (cap_rows > INT32_MAX - 255) return fail(c, MMW_E_ARG, "%s: cap_rows = %d is too large", who, cap_rows);
     if (!posture_model_ok(m, d, true))
@@ -328,9 +325,9 @@ static int posture_attach_impl(mmw_ctx *c, const mmw_posture_model *m, int frame
         // the split Dense-1 operand, once; every weight that meets the split arithmetic must lie inside fp16's range
         int32_t *flag = b->words + kPbWordWeights;
         launch_split_weights(m->dense1_w, m->dense1_ld, b->w16, 2 * d.flat, d.hidden, d.flat, flag, c->stream);
-        launch_range_check(m->conv1_w, taps * 5 * 16, flag, c->stream);
+        launch_range_check(m->conv1_w, d.taps * 5 * 16, flag, c->stream);
         launch_range_check(m->conv1_b, 16, flag, c->stream);
-        launch_range_check(m->conv2_w, taps * 16 * 32, flag, c->stream);
+        launch_range_check(m->conv2_w, d.taps * 16 * 32, flag, c->stream);
         launch_range_check(m->conv2_b, 32, flag, c->stream);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
@@ -388,8 +385,7 @@ int mmw_estimate_posture(mmw_ctx *c, int32_t *n_rows)
         return fail(c, MMW_E_HIP, "mmw_estimate_posture: hipFuncSetAttribute(max dynamic LDS) failed on this device");
     launch_mars_dense2(b->hidden, d.hidden, m.dense2_w, m.dense2_b, b->kp, total, d.hidden, c->stream);
     HIPCHK(c, hipGetLastError());
-    const int rc = range_fixup_impl("mmw_mars_range_fixup", c->stream, b->frames, b->feat, list, total, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, m.dense1_w, m.dense1_ld, m.dense1_b,
-                                        m.dense2_w, m.dense2_b, b->fix_scratch, b->kp, range);
+    const int rc = range_fixup_impl("mmw_mars_range_fixup", c->stream, b->frames, b->feat, list, total, m, b->fix_scratch, b->kp, range);
     if (rc) return fail(c, rc, "mmw_estimate_posture: %s", mmw_last_error(nullptr));
     launch_set_kp(c->dc, c->st, b->kp, b->owner, total, c->stream);
     HIPCHK(c, hipGetLastError());

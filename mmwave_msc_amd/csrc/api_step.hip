@@ -155,14 +155,9 @@ static int frame_impl(mmw_ctx *c, const double *raw, const double *pts, const in
     if (posture) {
         // TrackBuffer.estimate_posture behind the step, unless the frame was skipped (k_features reads the frame's row count): the
         // rows are counted on the device, every launch covers the capacity and its surplus workgroups leave on that word
-        const mmw_posture_model &m = c->model;
         const int cap = c->dc.t_cap;
         launch_features(c->dc, sites_or_null(c), c->st, nullptr, c->pc_feat, c->pc_owner, nullptr, cap, c->stream, d_cnt, c->d_prows);
-        const CnnDims d = cnn_dims(c->model_frames);
-        if (c->model_frames == 3) launch_mars_conv(c->pc_feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, c->pc_act, cap, c->stream, c->d_prows);
-        else launch_mars_conv2d(c->pc_feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, c->pc_act, cap, c->stream, c->d_prows);
-        launch_mars_head_small(c->pc_act, d.flat, m.dense1_w, m.dense1_ld, m.dense1_b, m.dense2_w, m.dense2_b, c->pc_hidden, c->pc_kp, cap, d.flat, d.hidden,
-                               MMW_NKP, c->stream, c->d_prows);
+        launch_mars_small_f32(c->model_frames, c->pc_feat, c->model, c->pc_act, c->pc_hidden, c->pc_kp, cap, c->stream, c->d_prows);
         launch_set_kp(c->dc, c->st, c->pc_kp, c->pc_owner, cap, c->stream, c->d_prows);
         HIPCHK(c, hipGetLastError());
     }

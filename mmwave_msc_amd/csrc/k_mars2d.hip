@@ -131,4 +131,11 @@ void launch_mars_conv2d(const float *feat, const float *w1, const float *b1, con
     hipLaunchKernelGGL(k_mars_conv2d, dim3(grid), dim3(128), 0, stream, feat, w1, b1, w2, b2, out, B, dev_rows);
 }
 
+void launch_mars_conv_f32(int frames, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B,
+                          hipStream_t stream, const int32_t *dev_rows)
+{
+    if (frames == 3) launch_mars_conv(feat, w1, b1, w2, b2, out, B, stream, dev_rows);
+    else launch_mars_conv2d(feat, w1, b1, w2, b2, out, B, stream, dev_rows);
+}
+
 }  // namespace mmw

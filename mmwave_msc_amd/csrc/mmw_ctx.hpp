@@ -15,10 +15,21 @@ using namespace mmw;
 struct EventPair { hipEvent_t a, b; int kid; };
 
 // the posture CNN's shapes, floats per row: feature tensor, conv output, hidden layer -- by model: frames = 3 (define_CNN_3D,
-// train.py:71-106: 960, 6144, 1536) or 1 (define_CNN, train.py:33-68: 320, 2048, 512) -- and keypoints (MMW_NKP = 57, padded)
+// train.py:71-106: 960, 6144, 1536) or 1 (define_CNN, train.py:33-68: 320, 2048, 512) -- and keypoints (MMW_NKP = 57, padded);
+// taps = the conv kernels' positions (3 x 3 x 3 or 3 x 3).  marsweights.model_dims is the same table in Python.
 constexpr int kCnnKpPad = 64;
-struct CnnDims { int per, flat, hidden; };
-static inline CnnDims cnn_dims(int frames) { return CnnDims{frames * 8 * 8 * 5, frames * 64 * 32, frames * 512}; }
+struct CnnDims { int per, flat, hidden, taps; };
+static inline CnnDims cnn_dims(int frames) { return CnnDims{frames * 8 * 8 * 5, frames * 64 * 32, frames * 512, frames == 3 ? 27 : 9}; }
+
+// The fp32 small chain of either model: the conv pair, then the thin Dense-1 / Dense-2 kernels, `rows` rows of feat -> kp[rows][nkp]
+// through act[rows][flat] and hidden[rows][hidden]; dev_rows (device word or nullptr) = the rows that exist, as the launchers take it
+static inline void launch_mars_small_f32(int frames, const float *feat, const mmw_posture_model &m, float *act, float *hidden, float *kp, int rows,
+                                         hipStream_t st, const int32_t *dev_rows)
+{
+    const CnnDims d = cnn_dims(frames);
+    launch_mars_conv_f32(frames, feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, act, rows, st, dev_rows);
+    launch_mars_head_small(act, d.flat, m.dense1_w, m.dense1_ld, m.dense1_b, m.dense2_w, m.dense2_b, hidden, kp, rows, d.flat, d.hidden, MMW_NKP, st, dev_rows);
+}
 constexpr int kTickets = 4;
 // the counters of mmw_stats_get in st.stats (the probe words of the diagnostic build lie behind them)
 constexpr size_t kStatBytes = (size_t)kStatSlots * kStatWords * sizeof(unsigned long long);

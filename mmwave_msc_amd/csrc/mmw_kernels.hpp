@@ -75,6 +75,8 @@ void launch_samples(const DevCfg &cfg, const mmw_scene_site *sites, const DevSta
 void launch_mars_conv(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
 // k_mars2d.hip: the Conv2D pair of the single-frame model (define_CNN) in fp32; dev_rows as launch_mars_conv's
 void launch_mars_conv2d(const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
+// ... and the fp32 conv pair of either model: launch_mars_conv for frames = 3, launch_mars_conv2d for frames = 1
+void launch_mars_conv_f32(int frames, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2, float *out, int B, hipStream_t stream, const int32_t *dev_rows = nullptr);
 void launch_range_gather(const float *feat, int32_t *list, int n, int per, int cap, float *small, int32_t *range_flag, hipStream_t stream);
 void launch_range_scatter(const float *kp_small, const int32_t *list, float *kp, int cap, int nout, int n, hipStream_t stream);
 // Dense-1's tile plan (k_dense.hip): bands of 256 rows per instantiation -- 256 x 192 tiles, 256 x 128 tiles, 128 x 128 half tiles

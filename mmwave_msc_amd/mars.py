@@ -24,8 +24,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-BN_EPS = 1e-3
-N_KEYPOINTS = 57
+from . import _lib   # (constants, the struct mirrors and check(): the library itself is loaded on first use)
+from ._lib import RANGE_FIXUP_CAP, RANGE_FIXUP_SCRATCH
+# the models' facts live in the torch-free module (CPU-side tools import it without torch); re-exported for this module's callers
+from .marsweights import BN_EPS, N_KEYPOINTS, fold_keras_weights, model_dims, random_keras_weights  # noqa: F401
+
 SPLIT_SCALE = 2048.0   # 2^11: fp16 keeps 11 significant bits (csrc/k_mars.hip: kSplitScale)
 FP16_SAFE_MAX = 6.0e4  # weights at or above this magnitude do not go through the split-fp16 arithmetic (fp16 max = 65 504)
 
@@ -44,10 +47,6 @@ def deinterleave_split(a2: torch.Tensor):
     r = a2.shape[0]
     v = a2.reshape(r, -1, 2, 32)
     return v[:, :, 0, :].reshape(r, -1), v[:, :, 1, :].reshape(r, -1)
-
-
-from ._lib import RANGE_FIXUP_CAP, RANGE_FIXUP_SCRATCH  # noqa: E402  (constants only: the library itself is loaded on first use)
-from .marsweights import random_keras_weights  # noqa: E402,F401  (torch-free module: CPU-side tools import it without torch)
 
 
 class MarsCNN(nn.Module):
@@ -72,24 +71,24 @@ class MarsCNN(nn.Module):
         self.range_recomputed = 0    # range_overflow() reads that found the device-side fp32 fix-up had run (3-frame model)
         self._sflags = None          # per-sample range verdicts of the split conv kernel (device int32, kept zero between calls)
         self._fix_scratch = None     # mmw_mars_range_fixup's device scratch
-        self.frames = int(frames)
-        self.three_d = self.frames > 1
+        self.dims = d = model_dims(frames)
+        self.frames = d.frames
+        self.three_d = len(d.kernel) == 3
         conv = nn.Conv3d if self.three_d else nn.Conv2d
         self.conv1 = conv(5, 16, 3, padding=1)
         self.conv2 = conv(16, 32, 3, padding=1)
-        flat = (self.frames if self.three_d else 1) * 64 * 32
-        hidden = 512 * (3 if self.three_d else 1)
+        flat, hidden = d.flat, d.hidden
         self.dense1 = nn.Linear(flat, hidden)   # BN1 folded in, rows in channels-first flatten order
         self.dense2 = nn.Linear(hidden, N_KEYPOINTS)  # BN2 folded in
         # hand-written fused conv pair (csrc/k_mars.hip): Keras-layout kernels and a Dense-1 whose rows follow Keras' own
         # (d,h,w,c) flatten order.  The fp16-split kernel (arith "f16x3") serves both models; the fp32-MFMA kernel
-        # (arith "f32") exists for the 3-frame model only -- the single-frame model then uses torch's convolutions.
+        # (arith "f32") is used for the 3-frame model only -- the library's single-frame one (k_mars2d.hip) is not used by this
+        # class yet: the single-frame model then uses torch's convolutions.
         self.use_hip_conv = self.frames in (3, 1)
         self.use_hip_conv_f32 = self.frames == 3
-        kt = 27 if self.three_d else 9
-        self.register_buffer("k_w1", torch.zeros(kt * 5 * 16))
+        self.register_buffer("k_w1", torch.zeros(d.taps * 5 * 16))
         self.register_buffer("k_b1", torch.zeros(16))
-        self.register_buffer("k_w2", torch.zeros(kt * 16 * 32))
+        self.register_buffer("k_w2", torch.zeros(d.taps * 16 * 32))
         self.register_buffer("k_b2", torch.zeros(32))
         self.dense1_dhwc = nn.Linear(flat, hidden)
         # the same matrix split for the fp16 matrix cores, transposed (K contiguous) with the halves interleaved in runs of 32,
@@ -102,45 +101,31 @@ class MarsCNN(nn.Module):
 
     @classmethod
     def from_keras_weights(cls, w: dict, arith: str = "f16x3") -> "MarsCNN":
-        three_d = np.asarray(w["conv1_w"]).ndim == 5
-        flat = np.asarray(w["dense1_w"]).shape[0]
-        frames = flat // (64 * 32) if three_d else 1
-        m = cls(frames if three_d else 1, arith)
-        f64 = {k: np.asarray(v, dtype=np.float64) for k, v in w.items()}
-        perm = (4, 3, 0, 1, 2) if three_d else (3, 2, 0, 1)
-        m.conv1.weight.copy_(torch.from_numpy(f64["conv1_w"].transpose(perm).copy()).float())
-        m.conv1.bias.copy_(torch.from_numpy(f64["conv1_b"]).float())
-        m.conv2.weight.copy_(torch.from_numpy(f64["conv2_w"].transpose(perm).copy()).float())
-        m.conv2.bias.copy_(torch.from_numpy(f64["conv2_b"]).float())
-        # BN1 (per channel c) folded into dense1, rows re-ordered (d,h,w,c) -> (c,d,h,w)
-        a1 = f64["bn1_gamma"] / np.sqrt(f64["bn1_var"] + BN_EPS)
-        c1 = f64["bn1_beta"] - a1 * f64["bn1_mean"]
-        spatial = flat // 32
-        w1 = f64["dense1_w"].reshape(spatial, 32, -1)            # [s, c, out]
-        b1 = f64["dense1_b"] + np.einsum("c,sco->o", c1, w1)
-        w1 = (w1 * a1[None, :, None]).transpose(1, 0, 2).reshape(flat, -1)  # [(c,s), out]
-        m.k_w1.copy_(torch.from_numpy(f64["conv1_w"].reshape(-1)).float())
-        m.k_b1.copy_(torch.from_numpy(f64["conv1_b"]).float())
-        m.k_w2.copy_(torch.from_numpy(f64["conv2_w"].reshape(-1)).float())
-        m.k_b2.copy_(torch.from_numpy(f64["conv2_b"]).float())
-        wk = (f64["dense1_w"].reshape(spatial, 32, -1) * a1[None, :, None]).reshape(flat, -1)  # Keras row order kept
-        m.dense1_dhwc.weight.copy_(torch.from_numpy(wk.T.copy()).float())
-        m.dense1_dhwc.bias.copy_(torch.from_numpy(b1).float())
-        w32 = torch.from_numpy(wk.copy()).float()                    # (K, N), what the fp32 GEMM multiplies with
-        m.d1_w2_t.copy_(interleave_split(w32.t().contiguous()))
+        f = fold_keras_weights(w)   # the one BatchNorm fold (fp64, rounded once): this model's tensors are copies and permutations of it
+        m = cls(f["frames"], arith)
+        d, t = m.dims, {k: torch.from_numpy(v) for k, v in f.items() if k != "frames"}
+        for n, cin in ((1, 5), (2, 16)):
+            w_, b_, conv = t[f"conv{n}_w"], t[f"conv{n}_b"], getattr(m, f"conv{n}")
+            getattr(m, f"k_w{n}").copy_(w_)
+            getattr(m, f"k_b{n}").copy_(b_)
+            # torch's layout for the CPU / arith="torch" path: Keras' (k..., in, out) -> (out, in, k...)
+            conv.weight.copy_(w_.reshape(d.kernel + (cin, -1)).permute(-1, -2, *range(len(d.kernel))))
+            conv.bias.copy_(b_)
+        w1 = t["dense1_w"]                                   # (hidden, flat), columns in Keras' (d,h,w,c) flatten order
+        m.dense1_dhwc.weight.copy_(w1)
+        m.d1_w2_t.copy_(interleave_split(w1))
+        # ... and in the channels-first (c,d,h,w) order torch's convolutions flatten to: the same elements, permuted
+        m.dense1.weight.copy_(w1.reshape(d.hidden, d.flat // 32, 32).transpose(1, 2).reshape(d.hidden, d.flat))
+        for lin in (m.dense1, m.dense1_dhwc):
+            lin.bias.copy_(t["dense1_b"])
+        m.dense2.weight.copy_(t["dense2_w"])
+        m.dense2.bias.copy_(t["dense2_b"])
         # fp16's range is the split arithmetic's: a folded weight outside it would become inf in its hi half
-        wmax = max(float(np.abs(f64[k]).max()) for k in ("conv1_w", "conv2_w", "conv1_b", "conv2_b"))
-        if m.arith == "f16x3" and max(wmax, float(w32.abs().max())) >= FP16_SAFE_MAX:
+        wmax = max(float(np.abs(f[k]).max()) for k in ("conv1_w", "conv2_w", "conv1_b", "conv2_b", "dense1_w"))
+        if m.arith == "f16x3" and wmax >= FP16_SAFE_MAX:
             m.arith = m.fp32_arith()
-            m.arith_fallback = (f"a weight of magnitude {max(wmax, float(w32.abs().max())):.3g} does not fit fp16: "
-                                + ("fp32 matrix cores instead" if m.arith == "f32" else "torch's fp32 kernels instead (the single-frame model has no fp32 HIP kernel)"))
-        m.dense1.weight.copy_(torch.from_numpy(w1.T.copy()).float())
-        m.dense1.bias.copy_(torch.from_numpy(b1).float())
-        a2 = f64["bn2_gamma"] / np.sqrt(f64["bn2_var"] + BN_EPS)
-        c2 = f64["bn2_beta"] - a2 * f64["bn2_mean"]
-        w2 = f64["dense2_w"]
-        m.dense2.weight.copy_(torch.from_numpy((w2 * a2[:, None]).T.copy()).float())
-        m.dense2.bias.copy_(torch.from_numpy(f64["dense2_b"] + c2 @ w2).float())
+            m.arith_fallback = (f"a weight of magnitude {wmax:.3g} does not fit fp16: "
+                                + ("fp32 matrix cores instead" if m.arith == "f32" else "torch's fp32 kernels instead (MarsCNN does not use the single-frame fp32 HIP kernel yet)"))
         return m
 
     @classmethod
@@ -161,15 +146,11 @@ class MarsCNN(nn.Module):
         return cls.from_h5(path) if path.lower().endswith((".h5", ".hdf5")) else cls.from_npz(path)
 
     def _hip_convs(self, x: torch.Tensor) -> torch.Tensor:
-        """Conv3D+ReLU twice in one HIP kernel on the fp32 matrix cores (mmw_mars_conv3d) -> (B, 6144) in (d,h,w,c) order."""
-        from . import _lib
-        L = _lib.load()
+        """Conv3D+ReLU twice in one HIP kernel on the fp32 matrix cores (mmw_mars_conv3d) -> (B, flat) in (d,h,w,c) order."""
         x = x.contiguous()
-        out = torch.empty((x.shape[0], 6144), dtype=torch.float32, device=x.device)
-        rc = L.mmw_mars_conv3d(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), self.k_w1.data_ptr(),
-                               self.k_b1.data_ptr(), self.k_w2.data_ptr(), self.k_b2.data_ptr(), out.data_ptr(), x.shape[0])
-        if rc != 0:
-            raise _lib.MmwError(rc, (L.mmw_last_error(None) or b"").decode())
+        out = torch.empty((x.shape[0], self.dims.flat), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().mmw_mars_conv3d(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), self.k_w1.data_ptr(),
+                                               self.k_b1.data_ptr(), self.k_w2.data_ptr(), self.k_b2.data_ptr(), out.data_ptr(), x.shape[0]))
         return out
 
     # the activation's row stride: 2 * flat values + 256: whole rows then start 24.25 / 8.25 KB apart instead of a multiple
@@ -178,13 +159,11 @@ class MarsCNN(nn.Module):
 
     def _hip_convs_split(self, x: torch.Tensor, sflags: torch.Tensor | None = None) -> torch.Tensor:
         """The conv pair on the fp16 matrix cores with split operands (mmw_mars_conv_split), the activation already split
-        for Dense-1: (B, 2 * flat) fp16, halves interleaved in runs of 32 (interleave_split), flat = frames * 2048 in (d,h,w,c)
-        order.  The result is a VIEW: its rows are 2 * flat + ROW_PAD apart and the storage holds whole 256-row tiles (the rows
-        past B are never written: Dense-1's kernel reads them, into rows nobody reads)."""
-        from . import _lib
-        L = _lib.load()
+        for Dense-1: (B, 2 * flat) fp16, halves interleaved in runs of 32 (interleave_split), flat = model_dims(frames).flat in
+        (d,h,w,c) order.  The result is a VIEW: its rows are 2 * flat + ROW_PAD apart and the storage holds whole 256-row tiles (the
+        rows past B are never written: Dense-1's kernel reads them, into rows nobody reads)."""
         x = x.contiguous()
-        flat = self.frames * 2048
+        flat = self.dims.flat
         rows = (x.shape[0] + 255) // 256 * 256
         ld = 2 * flat + self.ROW_PAD
         out = torch.empty((rows, ld), dtype=torch.float16, device=x.device)
@@ -196,18 +175,14 @@ class MarsCNN(nn.Module):
             if self._sflags is None or self._sflags.device != x.device:
                 self._sflags = torch.zeros((2 + RANGE_FIXUP_CAP,), dtype=torch.int32, device=x.device)
             sflags = self._sflags.data_ptr()
-        rc = L.mmw_mars_conv_split(torch.cuda.current_stream(x.device).cuda_stream, self.frames, x.data_ptr(), self.k_w1.data_ptr(),
-                                   self.k_b1.data_ptr(), self.k_w2.data_ptr(), self.k_b2.data_ptr(), out.data_ptr(), ld, x.shape[0],
-                                   self.range_flag.data_ptr(), sflags)
-        if rc != 0:
-            raise _lib.MmwError(rc, (L.mmw_last_error(None) or b"").decode())
+        _lib.check(_lib.load().mmw_mars_conv_split(torch.cuda.current_stream(x.device).cuda_stream, self.frames, x.data_ptr(), self.k_w1.data_ptr(),
+                                                   self.k_b1.data_ptr(), self.k_w2.data_ptr(), self.k_b2.data_ptr(), out.data_ptr(), ld, x.shape[0],
+                                                   self.range_flag.data_ptr(), sflags))
         return out[: x.shape[0], : 2 * flat]
 
     def _dense1_split(self, a2: torch.Tensor) -> torch.Tensor:
         """relu(bias + hi.W_hi + 2^-11 (hi.W_lo' + lo'.W_hi)) in one kernel (mmw_mars_dense1_split, csrc/k_dense.hip) on the view
         _hip_convs_split returns (any other (B, 2 flat) interleaved fp16 tensor is copied into a padded buffer first)."""
-        from . import _lib
-        L = _lib.load()
         B, k2 = a2.shape
         rows = (B + 255) // 256 * 256
         ld = a2.stride(0)
@@ -217,10 +192,8 @@ class MarsCNN(nn.Module):
             a2, ld = buf[:B, :k2], k2 + self.ROW_PAD
         n = self.d1_w2_t.shape[0]
         h = torch.empty((rows, n), dtype=torch.float32, device=a2.device)
-        rc = L.mmw_mars_dense1_split(torch.cuda.current_stream(a2.device).cuda_stream, a2.data_ptr(), ld, self.d1_w2_t.data_ptr(), k2,
-                                     self.dense1_dhwc.bias.data_ptr(), h.data_ptr(), rows, k2 // 2, n)
-        if rc != 0:
-            raise _lib.MmwError(rc, (L.mmw_last_error(None) or b"").decode())
+        _lib.check(_lib.load().mmw_mars_dense1_split(torch.cuda.current_stream(a2.device).cuda_stream, a2.data_ptr(), ld, self.d1_w2_t.data_ptr(), k2,
+                                                     self.dense1_dhwc.bias.data_ptr(), h.data_ptr(), rows, k2 // 2, n))
         return h[:B]
 
     def has_range_fixup(self) -> bool:
@@ -239,19 +212,16 @@ class MarsCNN(nn.Module):
             self._range_fixup(x, kp, sflags)
 
     def _range_fixup(self, x: torch.Tensor, kp: torch.Tensor, sflags: torch.Tensor | None = None):
-        """mmw_mars_range_fixup behind a split-arithmetic forward: the flagged samples' rows of kp recomputed in Keras' fp32 -- no host
-        wait; a batch without such samples pays four empty launches."""
-        from . import _lib
-        L = _lib.load()
+        """mmw_mars_range_fixup_frames behind a split-arithmetic forward: the flagged samples' rows of kp recomputed in Keras' fp32 -- no
+        host wait; a batch without such samples pays four empty launches."""
         if self._fix_scratch is None or self._fix_scratch.device != x.device:
             self._fix_scratch = torch.empty((RANGE_FIXUP_SCRATCH,), dtype=torch.uint8, device=x.device)
         w1 = self.dense1_dhwc.weight
-        rc = L.mmw_mars_range_fixup(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), (sflags if sflags is not None else self._sflags).data_ptr(), x.shape[0],
-                                    self.k_w1.data_ptr(), self.k_b1.data_ptr(), self.k_w2.data_ptr(), self.k_b2.data_ptr(), w1.data_ptr(), w1.stride(0),
-                                    self.dense1_dhwc.bias.data_ptr(), self.dense2.weight.data_ptr(), self.dense2.bias.data_ptr(),
-                                    self._fix_scratch.data_ptr(), kp.data_ptr(), self.range_flag.data_ptr())
-        if rc != 0:
-            raise _lib.MmwError(rc, (L.mmw_last_error(None) or b"").decode())
+        _lib.check(_lib.load().mmw_mars_range_fixup_frames(
+            torch.cuda.current_stream(x.device).cuda_stream, self.frames, x.data_ptr(), (sflags if sflags is not None else self._sflags).data_ptr(), x.shape[0],
+            self.k_w1.data_ptr(), self.k_b1.data_ptr(), self.k_w2.data_ptr(), self.k_b2.data_ptr(), w1.data_ptr(), w1.stride(0),
+            self.dense1_dhwc.bias.data_ptr(), self.dense2.weight.data_ptr(), self.dense2.bias.data_ptr(),
+            self._fix_scratch.data_ptr(), kp.data_ptr(), self.range_flag.data_ptr()))
 
     SMALL_BATCH = 64   # mmw_mars_head_small's limit
 
@@ -262,28 +232,24 @@ class MarsCNN(nn.Module):
         """A handful of samples (one scene's tracks: the drop-in's estimate_posture): the fp32 conv kernel (mmw_mars_conv3d) and
         the thin Dense-1 / Dense-2 kernels of mmw_mars_head_small -- Keras' own fp32 arithmetic, the weight matrix cut over the
         whole chip instead of one band of tiles (~100 us less for 2 rows), no fp16 range to watch.  3-frame model, B <= 64."""
-        from . import _lib
         if not (x.is_cuda and x.dtype == torch.float32 and self.use_hip_conv_f32 and x.shape[0] <= self.SMALL_BATCH):
             raise ValueError("MarsCNN.forward_small: a CUDA fp32 batch of at most 64 samples of the 3-frame model")
-        L = _lib.load()
         with torch.cuda.device(x.device):
             act = self._hip_convs(x)
             B = act.shape[0]
             w1 = self.dense1_dhwc.weight
             hidden = torch.empty((B, w1.shape[0]), dtype=torch.float32, device=x.device)
             kp = torch.empty((B, N_KEYPOINTS), dtype=torch.float32, device=x.device)
-            rc = L.mmw_mars_head_small(torch.cuda.current_stream(x.device).cuda_stream, act.data_ptr(), act.stride(0), w1.data_ptr(), w1.stride(0),
-                                       self.dense1_dhwc.bias.data_ptr(), self.dense2.weight.data_ptr(), self.dense2.bias.data_ptr(),
-                                       hidden.data_ptr(), kp.data_ptr(), B, w1.shape[1], w1.shape[0])
-            if rc != 0:
-                raise _lib.MmwError(rc, (L.mmw_last_error(None) or b"").decode())
+            _lib.check(_lib.load().mmw_mars_head_small(torch.cuda.current_stream(x.device).cuda_stream, act.data_ptr(), act.stride(0), w1.data_ptr(), w1.stride(0),
+                                                       self.dense1_dhwc.bias.data_ptr(), self.dense2.weight.data_ptr(), self.dense2.bias.data_ptr(),
+                                                       hidden.data_ptr(), kp.data_ptr(), B, w1.shape[1], w1.shape[0]))
         return kp
 
     def range_overflow(self, clear: bool = True) -> bool:
         """True when a split-arithmetic forward since the last call left some sample's keypoints MEANINGLESS: an input or
         activation outside fp16's range that was not repaired.  The 3-frame model repairs such samples itself (forward():
         mmw_mars_range_fixup recomputes them in fp32 on the device), so for it this only reports a batch with more than 64 of
-        them; the single-frame model has no fp32 kernel and reports every one.  `range_recomputed` says how often the repair
+        them; for the single-frame model MarsCNN does not use the library's fp32 kernel yet and reports every one.  `range_recomputed` says how often the repair
         ran.  Reads one device word: synchronises."""
         word = int(self.range_flag.item())
         if word and clear:
@@ -294,7 +260,8 @@ class MarsCNN(nn.Module):
 
     def fp32_arith(self) -> str:
         """What replaces the split arithmetic where it cannot be used (weights / activations beyond fp16's range): the fp32
-        matrix-core kernel for the 3-frame model, torch's fp32 kernels for the single-frame one (no fp32 HIP kernel exists)."""
+        matrix-core kernel for the 3-frame model, torch's fp32 kernels for the single-frame one (MarsCNN does not use its fp32 HIP kernel, k_mars2d.hip,
+        yet)."""
         return "f32" if self.use_hip_conv_f32 else "torch"
 
     def forward(self, x: torch.Tensor, arith: str | None = None, fixup: bool = True, sflags: torch.Tensor | None = None,
@@ -310,7 +277,7 @@ class MarsCNN(nn.Module):
                 raise TypeError(f"MarsCNN: the HIP kernels take fp32 feature tensors (what mmw_features writes), got {x.dtype}; "
                                 "convert the batch, or ask for torch's kernels with arith='torch'")
             if arith == "f32" and not self.use_hip_conv_f32:
-                raise ValueError("MarsCNN: the single-frame model has no fp32 HIP kernel; arith='f16x3' (default) runs k_mars_conv16, "
+                raise ValueError("MarsCNN does not use the single-frame model's fp32 HIP kernel yet; arith='f16x3' (default) runs k_mars_conv16, "
                                  "arith='torch' torch's convolutions")
             with torch.cuda.device(x.device):
                 if arith == "f16x3":

@@ -33,9 +33,7 @@ def inspect(blob) -> dict:
     L = _lib.load()
     info = _lib.MmwSnapshotInfo()
     buf = C.create_string_buffer(b, len(b))
-    rc = L.mmw_snapshot_inspect(buf, len(b), C.byref(info))
-    if rc != 0:
-        raise _lib.error_for(rc, (L.mmw_last_error(None) or b"").decode())
+    _lib.check(L.mmw_snapshot_inspect(buf, len(b), C.byref(info)))
     h = info.header
     head = {name: getattr(h, name) for name, _ in _lib.MmwSnapshotHeader._fields_ if name != "config"}
     cfg = {}

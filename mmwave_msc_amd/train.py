@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .mars import BN_EPS, N_KEYPOINTS, MarsCNN
+from .mars import BN_EPS, N_KEYPOINTS, MarsCNN, model_dims
 
 BATCH_SIZE = 128   # train.py:29
 EPOCHS = 150       # train.py:30
@@ -64,17 +64,16 @@ class MarsTrainNet(nn.Module):
 
     def __init__(self, frames: int = 3, n_keypoints: int = N_KEYPOINTS):
         super().__init__()
-        self.frames = int(frames)
-        self.three_d = self.frames > 1
+        d = model_dims(frames)
+        self.frames = d.frames
+        self.three_d = len(d.kernel) == 3
         conv = nn.Conv3d if self.three_d else nn.Conv2d
         self.conv1 = conv(5, 16, 3, padding=1)
         self.conv2 = conv(16, 32, 3, padding=1)
         self.bn1 = KerasBatchNorm(32, BN_EPS, 0.95)          # train.py:45,83
-        flat = (self.frames if self.three_d else 1) * 64 * 32
-        hidden = 512 * (3 if self.three_d else 1)
-        self.dense1 = nn.Linear(flat, hidden)
-        self.bn2 = KerasBatchNorm(hidden, BN_EPS, 0.95)
-        self.dense2 = nn.Linear(hidden, n_keypoints)
+        self.dense1 = nn.Linear(d.flat, d.hidden)
+        self.bn2 = KerasBatchNorm(d.hidden, BN_EPS, 0.95)
+        self.dense2 = nn.Linear(d.hidden, n_keypoints)
         for m in (self.conv1, self.conv2, self.dense1, self.dense2):  # Keras defaults: glorot_uniform, zeros
             nn.init.xavier_uniform_(m.weight)
             nn.init.zeros_(m.bias)

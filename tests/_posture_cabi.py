@@ -6,6 +6,9 @@ import numpy as np
 KW = dict(tr_max_tracks=4, tr_lifetime_dynamic=0.25, tr_lifetime_static=0.25)   # short lifetimes: tracks expire inside 12 frames
 F_STEPS, N_PTS = 12, 128
 MARK = 12345.0
+# what oracle_run gives on scenario(48) at FB_FRAMES_BATCH = 0 (the single-frame model), pinned: eligible tracks per frame, scenes
+# tracked by frame 4, scene-frames in which a track expired, surviving CNN samples
+SINGLE_FRAME_48 = dict(rows=[64, 70, 71, 72, 72, 96, 96, 72, 72, 72, 72, 72], tracked_by_4=48, expired=16, samples_cnn=72)
 
 
 def scenario(S, seed=5000, F=F_STEPS, N=N_PTS):

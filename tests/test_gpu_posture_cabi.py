@@ -1,5 +1,7 @@
-"""GPU tests of the batched estimate_posture behind the C-ABI (include/mmw.h: mmw_posture_attach, mmw_estimate_posture,
-mmw_posture_range) and of its two kernels (mmw_mars_dense2, mmw_mars_split_weights; csrc/k_dense2.hip).
+"""GPU tests of the batched estimate_posture behind the C-ABI (include/mmw.h: mmw_posture_attach / mmw_posture_attach_frames,
+mmw_estimate_posture, mmw_posture_range) for both models -- the 3-frame define_CNN_3D and the single-frame define_CNN, one test body
+per assertion, parametrised over `frames` -- and of its two kernels (mmw_mars_dense2, mmw_mars_split_weights; csrc/k_dense2.hip).
+What exists for the single-frame model only is in test_gpu_posture_single_frame.py.
 
 Tolerances are the project's: keypoints within 1e-4 * max(1, |want|) of the fp64 oracle, tracker state bit
 for bit.  Dense-2 is additionally held against the kernel it stands in for (torch.addmm, MarsCNN's call) in the form the Dense-1
@@ -11,20 +13,9 @@ import pytest
 
 from tests import _posture_cabi as pc
 from tests._layouts import make_checked
+from tests._posture_gpu import CANARY, KP_TOL, KW, N, CModel, _live, _step, _stream, _weights, attach_batch
 
 pytestmark = pytest.mark.gpu
-KP_TOL = 1e-4
-N = pc.N_PTS
-
-
-def _weights(seed=0):
-    from mmwave_msc_amd.marsweights import random_keras_weights
-    return random_keras_weights(seed, 3)
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream or None
 
 
 # ---- 1. k_split_weights ------------------------------------------------------------------------------------------------------
@@ -47,7 +38,7 @@ def test_split_weights_equals_interleave_split_bit_for_bit():
     import torch
     from mmwave_msc_amd.mars import interleave_split
     from mmwave_msc_amd.marsweights import fold_keras_weights
-    w32 = torch.from_numpy(fold_keras_weights(_weights(3))["dense1_w"])
+    w32 = torch.from_numpy(fold_keras_weights(_weights(3, 3))["dense1_w"])
     assert tuple(w32.shape) == (1536, 6144)
     got, flag = _split_on_device(w32)
     assert flag == 0
@@ -75,12 +66,11 @@ def test_dense2_against_fp64_and_addmm(n):
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.marsweights import fold_keras_weights
     L = _lib.load()
-    f = fold_keras_weights(_weights(5))
+    f = fold_keras_weights(_weights(5, 3))
     dev = torch.device("cuda", 0)
     w2, b2 = torch.from_numpy(f["dense2_w"]).to(dev), torch.from_numpy(f["dense2_b"]).to(dev)
     g = torch.Generator(device="cpu").manual_seed(100 + n)
     hidden = torch.relu(torch.randn((n, 1536), generator=g) * 1.5 + 0.3).to(dev)   # what Dense-1's relu leaves: about 40 % zeros
-    CANARY = -777.25
     pad = 300   # canary rows behind the batch: a 128-row tile and more
 
     def run(h):
@@ -125,53 +115,37 @@ def test_dense2_against_fp64_and_addmm(n):
 
 
 # ---- 3. + 4. end to end through the C entries, against the oracle and against PosturePipeline ----------------------------------
-class CModel:
-    """The weights of struct mmw_posture_model in device memory of a context, uploaded through mmw_dev_alloc / mmw_memcpy_h2d."""
-
-    def __init__(self, sb, weights, **replace):
-        from mmwave_msc_amd import _lib
-        from mmwave_msc_amd.batch import DevBuf
-        from mmwave_msc_amd.marsweights import fold_keras_weights
-        f = dict(fold_keras_weights(weights), **replace)
-        keys = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "dense1_w", "dense1_b", "dense2_w", "dense2_b")
-        self.bufs = {k: DevBuf(sb, f[k].nbytes).upload(f[k]) for k in keys}
-        b = self.bufs
-        self.struct = _lib.MmwPostureModel(b["conv1_w"].ptr, b["conv1_b"].ptr, b["conv2_w"].ptr, b["conv2_b"].ptr, b["dense1_w"].ptr, 6144,
-                                           b["dense1_b"].ptr, b["dense2_w"].ptr, b["dense2_b"].ptr)
-
-    def free(self):
-        for b in self.bufs.values():
-            b.free()
+PINNED = {(1, 48): pc.SINGLE_FRAME_48}   # (frames, S) -> what the oracle run is known to give
+_REF = {}
 
 
-def _step(sb, pts_f, cnt_f, dt_f):
-    S = sb.S
-    b_p = sb.buf("pc_pts", S * N * 64).upload(pts_f)
-    b_n = sb.buf("pc_n", S * 4).upload(cnt_f)
-    b_d = sb.buf("pc_dt", S * 8).upload(dt_f)
-    sb.step_dev(b_p.ptr, b_n.ptr, b_d.ptr)
+def _ref(frames, S):
+    """scenario(S) and its oracle run for the model of `frames` frames, computed once for the cases that follow one another and
+    never changed (one slot: the 640-scene run is not kept)."""
+    if (frames, S) not in _REF:
+        _REF.clear()
+        pts, cnt, dts = pc.scenario(S)
+        w = _weights(0, frames)
+        _REF[frames, S] = dict(pts=pts, cnt=cnt, dts=dts, w=w, ref=pc.oracle_run(pts, cnt, dts, w, cfg_kw=KW[frames]))
+    return _REF[frames, S]
 
 
-def _live(sb):
-    sb.check()
-    ntr = sb.num_tracks()
-    return ntr, sb.tracks(cap=max(int(ntr.max()), 1))
-
-
-@pytest.mark.parametrize("S,layout", [(48, "one_workgroup"), (640, "track_wise")])
-def test_estimate_posture_through_the_c_entries_vs_oracle_and_pipeline(S, layout):
-    from mmwave_msc_amd import _lib
-    pts, cnt, dts = pc.scenario(S)
+@pytest.mark.parametrize("frames,S,layout", [(3, 48, "one_workgroup"), (3, 640, "track_wise"), (1, 48, "one_workgroup"), (1, 48, "per_scene")],
+                         ids=["48-one_workgroup", "640-track_wise", "single_frame-48-one_workgroup", "single_frame-48-per_scene"])
+def test_estimate_posture_through_the_c_entries_vs_oracle_and_pipeline(frames, S, layout):
+    from mmwave_msc_amd.marsweights import model_dims
+    r = _ref(frames, S)
+    pts, cnt, dts, w, ref = r["pts"], r["cnt"], r["dts"], r["w"], r["ref"]
     F = cnt.shape[0]
-    w = _weights(0)
-    ref = pc.oracle_run(pts, cnt, dts, w)
     assert 3 * ref["tracked_by_4"] >= S and ref["expired"] >= 1
+    for name, value in PINNED.get((frames, S), {}).items():
+        assert ref[name] == value, name
     # -- the C entries only: ctypes, mmw_dev_alloc / mmw_memcpy_*, no torch tensor on the path
-    sb = make_checked(S, N, layout, **pc.KW)
-    assert sb.step_kind() == (1 if layout == "one_workgroup" else 4)
-    L, model = sb.L, None
+    sb = make_checked(S, N, layout, **KW[frames])
+    assert sb.ring == frames and (sb.step_kind() == 1) == (layout == "one_workgroup") and (sb.step_kind() == 4 or layout != "track_wise")
+    L = sb.L
     model = CModel(sb, w)
-    assert L.mmw_posture_attach(sb.h, C.byref(model.struct), S * sb.track_cap) == 0, L.mmw_last_error(sb.h)
+    assert attach_batch(sb, frames, model.struct, S * sb.track_cap) == 0, L.mmw_last_error(sb.h)
     for f in range(F):
         _step(sb, pts[f], cnt[f], dts[f])
         rows = C.c_int32(-1)
@@ -188,7 +162,7 @@ def test_estimate_posture_through_the_c_entries_vs_oracle_and_pipeline(S, layout
             assert np.array_equal(got[name], want[name]), (s, name)
         worst = max(worst, pc.kp_err(got["keypoints"], ref["want_kp"][s]))
         checked += len(want)
-    print(f"C entries, {S} scenes: {checked} tracks, keypoint error {worst:.3e}")
+    print(f"C entries, {frames}-frame model, {S} scenes, {layout}: {checked} tracks, keypoint error {worst:.3e}")
     assert checked == ref["samples_cnn"] >= S // 3
     assert worst <= KP_TOL, worst
     feat_c, owner_c = sb.features_host()
@@ -196,8 +170,9 @@ def test_estimate_posture_through_the_c_entries_vs_oracle_and_pipeline(S, layout
     import torch
     from mmwave_msc_amd.mars import MarsCNN
     from mmwave_msc_amd.posture import PosturePipeline
-    twin = make_checked(S, N, layout, **pc.KW)
+    twin = make_checked(S, N, layout, **KW[frames])
     cnn = MarsCNN.from_keras_weights(w).to("cuda:0")
+    assert cnn.frames == frames
     pipe = PosturePipeline(twin, cnn, S * twin.track_cap, overlap=False)
     for f in range(F):
         _step(twin, pts[f], cnt[f], dts[f])
@@ -216,8 +191,8 @@ def test_estimate_posture_through_the_c_entries_vs_oracle_and_pipeline(S, layout
     assert between <= KP_TOL, between
     feat_p, owner_p = twin.features_host()
     assert np.array_equal(owner_c, owner_p) and np.array_equal(owner_c, ref["owners"][F - 1])
-    assert feat_c.tobytes() == feat_p.tobytes() and feat_c.shape[0] == ref["rows"][F - 1]
-    assert L.mmw_posture_attach(sb.h, None, 0) == 0
+    assert feat_c.shape == (ref["rows"][F - 1],) + model_dims(frames).input and feat_c.tobytes() == feat_p.tobytes()
+    assert attach_batch(sb, frames, None, 0) == 0
     model.free()
     twin.close()
     sb.close()
@@ -225,22 +200,37 @@ def test_estimate_posture_through_the_c_entries_vs_oracle_and_pipeline(S, layout
 
 
 # ---- 5. range ----------------------------------------------------------------------------------------------------------------
-def test_out_of_range_sample_is_repaired_and_bad_weights_are_refused():
-    """The intensities of the last frame of a one-person scene scaled by 1e5 push ONE feature tensor of the last call out of fp16's
-    range: the device-side fp32 repair recomputes that sample (bit 0 of the range word, read once), its keypoints -- and everybody
-    else's -- stay within 1e-4 of the fp64 oracle.  A model with a BatchNorm-folded Dense-1 row of 3e6, or a conv bias that is not
-    finite, is refused with MMW_E_ARG and the context goes on stepping."""
-    from mmwave_msc_amd import _lib
+def _outside_fp16(w):
+    """Two sets of folded-tensor replacements for CModel that the batched chain must refuse: a BatchNorm-folded Dense-1 row of
+    3e6, and a conv bias that is not finite."""
     from mmwave_msc_amd.marsweights import fold_keras_weights
+    f32 = fold_keras_weights(w)
+    d1 = f32["dense1_w"].copy()
+    d1[100] *= np.float32(3e6 / np.abs(d1[100]).max())
+    cb = f32["conv2_b"].copy()
+    cb[3] = np.float32("inf")
+    return dict(dense1_w=d1), dict(conv2_b=cb)
+
+
+# (the largest keypoint the oracle gives the repaired sample: both far outside fp16's range; the single-frame model's is pinned)
+@pytest.mark.parametrize("frames,hot_kp", [(3, (1e3, np.inf)), (1, (1.3e5, 1.5e5))], ids=["3", "1"])
+def test_out_of_range_sample_is_repaired_and_bad_weights_are_refused(frames, hot_kp):
+    """The intensities of the last frame of a one-person scene scaled by 1e5 push ONE feature tensor of the last call out of fp16's
+    range: the device-side fp32 repair (k_mars_conv / k_mars_conv2d) recomputes that sample (bit 0 of the range word, read once),
+    its keypoints -- and everybody else's -- stay within 1e-4 of the fp64 oracle.  A model with a BatchNorm-folded Dense-1 row of
+    3e6, or a conv bias that is not finite, is refused with MMW_E_ARG and the context goes on stepping."""
+    from mmwave_msc_amd import _lib
     S, HOT = 16, 2
     pts, cnt, dts = pc.scenario(S, seed=6100)
     F = cnt.shape[0]
     pts[F - 1, HOT, :, 7] *= 1e5   # peakVal: (1e5 * 30 - mu) / std leaves 65 504 far behind; the tracker does not read the column
-    w = _weights(2)
-    ref = pc.oracle_run(pts, cnt, dts, w)
+    w = _weights(2, frames)
+    ref = pc.oracle_run(pts, cnt, dts, w, cfg_kw=KW[frames])
     hot = [int((np.abs(f.reshape(len(f), -1)).max(axis=1) >= 65504.0).sum()) if len(f) else 0 for f in ref["feats"]]
     assert hot == [0] * (F - 1) + [1], hot
-    sb = make_checked(S, N, "per_scene", **pc.KW)
+    largest = float(np.abs(ref["want_kp"][HOT]).max()) if len(ref["want_kp"][HOT]) else 0.0
+    assert hot_kp[0] < largest < hot_kp[1], largest
+    sb = make_checked(S, N, "per_scene", **KW[frames])
     sb.attach_posture_batch(w, S * sb.track_cap)
     for f in range(F):
         if f == F - 1:
@@ -255,20 +245,14 @@ def test_out_of_range_sample_is_repaired_and_bad_weights_are_refused():
         assert len(ref["finals"][s]) == int(ntr[s])
         e = pc.kp_err(trk[s, : ntr[s]]["keypoints"], ref["want_kp"][s])
         worst, worst_hot = max(worst, e), (e if s == HOT else worst_hot)
-    print(f"range: keypoint error {worst:.3e} over all tracks, {worst_hot:.3e} for the repaired sample")
-    assert int(ntr[HOT]) >= 1 and float(np.abs(ref["want_kp"][HOT]).max()) > 1e3 and worst <= KP_TOL, (worst, worst_hot)
+    print(f"range, {frames}-frame model: keypoint error {worst:.3e} over all tracks, {worst_hot:.3e} for the repaired sample")
+    assert int(ntr[HOT]) >= 1 and worst <= KP_TOL, (worst, worst_hot)
     # weights outside fp16's range: refused, loudly, and nothing changes
     before = trk.tobytes()
-    f32 = fold_keras_weights(w)
-    d1 = f32["dense1_w"].copy()
-    d1[100] *= np.float32(3e6 / np.abs(d1[100]).max())
-    bad = CModel(sb, w, dense1_w=d1)
-    assert sb.L.mmw_posture_attach(sb.h, C.byref(bad.struct), 64) == _lib.E_ARG
+    bad, bad2 = (CModel(sb, w, **rep) for rep in _outside_fp16(w))
+    assert attach_batch(sb, frames, bad.struct, 64) == _lib.E_ARG
     assert b"fp16" in sb.L.mmw_last_error(sb.h)
-    cb = f32["conv2_b"].copy()
-    cb[3] = np.float32("inf")
-    bad2 = CModel(sb, w, conv2_b=cb)
-    assert sb.L.mmw_posture_attach(sb.h, C.byref(bad2.struct), 64) == _lib.E_ARG
+    assert attach_batch(sb, frames, bad2.struct, 64) == _lib.E_ARG
     assert _live(sb)[1].tobytes() == before
     _step(sb, pts[F - 1], cnt[F - 1], dts[F - 1])          # the context still steps, and the earlier model is still attached
     assert sb.estimate_posture() >= 1
@@ -278,52 +262,52 @@ def test_out_of_range_sample_is_repaired_and_bad_weights_are_refused():
 
 
 # ---- 6. refusals, capacity, detach, sites ------------------------------------------------------------------------------------
-def test_refusals_capacity_and_detach():
+@pytest.mark.parametrize("frames,null_field,short_ld", [(3, "dense2_b", 6142), (1, "conv2_w", 2044)], ids=["3", "1"])
+def test_refusals_capacity_and_detach(frames, null_field, short_ld):
     from mmwave_msc_amd import _lib
-    from mmwave_msc_amd.batch import SceneBatch
     S = 16
     pts, cnt, dts = pc.scenario(S, seed=6300)
-    w = _weights(1)
-    sb = make_checked(S, N, "per_scene", **pc.KW)
+    w = _weights(1, frames)
+    sb = make_checked(S, N, "per_scene", **KW[frames])
     L = sb.L
     rows, word = C.c_int32(5), C.c_int32(5)
     assert L.mmw_estimate_posture(sb.h, C.byref(rows)) == _lib.E_ARG and rows.value == 0      # no model
     assert L.mmw_posture_range(sb.h, C.byref(word)) == _lib.E_ARG
     model = CModel(sb, w)
-    assert L.mmw_posture_attach(sb.h, C.byref(model.struct), 0) == _lib.E_ARG                  # cap_rows < 1
+    assert attach_batch(sb, frames, model.struct, 0) == _lib.E_ARG                             # cap_rows < 1
     null = _lib.MmwPostureModel.from_buffer_copy(model.struct)
-    null.dense2_b = None
-    assert L.mmw_posture_attach(sb.h, C.byref(null), 64) == _lib.E_ARG                         # a null pointer
+    setattr(null, null_field, None)
+    assert attach_batch(sb, frames, null, 64) == _lib.E_ARG                                    # a null pointer
     off = _lib.MmwPostureModel.from_buffer_copy(model.struct)
-    off.dense1_ld = 6142
-    assert L.mmw_posture_attach(sb.h, C.byref(off), 64) == _lib.E_ARG                          # dense1_ld
+    off.dense1_ld = short_ld
+    assert attach_batch(sb, frames, off, 64) == _lib.E_ARG                                     # dense1_ld
+    for rep in _outside_fp16(w):                                                               # weights outside fp16's range
+        bad = CModel(sb, w, **rep)
+        assert attach_batch(sb, frames, bad.struct, 64) == _lib.E_ARG and b"fp16" in L.mmw_last_error(sb.h)
+        bad.free()
     assert L.mmw_estimate_posture(sb.h, None) == _lib.E_ARG                                    # ... none of them attached anything
-    single = SceneBatch(_lib.default_config(fb_frames_batch=0, **pc.KW), 4, N)
-    sm = CModel(single, w)
-    assert single.L.mmw_posture_attach(single.h, C.byref(sm.struct), 64) == _lib.E_ARG         # FB_FRAMES_BATCH = 0
-    assert b"FB_FRAMES_BATCH" in single.L.mmw_last_error(single.h)
-    sm.free(); single.close()
     # capacity: one row short of the eligible tracks
-    for f in range(6):
+    for f in range(6):                                                                         # (and the context still steps)
         _step(sb, pts[f], cnt[f], dts[f])
+    sb.check()
     feat, owner = sb.features_host()
     eligible = len(owner)
     assert eligible >= 8
-    assert L.mmw_posture_attach(sb.h, C.byref(model.struct), eligible) == 0, L.mmw_last_error(sb.h)
+    assert attach_batch(sb, frames, model.struct, eligible) == 0, L.mmw_last_error(sb.h)
     assert L.mmw_estimate_posture(sb.h, C.byref(rows)) == 0 and rows.value == eligible
     _, before = _live(sb)
     _step(sb, pts[6], cnt[6], dts[6])
     eligible = len(sb.features_host()[1])
     _, stepped = _live(sb)
-    assert L.mmw_posture_attach(sb.h, C.byref(model.struct), eligible - 1) == 0
+    assert attach_batch(sb, frames, model.struct, eligible - 1) == 0
     assert L.mmw_estimate_posture(sb.h, C.byref(rows)) == _lib.E_CAPACITY and rows.value == 0
     assert b"cap_rows" in L.mmw_last_error(sb.h)
     assert sb.tracks(cap=stepped.shape[1]).tobytes() == stepped.tobytes(), "a keypoint changed in a refused call"
     assert stepped["keypoints"].tobytes() != np.zeros_like(stepped["keypoints"]).tobytes() and before.shape[0] == S
     # detach, then MMW_E_ARG again
-    assert L.mmw_posture_attach(sb.h, None, 0) == 0
+    assert attach_batch(sb, frames, None, 0) == 0
     assert L.mmw_estimate_posture(sb.h, C.byref(rows)) == _lib.E_ARG
-    assert L.mmw_posture_attach(sb.h, None, 0) == 0   # (detaching twice is fine)
+    assert attach_batch(sb, frames, None, 0) == 0   # (detaching twice is fine)
     model.free()
     sb.close()
 
@@ -336,7 +320,7 @@ def test_mixed_sites_give_each_scene_the_keypoints_of_its_uniform_context():
     from tests.test_gpu_sites import KW, SITES, _inputs, _site_rows
     S, F = 12, 10
     raw, cnt, dts, which = _inputs(S, 256, F, seed=2500)
-    w = _weights(4)
+    w = _weights(4, 3)
 
     def run(sb):
         sb.attach_posture_batch(w, S * sb.track_cap)

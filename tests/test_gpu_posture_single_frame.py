@@ -1,7 +1,8 @@
 """GPU tests of the single-frame posture model (define_CNN, train.py:33-68) behind the C-ABI: the fp32 Conv2D pair
-(mmw_mars_conv2d; csrc/k_mars2d.hip), Dense-2 at k = 512, the range repair (mmw_mars_range_fixup_frames), the batched chain
-(mmw_posture_attach_frames / mmw_estimate_posture / mmw_posture_range) and the one-scene chain (mmw_attach_posture_frames /
-mmw_frame_posture_host) on contexts with FB_FRAMES_BATCH = 0.
+(mmw_mars_conv2d; csrc/k_mars2d.hip), Dense-2 at k = 512, the range repair (mmw_mars_range_fixup_frames), the `frames` argument of
+mmw_posture_attach_frames and the one-scene chain (mmw_attach_posture_frames / mmw_frame_posture_host) on contexts with
+FB_FRAMES_BATCH = 0.  The batched chain itself (mmw_posture_attach_frames / mmw_estimate_posture / mmw_posture_range) is tested
+for both models in test_gpu_posture_cabi.py.
 
 Tolerances are the project's: conv activations within 1e-4 of the fp64 _conv_same (test_hip_convs_match_torch_and_oracle),
 keypoints within 1e-4 * max(1, |want|) of oracle/mars_np.py (tests/_posture_cabi.kp_err), the range repair within 1e-4 of the
@@ -14,28 +15,10 @@ import pytest
 
 from tests import _posture_cabi as pc
 from tests._layouts import make_checked
+from tests._posture_gpu import CANARY, KP_TOL, KW, N, CModel, _dev, _live, _step, _stream, _weights
 
 pytestmark = pytest.mark.gpu
-KP_TOL = 1e-4
-N = pc.N_PTS
-KW1 = dict(pc.KW, fb_frames_batch=0)
-ROWS_48 = [64, 70, 71, 72, 72, 96, 96, 72, 72, 72, 72, 72]
-CANARY = -777.25
-
-
-def _weights(seed, frames=1):
-    from mmwave_msc_amd.marsweights import random_keras_weights
-    return random_keras_weights(seed, frames)
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream or None
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+KW1 = KW[1]
 
 
 # ---- 1. k_mars_conv2d ----------------------------------------------------------------------------------------------------------
@@ -45,7 +28,7 @@ def test_conv2d_against_fp64_and_torch(batch):
     from mmwave_msc_amd import _lib
     from oracle.mars_np import _conv_same
     L = _lib.load()
-    w = _weights(11)
+    w = _weights(11, 1)
     rng = np.random.default_rng(batch)
     x = rng.normal(0, 0.5, size=(batch, 8, 8, 5)).astype(np.float32)
     x[:, 6:, :, :] = 0.0   # zero-padded rows as real feature maps have
@@ -100,7 +83,7 @@ def test_dense2_at_k_512_against_fp64_and_addmm(n):
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.marsweights import fold_keras_weights
     L = _lib.load()
-    f = fold_keras_weights(_weights(5))
+    f = fold_keras_weights(_weights(5, 1))
     assert f["dense2_w"].shape == (57, 512)
     dev = torch.device("cuda", 0)
     w2, b2 = torch.from_numpy(f["dense2_w"]).to(dev), torch.from_numpy(f["dense2_b"]).to(dev)
@@ -150,17 +133,17 @@ def test_range_fixup_single_frame_rewrites_exactly_the_flagged_rows(hot):
     keeps the canary, the list is emptied; 70 flagged samples raise bit 1 and exactly 64 of them are rewritten."""
     import torch
     from mmwave_msc_amd import _lib
-    from mmwave_msc_amd.marsweights import fold_keras_weights
+    from mmwave_msc_amd.marsweights import FOLDED_KEYS, fold_keras_weights
     from oracle.mars_np import mars_forward_np
     L = _lib.load()
     n = 200
-    w = _weights(3)
+    w = _weights(3, 1)
     f = fold_keras_weights(w)
     rng = np.random.default_rng(17)
     feat = rng.normal(0, 0.5, size=(n, 8, 8, 5)).astype(np.float32)
     feat[list(hot)] *= np.float32(1e5)
     want = mars_forward_np(w, feat[list(hot)].astype(np.float64))
-    d = {k: _dev(f[k]) for k in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "dense1_w", "dense1_b", "dense2_w", "dense2_b")}
+    d = {k: _dev(f[k]) for k in FOLDED_KEYS}
     x = _dev(feat)
     ld = 2 * 2048 + 256
     act16 = torch.zeros((256, ld), dtype=torch.float16, device="cuda")
@@ -198,161 +181,15 @@ def test_range_fixup_single_frame_rewrites_exactly_the_flagged_rows(hot):
     assert err <= 1e-4 and float(np.abs(want).max()) > 1e3, err
 
 
-# ---- 4. - 6. the batched chain through the C entries ---------------------------------------------------------------------------
-class CModel:
-    """The weights of struct mmw_posture_model in device memory of a context, uploaded through mmw_dev_alloc / mmw_memcpy_h2d."""
-
-    def __init__(self, sb, weights, **replace):
-        from mmwave_msc_amd import _lib
-        from mmwave_msc_amd.batch import DevBuf
-        from mmwave_msc_amd.marsweights import fold_keras_weights
-        f = dict(fold_keras_weights(weights), **replace)
-        keys = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "dense1_w", "dense1_b", "dense2_w", "dense2_b")
-        self.bufs = {k: DevBuf(sb, f[k].nbytes).upload(f[k]) for k in keys}
-        b = self.bufs
-        self.struct = _lib.MmwPostureModel(b["conv1_w"].ptr, b["conv1_b"].ptr, b["conv2_w"].ptr, b["conv2_b"].ptr, b["dense1_w"].ptr,
-                                           f["dense1_w"].shape[1], b["dense1_b"].ptr, b["dense2_w"].ptr, b["dense2_b"].ptr)
-
-    def free(self):
-        for b in self.bufs.values():
-            b.free()
-
-
-def _step(sb, pts_f, cnt_f, dt_f):
-    S = sb.S
-    b_p = sb.buf("pc_pts", S * N * 64).upload(pts_f)
-    b_n = sb.buf("pc_n", S * 4).upload(cnt_f)
-    b_d = sb.buf("pc_dt", S * 8).upload(dt_f)
-    sb.step_dev(b_p.ptr, b_n.ptr, b_d.ptr)
-
-
-def _live(sb):
-    sb.check()
-    ntr = sb.num_tracks()
-    return ntr, sb.tracks(cap=max(int(ntr.max()), 1))
-
-
-_REF48 = {}
-
-
-def _ref48():
-    """scenario(48) and its oracle run at FB_FRAMES_BATCH = 0, computed once for both layouts and never changed."""
-    if not _REF48:
-        pts, cnt, dts = pc.scenario(48)
-        w = _weights(0)
-        _REF48.update(pts=pts, cnt=cnt, dts=dts, w=w, ref=pc.oracle_run(pts, cnt, dts, w, cfg_kw=KW1))
-    return _REF48
-
-
-@pytest.mark.parametrize("layout", ["one_workgroup", "per_scene"])
-def test_single_frame_estimate_posture_through_the_c_entries_vs_oracle_and_pipeline(layout):
-    S = 48
-    r48 = _ref48()
-    pts, cnt, dts, w, ref = r48["pts"], r48["cnt"], r48["dts"], r48["w"], r48["ref"]
-    F = cnt.shape[0]
-    assert ref["rows"] == ROWS_48 and ref["tracked_by_4"] == 48 and ref["expired"] == 16 and ref["samples_cnn"] == 72
-    # -- the C entries only: ctypes, mmw_dev_alloc / mmw_memcpy_*, no torch tensor on the path
-    sb = make_checked(S, N, layout, **KW1)
-    assert sb.ring == 1 and (sb.step_kind() == 1) == (layout == "one_workgroup")
-    L = sb.L
-    model = CModel(sb, w)
-    assert L.mmw_posture_attach_frames(sb.h, C.byref(model.struct), 1, S * sb.track_cap) == 0, L.mmw_last_error(sb.h)
-    for f in range(F):
-        _step(sb, pts[f], cnt[f], dts[f])
-        rows = C.c_int32(-1)
-        assert L.mmw_estimate_posture(sb.h, C.byref(rows)) == 0, L.mmw_last_error(sb.h)
-        assert rows.value == ref["rows"][f], (f, rows.value, ref["rows"][f])
-    ntr, trk = _live(sb)
-    word = C.c_int32(-1)
-    assert L.mmw_posture_range(sb.h, C.byref(word)) == 0 and word.value == 0
-    checked, worst = 0, 0.0
-    for s in range(S):   # every live track of every scene
-        want, got = ref["finals"][s], trk[s, : ntr[s]]
-        assert len(want) == int(ntr[s]), s
-        for name in pc.STATE_FIELDS:
-            assert np.array_equal(got[name], want[name]), (s, name)
-        worst = max(worst, pc.kp_err(got["keypoints"], ref["want_kp"][s]))
-        checked += len(want)
-    print(f"C entries, single-frame model, {layout}: {checked} tracks, keypoint error {worst:.3e}")
-    assert checked == ref["samples_cnn"] == 72
-    assert worst <= KP_TOL, worst
-    feat_c, owner_c = sb.features_host()
-    # -- the same frames through PosturePipeline(overlap=False) + MarsCNN on a twin context
-    import torch
-    from mmwave_msc_amd.mars import MarsCNN
-    from mmwave_msc_amd.posture import PosturePipeline
-    twin = make_checked(S, N, layout, **KW1)
-    cnn = MarsCNN.from_keras_weights(w).to("cuda:0")
-    assert cnn.frames == 1
-    pipe = PosturePipeline(twin, cnn, S * twin.track_cap, overlap=False)
-    for f in range(F):
-        _step(twin, pts[f], cnt[f], dts[f])
-        pipe.after_step()
-        twin.synchronize()   # (the input buffers are rewritten by the next frame's uploads)
-    pipe.close()
-    ntr2, trk2 = _live(twin)
-    assert np.array_equal(ntr, ntr2)
-    between = 0.0
-    for s in range(S):
-        a, b = trk[s, : ntr[s]], trk2[s, : ntr2[s]]
-        for name in pc.STATE_FIELDS + ("uid", "min_vals", "max_vals", "n_est", "ring_len"):
-            assert np.array_equal(a[name], b[name]), (s, name)
-        between = max(between, pc.kp_err(a["keypoints"], b["keypoints"].astype(np.float64)))
-    print(f"C entries against PosturePipeline: keypoints differ by {between:.3e}")
-    assert between <= KP_TOL, between
-    feat_p, owner_p = twin.features_host()
-    assert np.array_equal(owner_c, owner_p) and np.array_equal(owner_c, ref["owners"][F - 1])
-    assert feat_c.shape == (ref["rows"][F - 1], 8, 8, 5) and feat_c.tobytes() == feat_p.tobytes()
-    assert L.mmw_posture_attach_frames(sb.h, None, 1, 0) == 0
-    model.free()
-    twin.close()
-    sb.close()
-    torch.cuda.synchronize()
-
-
-def test_single_frame_out_of_range_sample_is_repaired_through_the_c_entries():
-    """The intensities of the last frame of scene 2 scaled by 1e5 push ONE single-frame tensor of the last call out of fp16's
-    range: k_mars_conv2d's fp32 repair recomputes that sample on the device (bit 0 of the range word, read once), and its
-    keypoints -- 1.4e5 on the oracle -- and everybody else's stay within 1e-4 of the fp64 oracle."""
-    S, HOT = 16, 2
-    pts, cnt, dts = pc.scenario(S, seed=6100)
-    F = cnt.shape[0]
-    pts[F - 1, HOT, :, 7] *= 1e5
-    w = _weights(2)
-    ref = pc.oracle_run(pts, cnt, dts, w, cfg_kw=KW1)
-    hot = [int((np.abs(f.reshape(len(f), -1)).max(axis=1) >= 65504.0).sum()) if len(f) else 0 for f in ref["feats"]]
-    assert hot == [0] * (F - 1) + [1], hot
-    assert len(ref["want_kp"][HOT]) >= 1 and 1.3e5 < float(np.abs(ref["want_kp"][HOT]).max()) < 1.5e5, float(np.abs(ref["want_kp"][HOT]).max())
-    sb = make_checked(S, N, "per_scene", **KW1)
-    sb.attach_posture_batch(w, S * sb.track_cap)
-    for f in range(F):
-        if f == F - 1:
-            assert sb.posture_range() == 0, "nothing left fp16's range before the last frame"
-        _step(sb, pts[f], cnt[f], dts[f])
-        assert sb.estimate_posture() == ref["rows"][f]
-    ntr, trk = _live(sb)
-    assert sb.posture_range() == 1, "bit 0: a sample was repaired; bit 1 (surplus) must be clear"
-    assert sb.posture_range() == 0, "the word is cleared by the read"
-    worst, worst_hot = 0.0, 0.0
-    for s in range(S):
-        assert len(ref["finals"][s]) == int(ntr[s])
-        e = pc.kp_err(trk[s, : ntr[s]]["keypoints"], ref["want_kp"][s])
-        worst, worst_hot = max(worst, e), (e if s == HOT else worst_hot)
-    print(f"range, single-frame model: keypoint error {worst:.3e} over all tracks, {worst_hot:.3e} for the repaired sample")
-    assert worst <= KP_TOL, (worst, worst_hot)
-    sb.close()
-
-
-def test_frames_refusals_capacity_detach_and_frames_3_equivalence():
+# ---- 4. - 6. the batched chain: end to end, the range repair, refusals / capacity / detach are test_gpu_posture_cabi.py's tests,
+#      parametrised over the model; here is what only the `frames` argument brings -------------------------------------------------
+def test_frames_argument_and_the_model_are_held_to_the_contexts_ring():
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.batch import SceneBatch
-    from mmwave_msc_amd.marsweights import fold_keras_weights
     S = 16
-    pts, cnt, dts = pc.scenario(S, seed=6300)
     w1, w3 = _weights(1, 1), _weights(1, 3)
     sb = make_checked(S, N, "per_scene", **KW1)
     L = sb.L
-    rows = C.c_int32(5)
     model = CModel(sb, w1)
     # frames against the ring, both ways; rings nobody has a model for
     three = SceneBatch(_lib.default_config(**pc.KW), 4, N)
@@ -361,6 +198,11 @@ def test_frames_refusals_capacity_detach_and_frames_3_equivalence():
         assert L.mmw_posture_attach_frames(ctx.h, C.byref(mod.struct), bad, 64) == _lib.E_ARG, bad
         assert b"FB_FRAMES_BATCH" in L.mmw_last_error(ctx.h)
         assert L.mmw_estimate_posture(ctx.h, None) == _lib.E_ARG   # ... nothing was attached
+    single = SceneBatch(_lib.default_config(fb_frames_batch=0, **pc.KW), 4, N)
+    sm = CModel(single, w3)
+    assert single.L.mmw_posture_attach(single.h, C.byref(sm.struct), 64) == _lib.E_ARG         # the legacy entry: FB_FRAMES_BATCH = 2 only
+    assert b"FB_FRAMES_BATCH" in single.L.mmw_last_error(single.h)
+    sm.free(); single.close()
     with pytest.raises(ValueError, match="3-frame.*FB_FRAMES_BATCH = 0"):
         sb.attach_posture_batch(w3)
     with pytest.raises(ValueError, match="1-frame.*FB_FRAMES_BATCH = 2"):
@@ -369,50 +211,20 @@ def test_frames_refusals_capacity_detach_and_frames_3_equivalence():
     assert L.mmw_attach_posture_frames(one3.h, C.byref(m3.struct), 1) == _lib.E_ARG and b"FB_FRAMES_BATCH" in L.mmw_last_error(one3.h)
     one3.close()
     assert L.mmw_attach_posture_frames(sb.h, C.byref(model.struct), 1) == _lib.E_ARG and b"one-scene" in L.mmw_last_error(sb.h)
-    # the model struct
-    off = _lib.MmwPostureModel.from_buffer_copy(model.struct)
-    off.dense1_ld = 2044
-    assert L.mmw_posture_attach_frames(sb.h, C.byref(off), 1, 64) == _lib.E_ARG
-    null = _lib.MmwPostureModel.from_buffer_copy(model.struct)
-    null.conv2_w = None
-    assert L.mmw_posture_attach_frames(sb.h, C.byref(null), 1, 64) == _lib.E_ARG
-    assert L.mmw_posture_attach_frames(sb.h, C.byref(model.struct), 1, 0) == _lib.E_ARG        # cap_rows < 1
-    f32 = fold_keras_weights(w1)
-    d1 = f32["dense1_w"].copy()
-    d1[100] *= np.float32(3e6 / np.abs(d1[100]).max())
-    bad = CModel(sb, w1, dense1_w=d1)
-    assert L.mmw_posture_attach_frames(sb.h, C.byref(bad.struct), 1, 64) == _lib.E_ARG and b"fp16" in L.mmw_last_error(sb.h)
-    cb = f32["conv2_b"].copy()
-    cb[3] = np.float32("inf")
-    bad2 = CModel(sb, w1, conv2_b=cb)
-    assert L.mmw_posture_attach_frames(sb.h, C.byref(bad2.struct), 1, 64) == _lib.E_ARG and b"fp16" in L.mmw_last_error(sb.h)
-    assert L.mmw_estimate_posture(sb.h, None) == _lib.E_ARG                                    # none of them attached anything
-    for f in range(6):                                                                         # ... and the context still steps
-        _step(sb, pts[f], cnt[f], dts[f])
-    sb.check()
-    bad.free(); bad2.free()
-    # capacity: one row short of the eligible tracks
-    eligible = len(sb.features_host()[1])
-    assert eligible >= 8
-    assert L.mmw_posture_attach_frames(sb.h, C.byref(model.struct), 1, eligible) == 0, L.mmw_last_error(sb.h)
-    assert L.mmw_estimate_posture(sb.h, C.byref(rows)) == 0 and rows.value == eligible
-    _step(sb, pts[6], cnt[6], dts[6])
-    eligible = len(sb.features_host()[1])
-    _, stepped = _live(sb)
-    assert L.mmw_posture_attach_frames(sb.h, C.byref(model.struct), 1, eligible - 1) == 0
-    assert L.mmw_estimate_posture(sb.h, C.byref(rows)) == _lib.E_CAPACITY and rows.value == 0
-    assert b"cap_rows" in L.mmw_last_error(sb.h)
-    assert sb.tracks(cap=stepped.shape[1]).tobytes() == stepped.tobytes(), "a keypoint changed in a refused call"
-    assert stepped["keypoints"].tobytes() != np.zeros_like(stepped["keypoints"]).tobytes()
-    assert L.mmw_posture_attach_frames(sb.h, None, 1, 0) == 0
-    assert L.mmw_estimate_posture(sb.h, C.byref(rows)) == _lib.E_ARG
-    assert L.mmw_posture_attach_frames(sb.h, None, 1, 0) == 0   # (detaching twice is fine)
     model.free(); m3.free()
     three.close(); sb.close()
-    # frames = 3 IS mmw_posture_attach: twin 16-scene contexts, byte-equal keypoints
+
+
+def test_frames_3_is_the_legacy_entry():
+    """frames = 3 IS mmw_posture_attach: twin 16-scene contexts, byte-equal keypoints."""
+    S = 16
+    pts, cnt, dts = pc.scenario(S, seed=6300)
+    w3 = _weights(1, 3)
+    rows = C.c_int32(5)
     kps = []
     for entry in ("mmw_posture_attach", "mmw_posture_attach_frames"):
         ctx = make_checked(S, N, "per_scene", **pc.KW)
+        L = ctx.L
         mod = CModel(ctx, w3)
         args = (ctx.h, C.byref(mod.struct), S * ctx.track_cap) if entry == "mmw_posture_attach" else (ctx.h, C.byref(mod.struct), 3, S * ctx.track_cap)
         assert getattr(L, entry)(*args) == 0, L.mmw_last_error(ctx.h)
@@ -442,7 +254,7 @@ def test_one_scene_chain_runs_the_single_frame_model_behind_the_step():
     F = 12
     p, c, d = make_scene(4242, F, N, 2)
     pts, cnt, dts = p.astype(np.float64)[:, None], c[:, None], d[:, None]
-    w = _weights(7)
+    w = _weights(7, 1)
     ref = pc.oracle_run(pts, cnt, dts, w, cfg_kw=KW1)
     assert max(ref["rows"]) >= 2 and sum(ref["rows"]) >= 12, ref["rows"]
     model = MarsCNN.from_keras_weights(w).to("cuda:0")
@@ -498,7 +310,7 @@ def test_trackbuffer_attaches_a_single_frame_model_under_fb_frames_batch_0(monke
     from mmwave_msc_amd.mars import MarsCNN
     from mmwave_msc_amd.synth import make_scene
     from mmwave_msc_amd.tracking import BatchedData, TrackBuffer
-    w = _weights(9)
+    w = _weights(9, 1)
     model = MarsCNN.from_keras_weights(w).to("cuda:0")
     model3 = MarsCNN.from_keras_weights(_weights(9, 3)).to("cuda:0")
     ring3 = TrackBuffer(max_pts=256)

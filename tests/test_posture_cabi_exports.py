@@ -107,6 +107,49 @@ def test_fp64_dense2_statement_is_the_oracles_last_layer():
     assert pc.kp_err(folded, want) <= 1e-5   # (fp32 rounding of 1536 weights per output: far inside the 1e-4 of the keypoints)
 
 
+@pytest.mark.parametrize("frames", [3, 1])
+def test_folded_dense1_is_the_oracles_hidden_layer(frames):
+    """The Dense-1 counterpart: BatchNormalization + Dense-1 + relu of oracle.mars_np (pc.hidden_fp64) against the folded fp32
+    Dense-1 of fold_keras_weights on the same fp64 conv activations.  The bound is what rounding each folded weight and bias to
+    fp32 allows: half an ulp, 2^-24, of every term's magnitude, with a factor 2 for stating it on the rounded values."""
+    from mmwave_msc_amd.marsweights import fold_keras_weights, model_dims, random_keras_weights
+    from oracle.mars_np import _conv_same
+    d = model_dims(frames)
+    w = random_keras_weights(seed=5, frames=frames)
+    w64 = {k: np.asarray(v, dtype=np.float64) for k, v in w.items()}
+    x = np.random.default_rng(3).normal(0.0, 1.0, size=(6,) + d.input)
+    a = np.maximum(_conv_same(x, w64["conv1_w"], w64["conv1_b"]), 0.0)
+    a_flat = np.maximum(_conv_same(a, w64["conv2_w"], w64["conv2_b"]), 0.0).reshape(6, -1)
+    f = fold_keras_weights(w)
+    w1, b1 = f["dense1_w"].astype(np.float64), f["dense1_b"].astype(np.float64)
+    assert a_flat.shape == (6, d.flat) and w1.shape == (d.hidden, d.flat)
+    got = np.maximum(a_flat @ w1.T + b1, 0.0)
+    want = pc.hidden_fp64(w, x)
+    bound = 2.0 ** -23 * (np.abs(a_flat) @ np.abs(w1).T + np.abs(b1))
+    print(f"folded Dense-1, frames={frames}: largest error / bound = {(np.abs(got - want) / bound).max():.3f}")
+    assert (want > 0).any() and (np.abs(got - want) <= bound).all()
+
+
+@pytest.mark.parametrize("frames", [3, 1])
+def test_model_dims_are_the_librarys_through_its_own_refusals(frames):
+    """marsweights.model_dims against cnn_dims() of csrc/mmw_ctx.hpp, without a device: the entries that take the model's flat size
+    as a leading dimension accept exactly it and refuse anything shorter (their argument checks come before any HIP call and
+    allow null buffers at n = 0)."""
+    from mmwave_msc_amd.marsweights import model_dims
+    L = _lib.load()
+    flat = model_dims(frames).flat
+
+    def fixup(ldw):
+        return L.mmw_mars_range_fixup_frames(None, frames, None, None, 0, None, None, None, None, None, ldw, None, None, None, None, None, None)
+
+    def conv_split(ld_out):
+        return L.mmw_mars_conv_split(None, frames, None, None, None, None, None, None, ld_out, 0, None, None)
+
+    assert fixup(flat) == _lib.MMW_OK and fixup(flat - 4) == _lib.E_ARG
+    # (accepted = past the argument check: with nothing to launch the entry still asks HIP for its last error, MMW_E_HIP without a GPU)
+    assert conv_split(2 * flat) in (_lib.MMW_OK, _lib.E_HIP) and conv_split(2 * flat - 8) == _lib.E_ARG
+
+
 @pytest.mark.parametrize("S", [48, 640])
 def test_gpu_scenario_moves_its_track_lists(S):
     """The inputs of the end-to-end GPU test, with the oracle alone: at least a third of the scenes hold tracks by frame 4, at least

@@ -13,7 +13,6 @@ from tests import _posture_cabi as pc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmw_mars_conv2d", "mmw_mars_range_fixup_frames", "mmw_posture_attach_frames", "mmw_attach_posture_frames")
-ROWS_48 = [64, 70, 71, 72, 72, 96, 96, 72, 72, 72, 72, 72]   # eligible tracks per frame of scenario(48) at FB_FRAMES_BATCH = 0
 
 
 def test_new_entries_are_declared_bound_and_exported():
@@ -71,8 +70,8 @@ def test_gpu_scenario_at_one_frame_per_track():
     from mmwave_msc_amd.marsweights import random_keras_weights
     pts, cnt, dts = pc.scenario(48)
     ref = pc.oracle_run(pts, cnt, dts, random_keras_weights(0, 1), cfg_kw=dict(pc.KW, fb_frames_batch=0))
-    assert ref["rows"] == ROWS_48, ref["rows"]
-    assert ref["tracked_by_4"] == 48 and ref["expired"] == 16 and ref["samples_cnn"] == 72
+    for name, value in pc.SINGLE_FRAME_48.items():
+        assert ref[name] == value, (name, ref[name])
     assert all(f.shape[1:] == (8, 8, 5) for f in ref["feats"])
 
 
