@@ -379,6 +379,48 @@ int mmw_posture_attach(mmw_ctx *ctx, const mmw_posture_model *model, int32_t cap
 int mmw_posture_attach_frames(mmw_ctx *ctx, const mmw_posture_model *model, int32_t frames, int32_t cap_rows);
 int mmw_estimate_posture(mmw_ctx *ctx, int32_t *n_rows);
 int mmw_posture_range(mmw_ctx *ctx, int32_t *word);
+/* ---- per-scene posture models ----
+ * SEVERAL models behind one mmw_estimate_posture: every scene names the model that estimates it -- the model trained on the data
+ * set its site's intensity scale was computed for (mmw_set_sites), a new model on a few scenes before it gets all of them -- or
+ * MMW_POSTURE_NONE: no model, its tracks keep the keypoints they have (default_posture for a track that never had any) and cost
+ * no CNN row.  The models are of ONE frame count, the context's.
+ * mmw_posture_attach_models: models[n_models] (1 .. MMW_POSTURE_MODELS_MAX; each as mmw_posture_attach_frames takes it and held to
+ * the same rules), frames as mmw_posture_attach_frames, scene_model host [n_scenes] with entries in [-1, n_models) (NULL: every
+ * scene on model 0).  Every model gets its own split Dense-1 operand (37.7 MB for the 3-frame model, 4.2 MB for the single-frame
+ * one) and fix-up list; feature, activation, hidden, keypoint, owner and uid buffers are shared and hold
+ * pad256(cap_rows) + 256 * n_models rows (n_models > 1), so that every model's rows start on a multiple of 256 and cap_rows keeps
+ * its meaning: the most rows one call estimates, summed over the models.  Replaces whatever was attached, single or multiple.
+ * Refused with MMW_E_ARG, a message that names the index of an offending model, and nothing changed (an earlier attachment stays
+ * and keeps working): n_models outside 1 .. 8, a map entry outside [-1, n_models), frames, cap_rows < 1, a model
+ * mmw_posture_attach_frames would refuse; MMW_E_HIP, equally atomic, for a failed allocation.  models == NULL is MMW_E_ARG:
+ * mmw_posture_attach(ctx, NULL, 0) / mmw_posture_attach_frames(ctx, NULL, ..) detach either kind.  mmw_posture_attach and
+ * mmw_posture_attach_frames ARE the one-model case (the map: every scene on model 0).  Sync.
+ * mmw_posture_set_scene_models: the listed scenes (host array of n indices; NULL = scenes 0 .. n-1) move to model_of[n] (host).
+ * The rules of mmw_set_sites: checked on the host before anything changes (an index out of range or listed twice, n < 0,
+ * n > n_scenes, model_of == NULL with n > 0, an id outside [-1, n_models): MMW_E_ARG, the message names the entry, the map stays),
+ * the new map travels as one copy ordered on the context's stream and holds from the next mmw_estimate_posture on.  Tracker state
+ * is not touched: a track keeps the keypoints it last got (track.keypoints persists between estimates in the reference too).  The
+ * map belongs to the attachment: mmw_reset / mmw_reset_scenes keep it, a snapshot blob carries neither map nor models, attaching
+ * anew starts a new map.  Needs an attachment (MMW_E_ARG without one).  Sync.
+ * mmw_posture_get_scene_models: the map, host [n_scenes], from its host mirror.
+ * mmw_estimate_posture on such a context: the eligible tracks' rows are handed out model by model (one more one-workgroup kernel in
+ * place of the scan), the host waits for every model's row count in one copy, and the chain of the CNN kernels runs once per model
+ * that has rows, on that model's rows alone.  *n_rows = the rows of all models; more than cap_rows: MMW_E_CAPACITY before any CNN
+ * launch, no keypoint changed; no rows anywhere: MMW_OK with 0.  mmw_posture_range is the OR over the models.  A context with ONE
+ * model and every scene on it launches exactly what mmw_posture_attach's always did; with one model and scenes on
+ * MMW_POSTURE_NONE it runs the model-by-model scan and one chain.
+ * mmw_posture_group_rows / mmw_posture_owners report the LAST mmw_estimate_posture (a refused or empty call: no rows):
+ * rows[n_models] (host) = the rows each model estimated, *n_models = their number; owner[n][2] (host, cap rows) = (scene, track
+ * list position) of every estimated row, model by model and within a model by ascending scene, *n_rows = n; more rows than cap:
+ * MMW_E_CAPACITY, nothing written.  mmw_posture_owners is sync.  A NULL context is MMW_E_ARG and leaves the outputs alone. */
+#define MMW_POSTURE_MODELS_MAX 8
+#define MMW_POSTURE_NONE      (-1)     /* a scene no model estimates */
+int mmw_posture_attach_models(mmw_ctx *ctx, const mmw_posture_model *models, int32_t n_models, int32_t frames,
+                              const int32_t *scene_model /* host [S]; NULL = every scene model 0 */, int32_t cap_rows);
+int mmw_posture_set_scene_models(mmw_ctx *ctx, const int32_t *scenes, int32_t n, const int32_t *model_of /* host [n] */);
+int mmw_posture_get_scene_models(mmw_ctx *ctx, int32_t *out /* host [S] */);
+int mmw_posture_group_rows(mmw_ctx *ctx, int32_t *rows /* host [n_models] */, int32_t *n_models);
+int mmw_posture_owners(mmw_ctx *ctx, int32_t *owner /* host [cap][2] */, int32_t cap, int32_t *n_rows);
 
 /* Utils.apply_DBscan (Utils.py:250-291) on arbitrary clouds: pts[S][max_n][8], n[S]
  * -> labels[S][max_n], n_clusters[S] (dev pointers; max_n <= ring*max_pts; max_n > 1920: the global-memory path).

@@ -33,6 +33,8 @@ ERRBIT_SINGULAR, ERRBIT_DIVZERO, ERRBIT_CAPACITY, ERRBIT_BADCOUNT, ERRBIT_NONFIN
 K_TRACK, K_DBSCAN, K_FEATURES, K_NORMALIZE, K_TABLE, K_PREDICT, K_POST, K_COUNT = range(8)
 RANGE_FIXUP_CAP = 64               # out-of-range samples one call of the posture chain repairs in fp32
 RANGE_FIXUP_SCRATCH = 2226944      # bytes of device scratch mmw_mars_range_fixup* takes (the header's expression, evaluated)
+POSTURE_MODELS_MAX = 8             # models one mmw_posture_attach_models call takes
+POSTURE_NONE = -1                  # MMW_POSTURE_NONE: the map entry of a scene no model estimates
 EXPORT_TICKETS = 4                 # kTickets (csrc/mmw_ctx.hpp): `*_async` calls of one export that may be outstanding; the
                                    # one-call form of each export (mmw_report, mmw_clouds, ...) uses the last ticket itself
 REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
@@ -297,6 +299,11 @@ def _signatures():
         "mmw_mars_range_fixup_frames": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]),
         "mmw_posture_attach_frames": (C.c_int, [vp, vp, i32, i32]),
         "mmw_attach_posture_frames": (C.c_int, [vp, vp, i32]),
+        "mmw_posture_attach_models": (C.c_int, [vp, vp, i32, i32, vp, i32]),
+        "mmw_posture_set_scene_models": (C.c_int, [vp, vp, i32, vp]),
+        "mmw_posture_get_scene_models": (C.c_int, [vp, vp]),
+        "mmw_posture_group_rows": (C.c_int, [vp, vp, i32p]),
+        "mmw_posture_owners": (C.c_int, [vp, vp, i32, i32p]),
     }
 
 

@@ -461,6 +461,80 @@ class SceneBatch:
                 b.free()
         self._posture_batch = None
 
+    # -- per-scene posture models ----------------------------------------------
+    def attach_posture_models(self, weights_list, scene_model=None, cap_rows: int = None):
+        """mmw_posture_attach_models: several models behind one `estimate_posture`.  `weights_list`: 1 .. 8 entries, each whatever
+        `attach_posture_batch` takes (folded by `marsweights.fold_keras_weights`, uploaded and kept by this object); `scene_model`:
+        the model index of every scene, int[S] with `_lib.POSTURE_NONE` (-1) for a scene no model estimates (default: every scene
+        on model 0); `cap_rows` (default: S * track_cap) = the most tracks one call can estimate, over all models.  Replaces an
+        earlier attachment of either kind; `attach_posture_batch(None)` detaches.  Refused with nothing changed: a model whose
+        frame count is not the context's FB_FRAMES_BATCH + 1, a map of another length (ValueError); with MmwError, E_ARG: a count
+        outside 1 .. 8, a map entry outside [-1, n_models), cap_rows < 1, a weight outside fp16's range (the message names the
+        model)."""
+        from .marsweights import FOLDED_KEYS, fold_keras_weights, load_keras_weights
+        folded = [fold_keras_weights(load_keras_weights(w)) for w in weights_list]
+        for i, f in enumerate(folded):
+            if f["frames"] != self.ring:
+                raise ValueError(f"attach_posture_models: model {i} is the {f['frames']}-frame model, this context holds {self.ring} "
+                                 f"frame(s) per track (FB_FRAMES_BATCH = {self.ring - 1})")
+        smap = None
+        if scene_model is not None:
+            smap = np.ascontiguousarray(np.asarray(scene_model, dtype=np.int32).reshape(-1))
+            if len(smap) != self.S:
+                raise ValueError(f"attach_posture_models: a map of {len(smap)} entries for {self.S} scenes")
+        cap = int(cap_rows if cap_rows is not None else self.S * self.track_cap)
+        bufs = {}
+        try:
+            for i, f in enumerate(folded):
+                for k in FOLDED_KEYS:
+                    bufs[i, k] = DevBuf(self, f[k].nbytes).upload(f[k])
+            structs = (_lib.MmwPostureModel * max(len(folded), 1))(*(
+                _lib.MmwPostureModel.of(*(bufs[i, k].ptr for k in FOLDED_KEYS), dense1_ld=f["dense1_w"].shape[1]) for i, f in enumerate(folded)))
+            rc = self.L.mmw_posture_attach_models(self.h, structs, len(folded), self.ring, smap.ctypes.data if smap is not None else None, cap)
+        except BaseException:
+            for b in bufs.values():
+                b.free()
+            raise
+        if rc != 0:   # (refused atomically: an earlier attachment stays, with its own buffers)
+            for b in bufs.values():
+                b.free()
+            self._chk(rc)
+        self._free_posture_batch()
+        self._posture_batch = bufs
+
+    def set_scene_models(self, model_of, scenes=None):
+        """mmw_posture_set_scene_models: move `scenes` (default: scenes 0 .. len(model_of)-1) to the models `model_of` (indices into
+        the attached list, `_lib.POSTURE_NONE` = no model), from the next `estimate_posture` on.  The tracks keep the keypoints
+        they have.  Refused (MmwError, E_ARG) with the map unchanged for an index out of range or listed twice, more entries than
+        scenes, an id outside [-1, n_models), or no attachment."""
+        a = np.ascontiguousarray(np.asarray(model_of, dtype=np.int32).reshape(-1))
+        idx = None
+        if scenes is not None:
+            idx = np.ascontiguousarray(np.asarray(scenes, dtype=np.int32).reshape(-1))
+            if len(idx) != len(a):
+                raise ValueError(f"set_scene_models: {len(a)} models for {len(idx)} scenes")
+        self._chk(self.L.mmw_posture_set_scene_models(self.h, idx.ctypes.data if idx is not None else None, len(a), a.ctypes.data if len(a) else None))
+
+    def scene_models(self) -> np.ndarray:
+        """mmw_posture_get_scene_models: the model index of every scene, int32[S] (`_lib.POSTURE_NONE` = no model)."""
+        out = np.zeros(self.S, dtype=np.int32)
+        self._chk(self.L.mmw_posture_get_scene_models(self.h, out.ctypes.data))
+        return out
+
+    def posture_group_rows(self) -> np.ndarray:
+        """mmw_posture_group_rows: the rows every model estimated in the last `estimate_posture`, int32[n_models]."""
+        rows, n = np.zeros(_lib.POSTURE_MODELS_MAX, dtype=np.int32), C.c_int32(0)
+        self._chk(self.L.mmw_posture_group_rows(self.h, rows.ctypes.data, C.byref(n)))
+        return rows[: n.value].copy()
+
+    def posture_owners(self) -> np.ndarray:
+        """mmw_posture_owners: (scene, track list position) of every row the last `estimate_posture` estimated, int32[n, 2], model
+        by model and within a model by ascending scene.  Synchronises."""
+        cap = int(self.posture_group_rows().sum())
+        out, n = np.zeros((max(cap, 1), 2), dtype=np.int32), C.c_int32(0)
+        self._chk(self.L.mmw_posture_owners(self.h, out.ctypes.data, cap, C.byref(n)))
+        return out[: n.value].copy()
+
     def estimate_posture(self) -> int:
         """mmw_estimate_posture: features -> CNN -> `track.keypoints` for every eligible track of every scene, queued behind the
         last step on the context's stream (the host waits for the row count only).  Returns the tracks estimated."""

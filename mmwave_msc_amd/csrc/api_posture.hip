@@ -1,19 +1,26 @@
 // api_posture.hip -- the C-ABI (include/mmw.h): posture.  Feature tensors and keypoints of the tracks, the one-scene fp32 chain's
-// model (mmw_attach_posture / _frames; mmw_frame_posture_host runs it), the batched chain (mmw_posture_attach / _frames,
-// mmw_estimate_posture) and the stateless mmw_mars_* entries over the CNN kernels.  Both chains serve the 3-frame model
+// model (mmw_attach_posture / _frames; mmw_frame_posture_host runs it), the batched chain (mmw_posture_attach / _frames / _models,
+// the scene -> model map, mmw_estimate_posture) and the stateless mmw_mars_* entries over the CNN kernels.  Both chains serve the 3-frame model
 // (define_CNN_3D) and the single-frame one (define_CNN): CnnDims has what differs between them.
 #include <new>
 
 #include "mmw_ctx.hpp"
 
 static long long pb_act_ld(const CnnDims &d) { return 2LL * d.flat + 256; }   // the batched chain's activation row stride: mars.MarsCNN.ROW_PAD
-constexpr int kPbWordRange = 0, kPbWordWeights = 1, kPbWordList = 2;
+constexpr int kPbWordRange = 0, kPbWordList = 2;
+constexpr size_t pb_list_words = 2 + MMW_RANGE_FIXUP_CAP;   // one model's fix-up list
+static void posture_refresh_grouped(PostureBatch *b)
+{
+    b->grouped = b->n_models > 1;
+    for (int32_t m : b->h_map) b->grouped |= m == MMW_POSTURE_NONE;
+}
 
 void posture_batch_free(PostureBatch *b)
 {
     if (!b) return;
-    void *ptrs[] = {b->feat, b->hidden, b->kp, b->owner, b->uid, b->words, b->act16, b->w16, b->fix_scratch};
+    void *ptrs[] = {b->feat, b->hidden, b->kp, b->owner, b->uid, b->words, b->act16, b->fix_scratch, b->d_map, b->d_groups};
     for (void *p : ptrs) if (p) hipFree(p);
+    for (void *p : b->w16) if (p) hipFree(p);
     if (b->h_total) hipHostFree(b->h_total);
     if (b->total_ev) hipEventDestroy(b->total_ev);
     delete b;
@@ -291,21 +298,35 @@ static int posture_detach(mmw_ctx *c)
     return MMW_OK;
 }
 
-static int posture_attach_impl(mmw_ctx *c, const mmw_posture_model *m, int frames, int32_t cap_rows, const char *who)
+// (indexed: the entry takes an array of models and its messages name the offending one)
+static int posture_attach_impl(mmw_ctx *c, const mmw_posture_model *models, int n_models, bool indexed, int frames, const int32_t *scene_model,
+                               int32_t cap_rows, const char *who)
 {
     const CnnDims d = cnn_dims(frames);
+    const int S = c->dc.n_scenes;
+    char at[32] = "";
+    auto name = [&](int i) { if (indexed) snprintf(at, sizeof(at), " model %d:", i); return at; };
     if (cap_rows < 1) return fail(c, MMW_E_ARG, "%s: cap_rows = %d must be >= 1", who, cap_rows);
-    if (cap_rows > INT32_MAX - 255) return fail(c, MMW_E_ARG, "%s: cap_rows = %d is too large", who, cap_rows);
-    if (!posture_model_ok(m, d, true))
-        return fail(c, MMW_E_ARG, "%s: null weight pointer, or Dense-1 / Dense-2 not 16-byte aligned, or Dense-1's leading dimension not a multiple of 4 that is >= %d", who, d.flat);
+    if (cap_rows > INT32_MAX - 255 - 256 * MMW_POSTURE_MODELS_MAX) return fail(c, MMW_E_ARG, "%s: cap_rows = %d is too large", who, cap_rows);
+    for (int i = 0; i < n_models; i++)
+        if (!posture_model_ok(models + i, d, true))
+            return fail(c, MMW_E_ARG, "%s:%s null weight pointer, or Dense-1 / Dense-2 not 16-byte aligned, or Dense-1's leading dimension not a multiple of 4 that is >= %d", who, name(i), d.flat);
+    for (int s = 0; scene_model && s < S; s++)
+        if (scene_model[s] < MMW_POSTURE_NONE || scene_model[s] >= n_models)
+            return fail(c, MMW_E_ARG, "%s: scene %d is given model %d, there are %d models (MMW_POSTURE_NONE = -1: no model)", who, s, scene_model[s], n_models);
     HIPCHK(c, hipSetDevice(c->device));
     PostureBatch *b = new (std::nothrow) PostureBatch();
     if (!b) return fail(c, MMW_E_HIP, "%s: out of host memory", who);
-    const size_t cap = ((size_t)cap_rows + 255) & ~(size_t)255;
-    b->model = *m;
+    b->n_models = n_models;
+    for (int i = 0; i < n_models; i++) b->model[i] = models[i];
     b->frames = frames;
     b->cap = cap_rows;
-    const size_t n_words = kPbWordList + 2 + MMW_RANGE_FIXUP_CAP;
+    const size_t cap = (((size_t)cap_rows + 255) & ~(size_t)255) + (n_models > 1 ? 256 * (size_t)n_models : 0);
+    b->rows = (int32_t)cap;
+    b->h_map.assign((size_t)S, 0);
+    if (scene_model) b->h_map.assign(scene_model, scene_model + S);
+    posture_refresh_grouped(b);
+    const size_t n_lists = kPbWordList + (size_t)n_models * pb_list_words, n_words = n_lists + MMW_POSTURE_MODELS_MAX;
     hipError_t e = hipSuccess;
     auto grab = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
     grab((void **)&b->feat, cap * d.per * sizeof(float));
@@ -316,30 +337,39 @@ static int posture_attach_impl(mmw_ctx *c, const mmw_posture_model *m, int frame
     grab((void **)&b->kp, cap * MMW_NKP * sizeof(float));
     grab((void **)&b->words, n_words * sizeof(int32_t));
     grab(&b->fix_scratch, MMW_RANGE_FIXUP_SCRATCH);
-    grab(&b->w16, (size_t)d.hidden * 2 * d.flat * 2);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_total, sizeof(int32_t));
+    for (int i = 0; i < n_models; i++) grab(&b->w16[i], (size_t)d.hidden * 2 * d.flat * 2);
+    grab((void **)&b->d_map, (size_t)S * sizeof(int32_t));
+    grab((void **)&b->d_groups, 16 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_total, 16 * sizeof(int32_t));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&b->total_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMemsetAsync(b->words, 0, n_words * sizeof(int32_t), c->stream);
-    int32_t bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_groups, 0, 16 * sizeof(int32_t), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->d_map, b->h_map.data(), (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    int32_t bad[MMW_POSTURE_MODELS_MAX] = {};
     if (e == hipSuccess) {
-        // the split Dense-1 operand, once; every weight that meets the split arithmetic must lie inside fp16's range
-        int32_t *flag = b->words + kPbWordWeights;
-        launch_split_weights(m->dense1_w, m->dense1_ld, b->w16, 2 * d.flat, d.hidden, d.flat, flag, c->stream);
-        launch_range_check(m->conv1_w, d.taps * 5 * 16, flag, c->stream);
-        launch_range_check(m->conv1_b, 16, flag, c->stream);
-        launch_range_check(m->conv2_w, d.taps * 16 * 32, flag, c->stream);
-        launch_range_check(m->conv2_b, 32, flag, c->stream);
+        // every model's split Dense-1 operand, once; every weight that meets the split arithmetic must lie inside fp16's range
+        for (int i = 0; i < n_models; i++) {
+            const mmw_posture_model *m = models + i;
+            int32_t *flag = b->words + n_lists + i;
+            launch_split_weights(m->dense1_w, m->dense1_ld, b->w16[i], 2 * d.flat, d.hidden, d.flat, flag, c->stream);
+            launch_range_check(m->conv1_w, d.taps * 5 * 16, flag, c->stream);
+            launch_range_check(m->conv1_b, 16, flag, c->stream);
+            launch_range_check(m->conv2_w, d.taps * 16 * 32, flag, c->stream);
+            launch_range_check(m->conv2_b, 32, flag, c->stream);
+        }
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(bad, b->words + n_lists, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
     if (e != hipSuccess) {
+        hipStreamSynchronize(c->stream);   // (the map's copy may still be reading the mirror that is about to go)
         posture_batch_free(b);
-        return fail(c, MMW_E_HIP, "%s: %s (cap_rows = %d)", who, hipGetErrorString(e), cap_rows);
+        return fail(c, MMW_E_HIP, "%s: %s (cap_rows = %d, %d model(s))", who, hipGetErrorString(e), cap_rows, n_models);
     }
-    if (bad) {
+    for (int i = 0; i < n_models; i++) {
+        if (!bad[i]) continue;
         posture_batch_free(b);
-        return fail(c, MMW_E_ARG, "%s: a conv or Dense-1 weight is not finite or has a magnitude >= 65504: outside fp16's range, where the split arithmetic of this path is not exact (use a one-scene context's fp32 path, mmw_attach_posture, for such a model)", who);
+        return fail(c, MMW_E_ARG, "%s:%s a conv or Dense-1 weight is not finite or has a magnitude >= 65504: outside fp16's range, where the split arithmetic of this path is not exact (use a one-scene context's fp32 path, mmw_attach_posture, for such a model)", who, name(i));
     }
     if (c->pb) posture_batch_free(c->pb);   // (the stream was waited for above: nothing of the old chain is running)
     c->pb = b;
@@ -351,7 +381,86 @@ int mmw_posture_attach(mmw_ctx *c, const mmw_posture_model *m, int32_t cap_rows)
     if (!c) return fail(c, MMW_E_ARG, "mmw_posture_attach: null context");
     if (!m) return posture_detach(c);
     if (c->dc.ring != 3) return fail(c, MMW_E_ARG, "mmw_posture_attach: the 3-frame model only (FB_FRAMES_BATCH = 2), this context has FB_FRAMES_BATCH = %d", c->dc.ring - 1);
-    return posture_attach_impl(c, m, 3, cap_rows, "mmw_posture_attach");
+    return posture_attach_impl(c, m, 1, false, 3, nullptr, cap_rows, "mmw_posture_attach");
+}
+
+int mmw_posture_attach_models(mmw_ctx *c, const mmw_posture_model *models, int32_t n_models, int32_t frames, const int32_t *scene_model, int32_t cap_rows)
+{
+    if (!c) return fail(c, MMW_E_ARG, "mmw_posture_attach_models: null context");
+    if (!models) return fail(c, MMW_E_ARG, "mmw_posture_attach_models: models is NULL (mmw_posture_attach(ctx, NULL, 0) detaches)");
+    if (n_models < 1 || n_models > MMW_POSTURE_MODELS_MAX)
+        return fail(c, MMW_E_ARG, "mmw_posture_attach_models: n_models = %d must be 1 .. %d", n_models, MMW_POSTURE_MODELS_MAX);
+    MMW_TRY(frames_ok(c, frames, "mmw_posture_attach_models"));
+    return posture_attach_impl(c, models, n_models, true, frames, scene_model, cap_rows, "mmw_posture_attach_models");
+}
+
+int mmw_posture_set_scene_models(mmw_ctx *c, const int32_t *scenes, int32_t n, const int32_t *model_of)
+{
+    if (!c) return fail(nullptr, MMW_E_ARG, "mmw_posture_set_scene_models: null context");
+    PostureBatch *b = c->pb;
+    if (!b) return fail(c, MMW_E_ARG, "mmw_posture_set_scene_models: no model attached (mmw_posture_attach_models)");
+    const int S = c->dc.n_scenes;
+    // every check first: a refused call changes no scene's model
+    if (n < 0 || n > S) return fail(c, MMW_E_ARG, "mmw_posture_set_scene_models: n = %d, the context has %d scenes", n, S);
+    if (n > 0 && !model_of) return fail(c, MMW_E_ARG, "mmw_posture_set_scene_models: model_of is NULL with n = %d", n);
+    std::vector<char> seen(scenes ? (size_t)S : 0, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = scenes ? scenes[i] : i;
+        if (s < 0 || s >= S) return fail(c, MMW_E_ARG, "mmw_posture_set_scene_models: entry %d names scene %d, the context has %d scenes", i, s, S);
+        if (scenes) {
+            if (seen[s]) return fail(c, MMW_E_ARG, "mmw_posture_set_scene_models: entry %d names scene %d a second time", i, s);
+            seen[s] = 1;
+        }
+        if (model_of[i] < MMW_POSTURE_NONE || model_of[i] >= b->n_models)
+            return fail(c, MMW_E_ARG, "mmw_posture_set_scene_models: entry %d (scene %d) asks for model %d, there are %d models (MMW_POSTURE_NONE = -1: no model)", i, s, model_of[i], b->n_models);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // the new map is put together on the host and travels as ONE copy, ordered on the context's stream (as mmw_set_sites' table)
+    std::vector<int32_t> next = b->h_map;
+    for (int i = 0; i < n; i++) next[scenes ? scenes[i] : i] = model_of[i];
+    HIPCHK(c, hipMemcpyAsync(b->d_map, next.data(), sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (`next` is pageable and goes away)
+    b->h_map.swap(next);
+    posture_refresh_grouped(b);
+    return MMW_OK;
+}
+
+int mmw_posture_get_scene_models(mmw_ctx *c, int32_t *out)
+{
+    if (!c || !out) return fail(c, MMW_E_ARG, "mmw_posture_get_scene_models: null argument");
+    if (!c->pb) return fail(c, MMW_E_ARG, "mmw_posture_get_scene_models: no model attached (mmw_posture_attach_models)");
+    memcpy(out, c->pb->h_map.data(), c->pb->h_map.size() * sizeof(int32_t));   // (the host mirror: no device access)
+    return MMW_OK;
+}
+
+int mmw_posture_group_rows(mmw_ctx *c, int32_t *rows, int32_t *n_models)
+{
+    if (!c || !rows || !n_models) return fail(c, MMW_E_ARG, "mmw_posture_group_rows: null argument");
+    if (!c->pb) return fail(c, MMW_E_ARG, "mmw_posture_group_rows: no model attached (mmw_posture_attach_models)");
+    for (int i = 0; i < c->pb->n_models; i++) rows[i] = c->pb->last_total[i];
+    *n_models = c->pb->n_models;
+    return MMW_OK;
+}
+
+int mmw_posture_owners(mmw_ctx *c, int32_t *owner, int32_t cap, int32_t *n_rows)
+{
+    if (!c || !n_rows || cap < 0 || (cap > 0 && !owner)) return fail(c, MMW_E_ARG, "mmw_posture_owners: bad argument");
+    PostureBatch *b = c->pb;
+    if (!b) return fail(c, MMW_E_ARG, "mmw_posture_owners: no model attached (mmw_posture_attach_models)");
+    int64_t total = 0;
+    for (int i = 0; i < b->n_models; i++) total += b->last_total[i];
+    if (total > cap) return fail(c, MMW_E_CAPACITY, "mmw_posture_owners: the last call estimated %lld rows but cap=%d (nothing was written)", (long long)total, cap);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int32_t *dst = owner;
+    for (int i = 0; i < b->n_models; i++) {   // band by band, without the padding between them
+        if (b->last_total[i] <= 0) continue;
+        HIPCHK(c, hipMemcpyAsync(dst, b->owner + (size_t)b->last_base[i] * 2, (size_t)b->last_total[i] * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        dst += (size_t)b->last_total[i] * 2;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_rows = (int32_t)total;
+    return MMW_OK;
 }
 
 int mmw_posture_attach_frames(mmw_ctx *c, const mmw_posture_model *m, int32_t frames, int32_t cap_rows)
@@ -359,7 +468,58 @@ int mmw_posture_attach_frames(mmw_ctx *c, const mmw_posture_model *m, int32_t fr
     if (!c) return fail(c, MMW_E_ARG, "mmw_posture_attach_frames: null context");
     if (!m) return posture_detach(c);
     MMW_TRY(frames_ok(c, frames, "mmw_posture_attach_frames"));
-    return posture_attach_impl(c, m, frames, cap_rows, "mmw_posture_attach_frames");
+    return posture_attach_impl(c, m, 1, false, frames, nullptr, cap_rows, "mmw_posture_attach_frames");
+}
+
+// one band of a call: the chain of the CNN kernels on `total` rows from row `base` of the shared buffers (a multiple of 256), with
+// model i's weights, split operand and fix-up list, then track.keypoints = the band's rows
+static int posture_band(mmw_ctx *c, PostureBatch *b, int i, int32_t base, int32_t total)
+{
+    const mmw_posture_model &m = b->model[i];
+    const CnnDims d = cnn_dims(b->frames);
+    const long long act_ld = pb_act_ld(d);
+    const int rows_padded = (total + 255) & ~255;
+    int32_t *range = b->words + kPbWordRange, *list = b->words + kPbWordList + (size_t)i * pb_list_words;
+    float *feat = b->feat + (size_t)base * d.per, *hidden = b->hidden + (size_t)base * d.hidden, *kp = b->kp + (size_t)base * MMW_NKP;
+    void *act16 = reinterpret_cast<char *>(b->act16) + (size_t)base * (size_t)act_ld * 2;
+    if (launch_mars_conv16(b->frames, feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, act16, act_ld, total, range, list, c->stream) != 0 ||
+        launch_mars_dense1(act16, act_ld, b->w16[i], 2 * d.flat, m.dense1_b, hidden, rows_padded, d.flat, d.hidden, c->stream) != 0)
+        return fail(c, MMW_E_HIP, "mmw_estimate_posture: hipFuncSetAttribute(max dynamic LDS) failed on this device");
+    launch_mars_dense2(hidden, d.hidden, m.dense2_w, m.dense2_b, kp, total, d.hidden, c->stream);
+    HIPCHK(c, hipGetLastError());
+    const int rc = range_fixup_impl("mmw_mars_range_fixup", c->stream, b->frames, feat, list, total, m, b->fix_scratch, kp, range);
+    if (rc) return fail(c, rc, "mmw_estimate_posture: %s", mmw_last_error(nullptr));
+    launch_set_kp(c->dc, c->st, kp, b->owner + (size_t)base * 2, total, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MMW_OK;
+}
+
+// mmw_estimate_posture of a context with several models, or with scenes on MMW_POSTURE_NONE: rows model by model
+static int estimate_posture_grouped(mmw_ctx *c, PostureBatch *b, int32_t *n_rows)
+{
+    EventPair ep;
+    launch_feat_count(c->dc, c->st, c->d_row_off, c->stream);
+    launch_feat_scan_models(c->dc.n_scenes, b->n_models, b->rows, b->d_map, c->d_row_off, b->d_groups, c->stream);
+    prof_begin(c, MMW_K_FEATURES, ep);
+    // (cap_rows = the buffers' rows: an excluded scene's offset, and whatever a call that exceeds cap_rows would place behind them)
+    launch_features(c->dc, sites_or_null(c), c->st, c->d_row_off, b->feat, b->owner, b->uid, b->rows, c->stream);
+    prof_end(c, ep);
+    HIPCHK(c, hipGetLastError());
+    // every band's total and base in ONE copy; the host waits for them (not for the stream)
+    HIPCHK(c, hipMemcpyAsync(b->h_total, b->d_groups, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(b->total_ev, c->stream));
+    HIPCHK(c, hipEventSynchronize(b->total_ev));
+    int64_t total = 0;
+    for (int i = 0; i < b->n_models; i++) total += b->h_total[i];
+    if (total > b->cap)
+        return fail(c, MMW_E_CAPACITY, "mmw_estimate_posture: %lld eligible tracks over %d models but cap_rows=%d (no keypoint was changed)", (long long)total, b->n_models, b->cap);
+    for (int i = 0; i < b->n_models; i++) {
+        b->last_total[i] = b->h_total[i];
+        b->last_base[i] = b->h_total[8 + i];
+        if (b->h_total[i] > 0) MMW_TRY(posture_band(c, b, i, b->h_total[8 + i], b->h_total[i]));
+    }
+    if (n_rows) *n_rows = (int32_t)total;
+    return MMW_OK;
 }
 
 int mmw_estimate_posture(mmw_ctx *c, int32_t *n_rows)
@@ -369,26 +529,17 @@ int mmw_estimate_posture(mmw_ctx *c, int32_t *n_rows)
     PostureBatch *b = c->pb;
     if (!b) return fail(c, MMW_E_ARG, "mmw_estimate_posture: no model attached (mmw_posture_attach)");
     HIPCHK(c, hipSetDevice(c->device));
-    const mmw_posture_model &m = b->model;
-    const CnnDims d = cnn_dims(b->frames);
-    const long long act_ld = pb_act_ld(d);
+    for (int i = 0; i < b->n_models; i++) b->last_total[i] = b->last_base[i] = 0;   // (a refused or empty call estimated nothing)
+    if (b->grouped) return estimate_posture_grouped(c, b, n_rows);
+    // one model, every scene on it: one band from row 0, behind k_feat_scan
     // the matrix kernels need their exact batch size: the host waits for the total (not for the stream)
     MMW_TRY(features_and_total(c, b->feat, b->owner, b->uid, b->cap, b->h_total, b->total_ev));
     HIPCHK(c, hipEventSynchronize(b->total_ev));
     const int32_t total = *b->h_total;
     if (total > b->cap) return fail(c, MMW_E_CAPACITY, "mmw_estimate_posture: %d eligible tracks but cap_rows=%d (no keypoint was changed)", total, b->cap);
     if (total <= 0) return MMW_OK;
-    const int rows_padded = (total + 255) & ~255;
-    int32_t *range = b->words + kPbWordRange, *list = b->words + kPbWordList;
-    if (launch_mars_conv16(b->frames, b->feat, m.conv1_w, m.conv1_b, m.conv2_w, m.conv2_b, b->act16, act_ld, total, range, list, c->stream) != 0 ||
-        launch_mars_dense1(b->act16, act_ld, b->w16, 2 * d.flat, m.dense1_b, b->hidden, rows_padded, d.flat, d.hidden, c->stream) != 0)
-        return fail(c, MMW_E_HIP, "mmw_estimate_posture: hipFuncSetAttribute(max dynamic LDS) failed on this device");
-    launch_mars_dense2(b->hidden, d.hidden, m.dense2_w, m.dense2_b, b->kp, total, d.hidden, c->stream);
-    HIPCHK(c, hipGetLastError());
-    const int rc = range_fixup_impl("mmw_mars_range_fixup", c->stream, b->frames, b->feat, list, total, m, b->fix_scratch, b->kp, range);
-    if (rc) return fail(c, rc, "mmw_estimate_posture: %s", mmw_last_error(nullptr));
-    launch_set_kp(c->dc, c->st, b->kp, b->owner, total, c->stream);
-    HIPCHK(c, hipGetLastError());
+    b->last_total[0] = total;
+    MMW_TRY(posture_band(c, b, 0, 0, total));
     if (n_rows) *n_rows = total;
     return MMW_OK;
 }

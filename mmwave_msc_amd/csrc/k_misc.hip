@@ -478,6 +478,11 @@ void launch_feat_scan(const DevCfg &cfg, const DevState &s, int32_t *row_off, hi
     hipLaunchKernelGGL(k_feat_count, dim3((cfg.n_scenes + 3) / 4), dim3(256), 0, st, cfg, s, row_off);
     hipLaunchKernelGGL(k_feat_scan, dim3(1), dim3(1024), 0, st, cfg, row_off);
 }
+// (the counts alone: the scan of a context with several posture models, k_feat_models.hip, follows)
+void launch_feat_count(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_feat_count, dim3((cfg.n_scenes + 3) / 4), dim3(256), 0, st, cfg, s, row_off);
+}
 void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner,
                      int32_t *uid, int cap, hipStream_t st, const int32_t *n_in, int32_t *total_out)
 {

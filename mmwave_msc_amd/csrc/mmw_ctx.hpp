@@ -35,16 +35,28 @@ constexpr int kTickets = 4;
 constexpr size_t kStatBytes = (size_t)kStatSlots * kStatWords * sizeof(unsigned long long);
 
 // mmw_posture_attach: the model, its split Dense-1 operand and the buffers of the batched CNN chain ([cap] rows, cap a multiple of 256)
+// mmw_posture_attach_models: the same with n_models models -- one split operand and one fix-up list each, everything else shared, the
+// rows of a call in one band per model.  mmw_posture_attach / _frames are its one-model case.
 struct PostureBatch {
-    mmw_posture_model model = {};
-    int frames = 3;                   // the model: 3 = define_CNN_3D, 1 = define_CNN (= the context's ring)
-    int32_t cap = 0;
+    int n_models = 1;
+    mmw_posture_model model[MMW_POSTURE_MODELS_MAX] = {};
+    void *w16[MMW_POSTURE_MODELS_MAX] = {};   // each model's split Dense-1 operand
+    int frames = 3;                   // the models: 3 = define_CNN_3D, 1 = define_CNN (= the context's ring)
+    int32_t cap = 0;                  // cap_rows: the most rows one call estimates, summed over the models
+    int32_t rows = 0;                 // rows of the shared buffers: pad256(cap), + 256 per model when there are several (every band starts on a multiple of 256)
     float *feat = nullptr, *hidden = nullptr, *kp = nullptr;
     int32_t *owner = nullptr, *uid = nullptr;
-    int32_t *words = nullptr;         // [0] the sticky range word, [1] the attach-time weight check, [2 ..] the fix-up list (2 + MMW_RANGE_FIXUP_CAP)
-    void *act16 = nullptr, *w16 = nullptr, *fix_scratch = nullptr;
-    int32_t *h_total = nullptr;       // pinned: the eligible-track total of the call in flight
+    int32_t *words = nullptr;         // [0] the sticky range word, [1] unused, [2 ..] a fix-up list (2 + MMW_RANGE_FIXUP_CAP) per model, then the attach-time weight check per model
+    void *act16 = nullptr, *fix_scratch = nullptr;
+    int32_t *h_total = nullptr;       // pinned [16]: the eligible-track total of the call in flight; several bands: totals[8] | bases[8]
     hipEvent_t total_ev = nullptr;
+    // the scene -> model map (MMW_POSTURE_NONE: no model estimates the scene): device words, host mirror
+    int32_t *d_map = nullptr;         // [S]
+    int32_t *d_groups = nullptr;      // [16] k_feat_scan_models' totals and bases
+    std::vector<int32_t> h_map;
+    bool grouped = false;             // more than one model, or a scene on MMW_POSTURE_NONE: mmw_estimate_posture runs the grouped scan and a chain per band
+    // the last mmw_estimate_posture: rows and first row of every band (mmw_posture_group_rows, mmw_posture_owners)
+    int32_t last_total[MMW_POSTURE_MODELS_MAX] = {}, last_base[MMW_POSTURE_MODELS_MAX] = {};
 };
 
 // What the three live-track exports (mmw_report_*, mmw_clouds_*, mmw_skeletons_*), the radar log (mmw_uart_log_*) and the training samples (mmw_samples_*) keep on the host: the device scratch of the call

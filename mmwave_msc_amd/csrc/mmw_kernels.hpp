@@ -42,6 +42,9 @@ void launch_dbscan_only(const DevCfg &cfg, const DevState &st, int UM, const dou
 void launch_normalize(const DevCfg &cfg, const mmw_scene_site *sites, const void *raw, bool f32, const int32_t *n_raw, double *out, int32_t *n_out, hipStream_t st);
 void launch_normalize_tlv(const DevCfg &cfg, const mmw_scene_site *sites, const uint8_t *packets, long long packets_bytes, const long long *tlv_offset, double half_bins, double doppler_res, double *out, int32_t *n_out, hipStream_t st);
 void launch_feat_scan(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st);
+void launch_feat_count(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st);
+// k_feat_models.hip: behind launch_feat_count, the offsets model by model (map: dev [S]; groups: dev [16] = totals[8] | bases[8])
+void launch_feat_scan_models(int S, int n_models, int none_off, const int32_t *map, int32_t *row_off, int32_t *groups, hipStream_t st);
 void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner, int32_t *uid, int cap, hipStream_t st, const int32_t *n_in = nullptr, int32_t *total_out = nullptr);
 void launch_set_kp_uid(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, const int32_t *uid, int n_rows, hipStream_t st);
 void launch_format_frames(const DevCfg &cfg, const double *frames, const int32_t *counts, const double *ref, float *feat, int B, hipStream_t st);
