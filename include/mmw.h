@@ -448,7 +448,10 @@ int mmw_features_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows);   /* waits
 /* Utils.relative_coordinates + Utils.format_single_frame (Utils.py:437-520) on caller
  * frames: frames[B][ring][64][8] fp64 (only rows [:64] matter, Utils.py:505-510),
  * counts[B][ring] valid rows (<= 0 rows: frame stays zero, Utils.py:493), ref[B][2] = (x, y)
- * subtracted from columns 0,1 -> feat[B][ring][8][8][5] fp32.  All dev pointers. */
+ * subtracted from columns 0,1 -> feat[B][ring][8][8][5] fp32.  All dev pointers.
+ * The 64 rows of a frame (pad rows of zeros included) are ordered by the fp64 relative x as
+ * np.argsort(kind="stable") orders them: rows of equal x (-0.0 == 0.0) keep their row order, rows whose x is NaN come
+ * behind all others, +inf included, in row order.  Every input row is written exactly once. */
 int mmw_format_frames(mmw_ctx *ctx, const double *frames, const int32_t *counts, const double *ref, float *feat, int32_t n_items);
 /* track.keypoints = frame_keypoints[i] (Tracking.py:733-734): kp[n_rows][57] fp32 dev. */
 int mmw_set_keypoints(mmw_ctx *ctx, const float *kp, const int32_t *owner, int32_t n_rows);

@@ -261,7 +261,8 @@ __global__ __launch_bounds__(256) void k_features_site(DevCfg cfg, const mmw_sce
 }
 
 // Utils.format_single_frame (+ relative_coordinates) on caller-provided frames:
-// frames[B][ring][64][8] fp64, counts[B][ring] (rows valid, <0 = frame absent), ref[B][2].
+// frames[B][ring][64][8] fp64, counts[B][ring] (rows valid, <0 = frame absent), ref[B][2].  The rows are the caller's own, so
+// an x may be NaN: those rows go behind all others in row order, as np.argsort puts them (sort_rows_store_nan_last).
 __global__ __launch_bounds__(256) void k_format_frames(DevCfg cfg, const double *__restrict__ frames, const int32_t *__restrict__ counts,
                                                        const double *__restrict__ ref, float *__restrict__ feat, int B)
 {
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(256) void k_format_frames(DevCfg cfg, const double 
         v3 = p[6] - 0;
         v4 = ((p[7] - 0) - cfg.intensity_mu) / cfg.intensity_std;
     }
-    sort_rows_store(lane, v0, v1, v2, v3, v4, feat + (size_t)item * 64 * 5);
+    sort_rows_store_nan_last(lane, v0, v1, v2, v3, v4, feat + (size_t)item * 64 * 5);
 }
 
 __global__ void k_set_kp(DevCfg cfg, DevState st, const float *__restrict__ kp, const int32_t *__restrict__ owner, int n_rows,

@@ -54,6 +54,10 @@ __device__ __forceinline__ void bitonic_sort64(int lane, double &key, int &src)
 // np.argsort(padded[:, 0]) (Utils.py:513) + the gather it drives: a bitonic network over
 // the wave on (x, row) -- ties ordered by row position -- then 5 fp32 stores per lane.  18 of its 21 steps exchange by DPP (partners inside a row of
 // 16 lanes); with every step three trips through the LDS crossbar the kernel was a chain of ds_bpermute latencies (118 us at 98 k sorts).
+// The keys must not be NaN: bitonic_step's `<` and `==` are both false on a NaN, so both lanes of a pair keep the same element and
+// the result is no permutation.  The callers that feed it from a track's ring (k_features, k_features_site) cannot meet one: the
+// gate refuses a row whose x is not finite, DBSCAN raises on one, so no ring frame holds such a row, and the centroid subtracted
+// from it is a mean of ring rows.  Caller data (k_format_frames) goes through sort_rows_store_nan_last.
 __device__ inline void sort_rows_store(int lane, double v0, double v1, double v2, double v3, double v4, float *dst)
 {
     double key = v0;
@@ -66,6 +70,24 @@ __device__ inline void sort_rows_store(int lane, double v0, double v1, double v2
     bitonic_merge<64, 32>(lane, key, src);
     const double s0 = __shfl(v0, src), s1 = __shfl(v1, src), s2 = __shfl(v2, src), s3 = __shfl(v3, src), s4 = __shfl(v4, src);
     // a lane's five values are 20 consecutive bytes: one 16-byte and one 4-byte store (4-byte aligned: global memory takes that)
+    struct __attribute__((packed, aligned(4))) F4 { float a, b, c, d; };
+    *reinterpret_cast<F4 *>(dst + lane * 5) = F4{(float)s0, (float)s1, (float)s2, (float)s3};
+    dst[lane * 5 + 4] = (float)s4;
+}
+
+// The same for keys that may be NaN, as np.argsort orders them: rows with a NaN x behind every other row, +inf included, in row
+// order.  A NaN key sorts as +inf with bit 6 of its row set (the tie rule then puts it behind a true +inf, and NaN rows among
+// themselves by row); the bit is masked off before the gather, which moves the row's own values, the NaN with them.  (A function
+// of its own, gather and stores repeated: sort_rows_store, which k_features runs every frame, compiles instruction for instruction
+// as it did -- sharing the gather cost it an instruction and a register.)
+__device__ inline void sort_rows_store_nan_last(int lane, double v0, double v1, double v2, double v3, double v4, float *dst)
+{
+    const bool nan = v0 != v0;
+    double key = nan ? __builtin_huge_val() : v0;
+    int src = (nan ? 64 : 0) | lane;
+    bitonic_sort64(lane, key, src);
+    src &= 63;
+    const double s0 = __shfl(v0, src), s1 = __shfl(v1, src), s2 = __shfl(v2, src), s3 = __shfl(v3, src), s4 = __shfl(v4, src);
     struct __attribute__((packed, aligned(4))) F4 { float a, b, c, d; };
     *reinterpret_cast<F4 *>(dst + lane * 5) = F4{(float)s0, (float)s1, (float)s2, (float)s3};
     dst[lane * 5 + 4] = (float)s4;

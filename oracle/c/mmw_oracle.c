@@ -999,8 +999,11 @@ int orc_get_track_ring_frame(const orc_scene *s, int t, int k, double *rows, int
 
 /* relative_coordinates + format_single_frame Utils.py:437-520, gathered over
  * tracks as TrackBuffer.estimate_posture does (Tracking.py:718-728).  Ties in x
- * are ordered by row position (np.argsort's default sort is not stable; ties
- * among real rows do not occur with continuous data, zero-pad rows are identical). */
+ * are ordered by row position: a stable sort (np.argsort's default sort is not
+ * stable, so the reference leaves the order open).  Ties among real rows are the
+ * normal case -- a radar x is int16 / 2^Q and one centroid is subtracted from all
+ * rows of a frame --, and a row on the centroid's x ties with the zero-pad rows:
+ * tests/_edge_inputs.py `feature_ties` holds the kernels to this order. */
 int orc_features(const orc_scene *s, float *feat, int32_t *owner)
 {
     const orc_config *c = &s->cfg;

@@ -16,7 +16,8 @@ The fuzz scenes see only what track() decided, and a random point sits about 1e1
                   d_A == d_B, and the FIRST track takes the row, in either order of the clusters
   equality_scenes `lifetime > lim`, `speed < tr_vel_thres`, the spread clamps and `spread > old`, `nj > N_est`,
                   `T < tr_max_tracks`, `total > model_min_input`, 64 | 65 and ring_rows | ring_rows + 1 rows in a frame, each
-                  with constants that make the equality exact in binary -- and asserted to be, here, on the oracle
+                  with constants that make the equality exact in binary -- and asserted to be, here, on the oracle; and
+                  `feature_ties`: equal x among a track's rows, and x equal to the centroid's, in the feature maps' sort
 
 Everything is seeded, fp64, built once, cached and read-only.  Rows of the input buffer at and beyond a frame's count are
 copies of rows that lie well inside a gate: a kernel that gates a row past n changes point_num and the centroid."""
@@ -587,6 +588,66 @@ def _ring_rows():
     return Equality(scene, check, feature_frames=(1, 2, 3, 4), ring_frames=(1, 2, 3, 4))
 
 
+def _tied_cluster(rng, centre, n, vel):
+    """_exact_cluster with TIES in x, as a radar's quantised x gives them: x drawn with repetition from the seven multiples of 2^-6
+    within 3 / 64 of the centre, every draw with its mirror image (and the centre itself once more where n is odd), so the sum of
+    x is n * centre exactly, the centroid's x is the centre, and the rows on the centre have relative x == 0 -- the pad rows' key.
+    y, z, doppler and intensity dyadic and DISTINCT per row: two rows of a tie group exchanged change the feature map."""
+    assert 8 <= n <= 80
+    o = rng.integers(-3, 4, size=n // 2)
+    o[:2] = 0, 3                                                      # rows on the centre, always
+    o = np.concatenate([o, -o, np.zeros(n % 2, dtype=o.dtype)])
+    p = np.zeros((n, 8))
+    p[:, 0] = centre[0] + o[rng.permutation(n)] / 64.0
+    p[:, 1] = centre[1] + rng.permutation(np.arange(-40, 40))[:n] / 512.0
+    p[:, 2] = centre[2] + rng.permutation(np.arange(-40, 40))[:n] / 512.0
+    p[:, 3:6] = vel
+    p[:, 6] = rng.permutation(np.arange(-40, 40))[:n] / 8.0
+    p[:, 7] = rng.permutation(np.arange(1, 200))[:n] / 2.0
+    assert np.sum(p[:, 0]) == n * centre[0]
+    return p
+
+
+def ties_by_larger_row(feat):
+    """A feature tensor of the stable sort re-ordered as a sort that breaks ties by the LARGER row would leave it: every run of
+    equal x reversed (the pad rows are the rows behind a frame's real ones)."""
+    out = np.array(feat, np.float32).reshape(-1, 64, 5)
+    for fr in out:
+        x = fr[:, 0]
+        start = 0
+        for i in range(1, 65):
+            if i == 64 or x[i] != x[start]:
+                fr[start:i] = fr[start:i][::-1].copy()
+                start = i
+    return out.reshape(np.shape(feat))
+
+
+def _feature_ties():
+    """The feature maps' sort on tied keys from live tracks: one static track takes 20, 40, 64 and 65 rows of _tied_cluster about
+    one centre.  In every feature map, every ring frame has real rows of equal relative x and real rows of relative x == 0, which
+    tie with the pad rows; ordered by row position (the oracle's insertion sort) and not by the larger row."""
+    rng = np.random.default_rng(19)
+    c, z = (0.0, 2.0, 1.0), (0.0, 0.0, 0.0)
+    sizes = (20, 40, 64, 65)
+    frames = [_tied_cluster(rng, c, m, z) for m in sizes]
+    scene = _scene("feature_ties", _FEATURE_KW, 128, frames, EQ_DT, frames[0])
+
+    def check(fr):
+        assert len(fr[0].owner) == 0                                  # 20 rows: not eligible yet
+        for f in (1, 2, 3):
+            assert fr[f].n_tracks == 1 and fr[f].tracks["point_num"][0] == sizes[f] and list(fr[f].owner) == [0]
+            assert list(fr[f].tracks["ring_n"][0][:2]) == [sizes[f - 1], sizes[f]] and fr[f].tracks["centroid"][0][0] == c[0]
+            feat = fr[f].feat.reshape(2, 64, 5)
+            for k in range(2):
+                real = feat[k][feat[k][:, 2] != 0]                    # (z is about 1 on a real row, 0 on a pad row)
+                assert len(real) == min(64, sizes[f - 1 + k]) and len({r.tobytes() for r in real}) == len(real)
+                vals, cnt = np.unique(real[:, 0], return_counts=True)
+                assert cnt.max() >= 2 and len(vals) >= 3, (f, k, vals, cnt)        # a tie group of real rows
+                assert np.any(real[:, 0] == 0), (f, k)                             # a real row that ties with the pad rows
+            assert not np.array_equal(ties_by_larger_row(fr[f].feat), fr[f].feat), f
+    return Equality(scene, check, feature_frames=(0, 1, 2, 3), ring_frames=(2, 3))
+
+
 def _tie_equality(order):
     tie = exact_tie(dict(EQ_KW, fb_frames_batch=0), 128, order)
     return Equality(tie.scene, functools.partial(check_exact_tie, tie))
@@ -597,7 +658,7 @@ def equality_scenes():
     """name -> Equality.  Each builder's constants make its equality exact in binary; that it is met is asserted here, on the
     oracle, before anything else uses the scene."""
     out = {"lifetimes": _lifetimes(), "speed": _speed(), "spread": _spread(), "n_est": _n_est(), "dbscan_trigger": _trigger(),
-           "all_taken": _all_taken(), "model_min_input": _min_input(), "ring_rows": _ring_rows(),
+           "all_taken": _all_taken(), "model_min_input": _min_input(), "ring_rows": _ring_rows(), "feature_ties": _feature_ties(),
            "exact_tie_AB": _tie_equality("AB"), "exact_tie_BA": _tie_equality("BA")}
     for eq in out.values():
         eq.check(replay(eq.scene))

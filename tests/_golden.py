@@ -10,7 +10,9 @@ Tolerances (stated once, used everywhere):
     one 64-row frame.  The reference sorts with np.argsort's default (unstable,
     CPU-dispatch dependent) algorithm (Utils.py:513), so the order of tied rows
     is not defined by the reference; this build orders ties by row position.
-    `canon_feat` sorts every tie group by the remaining columns on both sides.
+    `canon_feat` sorts every tie group by the remaining columns on both sides, after asserting that both sides ARE sorted by
+    x (assert_feat_equal).  Where both sides are this build's own stable sort -- GPU, C oracle, the numpy restatements -- the
+    comparison is by bits and ties are not open (assert_feat_identical): tests/_sort_inputs.py has the frames that tie.
 """
 import glob
 import json
@@ -96,23 +98,43 @@ def overrides_to_cfg_kwargs(over):
 
 
 def canon_feat(feat):
-    """Canonical order inside equal-x groups of every 64-row frame (see module docstring)."""
+    """Canonical order inside equal-x groups of every 64-row frame (see module docstring).  Column 0 of every frame must be
+    sorted already -- non-decreasing, NaN at the end --: a frame that is not is refused here, whatever its rows are; rows are then
+    re-ordered (by the remaining columns) only inside runs of equal x, the NaN rows being one such run."""
     f = np.asarray(feat, dtype=np.float32)
     if f.size == 0:
         return f
     flat = f.reshape(-1, 64, 5).copy()
     for b in range(flat.shape[0]):
         blk = flat[b]
-        order = np.lexsort((blk[:, 4], blk[:, 3], blk[:, 2], blk[:, 1], blk[:, 0]))
+        x = blk[:, 0]
+        isn = np.isnan(x)
+        n = 64 - int(isn.sum())
+        assert not isn[:n].any() and np.all(x[: n - 1] <= x[1:n]), f"frame {b}: column 0 is not sorted (non-decreasing, NaN last): {x.tolist()}"
+        order = np.lexsort((blk[:, 4], blk[:, 3], blk[:, 2], blk[:, 1], np.where(isn, 0, x), isn))   # (x is sorted: only tie groups move)
         flat[b] = blk[order]
     return flat.reshape(f.shape)
 
 
 def assert_feat_equal(got, want, ctx=""):
+    """Equal up to the order of rows inside groups of equal x: for comparisons with the REFERENCE, whose tie order is open.  Both
+    sides must be sorted by x."""
     got = np.asarray(got, dtype=np.float32)
     want = np.asarray(want, dtype=np.float32)
     assert got.shape == want.shape, f"{ctx}: feature shape {got.shape} != {want.shape}"
     # (equal_nan: a NaN doppler / peakVal of an assigned point travels into its track's feature map on both sides)
-    if np.array_equal(got, want, equal_nan=True):
-        return
     assert np.array_equal(canon_feat(got), canon_feat(want), equal_nan=True), f"{ctx}: feature tensor differs"
+
+
+def assert_feat_identical(got, want, ctx=""):
+    """Equal bit for bit, as uint32 -- a -0.0 in the wrong row, or two rows of a tie group exchanged, is a difference: for
+    comparisons where both sides are this project's own stable sort (GPU, C oracle, the numpy restatements).  A NaN equals a
+    NaN whatever its sign and payload, which no operation of either side promises."""
+    got = np.asarray(got, dtype=np.float32)
+    want = np.asarray(want, dtype=np.float32)
+    assert got.shape == want.shape, f"{ctx}: feature shape {got.shape} != {want.shape}"
+    same = (got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))
+    if not same.all():
+        bad = np.argwhere(~same)
+        raise AssertionError(f"{ctx}: feature tensor not bit-equal at {len(bad)} entries, first {bad[:6].tolist()}: got {got[tuple(bad[0])]!r} "
+                             f"want {want[tuple(bad[0])]!r}")

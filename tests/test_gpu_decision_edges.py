@@ -4,8 +4,9 @@ The fuzz and parity tests compare what track() decided; a random point sits some
 nearest `d_j < d_k`, so a gate distance d = log|det C| + y'C^-1 y that is wrong in its last bits passes them all.  These scenes
 put rows on the surface itself -- pairs of ADJACENT doubles the oracle decides differently, run under five adjacent gates --, on
 exact ties between tracks, and on the equality side of `lifetime > lim`, `speed < tr_vel_thres`, the spread clamps, `nj > N_est`,
-`T < tr_max_tracks`, `total > model_min_input`, 64 | 65 and ring_rows | ring_rows + 1 rows.  That the inputs are that sharp is
-shown without a GPU in tests/test_edge_inputs.py.
+`T < tr_max_tracks`, `total > model_min_input`, 64 | 65 and ring_rows | ring_rows + 1 rows, and (`feature_ties`) on equal x among
+a track's rows and x equal to the centroid's in the feature maps' sort.  That the inputs are that sharp is shown without a GPU
+in tests/test_edge_inputs.py.
 
 NO expected value in this file comes from a GPU call: every `want` is oracle.c_oracle.OracleScene's on the same rows under the
 context's own tr_gate.  Everything is compared by bits after every frame: association, labels, db_n, the track list, the global

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from tests._golden import (GOLDEN, assert_feat_equal, assert_tracks_match, load_scenario,
+from tests._golden import (GOLDEN, assert_feat_equal, assert_feat_identical, assert_tracks_match, load_scenario,
                            overrides_to_cfg_kwargs, scenario_names, scenario_tol)
 
 pytestmark = pytest.mark.gpu
@@ -112,7 +112,7 @@ def test_golden_scenario(name):
             assert np.array_equal(owner[:, 1], g["owner"][f, :nf]) and np.all(owner[:, 0] == 0)
             assert_feat_equal(feat, g["feat"][f, :nf], ctx=f"{name} f{f}")
             o_feat, o_own = orc.features()
-            assert np.array_equal(feat, o_feat, equal_nan=True), f"{name} f{f}: features vs oracle"
+            assert_feat_identical(feat, o_feat, ctx=f"{name} f{f}: features vs oracle")   # (both order ties by row position)
     sb.close()
 
 

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests import _sample_ref as ref
+from tests._golden import canon_feat
 from tests._layouts import LAYOUTS, make_checked
 from tests._report_scenes import CFG_KW, F, N, S, scenario
 
@@ -389,9 +390,9 @@ def test_three_experiments_through_one_context(tmp_path):
         # the CNN inputs: the reference's, modulo the order inside groups of equal x (np.argsort leaves it open)
         want = gold["fmt_mmwave"]
         assert feats.dtype == np.float32 and feats.shape == want.shape
-        key = lambda a: np.array([r[np.lexsort(r.T[::-1])] for r in a.reshape(-1, 64, 5)])
+        # (canon_feat: both sides sorted by x, rows re-ordered inside runs of equal x only)
         assert np.array_equal(feats.reshape(-1, 64, 5)[:, :, 0], want.reshape(-1, 64, 5)[:, :, 0].astype(np.float32))
-        assert np.array_equal(key(feats), key(want.astype(np.float32)))
+        assert np.array_equal(canon_feat(feats), canon_feat(want.astype(np.float32)))
     alone = tmp_path / "alone"
     (alone / "kinect").mkdir(parents=True)
     p1, i1, c1 = dataset.preprocess_experiment(jobs[1][0], jobs[1][1], str(alone / "mmWave"), str(alone / "kinect" / "A1.csv"),
@@ -402,3 +403,31 @@ def test_three_experiments_through_one_context(tmp_path):
     assert open(jobs[1][3], "rb").read() == open(alone / "kinect" / "A1.csv", "rb").read()
     assert np.array_equal(np.load(jobs[1][4]), np.load(alone / "c.npy")) and len(feats) == len(cen)
     assert res[0][1] != invalid
+
+
+# 10 -----------------------------------------------------------------------------------------------------------------------
+def test_the_cnn_input_of_tied_rows_is_ordered_by_row_position():
+    """MMW_SAMPLE_INPUT from the `feature_ties` scene of tests/_edge_inputs.py: the newest frame's rows share a handful of x, some
+    of them the centroid's own, and tests/_sample_ref.py's rule -- (all-zero, row position) under a stable sort -- decides every
+    byte.  Expected values from the oracle's ring frames and centroid; a sort that breaks ties by the larger row differs on every
+    frame (asserted on the expectation)."""
+    from mmwave_msc_amd import _lib
+    from mmwave_msc_amd.batch import SceneBatch
+    from tests import _edge_inputs as ei
+    sc = ei.equality_scenes()["feature_ties"].scene
+    want_frames = ei.replay(sc)
+    sb = SceneBatch(_lib.default_config(**sc.cfg), 1, sc.max_pts)
+    mean, std = sb.cfg.intensity_mu, sb.cfg.intensity_std
+    for f in range(len(sc.cnt)):
+        sb.step_host(sc.pts[f][None], sc.cnt[f: f + 1], sc.dt[f: f + 1])
+        w = want_frames[f]
+        assert w.n_tracks == 1 and w.tracks["lifetime"][0] == 0
+        want = ref.input_of(ref.block_of(w.rings[0], w.tracks["centroid"][0][:2]), mean, std)
+        x = want.reshape(64, 5)[:, 0]
+        real = want.reshape(64, 5)[:, 2] != 0
+        assert real.sum() == min(64, int(sc.cnt[f])) and np.unique(x[real]).size < real.sum() // 2 and np.any(x[real] == 0)
+        assert not np.array_equal(ei.ties_by_larger_row(want), want)
+        d, feats = sb.samples_host(inputs=True)
+        assert len(d) == 1 and feats.shape == (1, 8, 8, 5) and feats.dtype == np.float32
+        assert feats[0].view(np.uint32).tobytes() == want.view(np.uint32).tobytes(), f
+    sb.close()

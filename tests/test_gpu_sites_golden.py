@@ -83,7 +83,7 @@ def test_feature_maps_under_recorded_sites_meet_the_pinned_restatement():
     tests/test_sites_golden.py -- of that track's own ring frames, taken relative to its centroid (relative_coordinates,
     Utils.py:455-463), under the SCENE's intensity scale; and not under the context's, where the two differ."""
     from mmwave_msc_amd.synth import make_batch
-    from tests._golden import assert_feat_equal
+    from tests._golden import assert_feat_identical
     from tests.test_sites_golden import format_single_frame_np
     g, kws, sb = _ctx(256)
     S, N, F = N_SITES, 256, 8
@@ -105,10 +105,51 @@ def test_feature_maps_under_recorded_sites_meet_the_pinned_restatement():
             fr[:, 1] -= rec["centroid"][1]
             frames.append(fr)
         want = format_single_frame_np(frames, kws[s]["intensity_mu"], kws[s]["intensity_std"]).astype(np.float32)
-        assert_feat_equal(feat[row], want, ctx=f"scene {s} track {j}")
+        assert_feat_identical(feat[row], want, ctx=f"scene {s} track {j}")   # (both sides order ties by row position)
         ctx_scale = format_single_frame_np(frames, sb.cfg.intensity_mu, sb.cfg.intensity_std).astype(np.float32)
         if (kws[s]["intensity_mu"], kws[s]["intensity_std"]) != (sb.cfg.intensity_mu, sb.cfg.intensity_std):
             assert not np.array_equal(ctx_scale, want)
             other += 1
     assert other >= 1
+    sb.close()
+
+
+def test_tied_feature_maps_under_a_scene_intensity_scale():
+    """k_features_site on the `feature_ties` scene of tests/_edge_inputs.py (rows of equal x, rows on the centroid's x): two scenes
+    fed the same frames, scene 0 under the context's intensity scale and scene 1 under its own.  After every frame each feature
+    tensor equals, bit for bit, format_frames_ref of the ORACLE's ring frames and centroid under the scene's scale; scene 0's is
+    the oracle's own tensor, and scene 1's differs from it in the intensity column alone -- the same tied order."""
+    from mmwave_msc_amd import _lib
+    from mmwave_msc_amd.batch import SceneBatch
+    from tests import _edge_inputs as ei
+    from tests._golden import assert_feat_identical
+    from tests._sort_inputs import MU, STD, format_frames_ref
+    sc = ei.equality_scenes()["feature_ties"].scene
+    want_frames = ei.replay(sc)
+    S = 2
+    sb = SceneBatch(_lib.default_config(**sc.cfg), S, sc.max_pts)
+    mu, std = [sb.cfg.intensity_mu, MU], [sb.cfg.intensity_std, STD]
+    assert (mu[0], std[0]) != (mu[1], std[1])
+    sb.set_sites(_lib.make_sites(sb.cfg, S, intensity_mu=mu, intensity_std=std))
+    assert sb.has_sites
+    ring, seen = sb.ring, 0
+    for f in range(len(sc.cnt)):
+        sb.step_host(np.stack([sc.pts[f]] * S), np.full(S, sc.cnt[f], np.int32), np.full(S, sc.dt[f]))
+        feat, owner = sb.features_host()
+        w = want_frames[f]
+        assert owner.tolist() == [[s, 0] for s in range(S) for _ in w.owner], f
+        if len(owner) == 0:
+            continue
+        frames, counts = np.zeros((1, ring, 64, 8)), np.full((1, ring), -1, np.int32)
+        for k, rows in enumerate(w.rings[0]):
+            m = min(64, len(rows))
+            frames[0, k, :m], counts[0, k] = rows[:m], w.tracks["ring_n"][0][k]
+        for s in range(S):
+            want = format_frames_ref(frames, counts, w.tracks["centroid"][0][:2], mu[s], std[s], ring)
+            assert_feat_identical(feat[s].reshape(ring, 64, 5), want[0], ctx=f"frame {f} scene {s}")
+        assert_feat_identical(feat[0], w.feat[0], ctx=f"frame {f}: the context's scale is the oracle's")
+        assert np.array_equal(feat[1][..., :4], feat[0][..., :4]) and not np.array_equal(feat[1][..., 4], feat[0][..., 4])
+        assert not np.array_equal(ei.ties_by_larger_row(w.feat[0]), w.feat[0])
+        seen += 1
+    assert seen == 3
     sb.close()
