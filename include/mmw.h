@@ -634,6 +634,79 @@ int mmw_skeletons(mmw_ctx *ctx, mmw_skeleton *out, int32_t cap, int32_t mode, in
  * tables are static; either pointer may be NULL. */
 int mmw_skeleton_tables(const int32_t **connections, const int32_t **joint_class);
 
+/* ---- zones ----
+ * Which part of the room is occupied, by whom, and who walked in or out since the last look: per scene up to MMW_ZONES_MAX
+ * axis-aligned rectangles in the scene's normalised frame, per defined zone a row of counts, and every change of a track's zone
+ * membership as an event carrying the track's uid -- decided on the device from the fp64 track state, in ONE call, with a hysteresis
+ * margin, so that a person standing on a boundary does not flicker between zones on the filter's jitter.
+ *
+ * Setting zones follows mmw_set_sites' rules.  mmw_set_zones gives scene scenes[i] (scenes == NULL: scene i) the first n_zones[i]
+ * entries of zones[i][MMW_ZONES_MAX] as its zones 0 .. n_zones[i] - 1; entries past n_zones[i] are not read.  The first call
+ * allocates the table -- every scene at 0 zones -- and the baseline below; scenes never listed keep what they have.  Every check is
+ * made on the host before anything changes, the new table then travels as ONE copy ordered on the context's stream (exports queued
+ * before the call read the old table), and the call is synchronous.  Refusal is atomic -- MMW_E_ARG, the message names the entry,
+ * nothing changes, nothing is allocated: n < 0 or n > n_scenes, a NULL array with n > 0, an index out of range or listed twice,
+ * n_zones[i] outside 0 .. MMW_ZONES_MAX, a NaN bound, x0 > x1 or y0 > y1, a margin that is negative or not finite, a non-zero
+ * reserved_.  Infinite bounds are allowed (half planes, strips).  Zones belong to the slot, like a site: mmw_reset* keeps them, a
+ * snapshot blob does not carry them (format version 1 is unchanged) and mmw_restore leaves the destination's zones alone.
+ * mmw_get_zones copies the host mirror (no device access; either output may be NULL; a context without a table: 0 zones
+ * everywhere, zeroed entries; entries past a scene's n_zones are zero).  mmw_clear_zones waits for the stream and frees table and
+ * baseline: the context then launches exactly what a context that never had zones launches, and the export entries return
+ * MMW_E_ARG again, as they do before the first mmw_set_zones.  mmw_has_zones: 1 while a table exists, else 0.
+ *
+ * Membership.  p = (x[0], x[1]) of the track's fp64 state (mmw_track_record.x; the same for dim_x 6 and 9).
+ *   core(z) = x0 <= px && px < x1 && y0 <= py && py < y1
+ *   wide(z) = the same test with x0 - margin, x1 + margin, y0 - margin, y1 + margin: ONE fp64 operation per bound
+ * A track is a member of zone z now iff it was a member at the previous export and wide(z), or it was not and core(z).  "Was a
+ * member": the scene's baseline, of the same generation, holds its uid with z's bit.  A NaN coordinate makes every comparison
+ * false: the track is in no zone.  Zones may overlap; a track can be a member of several.
+ *
+ * Baseline.  Per scene the context keeps the uid list of the previous SUCCESSFUL export with a 16-bit membership mask per uid, its
+ * length, and a generation and a seen-generation word: the report's mechanism, but the zones' own state -- reports need not be
+ * enabled, and the two are consumed at different times.  The baseline starts empty, so a track already inside gets its
+ * MMW_ZEV_ENTER at the first export: the event stream is complete, folding it gives the roster.  mmw_reset, mmw_reset_scenes and
+ * mmw_restore bump the generation of the scenes they touch (uids restart there), and mmw_set_zones that of the scenes it lists
+ * (their bits change meaning) -- one kernel, launched only while a table exists.  The next export of a bumped scene emits ONE
+ * MMW_ZEV_REBASED (uid -1, zone -1, id -1, slot = live tracks now: every earlier membership of the scene is void), no
+ * MMW_ZEV_LEAVE, evaluates membership with core alone, and emits the MMW_ZEV_ENTERs of that membership.
+ *
+ * Events are ordered by scene; inside a scene MMW_ZEV_REBASED first, then MMW_ZEV_LEAVE in baseline order -- zones ascending inside
+ * a track, slot = the track's position then --, then MMW_ZEV_ENTER in effective_tracks order, zones ascending, slot = its position
+ * now.  A baseline uid that is no longer live leaves every zone it was in.  Like the report this is a DIFFERENCE OF STATES, not a
+ * log: a track that entered and left between two exports appears in neither.
+ * Rows: one per DEFINED zone, in (scene, zone) order; count = members now, count_static = those with is_static, entered / left =
+ * this call's MMW_ZEV_ENTER / MMW_ZEV_LEAVE events of the zone; scene is offset by scene_base, as the events' is.
+ *
+ * Capacity, tickets and arguments are mmw_report_*'s.  Capacity is decided on the DEVICE against both caps: if the rows exceed
+ * cap_rows or the events exceed cap_events, nothing is written into either buffer, the baseline and the generations stay as they
+ * were, and mmw_zones_wait returns MMW_E_CAPACITY with both counts needed: a retry with larger buffers loses nothing.
+ * mmw_zones_async queues its kernels on the context's stream behind whatever was queued last (normally the frame's mmw_step); the
+ * counts follow into pinned memory and mmw_zones_wait(ticket) waits for THAT copy only.  ticket in [0,4), ticket 3 is mmw_zones'
+ * own.  rows / events: dev pointers, 4-byte aligned.  MMW_E_ARG, nothing touched: a NULL context, no zone table, a NULL buffer
+ * with a positive cap, a negative cap, a misaligned buffer, a bad ticket, a wait for a ticket with nothing outstanding.
+ * No step kernel reads any of this: a context that never defines a zone launches exactly what it did before zones existed. */
+#define MMW_ZONES_MAX 16
+typedef struct mmw_zone {          /* 48 bytes */
+    double x0, x1, y0, y1;         /* [x0, x1) x [y0, y1) in the scene's normalised frame: the frame of mmw_track_record.x[0], x[1] */
+    double margin;                 /* >= 0: hysteresis, above */
+    int32_t id;                    /* the caller's label, copied into rows and events */
+    int32_t reserved_;             /* must be 0 */
+} mmw_zone;
+typedef struct mmw_zone_row   { int32_t scene, zone, id, count, count_static, entered, left, reserved_; } mmw_zone_row;   /* 32 bytes */
+typedef struct mmw_zone_event { int32_t scene, uid, kind, zone, id, slot; } mmw_zone_event;                              /* 24 bytes */
+#define MMW_ZEV_ENTER 1     /* uid is a member of the zone now and was not at the previous export; slot = its position now */
+#define MMW_ZEV_LEAVE 2     /* uid was a member at the previous export and is not now (or is not live any more); slot = its position then */
+#define MMW_ZEV_REBASED 3   /* every earlier membership of the scene is void; uid = zone = id = -1, slot = live tracks now */
+int mmw_set_zones(mmw_ctx *ctx, const int32_t *scenes, int32_t n, const int32_t *n_zones /* host [n] */, const mmw_zone *zones /* host [n][MMW_ZONES_MAX] */);
+int mmw_get_zones(mmw_ctx *ctx, int32_t *n_zones /* host [S] */, mmw_zone *zones /* host [S][MMW_ZONES_MAX] */);   /* host mirror, no device access */
+int mmw_clear_zones(mmw_ctx *ctx);
+int mmw_has_zones(mmw_ctx *ctx);
+int mmw_zones_async(mmw_ctx *ctx, mmw_zone_row *rows, int32_t cap_rows, mmw_zone_event *events, int32_t cap_events, int32_t scene_base,
+                    int32_t ticket);
+int mmw_zones_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n_events);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_zones(mmw_ctx *ctx, mmw_zone_row *rows, int32_t cap_rows, mmw_zone_event *events, int32_t cap_events, int32_t scene_base,
+              int32_t *n_rows, int32_t *n_events);                                      /* async + wait */
+
 /* Snapshot / restore of scene state (format version 1).
  *
  * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global

@@ -37,7 +37,7 @@ POSTURE_MODELS_MAX = 8             # models one mmw_posture_attach_models call t
 POSTURE_NONE = -1                  # MMW_POSTURE_NONE: the map entry of a scene no model estimates
 EXPORT_TICKETS = 4                 # kTickets (csrc/mmw_ctx.hpp): `*_async` calls of one export that may be outstanding; the
                                    # one-call form of each export (mmw_report, mmw_clouds, ...) uses the last ticket itself
-REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
+REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
 
 EMPTY_FRAME = -1   # MMW_EMPTY_FRAME (include/mmw.h)
 BAD_FRAME = -3     # MMW_BAD_FRAME: n_out of mmw_normalize_tlv for a TLV body it refused to decode
@@ -171,6 +171,16 @@ SKEL_SKIPPED = 1                              # MMW_SKEL_SKIPPED: bit 0 of mmw_s
 SKEL_ALL, SKEL_DRAWN = 0, 1                   # MMW_SKEL_*: the mode of mmw_skeletons_*
 SKEL_CLASS_NAMES = ("blue", "green", "red")   # mmw_skeleton_tables' joint classes as the reference's colour names
 
+# struct mmw_zone / mmw_zone_row / mmw_zone_event (include/mmw.h): a scene's zones (48 bytes each), and the rows (32 bytes) and
+# events (24 bytes) of mmw_zones_*
+ZONES_MAX = 16                                # MMW_ZONES_MAX: zones per scene
+ZONE_FIELDS = ("x0", "x1", "y0", "y1", "margin", "id")
+ZONE_DTYPE = np.dtype([("x0", "f8"), ("x1", "f8"), ("y0", "f8"), ("y1", "f8"), ("margin", "f8"), ("id", "i4"), ("reserved_", "i4")], align=True)
+ZONE_ROW_DTYPE = np.dtype([("scene", "i4"), ("zone", "i4"), ("id", "i4"), ("count", "i4"), ("count_static", "i4"), ("entered", "i4"),
+                           ("left", "i4"), ("reserved_", "i4")], align=True)
+ZONE_EVENT_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("kind", "i4"), ("zone", "i4"), ("id", "i4"), ("slot", "i4")], align=True)
+ZEV_ENTER, ZEV_LEAVE, ZEV_REBASED = 1, 2, 3   # MMW_ZEV_*: mmw_zone_event.kind
+
 
 # C struct name in include/mmw.h -> its Python mirror; every `typedef struct mmw_*` but the opaque mmw_ctx.  Field names are the
 # header's own throughout, so a mirror needs no second spelling beside it.
@@ -178,6 +188,7 @@ ABI_STRUCTS = {
     "mmw_config": MmwConfig, "mmw_track_record": TRACK_DTYPE, "mmw_track_summary": SUMMARY_DTYPE, "mmw_scene_site": SITE_DTYPE,
     "mmw_posture_model": MmwPostureModel, "mmw_track_report": TRACK_REPORT_DTYPE, "mmw_track_event": TRACK_EVENT_DTYPE,
     "mmw_cloud_track": CLOUD_TRACK_DTYPE, "mmw_cloud_point": CLOUD_POINT_DTYPE, "mmw_skeleton": SKELETON_DTYPE,
+    "mmw_zone": ZONE_DTYPE, "mmw_zone_row": ZONE_ROW_DTYPE, "mmw_zone_event": ZONE_EVENT_DTYPE,
     "mmw_snapshot_header": MmwSnapshotHeader, "mmw_snapshot_entry": MmwSnapshotEntry, "mmw_snapshot_info": MmwSnapshotInfo,
     "mmw_uart_cfg": MmwUartCfg, "mmw_uart_frame": UART_FRAME_DTYPE, "mmw_uart_object": UART_OBJECT_DTYPE,
     "mmw_sample_entry": SAMPLE_ENTRY_DTYPE,
@@ -282,6 +293,13 @@ def _signatures():
         "mmw_skeletons_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_skeletons": (C.c_int, [vp, vp, i32, i32, i32, i32p, i32p]),
         "mmw_skeleton_tables": (C.c_int, [C.POINTER(i32p), C.POINTER(i32p)]),
+        "mmw_set_zones": (C.c_int, [vp, vp, i32, vp, vp]),
+        "mmw_get_zones": (C.c_int, [vp, vp, vp]),
+        "mmw_clear_zones": (C.c_int, [vp]),
+        "mmw_has_zones": (C.c_int, [vp]),
+        "mmw_zones_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
+        "mmw_zones_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_zones": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
         "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
         "mmw_uart_close": (C.c_int, [vp]),
         "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),
@@ -488,3 +506,31 @@ def make_sites(cfg: MmwConfig, n: int, **columns) -> np.ndarray:
         else:
             raise AttributeError(f"mmw_scene_site has no field {k!r}")
     return sites
+
+
+def make_zones(per_scene):
+    """(n_zones int32[n], zones ZONE_DTYPE[n, ZONES_MAX]) for `mmw_set_zones` from one list per scene of up to ZONES_MAX zones, each
+    a dict with keys of ZONE_FIELDS (`margin` and `id` may be left out: 0, and the zone's index) or a tuple
+    (x0, x1, y0, y1[, margin[, id]]).  Entries past a scene's zones stay zero."""
+    per_scene = list(per_scene)
+    n_zones = np.zeros(len(per_scene), np.int32)
+    zones = np.zeros((len(per_scene), ZONES_MAX), ZONE_DTYPE)
+    for i, zs in enumerate(per_scene):
+        zs = list(zs)
+        if len(zs) > ZONES_MAX:
+            raise ValueError(f"make_zones: scene entry {i} has {len(zs)} zones, at most {ZONES_MAX} fit")
+        n_zones[i] = len(zs)
+        for k, z in enumerate(zs):
+            if isinstance(z, dict):
+                unknown = set(z) - set(ZONE_FIELDS)
+                if unknown:
+                    raise AttributeError(f"mmw_zone has no field {sorted(unknown)[0]!r}")
+                vals = [z[f] for f in ZONE_FIELDS[:4]] + [z.get("margin", 0.0), z.get("id", k)]
+            else:
+                z = tuple(z)
+                if not 4 <= len(z) <= 6:
+                    raise ValueError(f"make_zones: a zone is (x0, x1, y0, y1[, margin[, id]]), not {len(z)} values")
+                vals = list(z) + [0.0, k][len(z) - 4:]
+            for f, v in zip(ZONE_FIELDS, vals):
+                zones[i, k][f] = v
+    return n_zones, zones

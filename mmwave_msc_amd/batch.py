@@ -872,6 +872,66 @@ class SceneBatch:
         return self._export_host("skeletons", lambda ptr, cap, ticket: self.skeletons_dev(ptr, cap, mode, ticket, scene_base),
                                  self.L.mmw_skeletons_wait, ("skeletons", _lib.SKELETON_DTYPE))[0]
 
+    # -- zone occupancy -------------------------------------------------------
+    def set_zones(self, zones, scenes=None):
+        """mmw_set_zones: give `scenes` (default: scenes 0 .. len(zones)-1) their zones -- `zones` is what `_lib.make_zones` takes (a
+        list per scene of dicts or tuples) or its result, the pair (n_zones, ZONE_DTYPE[n, 16]).  Scenes never listed keep what they
+        have; the listed scenes' memberships are void (their next export starts with a ZEV_REBASED).  Refused (MmwError, E_ARG) with
+        nothing changed for an index out of range or listed twice, more entries than scenes, a NaN bound, x0 > x1 or y0 > y1, a
+        margin that is negative or not finite, or a non-zero `reserved_`."""
+        if isinstance(zones, tuple) and len(zones) == 2 and isinstance(zones[1], np.ndarray) and zones[1].dtype == _lib.ZONE_DTYPE:
+            nz, zt = zones
+        else:
+            nz, zt = _lib.make_zones(zones)
+        nz = np.ascontiguousarray(np.asarray(nz, dtype=np.int32).reshape(-1))
+        zt = np.ascontiguousarray(zt.reshape(-1, _lib.ZONES_MAX))
+        if len(nz) != len(zt):
+            raise ValueError(f"set_zones: {len(nz)} counts for {len(zt)} scenes' zones")
+        idx = None
+        if scenes is not None:
+            idx = np.ascontiguousarray(np.asarray(scenes, dtype=np.int32).reshape(-1))
+            if len(idx) != len(nz):
+                raise ValueError(f"set_zones: {len(nz)} entries for {len(idx)} scenes")
+        self._chk(self.L.mmw_set_zones(self.h, idx.ctypes.data if idx is not None else None, len(nz), nz.ctypes.data if len(nz) else None,
+                                       zt.ctypes.data if len(nz) else None))
+
+    def zones(self):
+        """mmw_get_zones: (n_zones int32[S], zones ZONE_DTYPE[S, 16]) of every scene, from the host mirror; zero past a scene's zones."""
+        nz = np.zeros(self.S, dtype=np.int32)
+        zt = np.zeros((self.S, _lib.ZONES_MAX), dtype=_lib.ZONE_DTYPE)
+        self._chk(self.L.mmw_get_zones(self.h, nz.ctypes.data, zt.ctypes.data))
+        return nz, zt
+
+    def clear_zones(self):
+        """mmw_clear_zones: waits for the stream and frees table and baseline; the context launches what one without zones does."""
+        self._chk(self.L.mmw_clear_zones(self.h))
+
+    @property
+    def has_zones(self) -> bool:
+        rc = int(self.L.mmw_has_zones(self.h))
+        if rc < 0:
+            self._chk(rc)
+        return rc == 1
+
+    def zones_async(self, rows_ptr, cap_rows: int, events_ptr, cap_events: int, scene_base: int = 0, ticket: int = 0):
+        """mmw_zones_async: one `_lib.ZONE_ROW_DTYPE` row per defined zone in (scene, zone) order and the `_lib.ZONE_EVENT_DTYPE`
+        membership changes since the previous export into device buffers, queued behind the last step on the context's stream --
+        no host wait.  Tickets 0 .. 3 (`zones_host` uses 3)."""
+        self._chk(self.L.mmw_zones_async(self.h, rows_ptr, int(cap_rows), events_ptr, int(cap_events), int(scene_base), int(ticket)))
+
+    def zones_wait(self, ticket: int = 0):
+        """(n_rows, n_events) of the `zones_async` call with this ticket: waits for its counts only, not for the stream.  Buffers
+        too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written and the baseline is
+        unchanged, so the same export can be asked for again with room."""
+        return self._export_wait(self.L.mmw_zones_wait, ticket)
+
+    def zones_host(self, scene_base: int = 0):
+        """The zone export as two structured arrays: (rows[n_rows] ZONE_ROW_DTYPE, events[n_events] ZONE_EVENT_DTYPE); fold the events
+        with `zones.Roster`.  The buffers grow to what the device says it needs (a refused export loses nothing)."""
+        self._export_caps.setdefault("zones", (64, 64))   # (its entry exists from the first call on: a context without zones keeps the four it had)
+        return self._export_host("zones", lambda *a: self.zones_async(*a[:4], scene_base, a[4]), self.L.mmw_zones_wait,
+                                 ("zone_rows", _lib.ZONE_ROW_DTYPE), ("zone_events", _lib.ZONE_EVENT_DTYPE))
+
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):
         if scenes is None:

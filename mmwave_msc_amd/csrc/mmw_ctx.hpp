@@ -122,6 +122,11 @@ struct mmw_ctx {
     ExportCtx cloud;                  // mmw_clouds_*: allocated by the first call; not allocated = never called, nothing of it exists
     ExportCtx skel;                   // mmw_skeletons_*: allocated by the first call; not allocated = never called, nothing of it exists
     ExportCtx sample;                 // mmw_samples_*: allocated by the first call; not allocated = never called, nothing of it exists
+    ExportCtx zone;                   // mmw_set_zones allocates it, mmw_clear_zones frees it; not allocated = no zone table, nothing of it is launched
+    ZoneState zs = {};                // ... the zones' baseline, in front of zone's scratch in zone.d_block (zs.sc = zone.sc)
+    char *d_ztab = nullptr;           // ... the table as ONE copy lands in it: [S][MMW_ZONES_MAX] mmw_zone | [S] n_zones | [S] the call's scene flags
+    std::vector<mmw_zone> h_zones;    // host mirror of the table ([S][MMW_ZONES_MAX], zero past a scene's n_zones) ...
+    std::vector<int32_t> h_nzones;    // ... and of n_zones [S] (mmw_get_zones reads both)
     ExportCtx ulog_x;                 // mmw_uart_log_enable; not allocated = the radar log is off and mmw_uart_read launches what it always did
     UartLog ulog = {};                // ... the staged frames, in front of ulog_x's scratch in ulog_x.d_block
     std::vector<double> uart_range;   // [S] rangeIdxToMeters of the open readers (the log's range column)
@@ -142,6 +147,8 @@ int read_headers(mmw_ctx *c, std::vector<SceneHdr> &h);            // api_query.
 int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q);   // api_query.hip
 void posture_batch_free(PostureBatch *b);                          // api_posture.hip
 int report_rebase(mmw_ctx *c, const int32_t *dev_flags);           // api_report.hip: the scenes' uids restart (no-op while reports are off)
+int zone_rebase(mmw_ctx *c, const int32_t *dev_flags);             // api_zone.hip: the scenes' zone memberships are void (no-op while no zone table exists)
+void zone_free(mmw_ctx *c);                                        // api_zone.hip: table, baseline and mirrors (the caller has waited for the stream)
 int uart_log_rearm(mmw_ctx *c);                                    // api_uart_log.hip: every scene's log word as new, with its range scale (no-op while the log is off)
 void uart_log_free(mmw_ctx *c);                                    // api_uart_log.hip: ... and the log is off (the caller has waited for the stream)
 // api_export.hip: the ticketed counts of the three live-track exports (`name`: the entry the messages speak for)

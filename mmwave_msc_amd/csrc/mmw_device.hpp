@@ -187,6 +187,7 @@ struct DevState {
 // The scratch of one live-track export's call in flight (k_report.hip, k_cloud.hip, k_skeleton.hip; scanned by k_scan.hip).  All
 // device memory; nothing is kept between two calls.  What the two counts are:
 //   report     rows, events          clouds     directory entries, points          skeletons  emitted entries, live tracks
+//   zones      rows (defined zones), events
 struct ExportScratch {
     int32_t *off;         // [2][S + 1] the two counts per scene, scanned in place into offsets; [S] = the total
     int32_t *totals;      // [4] the two totals (saturated at INT32_MAX), 1 = both fit the caller's capacities (the device's decision), 0
@@ -198,6 +199,18 @@ struct ReportState {
     int32_t *gen;         // [S] generation of the scene's uids: bumped by mmw_reset / mmw_reset_scenes / mmw_restore (uids restart there)
     int32_t *seen;        // [S] the generation the baseline was taken in
     ExportScratch sc;     // rows / events of the report in flight
+};
+// mmw_set_zones: the zone table and what the zone export keeps between two exports (k_zone.hip).  All device memory.  The baseline is
+// the report's mechanism but the zones' own words: reports need not be enabled, and the two are consumed at different times.
+struct ZoneState {
+    const mmw_zone *zones;     // [S][MMW_ZONES_MAX] the table (one copy of mmw_set_zones; read with scalar loads)
+    const int32_t *n_zones;    // [S] zones defined per scene, behind the table in the same allocation
+    int32_t *base_uid;         // [S][t_cap] the uids live at the previous successful export, in effective_tracks order as it was then
+    int32_t *base_mask;        // [S][t_cap] ... and the zones each was a member of: bit z = zone z
+    int32_t *base_len;         // [S] ... and how many
+    int32_t *gen;              // [S] generation: bumped by mmw_reset / mmw_reset_scenes / mmw_restore and by mmw_set_zones for the scenes it lists
+    int32_t *seen;             // [S] the generation the baseline was taken in
+    ExportScratch sc;          // rows / events of the export in flight
 };
 
 // The live list of scene s, as every export walks it: T = live_tracks lanes, lane -> live_slot -> the scene's TrackRec.  Both are

@@ -11,6 +11,7 @@ namespace mmw {
 struct DevCfg;     // mmw_device.hpp (the CNN's kernel files do without it)
 struct DevState;
 struct ReportState;
+struct ZoneState;
 struct UartState;
 struct UartLog;
 struct ExportScratch;
@@ -67,6 +68,9 @@ void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevStat
 void launch_clouds(const DevCfg &cfg, const DevState &s, const ExportScratch &sc, mmw_cloud_track *dir, int cap_tracks, void *out, int cap_points, int mode, int scene_base, hipStream_t st);
 // k_skeleton.hip: the live tracks' room-frame skeletons (mode: MMW_SKEL_ALL / MMW_SKEL_DRAWN)
 void launch_skeletons(const DevCfg &cfg, const DevState &s, const ExportScratch &sc, mmw_skeleton *out, int cap, int mode, int scene_base, hipStream_t st);
+// k_zone.hip: zone occupancy (flags of the rebase: dev [S] or nullptr = every scene)
+void launch_zone_rebase(const DevCfg &cfg, const ZoneState &zs, const int32_t *flags, hipStream_t st);
+void launch_zones(const DevCfg &cfg, const DevState &s, const ZoneState &zs, mmw_zone_row *rows, int cap_rows, mmw_zone_event *events, int cap_events, int scene_base, hipStream_t st);
 // k_uart.hip: the device-resident radar readers (log: the radar log while it is enabled -- the k_uart_read*_log twins --, else nullptr)
 void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const UartLog *log, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);
