@@ -707,6 +707,80 @@ int mmw_zones_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n_eve
 int mmw_zones(mmw_ctx *ctx, mmw_zone_row *rows, int32_t cap_rows, mmw_zone_event *events, int32_t cap_events, int32_t scene_base,
               int32_t *n_rows, int32_t *n_events);                                      /* async + wait */
 
+/* ---- trails ----
+ * Where a person has been: per live uid the last `depth` positions, sampled on the device when the caller asks, with the time of the
+ * first sample and the distance walked over the uid's whole life -- a path to draw and a distance, without reading the report back
+ * every frame.  A TRAIL belongs to one uid of one scene: a ring of its last `depth` SAMPLES and three words that cover all of them,
+ * `total`, `t_first` and `travelled`.  A sample is taken only by mmw_trails_sample, normally once behind each mmw_step.  No step
+ * kernel reads or writes any of this: a context that never enables trails launches exactly what it did before trails existed.
+ *
+ * mmw_trails_enable(depth), depth in 1 .. MMW_TRAIL_DEPTH_MAX, allocates per scene t_cap trail slots (owner uid or -1 = free, total,
+ * t_first, travelled and the last fp64 (x, y): 40 bytes), t_cap x depth ring entries of 24 bytes, and three words: a generation, the
+ * generation seen and a call ordinal -- S * t_cap * (24 * depth + 40) bytes plus 12 S (t_cap = the context's track capacity: 329 MB
+ * at 4096 scenes, t_cap 51, depth 64).  Every slot starts free, every word at 0; the state is ordered on the context's stream.
+ * Enabling again, with any depth, starts over.  depth == 0 waits for the stream, frees the state and turns trails off (MMW_OK also
+ * when they were off).  depth outside 0 .. MMW_TRAIL_DEPTH_MAX: MMW_E_ARG, nothing changed.  A failed allocation: MMW_E_HIP, nothing
+ * changed -- an earlier enablement stays as it is.  Until enabled, mmw_trails_sample and the export entries return MMW_E_ARG.
+ *
+ * mmw_trails_sample is asynchronous: ONE kernel on the context's stream behind whatever was queued last.  Scene s is ASKED when
+ * scene_flags == NULL or scene_flags[s] != 0 -- the frame's n_pts array serves as the flags (MMW_EMPTY_FRAME counts as asked: track()
+ * ran).  For an asked scene, in this order:
+ *   1. generation != seen: every slot of the scene is freed and seen = generation -- a uid from before a reset never aliases one
+ *      from after it;
+ *   2. every slot whose owner is not among the live uids is freed (trails of expired tracks are not kept);
+ *   3. every live uid without a slot takes a free one (there always is one: live tracks <= t_cap; which one is not observable), with
+ *      total = 0 and travelled = 0;
+ *   4. every live track appends one sample:
+ *        x, y, z   mmw_track_record.x[0..2] of the fp64 state, each rounded once to fp32 (the same for dim_x 6 and 9)
+ *        t         t[s]; with t == NULL the scene's call ordinal as a double: the number of earlier mmw_trails_sample calls that
+ *                  asked this scene since mmw_trails_enable (resets do not restart it)
+ *        flags     MMW_TRAIL_STATIC | MMW_TRAIL_UPDATED as defined below
+ *      total == 0: t_first = t.  Otherwise dx = x - last_x; dy = y - last_y; travelled = travelled + sqrt(dx * dx + dy * dy) -- in
+ *      fp64 on the fp64 state, not on the rounded points, in exactly that operation order (no fused multiply-add: the library is
+ *      built with -ffp-contract=off).  Then last = (x, y), total += 1, and the sample goes to ring position (total - 1) % depth: it
+ *      overwrites the oldest.
+ * Non-finite values pass through: a NaN position makes travelled NaN and it stays NaN.  A scene that is not asked is not touched
+ * (nor is its ordinal).  Sampling twice without a step gives two samples.  scene_flags: dev pointer, 4-byte aligned; t: dev pointer,
+ * 8-byte aligned; else MMW_E_ARG.
+ *
+ * mmw_trails_async / _wait is a pure function of the trail state and the live lists: it writes the caller's buffers and the
+ * context's scratch, nothing else -- a refused call loses nothing, and the same state can be exported under several tickets.  One
+ * directory entry per live track in the report's order (scenes ascending, then effective_tracks order): entry i belongs to
+ * mmw_report row i of the same state; scene ids are offset by scene_base.  A track whose uid owns no slot (born since the last
+ * sample) has count = total = 0, t_first = travelled = 0, and so has every track of a scene whose generation != seen (reset or
+ * restored and not sampled since).  count = min(total, depth), cut to the NEWEST max_per_track when max_per_track > 0 (0 = all;
+ * < 0: MMW_E_ARG); total, t_first and travelled are the whole trail's either way.  The entries partition `points`, as in mmw_clouds:
+ * entry i owns points[first .. first + count), oldest first.
+ * Capacity is decided on the DEVICE against both caps, as the clouds': totals are formed in 64 bits, saturate at INT32_MAX and then
+ * never fit.  If anything does not fit, nothing is written and mmw_trails_wait returns MMW_E_CAPACITY with both counts needed.
+ * mmw_trails_async queues its kernels on the context's stream; the counts follow into pinned memory and mmw_trails_wait(ticket)
+ * waits for THAT copy only.  ticket in [0,4), ticket 3 is mmw_trails' own.  dir / points: dev pointers, 8-byte aligned.  MMW_E_ARG,
+ * nothing touched: a NULL context, trails not enabled, a NULL buffer with a positive cap, a negative cap, a misaligned buffer, a
+ * bad ticket, a wait for a ticket with nothing outstanding.
+ *
+ * Life cycle.  mmw_reset, mmw_reset_scenes and mmw_restore bump the generation of the scenes they touch (uids restart there) -- one
+ * kernel beside the report's and the zones', launched only while trails are enabled.  mmw_destroy frees the state.  Trails are not
+ * in a snapshot blob: format version 1 is unchanged and a restored scene starts new trails.  A uid sampled more than INT32_MAX
+ * times is not supported. */
+#define MMW_TRAIL_DEPTH_MAX 256
+#define MMW_TRAIL_STATIC 1    /* point flag: is_static at the sample */
+#define MMW_TRAIL_UPDATED 2   /* point flag: lifetime == 0 at the sample (the frame's points were associated) */
+typedef struct mmw_trail_point { double t; float x, y, z; int32_t flags; } mmw_trail_point;   /* 24 bytes */
+typedef struct mmw_trail_track {   /* 40 bytes: one directory entry */
+    int32_t scene, slot, uid;      /* as mmw_track_report's: entry i belongs to mmw_report row i of the same state */
+    int32_t first, count;          /* this entry's points are points[first .. first + count), oldest first */
+    int32_t total;                 /* samples ever taken of this uid (count <= min(total, depth)) */
+    double t_first;                /* t of the uid's first sample; 0 while total == 0 */
+    double travelled;              /* path length in the x/y plane over ALL its samples, above */
+} mmw_trail_track;
+int mmw_trails_enable(mmw_ctx *ctx, int32_t depth);   /* 1 .. MMW_TRAIL_DEPTH_MAX; 0 = off and freed */
+int mmw_trails_sample(mmw_ctx *ctx, const int32_t *scene_flags /* dev [S] or NULL */, const double *t /* dev [S] or NULL */);
+int mmw_trails_async(mmw_ctx *ctx, mmw_trail_track *dir, int32_t cap_tracks, mmw_trail_point *points, int32_t cap_points,
+                     int32_t max_per_track, int32_t scene_base, int32_t ticket);
+int mmw_trails_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_tracks, int32_t *n_points);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_trails(mmw_ctx *ctx, mmw_trail_track *dir, int32_t cap_tracks, mmw_trail_point *points, int32_t cap_points,
+               int32_t max_per_track, int32_t scene_base, int32_t *n_tracks, int32_t *n_points);   /* async + wait */
+
 /* Snapshot / restore of scene state (format version 1).
  *
  * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global

@@ -37,7 +37,7 @@ POSTURE_MODELS_MAX = 8             # models one mmw_posture_attach_models call t
 POSTURE_NONE = -1                  # MMW_POSTURE_NONE: the map entry of a scene no model estimates
 EXPORT_TICKETS = 4                 # kTickets (csrc/mmw_ctx.hpp): `*_async` calls of one export that may be outstanding; the
                                    # one-call form of each export (mmw_report, mmw_clouds, ...) uses the last ticket itself
-REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
+REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = TRAIL_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
 
 EMPTY_FRAME = -1   # MMW_EMPTY_FRAME (include/mmw.h)
 BAD_FRAME = -3     # MMW_BAD_FRAME: n_out of mmw_normalize_tlv for a TLV body it refused to decode
@@ -181,6 +181,13 @@ ZONE_ROW_DTYPE = np.dtype([("scene", "i4"), ("zone", "i4"), ("id", "i4"), ("coun
 ZONE_EVENT_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("kind", "i4"), ("zone", "i4"), ("id", "i4"), ("slot", "i4")], align=True)
 ZEV_ENTER, ZEV_LEAVE, ZEV_REBASED = 1, 2, 3   # MMW_ZEV_*: mmw_zone_event.kind
 
+# struct mmw_trail_track / mmw_trail_point (include/mmw.h): the directory entries (40 bytes) and points (24 bytes) of mmw_trails_*
+TRAIL_DEPTH_MAX = 256                         # MMW_TRAIL_DEPTH_MAX: samples a trail's ring holds at the most
+TRAIL_STATIC, TRAIL_UPDATED = 1, 2            # MMW_TRAIL_*: bits of mmw_trail_point.flags
+TRAIL_TRACK_DTYPE = np.dtype([("scene", "i4"), ("slot", "i4"), ("uid", "i4"), ("first", "i4"), ("count", "i4"), ("total", "i4"),
+                              ("t_first", "f8"), ("travelled", "f8")], align=True)
+TRAIL_POINT_DTYPE = np.dtype([("t", "f8"), ("x", "f4"), ("y", "f4"), ("z", "f4"), ("flags", "i4")], align=True)
+
 
 # C struct name in include/mmw.h -> its Python mirror; every `typedef struct mmw_*` but the opaque mmw_ctx.  Field names are the
 # header's own throughout, so a mirror needs no second spelling beside it.
@@ -189,6 +196,7 @@ ABI_STRUCTS = {
     "mmw_posture_model": MmwPostureModel, "mmw_track_report": TRACK_REPORT_DTYPE, "mmw_track_event": TRACK_EVENT_DTYPE,
     "mmw_cloud_track": CLOUD_TRACK_DTYPE, "mmw_cloud_point": CLOUD_POINT_DTYPE, "mmw_skeleton": SKELETON_DTYPE,
     "mmw_zone": ZONE_DTYPE, "mmw_zone_row": ZONE_ROW_DTYPE, "mmw_zone_event": ZONE_EVENT_DTYPE,
+    "mmw_trail_track": TRAIL_TRACK_DTYPE, "mmw_trail_point": TRAIL_POINT_DTYPE,
     "mmw_snapshot_header": MmwSnapshotHeader, "mmw_snapshot_entry": MmwSnapshotEntry, "mmw_snapshot_info": MmwSnapshotInfo,
     "mmw_uart_cfg": MmwUartCfg, "mmw_uart_frame": UART_FRAME_DTYPE, "mmw_uart_object": UART_OBJECT_DTYPE,
     "mmw_sample_entry": SAMPLE_ENTRY_DTYPE,
@@ -300,6 +308,11 @@ def _signatures():
         "mmw_zones_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
         "mmw_zones_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_zones": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
+        "mmw_trails_enable": (C.c_int, [vp, i32]),
+        "mmw_trails_sample": (C.c_int, [vp, vp, vp]),
+        "mmw_trails_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32]),
+        "mmw_trails_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_trails": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32p, i32p]),
         "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
         "mmw_uart_close": (C.c_int, [vp]),
         "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),

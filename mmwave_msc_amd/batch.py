@@ -932,6 +932,47 @@ class SceneBatch:
         return self._export_host("zones", lambda *a: self.zones_async(*a[:4], scene_base, a[4]), self.L.mmw_zones_wait,
                                  ("zone_rows", _lib.ZONE_ROW_DTYPE), ("zone_events", _lib.ZONE_EVENT_DTYPE))
 
+    # -- track trails ---------------------------------------------------------
+    def enable_trails(self, depth: int):
+        """mmw_trails_enable: per live uid a ring of its last `depth` (1 .. `_lib.TRAIL_DEPTH_MAX`) sampled positions, with the time
+        of its first sample and the distance it walked; every trail starts empty, also when trails were enabled before.  depth=0
+        frees them.  Until enabled, the trail calls are refused (E_ARG) and the context launches nothing of them."""
+        self._chk(self.L.mmw_trails_enable(self.h, int(depth)))
+
+    def sample_trails_dev(self, flags_ptr=None, t_ptr=None):
+        """mmw_trails_sample: one sample of every live track of the asked scenes, queued behind the last step on the context's
+        stream -- no host wait.  `flags_ptr`: device int32[S], non-zero = asked (the step's n_pts array serves; None = every
+        scene); `t_ptr`: device float64[S], the samples' time (None = each scene's count of earlier sample calls)."""
+        self._chk(self.L.mmw_trails_sample(self.h, flags_ptr, t_ptr))
+
+    def sample_trails(self, t=None, scenes=None):
+        """`sample_trails_dev` from host arrays: `t` float64[S] or a scalar for every scene (None = the call ordinals), `scenes` the
+        scenes to sample (default all)."""
+        t_ptr = None
+        if t is not None:
+            t_ptr = self.buf("trail_t", self.S * 8).upload(np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (self.S,)))).ptr
+        self.sample_trails_dev(self._scene_flags(scenes, "trail_flags"), t_ptr)
+
+    def trails_dev(self, dir_ptr, cap_tracks: int, points_ptr, cap_points: int, last: int = 0, ticket: int = 0, scene_base: int = 0):
+        """mmw_trails_async: every live track's trail into device buffers -- a `_lib.TRAIL_TRACK_DTYPE` directory entry per track in
+        the report's (scene, slot) order and, back to back, their points (`_lib.TRAIL_POINT_DTYPE`), oldest first; `last` > 0 cuts
+        every trail to its newest `last` points.  Queued on the context's stream -- no host wait.  Tickets 0 .. 3 (`trails_host`
+        uses 3).  Both pointers 8-byte aligned."""
+        self._chk(self.L.mmw_trails_async(self.h, dir_ptr, int(cap_tracks), points_ptr, int(cap_points), int(last), int(scene_base), int(ticket)))
+
+    def trails_wait(self, ticket: int = 0):
+        """(n_tracks, n_points) of the `trails_dev` call with this ticket: waits for its counts only, not for the stream.  Buffers
+        too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written."""
+        return self._export_wait(self.L.mmw_trails_wait, ticket)
+
+    def trails_host(self, last: int = 0, scene_base: int = 0):
+        """(dir[n_tracks] TRAIL_TRACK_DTYPE, points[n_points] TRAIL_POINT_DTYPE): entry i owns points[first : first + count], oldest
+        first, and is the track of `report_host` row i; `trails.split` gives the views.  The device buffers are kept and grow to
+        what the device says it needs (one retry; the export consumes nothing)."""
+        self._export_caps.setdefault("trails", (64, 4096))   # (its entry exists from the first call on, as the zones')
+        return self._export_host("trails", lambda *a: self.trails_dev(*a[:4], last, a[4], scene_base), self.L.mmw_trails_wait,
+                                 ("trail_dir", _lib.TRAIL_TRACK_DTYPE), ("trail_points", _lib.TRAIL_POINT_DTYPE))
+
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):
         if scenes is None:

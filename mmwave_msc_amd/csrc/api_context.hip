@@ -407,6 +407,7 @@ int mmw_destroy(mmw_ctx *c)
     export_free(c->skel);
     export_free(c->sample);
     zone_free(c);
+    trail_free(c);
     uart_log_free(c);
     if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->side_gate) hipEventDestroy(c->side_gate);
@@ -423,6 +424,7 @@ int mmw_reset(mmw_ctx *c)
     HIPCHK(c, hipGetLastError());
     MMW_TRY(report_rebase(c, nullptr));
     MMW_TRY(zone_rebase(c, nullptr));
+    MMW_TRY(trail_rebase(c, nullptr));
     c->dc.var_ring = 0;   // fresh BatchedData objects: default sizes again
     refresh_step_kind(c);
     c->ring_frames_bound = 0;
@@ -437,6 +439,7 @@ int mmw_reset_scenes(mmw_ctx *c, const int32_t *scene_flags)
         launch_reset(c->dc, c->st, f, c->stream);
         if (c->rep.d_block) launch_report_rebase(c->dc, c->rs, f, c->stream);   // (reports enabled: the reset scenes' uids restart)
         if (c->zone.d_block) launch_zone_rebase(c->dc, c->zs, f, c->stream);    // (zones defined: ... and their memberships are void)
+        if (c->trail.d_block) launch_trail_rebase(c->dc, c->ts, f, c->stream);  // (trails enabled: ... and their trails end)
     });
 }
 

@@ -229,6 +229,7 @@ int mmw_restore(mmw_ctx *c, const void *dev_blob, size_t bytes, const int32_t *s
         HIPCHK(c, hipGetLastError());
         MMW_TRY(report_rebase(c, x.flags));           // (reports enabled: the restored scenes carry another recording's uids)
         MMW_TRY(zone_rebase(c, x.flags));             // (zones defined: ... and no membership of before holds for them)
+        MMW_TRY(trail_rebase(c, x.flags));            // (trails enabled: ... and they start new trails)
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (the host vectors above go away)
     }
     // host-side bookkeeping: the large-cloud launches are carved for ring_frames_bound frames, and resized rings are k_track's

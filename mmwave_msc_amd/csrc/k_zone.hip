@@ -9,6 +9,7 @@
 #include <cstddef>
 #include "mmw_device.hpp"
 #include "mmw_math.hpp"
+#include "mmw_wave.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -95,18 +96,6 @@ __device__ __forceinline__ ZoneDiff zone_diff(const DevCfg &cfg, const DevState 
     }
     d.leave = bmask & ~still;
     return d;
-}
-
-// exclusive prefix sum over the wave and the wave's total (all 64 lanes call)
-__device__ __forceinline__ int wave_excl_sum(int v, int lane, int &total)
-{
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(inc, o);
-        inc += lane >= o ? up : 0;
-    }
-    total = __shfl(inc, 63);
-    return inc - v;
 }
 
 // flags == nullptr: every scene (mmw_reset); else the scenes whose flag is non-zero (mmw_reset_scenes, mmw_restore, mmw_set_zones)

@@ -127,6 +127,8 @@ struct mmw_ctx {
     char *d_ztab = nullptr;           // ... the table as ONE copy lands in it: [S][MMW_ZONES_MAX] mmw_zone | [S] n_zones | [S] the call's scene flags
     std::vector<mmw_zone> h_zones;    // host mirror of the table ([S][MMW_ZONES_MAX], zero past a scene's n_zones) ...
     std::vector<int32_t> h_nzones;    // ... and of n_zones [S] (mmw_get_zones reads both)
+    ExportCtx trail;                  // mmw_trails_enable allocates it (depth 0 frees it); not allocated = trails are off, nothing of them is launched
+    TrailState ts = {};               // ... the trail slots and rings, in front of trail's scratch in trail.d_block (ts.sc = trail.sc)
     ExportCtx ulog_x;                 // mmw_uart_log_enable; not allocated = the radar log is off and mmw_uart_read launches what it always did
     UartLog ulog = {};                // ... the staged frames, in front of ulog_x's scratch in ulog_x.d_block
     std::vector<double> uart_range;   // [S] rangeIdxToMeters of the open readers (the log's range column)
@@ -149,6 +151,8 @@ void posture_batch_free(PostureBatch *b);                          // api_postur
 int report_rebase(mmw_ctx *c, const int32_t *dev_flags);           // api_report.hip: the scenes' uids restart (no-op while reports are off)
 int zone_rebase(mmw_ctx *c, const int32_t *dev_flags);             // api_zone.hip: the scenes' zone memberships are void (no-op while no zone table exists)
 void zone_free(mmw_ctx *c);                                        // api_zone.hip: table, baseline and mirrors (the caller has waited for the stream)
+int trail_rebase(mmw_ctx *c, const int32_t *dev_flags);            // api_trail.hip: the scenes' trails end, their uids restart (no-op while trails are off)
+void trail_free(mmw_ctx *c);                                       // api_trail.hip: slots, rings and scratch (the caller has waited for the stream)
 int uart_log_rearm(mmw_ctx *c);                                    // api_uart_log.hip: every scene's log word as new, with its range scale (no-op while the log is off)
 void uart_log_free(mmw_ctx *c);                                    // api_uart_log.hip: ... and the log is off (the caller has waited for the stream)
 // api_export.hip: the ticketed counts of the three live-track exports (`name`: the entry the messages speak for)

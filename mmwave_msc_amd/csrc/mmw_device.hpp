@@ -187,7 +187,7 @@ struct DevState {
 // The scratch of one live-track export's call in flight (k_report.hip, k_cloud.hip, k_skeleton.hip; scanned by k_scan.hip).  All
 // device memory; nothing is kept between two calls.  What the two counts are:
 //   report     rows, events          clouds     directory entries, points          skeletons  emitted entries, live tracks
-//   zones      rows (defined zones), events
+//   zones      rows (defined zones), events                                        trails     directory entries, points
 struct ExportScratch {
     int32_t *off;         // [2][S + 1] the two counts per scene, scanned in place into offsets; [S] = the total
     int32_t *totals;      // [4] the two totals (saturated at INT32_MAX), 1 = both fit the caller's capacities (the device's decision), 0
@@ -211,6 +211,22 @@ struct ZoneState {
     int32_t *gen;              // [S] generation: bumped by mmw_reset / mmw_reset_scenes / mmw_restore and by mmw_set_zones for the scenes it lists
     int32_t *seen;             // [S] the generation the baseline was taken in
     ExportScratch sc;          // rows / events of the export in flight
+};
+// mmw_trails_enable: what the track trails keep from one mmw_trails_sample to the next (k_trail.hip).  All device memory.  A scene
+// has t_cap trail SLOTS; a slot belongs to one uid or is free, and which slot a uid has is not visible outside.  The slot words
+// are arrays over [S][t_cap] (lane j of a scene's wave holds slot j), 40 bytes a slot together.
+struct TrailState {
+    int32_t depth;             // ring entries per slot, 1 .. MMW_TRAIL_DEPTH_MAX
+    int32_t *owner;            // [S][t_cap] the slot's uid, -1 = free
+    int32_t *total;            // [S][t_cap] samples ever taken of that uid
+    double *t_first;           // [S][t_cap] t of its first sample
+    double *travelled;         // [S][t_cap] path length in the x/y plane over all its samples
+    double *last_x, *last_y;   // [S][t_cap] the fp64 position of its newest sample
+    mmw_trail_point *ring;     // [S][t_cap][depth] sample n (0-based) of a uid lies at n % depth
+    int32_t *gen;              // [S] generation of the scene's uids: bumped by mmw_reset / mmw_reset_scenes / mmw_restore
+    int32_t *seen;             // [S] the generation the scene's slots belong to (set by a sample call that asked the scene)
+    int32_t *ordinal;          // [S] sample calls that asked the scene since mmw_trails_enable
+    ExportScratch sc;          // entries / points of the export in flight
 };
 
 // The live list of scene s, as every export walks it: T = live_tracks lanes, lane -> live_slot -> the scene's TrackRec.  Both are

@@ -12,6 +12,7 @@ struct DevCfg;     // mmw_device.hpp (the CNN's kernel files do without it)
 struct DevState;
 struct ReportState;
 struct ZoneState;
+struct TrailState;
 struct UartState;
 struct UartLog;
 struct ExportScratch;
@@ -71,6 +72,10 @@ void launch_skeletons(const DevCfg &cfg, const DevState &s, const ExportScratch 
 // k_zone.hip: zone occupancy (flags of the rebase: dev [S] or nullptr = every scene)
 void launch_zone_rebase(const DevCfg &cfg, const ZoneState &zs, const int32_t *flags, hipStream_t st);
 void launch_zones(const DevCfg &cfg, const DevState &s, const ZoneState &zs, mmw_zone_row *rows, int cap_rows, mmw_zone_event *events, int cap_events, int scene_base, hipStream_t st);
+// k_trail.hip: track trails (flags: dev [S] or nullptr = every scene; t: dev [S] or nullptr = the scenes' call ordinals)
+void launch_trail_rebase(const DevCfg &cfg, const TrailState &ts, const int32_t *flags, hipStream_t st);
+void launch_trail_sample(const DevCfg &cfg, const DevState &s, const TrailState &ts, const int32_t *flags, const double *t, hipStream_t st);
+void launch_trails(const DevCfg &cfg, const DevState &s, const TrailState &ts, mmw_trail_track *dir, int cap_tracks, mmw_trail_point *points, int cap_points, int max_per_track, int scene_base, hipStream_t st);
 // k_uart.hip: the device-resident radar readers (log: the radar log while it is enabled -- the k_uart_read*_log twins --, else nullptr)
 void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const UartLog *log, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);
