@@ -422,9 +422,7 @@ int mmw_reset(mmw_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     launch_reset(c->dc, c->st, nullptr, c->stream);
     HIPCHK(c, hipGetLastError());
-    MMW_TRY(report_rebase(c, nullptr));
-    MMW_TRY(zone_rebase(c, nullptr));
-    MMW_TRY(trail_rebase(c, nullptr));
+    MMW_TRY(uid_rebase(c, nullptr));   // (report, zones, trails -- whichever is on: every scene's uids restart)
     c->dc.var_ring = 0;   // fresh BatchedData objects: default sizes again
     refresh_step_kind(c);
     c->ring_frames_bound = 0;
@@ -435,12 +433,12 @@ int mmw_reset_scenes(mmw_ctx *c, const int32_t *scene_flags)
 {
     if (!c || !scene_flags) return fail(c, MMW_E_ARG, "mmw_reset_scenes: null argument");
     HIPCHK(c, hipSetDevice(c->device));
-    return with_scene_flags(c, scene_flags, [&](const int32_t *f) {
+    int rebase_rc = MMW_OK;
+    MMW_TRY(with_scene_flags(c, scene_flags, [&](const int32_t *f) {
         launch_reset(c->dc, c->st, f, c->stream);
-        if (c->rep.d_block) launch_report_rebase(c->dc, c->rs, f, c->stream);   // (reports enabled: the reset scenes' uids restart)
-        if (c->zone.d_block) launch_zone_rebase(c->dc, c->zs, f, c->stream);    // (zones defined: ... and their memberships are void)
-        if (c->trail.d_block) launch_trail_rebase(c->dc, c->ts, f, c->stream);  // (trails enabled: ... and their trails end)
-    });
+        rebase_rc = uid_rebase(c, f);   // (report, zones, trails -- whichever is on: the reset scenes' uids restart)
+    }));
+    return rebase_rc;
 }
 
 int mmw_clear_errors(mmw_ctx *c, const int32_t *scene_flags, int32_t bits)

@@ -1,6 +1,6 @@
 // api_export.hip -- what mmw_report_*, mmw_clouds_* and mmw_skeletons_* share on the host (not part of the ABI): the device scratch
 // that k_pair_scan works on, and the tickets -- the totals of every call follow its kernels into a pinned slot of their own, and a
-// wait is for that copy only.
+// wait is for that copy only.  And the generation bump of the exports that remember uids.
 #include "mmw_ctx.hpp"
 
 void export_free(ExportCtx &x)
@@ -43,5 +43,17 @@ int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const ch
     HIPCHK(c, hipEventSynchronize(x.ev[ticket]));
     x.issued[ticket] = false;
     *counts = x.h_counts + ticket * 4;
+    return MMW_OK;
+}
+
+// mmw_reset / mmw_reset_scenes / mmw_restore: uids restart in the scenes flagged in dev_flags (device, [n_scenes]; nullptr = every
+// scene), so the report's baseline, the zones' memberships and the trails of those scenes are void.  One launch for the consumers
+// that are on, queued on the context's stream behind the kernel that emptied or refilled the scenes; nothing at all while none is.
+int uid_rebase(mmw_ctx *c, const int32_t *dev_flags)
+{
+    const UidGens g = {{c->rep.d_block ? c->rs.base.ug.gen : nullptr, c->zone.d_block ? c->zs.base.ug.gen : nullptr, c->trail.d_block ? c->ts.ug.gen : nullptr}};
+    if (!g.gen[0] && !g.gen[1] && !g.gen[2]) return MMW_OK;
+    launch_uid_rebase(c->dc.n_scenes, dev_flags, g, c->stream);
+    HIPCHK(c, hipGetLastError());
     return MMW_OK;
 }

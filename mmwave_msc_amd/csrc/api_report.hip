@@ -5,26 +5,16 @@
 static_assert(sizeof(mmw_track_report) == 324, "mmw_track_report: the ctypes / numpy layouts of mmwave_msc_amd/_lib.py");
 static_assert(sizeof(mmw_track_event) == 16, "mmw_track_event: the ctypes / numpy layouts of mmwave_msc_amd/_lib.py");
 
-// mmw_reset / mmw_reset_scenes / mmw_restore: uids restart in the scenes flagged in dev_flags (device, [n_scenes]; nullptr = every
-// scene).  Queued on the context's stream behind the kernel that emptied or refilled them; nothing at all while reports are off.
-int report_rebase(mmw_ctx *c, const int32_t *dev_flags)
-{
-    if (!c->rep.d_block) return MMW_OK;
-    launch_report_rebase(c->dc, c->rs, dev_flags, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return MMW_OK;
-}
-
 // the baseline lies in front of the scratch, in the same device block
 static int report_alloc(mmw_ctx *c)
 {
     const size_t S = c->dc.n_scenes, cap = c->dc.t_cap;
     MMW_TRY(export_alloc(c, c->rep, S * cap + 3 * S, "mmw_report_enable"));
     int32_t *p = reinterpret_cast<int32_t *>(c->rep.d_block);
-    c->rs.base_uid = p; p += S * cap;
-    c->rs.base_len = p; p += S;
-    c->rs.gen = p; p += S;
-    c->rs.seen = p;
+    c->rs.base.base_uid = p; p += S * cap;
+    c->rs.base.base_len = p; p += S;
+    c->rs.base.ug.gen = p; p += S;
+    c->rs.base.ug.seen = p;
     c->rs.sc = c->rep.sc;
     return MMW_OK;
 }

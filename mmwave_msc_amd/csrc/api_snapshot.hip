@@ -227,9 +227,7 @@ int mmw_restore(mmw_ctx *c, const void *dev_blob, size_t bytes, const int32_t *s
         launch_snap_restore(c->dc, c->st, blob, reinterpret_cast<const mmw_snapshot_entry *>(blob + sizeof(h)), x.sel, x.flags, ns, max_tracks, h.ring_rows,
                             c->stream);
         HIPCHK(c, hipGetLastError());
-        MMW_TRY(report_rebase(c, x.flags));           // (reports enabled: the restored scenes carry another recording's uids)
-        MMW_TRY(zone_rebase(c, x.flags));             // (zones defined: ... and no membership of before holds for them)
-        MMW_TRY(trail_rebase(c, x.flags));            // (trails enabled: ... and they start new trails)
+        MMW_TRY(uid_rebase(c, x.flags));              // (report, zones, trails -- whichever is on: the restored scenes carry another recording's uids)
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (the host vectors above go away)
     }
     // host-side bookkeeping: the large-cloud launches are carved for ring_frames_bound frames, and resized rings are k_track's

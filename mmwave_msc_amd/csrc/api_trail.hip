@@ -6,17 +6,6 @@
 static_assert(sizeof(mmw_trail_point) == 24, "mmw_trail_point: the numpy layout of mmwave_msc_amd/_lib.py");
 static_assert(sizeof(mmw_trail_track) == 40, "mmw_trail_track: the numpy layout of mmwave_msc_amd/_lib.py");
 
-// mmw_reset / mmw_reset_scenes / mmw_restore: the trails of the scenes flagged in dev_flags (device, [n_scenes]; nullptr = every
-// scene) end -- their uids restart.  Queued on the context's stream behind the kernel that emptied or refilled them; nothing at all
-// while trails are off.
-int trail_rebase(mmw_ctx *c, const int32_t *dev_flags)
-{
-    if (!c->trail.d_block) return MMW_OK;
-    launch_trail_rebase(c->dc, c->ts, dev_flags, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return MMW_OK;
-}
-
 void trail_free(mmw_ctx *c)
 {
     export_free(c->trail);
@@ -52,8 +41,8 @@ int mmw_trails_enable(mmw_ctx *c, int32_t depth)
     int32_t *p = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d) + ring_bytes);
     ts.owner = p; p += n;
     ts.total = p; p += n;
-    ts.gen = p; p += S;
-    ts.seen = p; p += S;
+    ts.ug.gen = p; p += S;
+    ts.ug.seen = p; p += S;
     ts.ordinal = p;
     ts.sc = nx.sc;
     // every slot free, every word 0 (the rings need no clearing: an entry is written before `total` lets anybody read it)

@@ -7,17 +7,6 @@ static_assert(sizeof(mmw_zone) == 48, "mmw_zone: the numpy layout of mmwave_msc_
 static_assert(sizeof(mmw_zone_row) == 32, "mmw_zone_row: the numpy layout of mmwave_msc_amd/_lib.py");
 static_assert(sizeof(mmw_zone_event) == 24, "mmw_zone_event: the numpy layout of mmwave_msc_amd/_lib.py");
 
-// mmw_reset / mmw_reset_scenes / mmw_restore: every membership of the scenes flagged in dev_flags (device, [n_scenes]; nullptr =
-// every scene) is void.  Queued on the context's stream behind the kernel that emptied or refilled them; nothing at all while no
-// zone table exists.
-int zone_rebase(mmw_ctx *c, const int32_t *dev_flags)
-{
-    if (!c->zone.d_block) return MMW_OK;
-    launch_zone_rebase(c->dc, c->zs, dev_flags, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return MMW_OK;
-}
-
 void zone_free(mmw_ctx *c)
 {
     export_free(c->zone);
@@ -46,11 +35,11 @@ static int zone_alloc(mmw_ctx *c)
         return fail(c, MMW_E_HIP, "mmw_set_zones: hipMemsetAsync failed");
     }
     int32_t *p = reinterpret_cast<int32_t *>(c->zone.d_block);
-    c->zs.base_uid = p; p += S * cap;
+    c->zs.base.base_uid = p; p += S * cap;
     c->zs.base_mask = p; p += S * cap;
-    c->zs.base_len = p; p += S;
-    c->zs.gen = p; p += S;
-    c->zs.seen = p;
+    c->zs.base.base_len = p; p += S;
+    c->zs.base.ug.gen = p; p += S;
+    c->zs.base.ug.seen = p;
     c->zs.sc = c->zone.sc;
     c->zs.zones = reinterpret_cast<const mmw_zone *>(c->d_ztab);
     c->zs.n_zones = reinterpret_cast<const int32_t *>(c->d_ztab + S * MMW_ZONES_MAX * sizeof(mmw_zone));
@@ -87,7 +76,7 @@ int mmw_set_zones(mmw_ctx *c, const int32_t *scenes, int32_t n, const int32_t *n
     if (fresh) MMW_TRY(zone_alloc(c));
     // The new table is put together on the host (from a copy of the mirror: a failure below leaves the mirror as it was) and travels
     // as ONE copy, ordered on the context's stream: what was queued before this call reads the old table.  The listed scenes' flags
-    // ride behind it, for the generation bump.
+    // ride behind it, for the generation bump -- of the zones' word alone: the report's baseline and the trails stand.
     const size_t zb = (size_t)S * MMW_ZONES_MAX * sizeof(mmw_zone);
     std::vector<mmw_zone> next = c->h_zones;
     std::vector<int32_t> next_n = c->h_nzones;
@@ -103,7 +92,7 @@ int mmw_set_zones(mmw_ctx *c, const int32_t *scenes, int32_t n, const int32_t *n
     for (int s = 0; s < S; s++) flags[s] = listed[s];
     hipError_t e = hipMemcpyAsync(c->d_ztab, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        launch_zone_rebase(c->dc, c->zs, c->zs.n_zones + S, c->stream);
+        launch_uid_rebase(S, c->zs.n_zones + S, UidGens{{c->zs.base.ug.gen, nullptr, nullptr}}, c->stream);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (`stage` is pageable and goes away)

@@ -2,12 +2,13 @@
 // every scene's uid list against the previous report's as events.  Reads SceneHdr, order and TrackRec after the step, the way
 // k_table and k_features do; nothing of the step is touched.
 //   k_report_baseline  the baseline of mmw_report_enable: the uids live now
-//   k_report_rebase    mmw_reset / mmw_reset_scenes / mmw_restore: the touched scenes' generation word
+//   k_uid_rebase       (k_scan.hip) mmw_reset / mmw_reset_scenes / mmw_restore: the touched scenes' generation word
 //   k_report_count     rows and events per scene: a wave per scene, a lane per track (t_cap <= 64)
 //   k_pair_scan        (k_scan.hip) one workgroup: the two offset scans, the capacity decision, the totals
 //   k_report_write     rows (staged in LDS, stored as contiguous 16-byte pieces), events, the new baseline -- only if everything fits
 #include <cstddef>
 #include "mmw_device.hpp"
+#include "mmw_uidlist.hpp"
 #include "mmw_math.hpp"
 #include "mmw_summary.hpp"
 #include "mmw_kernels.hpp"
@@ -24,8 +25,7 @@ constexpr int kStageRows = 16;                                 // rows staged pe
 constexpr int kStageWords = kStageRows * kRowWords + 4;        // + the alignment shift (below); a multiple of 4: every wave's block starts 16-byte aligned
 static_assert(kStageWords % 4 == 0, "stage blocks stay 16-byte aligned");
 
-// A scene's uid lists, current and baseline, one entry per lane, and which entries the other list does not hold.  Neither list is
-// sorted (effective_tracks order), so membership is a compare against every entry of the other list, broadcast lane by lane.
+// A scene's uid lists, current and baseline, one entry per lane, and which entries the other list does not hold (uid_find).
 // All 64 lanes of the wave call.  A scene whose generation moved since its baseline was taken has no BORN / GONE (its uids restarted).
 struct SceneDiff {
     int T, Tb;                       // live tracks now / at the previous report
@@ -37,17 +37,11 @@ __device__ __forceinline__ SceneDiff scene_diff(const DevCfg &cfg, const DevStat
 {
     SceneDiff d;
     d.T = live_tracks(cfg, st, s);
-    d.Tb = min(rp.base_len[s], cfg.t_cap);
-    d.rebased = rp.gen[s] != rp.seen[s];
-    d.cuid = lane < d.T ? st.trk[(size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane)].uid : -1;
-    d.buid = lane < d.Tb ? rp.base_uid[(size_t)s * cfg.t_cap + lane] : -1;
-    bool in_base = false, in_cur = false;
-    const int n = max(d.T, d.Tb);
-    for (int k = 0; k < n; k++) {   // (uniform)
-        const int c = __shfl(d.cuid, k), b = __shfl(d.buid, k);
-        in_base = in_base || (k < d.Tb && d.cuid == b);
-        in_cur = in_cur || (k < d.T && d.buid == c);
-    }
+    d.Tb = rp.base.len(s, cfg.t_cap);
+    d.rebased = rp.base.ug.rebased(s);
+    d.cuid = live_uid(cfg, st, s, lane, d.T);
+    d.buid = rp.base.uid(s, cfg.t_cap, lane, d.Tb);
+    const bool in_base = uid_find(d.cuid, d.buid, d.Tb) >= 0, in_cur = uid_find(d.buid, d.cuid, d.T) >= 0;   // (every lane, ahead of the conditions)
     d.born = __ballot(!d.rebased && lane < d.T && !in_base);
     d.gone = __ballot(!d.rebased && lane < d.Tb && !in_cur);
     return d;
@@ -56,23 +50,16 @@ __device__ __forceinline__ SceneDiff scene_diff(const DevCfg &cfg, const DevStat
 // mmw_report_enable: the tracks live now are the baseline -- they produce no event
 __global__ __launch_bounds__(256) void k_report_baseline(DevCfg cfg, DevState st, ReportState rp)
 {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const auto [s, lane] = wave_scene();
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
     const int T = live_tracks(cfg, st, s);
-    if (lane < T) rp.base_uid[(size_t)s * cfg.t_cap + lane] = st.trk[(size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane)].uid;
-    if (lane == 0) { rp.base_len[s] = T; rp.gen[s] = 0; rp.seen[s] = 0; }
-}
-
-// flags == nullptr: every scene (mmw_reset); else the scenes whose flag is non-zero (mmw_reset_scenes, mmw_restore)
-__global__ void k_report_rebase(DevCfg cfg, ReportState rp, const int32_t *__restrict__ flags)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < cfg.n_scenes && (!flags || flags[s])) rp.gen[s] += 1;
+    rp.base.store(s, cfg.t_cap, lane, T, live_uid(cfg, st, s, lane, T));
+    if (lane == 0) { rp.base.ug.gen[s] = 0; rp.base.ug.seen[s] = 0; }
 }
 
 __global__ __launch_bounds__(256) void k_report_count(DevCfg cfg, DevState st, ReportState rp)
 {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const auto [s, lane] = wave_scene();
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
     const SceneDiff d = scene_diff(cfg, st, rp, s, lane);
     if (lane == 0) {
@@ -92,8 +79,8 @@ __global__ __launch_bounds__(256) void k_report_write(DevCfg cfg, const mmw_scen
 {
     __shared__ __attribute__((aligned(16))) uint32_t stage[4][kStageWords];
     if (!rp.sc.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer, the baseline nor a generation is written
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int s = blockIdx.x * 4 + wave, S = cfg.n_scenes;
+    const auto [s, lane] = wave_scene();
+    const int S = cfg.n_scenes;
     if (s >= S) return;          // (wave-uniform)
     const SceneDiff d = scene_diff(cfg, st, rp, s, lane);
     const int row0 = rp.sc.off[s], ev0 = rp.sc.off[S + 1 + s];
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(256) void k_report_write(DevCfg cfg, const mmw_scen
         m_x = w->m_x; m_y = w->m_y; m_z = w->m_z;
         fade_max = w->v_screen_fade_size_max; fade_min = w->v_screen_fade_size_min; fade_weight = w->v_screen_fade_weight;
     }
-    uint32_t *lds = stage[wave];
+    uint32_t *lds = stage[s & 3];   // (the wave's own block)
     for (int c = 0; c < d.T; c += kStageRows) {   // (uniform)
         const int n = min(kStageRows, d.T - c);
         uint32_t *dst = reinterpret_cast<uint32_t *>(rows + row0 + c);
@@ -139,17 +126,13 @@ __global__ __launch_bounds__(256) void k_report_write(DevCfg cfg, const mmw_scen
     }
 
     // the current list is the next report's baseline (behind everything that read the old one)
-    if (lane < d.T) rp.base_uid[(size_t)s * cfg.t_cap + lane] = d.cuid;
-    if (lane == 0) { rp.base_len[s] = d.T; rp.seen[s] = rp.gen[s]; }
+    rp.base.store(s, cfg.t_cap, lane, d.T, d.cuid);
+    rp.base.ug.settle(s, lane);
 }
 
 void launch_report_baseline(const DevCfg &cfg, const DevState &s, const ReportState &rp, hipStream_t st)
 {
     hipLaunchKernelGGL(k_report_baseline, dim3((cfg.n_scenes + 3) / 4), dim3(256), 0, st, cfg, s, rp);
-}
-void launch_report_rebase(const DevCfg &cfg, const ReportState &rp, const int32_t *flags, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_report_rebase, dim3((cfg.n_scenes + 255) / 256), dim3(256), 0, st, cfg, rp, flags);
 }
 void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ReportState &rp, mmw_track_report *rows, int cap_rows,
                    mmw_track_event *events, int cap_events, int scene_base, hipStream_t st)

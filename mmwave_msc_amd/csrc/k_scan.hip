@@ -1,6 +1,6 @@
-// k_scan.hip -- the scan step the live-track exports share (k_report.hip, k_cloud.hip, k_skeleton.hip): each export's count kernel
-// leaves two counts per scene in off[2][S + 1], k_pair_scan turns both into offsets in place and takes the capacity decision that
-// the export's write kernel and the host read.
+// k_scan.hip -- the two kernels the live-track exports share.  k_pair_scan: each export's count kernel leaves two counts per scene
+// in off[2][S + 1], the scan turns both into offsets in place and takes the capacity decision that the export's write kernel and
+// the host read.  k_uid_rebase: the generation words of the exports that remember uids (mmw_uidlist.hpp), bumped in one launch.
 #include "mmw_scan.hpp"
 #include "mmw_kernels.hpp"
 
@@ -39,6 +39,22 @@ __global__ __launch_bounds__(1024) void k_pair_scan(int S, int32_t *off /*[2][S+
         totals[2] = (tot0 <= (long long)cap0 && tot1 <= (long long)cap1) ? 1 : 0;
         totals[3] = 0;
     }
+}
+
+// mmw_reset / mmw_reset_scenes / mmw_restore / mmw_set_zones: the uids of the touched scenes restart (or, for the zones alone, their
+// table changed), so every consumer's memory of them is void.  flags == nullptr: every scene; else the scenes whose flag is non-zero.
+__global__ __launch_bounds__(256) void k_uid_rebase(int n_scenes, const int32_t *__restrict__ flags, UidGens gens)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_scenes || (flags && !flags[s])) return;
+#pragma unroll
+    for (int i = 0; i < UidGens::kMax; i++)
+        if (gens.gen[i]) gens.gen[i][s] += 1;
+}
+
+void launch_uid_rebase(int n_scenes, const int32_t *flags, const UidGens &gens, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_uid_rebase, dim3((n_scenes + 255) / 256), dim3(256), 0, st, n_scenes, flags, gens);
 }
 
 void launch_pair_scan(int S, int32_t *off, int32_t *totals, int cap0, int cap1, hipStream_t st)

@@ -2,14 +2,15 @@
 // sample and the distance walked.  The one state of the exports that outlives a call: mmw_trails_sample appends to it, the export
 // reads it.  Reads SceneHdr, order and two lines of each live TrackRec after the step; nothing of the step is touched.  No LDS, no
 // atomics: a wave per scene, four scenes per workgroup, a lane per track AND per trail slot (t_cap <= 64) -- lane i holds track i's
-// uid, lane j slot j's words, and uid -> slot is the broadcast compare of k_zone.hip.
-//   k_trail_rebase  mmw_reset / mmw_reset_scenes / mmw_restore: the touched scenes' generation word
+// uid, lane j slot j's words, and uid -> slot is uid_find (mmw_uidlist.hpp).
+//   k_uid_rebase    (k_scan.hip) mmw_reset / mmw_reset_scenes / mmw_restore: the touched scenes' generation word
 //   k_trail_sample  free the slots of uids that are gone, hand free slots to the newcomers, append one sample per live track
 //   k_trail_count   entries (= live tracks) and points per scene
 //   k_pair_scan     (k_scan.hip) one workgroup: the two offset scans, the capacity decision, the totals
 //   k_trail_write   the directory and the points, rings unwrapped oldest first -- only if everything fits
 #include <cstddef>
 #include "mmw_device.hpp"
+#include "mmw_uidlist.hpp"
 #include "mmw_wave.hpp"
 #include "mmw_kernels.hpp"
 
@@ -21,39 +22,15 @@ static_assert(offsetof(mmw_trail_track, t_first) == 24 && offsetof(mmw_trail_poi
 static_assert(MMW_TRACK_CAP_LIMIT <= 64, "one lane per track, one lane per trail slot");
 static_assert(MMW_TRAIL_DEPTH_MAX == 256, "a scene's points stay below 2^14");
 
-// Which slot holds each live track's trail.  All 64 lanes call; `owner` is this lane's slot's owner (-1: free, or past t_cap), `cuid`
-// this lane's track's uid (lanes past the live list: anything).  Returns the slot of this lane's track or -1; `kept`: this lane's
-// slot belongs to a live uid.  uids are unique inside a scene, so at most one lane matches a slot; a free slot matches nobody.
-__device__ __forceinline__ int trail_slot_of(int t_cap, int T, int lane, int owner, int cuid, bool &kept)
-{
-    int slot = -1;
-    kept = false;
-    for (int k = 0; k < t_cap; k++) {   // (uniform)
-        const int o = __shfl(owner, k);
-        const bool hit = lane < T && o != -1 && cuid == o;
-        slot = hit ? k : slot;
-        const bool any = __ballot(hit) != 0ull;
-        kept = (lane == k) ? any : kept;
-    }
-    return slot;
-}
-
-// flags == nullptr: every scene (mmw_reset); else the scenes whose flag is non-zero (mmw_reset_scenes, mmw_restore)
-__global__ void k_trail_rebase(DevCfg cfg, TrailState ts, const int32_t *__restrict__ flags)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < cfg.n_scenes && (!flags || flags[s])) ts.gen[s] += 1;
-}
-
 __global__ __launch_bounds__(256) void k_trail_sample(DevCfg cfg, DevState st, TrailState ts, const int32_t *__restrict__ flags, const double *__restrict__ t)
 {
-    const int s = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const auto [s, lane] = wave_scene();
     if (s >= cfg.n_scenes) return;     // (wave-uniform)
     if (flags && !flags[s]) return;    // (wave-uniform) not asked: not touched
     const int cap = cfg.t_cap, T = live_tracks(cfg, st, s);
     const size_t base = (size_t)s * cap;
-    const int gen = ts.gen[s], ord = ts.ordinal[s];
-    const bool rebased = gen != ts.seen[s];
+    const int ord = ts.ordinal[s];
+    const bool rebased = ts.ug.rebased(s);
     const double tt = t ? t[s] : (double)ord;
 
     // this lane's track ...
@@ -78,8 +55,10 @@ __global__ __launch_bounds__(256) void k_trail_sample(DevCfg cfg, DevState st, T
     }
     const int owner = rebased ? -1 : raw_owner;   // (1.: a uid of another generation owns nothing)
 
-    bool kept;
-    int slot = trail_slot_of(cap, T, lane, owner, cuid, kept);
+    // the two lists of the wave -- lane i's track's uid (-1 past the live list), lane j's slot's owner (-1: free, or past t_cap) --
+    // matched both ways: the slot of this lane's track or -1, and whether this lane's slot belongs to a live uid
+    int slot = uid_find(cuid, owner, cap);
+    const bool kept = uid_find(owner, cuid, T) >= 0;
     // 2. + 3.: the r-th newcomer, in live order, takes the r-th free slot
     const unsigned long long below = (1ull << lane) - 1ull;
     const unsigned long long free_b = __ballot(lane < cap && !kept);
@@ -118,10 +97,8 @@ __global__ __launch_bounds__(256) void k_trail_sample(DevCfg cfg, DevState st, T
         ts.ring[at * (size_t)ts.depth + (unsigned)(total - 1) % (unsigned)ts.depth] = mmw_trail_point{tt, (float)x, (float)y, (float)z, pflags};
     }
     if (lane < cap && !kept && !taken && raw_owner != -1) ts.owner[base + lane] = -1;   // (freed and not handed on)
-    if (lane == 0) {
-        ts.seen[s] = gen;
-        ts.ordinal[s] = ord + 1;
-    }
+    ts.ug.settle(s, lane);
+    if (lane == 0) ts.ordinal[s] = ord + 1;
 }
 
 // What the export says of this lane's track.  All 64 lanes call.
@@ -137,11 +114,9 @@ __device__ __forceinline__ TrailView trail_view(const DevCfg &cfg, const DevStat
     const int cap = cfg.t_cap;
     const size_t base = (size_t)s * cap;
     v.T = live_tracks(cfg, st, s);
-    v.uid = lane < v.T ? st.trk[base + live_slot(cfg, st, s, lane)].uid : -1;
-    const bool rebased = ts.gen[s] != ts.seen[s];
-    const int owner = (lane < cap && !rebased) ? ts.owner[base + lane] : -1;
-    bool kept;
-    v.slot = trail_slot_of(cap, v.T, lane, owner, v.uid, kept);
+    v.uid = live_uid(cfg, st, s, lane, v.T);
+    const int owner = (lane < cap && !ts.ug.rebased(s)) ? ts.owner[base + lane] : -1;
+    v.slot = uid_find(v.uid, owner, cap);
     v.count = v.total = 0;
     v.t_first = v.travelled = 0.0;
     if (v.slot >= 0) {
@@ -156,7 +131,7 @@ __device__ __forceinline__ TrailView trail_view(const DevCfg &cfg, const DevStat
 
 __global__ __launch_bounds__(256) void k_trail_count(DevCfg cfg, DevState st, TrailState ts, int max_per_track)
 {
-    const int s = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const auto [s, lane] = wave_scene();
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
     const TrailView v = trail_view(cfg, st, ts, s, lane, max_per_track);
     int n_points;
@@ -171,7 +146,8 @@ __global__ __launch_bounds__(256) void k_trail_write(DevCfg cfg, DevState st, Tr
                                                      mmw_trail_point *__restrict__ points, int max_per_track, int scene_base)
 {
     if (!ts.sc.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer is written
-    const int s = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, S = cfg.n_scenes;
+    const auto [s, lane] = wave_scene();
+    const int S = cfg.n_scenes;
     if (s >= S) return;             // (wave-uniform)
     const TrailView v = trail_view(cfg, st, ts, s, lane, max_per_track);
     const int e0 = ts.sc.off[s], p0 = ts.sc.off[S + 1 + s];
@@ -192,10 +168,6 @@ __global__ __launch_bounds__(256) void k_trail_write(DevCfg cfg, DevState st, Tr
     }
 }
 
-void launch_trail_rebase(const DevCfg &cfg, const TrailState &ts, const int32_t *flags, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_trail_rebase, dim3((cfg.n_scenes + 255) / 256), dim3(256), 0, st, cfg, ts, flags);
-}
 void launch_trail_sample(const DevCfg &cfg, const DevState &s, const TrailState &ts, const int32_t *flags, const double *t, hipStream_t st)
 {
     hipLaunchKernelGGL(k_trail_sample, dim3((cfg.n_scenes + 3) / 4), dim3(256), 0, st, cfg, s, ts, flags, t);

@@ -2,12 +2,13 @@
 // since the previous export as an event with the track's uid.  Reads SceneHdr, order and three lines of each live TrackRec after
 // the step, the way k_report does; nothing of the step is touched.  No LDS, no atomics: a wave per scene, a lane per track
 // (t_cap <= 64), the scene's zones walked with the wave -- s is wave-uniform, so the table comes through scalar loads.
-//   k_zone_rebase   mmw_reset / mmw_reset_scenes / mmw_restore / mmw_set_zones: the touched scenes' generation word
+//   k_uid_rebase    (k_scan.hip) mmw_reset / mmw_reset_scenes / mmw_restore / mmw_set_zones: the touched scenes' generation word
 //   k_zone_count    rows (= defined zones) and events per scene
 //   k_pair_scan     (k_scan.hip) one workgroup: the two offset scans, the capacity decision, the totals
 //   k_zone_write    events, rows, the new baseline -- only if everything fits
 #include <cstddef>
 #include "mmw_device.hpp"
+#include "mmw_uidlist.hpp"
 #include "mmw_math.hpp"
 #include "mmw_wave.hpp"
 #include "mmw_kernels.hpp"
@@ -37,25 +38,25 @@ __device__ __forceinline__ ZoneDiff zone_diff(const DevCfg &cfg, const DevState 
 {
     ZoneDiff d;
     d.T = live_tracks(cfg, st, s);
-    d.Tb = min(zs.base_len[s], cfg.t_cap);
+    d.Tb = zs.base.len(s, cfg.t_cap);
     d.nz = min(max(zs.n_zones[s], 0), MMW_ZONES_MAX);
-    d.rebased = zs.gen[s] != zs.seen[s];
+    d.rebased = zs.base.ug.rebased(s);
     double px = 0.0, py = 0.0;
     d.cuid = -1;
     d.is_static = false;
-    if (lane < d.T) {
+    if (lane < d.T) {   // (uid, position and is_static off one record pointer: live_uid would load the order word twice)
         const TrackRec *rec = st.trk + (size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane);
         d.cuid = rec->uid;
         px = rec->x[0];
         py = rec->x[1];
         d.is_static = rec->is_static != 0;
     }
-    d.buid = lane < d.Tb ? zs.base_uid[(size_t)s * cfg.t_cap + lane] : -1;
+    d.buid = zs.base.uid(s, cfg.t_cap, lane, d.Tb);
     const unsigned all = (1u << d.nz) - 1u;
     const unsigned bmask = (lane < d.Tb && !d.rebased) ? ((unsigned)zs.base_mask[(size_t)s * cfg.t_cap + lane] & all) : 0u;
 
-    // what the baseline holds for this lane's track: neither list is sorted, so the compare is broadcast lane by lane (uids are
-    // unique inside a scene: at most one entry matches)
+    // what the baseline holds for this lane's track.  uid_find's loop with the mask dragged along: on uid_find and one fetch of the
+    // mask behind it, k_zone_count and k_zone_write both take a 30th VGPR (profiles/uid_state_isa.txt)
     unsigned prev = 0u;
     for (int k = 0; k < d.Tb; k++) {   // (uniform)
         const int b = __shfl(d.buid, k);
@@ -88,26 +89,15 @@ __device__ __forceinline__ ZoneDiff zone_diff(const DevCfg &cfg, const DevState 
     d.enter = d.now & ~prev;
 
     // what is left of every baseline entry's memberships
-    unsigned still = 0u;
-    for (int k = 0; k < d.T; k++) {   // (uniform)
-        const int c = __shfl(d.cuid, k);
-        const unsigned m = (unsigned)__shfl((int)d.now, k);
-        still |= (lane < d.Tb && d.buid == c) ? m : 0u;
-    }
-    d.leave = bmask & ~still;
+    const int at = uid_find(d.buid, d.cuid, d.T);
+    const unsigned still = (unsigned)__shfl((int)d.now, at);   // (at = -1 reads lane 63: discarded)
+    d.leave = bmask & ~(at >= 0 ? still : 0u);
     return d;
-}
-
-// flags == nullptr: every scene (mmw_reset); else the scenes whose flag is non-zero (mmw_reset_scenes, mmw_restore, mmw_set_zones)
-__global__ void k_zone_rebase(DevCfg cfg, ZoneState zs, const int32_t *__restrict__ flags)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < cfg.n_scenes && (!flags || flags[s])) zs.gen[s] += 1;
 }
 
 __global__ __launch_bounds__(256) void k_zone_count(DevCfg cfg, DevState st, ZoneState zs)
 {
-    const int s = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const auto [s, lane] = wave_scene();
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
     const ZoneDiff d = zone_diff(cfg, st, zs, s, lane);
     int n_leave, n_enter;
@@ -133,7 +123,8 @@ __global__ __launch_bounds__(256) void k_zone_write(DevCfg cfg, DevState st, Zon
                                                     mmw_zone_event *__restrict__ events, int scene_base)
 {
     if (!zs.sc.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer, the baseline nor a generation is written
-    const int s = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, S = cfg.n_scenes;
+    const auto [s, lane] = wave_scene();
+    const int S = cfg.n_scenes;
     if (s >= S) return;             // (wave-uniform)
     const ZoneDiff d = zone_diff(cfg, st, zs, s, lane);
     const int row0 = zs.sc.off[s], ev0 = zs.sc.off[S + 1 + s];
@@ -159,17 +150,11 @@ __global__ __launch_bounds__(256) void k_zone_write(DevCfg cfg, DevState st, Zon
     if (lane < d.nz) rows[row0 + lane] = mmw_zone_row{scene_base + s, lane, id, count, count_static, entered, left, 0};
 
     // the current list is the next export's baseline (behind everything that read the old one: every lane's old entry is in its registers)
-    if (lane < d.T) {
-        zs.base_uid[(size_t)s * cfg.t_cap + lane] = d.cuid;
-        zs.base_mask[(size_t)s * cfg.t_cap + lane] = (int32_t)d.now;
-    }
-    if (lane == 0) { zs.base_len[s] = d.T; zs.seen[s] = zs.gen[s]; }
+    zs.base.store(s, cfg.t_cap, lane, d.T, d.cuid);
+    if (lane < d.T) zs.base_mask[(size_t)s * cfg.t_cap + lane] = (int32_t)d.now;
+    zs.base.ug.settle(s, lane);
 }
 
-void launch_zone_rebase(const DevCfg &cfg, const ZoneState &zs, const int32_t *flags, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_zone_rebase, dim3((cfg.n_scenes + 255) / 256), dim3(256), 0, st, cfg, zs, flags);
-}
 void launch_zones(const DevCfg &cfg, const DevState &s, const ZoneState &zs, mmw_zone_row *rows, int cap_rows, mmw_zone_event *events, int cap_events,
                   int scene_base, hipStream_t st)
 {

@@ -148,10 +148,7 @@ int probe_side_streams(mmw_ctx *c);                                // api_contex
 int read_headers(mmw_ctx *c, std::vector<SceneHdr> &h);            // api_query.hip
 int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q);   // api_query.hip
 void posture_batch_free(PostureBatch *b);                          // api_posture.hip
-int report_rebase(mmw_ctx *c, const int32_t *dev_flags);           // api_report.hip: the scenes' uids restart (no-op while reports are off)
-int zone_rebase(mmw_ctx *c, const int32_t *dev_flags);             // api_zone.hip: the scenes' zone memberships are void (no-op while no zone table exists)
 void zone_free(mmw_ctx *c);                                        // api_zone.hip: table, baseline and mirrors (the caller has waited for the stream)
-int trail_rebase(mmw_ctx *c, const int32_t *dev_flags);            // api_trail.hip: the scenes' trails end, their uids restart (no-op while trails are off)
 void trail_free(mmw_ctx *c);                                       // api_trail.hip: slots, rings and scratch (the caller has waited for the stream)
 int uart_log_rearm(mmw_ctx *c);                                    // api_uart_log.hip: every scene's log word as new, with its range scale (no-op while the log is off)
 void uart_log_free(mmw_ctx *c);                                    // api_uart_log.hip: ... and the log is off (the caller has waited for the stream)
@@ -160,6 +157,7 @@ int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name)
 void export_free(ExportCtx &x);                                    // ... and x is as never allocated
 int export_issue(mmw_ctx *c, ExportCtx &x, int ticket);           // behind the launch: its error, the totals into the ticket's pinned slot, the event
 int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const char *none, const int32_t **counts);   // -> the ticket's four words
+int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones and trails, none while all three are off
 #pragma GCC visibility pop
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)

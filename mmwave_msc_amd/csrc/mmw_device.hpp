@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/mmw.h"
+#include "mmw_uidlist.hpp"
 
 namespace mmw {
 
@@ -194,22 +195,17 @@ struct ExportScratch {
 };
 // mmw_report_enable: what the live-track report keeps between two reports (k_report.hip).  All device memory.
 struct ReportState {
-    int32_t *base_uid;    // [S][t_cap] the uids live at the previous report, in effective_tracks order as it was then (the BASELINE)
-    int32_t *base_len;    // [S] ... and how many
-    int32_t *gen;         // [S] generation of the scene's uids: bumped by mmw_reset / mmw_reset_scenes / mmw_restore (uids restart there)
-    int32_t *seen;        // [S] the generation the baseline was taken in
+    UidBaseline base;     // the uids live at the previous report, and the generation they were taken in (mmw_uidlist.hpp)
     ExportScratch sc;     // rows / events of the report in flight
 };
-// mmw_set_zones: the zone table and what the zone export keeps between two exports (k_zone.hip).  All device memory.  The baseline is
-// the report's mechanism but the zones' own words: reports need not be enabled, and the two are consumed at different times.
+// mmw_set_zones: the zone table and what the zone export keeps between two exports (k_zone.hip).  All device memory.  A baseline of
+// its own, of the report's type: reports need not be enabled, the two are consumed at different times, and mmw_set_zones bumps
+// this generation alone, for the scenes it lists.
 struct ZoneState {
     const mmw_zone *zones;     // [S][MMW_ZONES_MAX] the table (one copy of mmw_set_zones; read with scalar loads)
     const int32_t *n_zones;    // [S] zones defined per scene, behind the table in the same allocation
-    int32_t *base_uid;         // [S][t_cap] the uids live at the previous successful export, in effective_tracks order as it was then
+    UidBaseline base;          // the uids live at the previous successful export ...
     int32_t *base_mask;        // [S][t_cap] ... and the zones each was a member of: bit z = zone z
-    int32_t *base_len;         // [S] ... and how many
-    int32_t *gen;              // [S] generation: bumped by mmw_reset / mmw_reset_scenes / mmw_restore and by mmw_set_zones for the scenes it lists
-    int32_t *seen;             // [S] the generation the baseline was taken in
     ExportScratch sc;          // rows / events of the export in flight
 };
 // mmw_trails_enable: what the track trails keep from one mmw_trails_sample to the next (k_trail.hip).  All device memory.  A scene
@@ -223,8 +219,7 @@ struct TrailState {
     double *travelled;         // [S][t_cap] path length in the x/y plane over all its samples
     double *last_x, *last_y;   // [S][t_cap] the fp64 position of its newest sample
     mmw_trail_point *ring;     // [S][t_cap][depth] sample n (0-based) of a uid lies at n % depth
-    int32_t *gen;              // [S] generation of the scene's uids: bumped by mmw_reset / mmw_reset_scenes / mmw_restore
-    int32_t *seen;             // [S] the generation the scene's slots belong to (set by a sample call that asked the scene)
+    UidGen ug;                 // the generation the scene's slots belong to (settled by a sample call that asked the scene)
     int32_t *ordinal;          // [S] sample calls that asked the scene since mmw_trails_enable
     ExportScratch sc;          // entries / points of the export in flight
 };
@@ -235,6 +230,11 @@ __device__ __forceinline__ int live_tracks(const DevCfg &cfg, const DevState &st
 __device__ __forceinline__ int live_slot(const DevCfg &cfg, const DevState &st, int s, int lane)
 {
     return min(max(st.order[(size_t)s * cfg.t_cap + lane], 0), cfg.t_cap - 1);
+}
+// ... and this lane's live uid, -1 past the list (T = live_tracks)
+__device__ __forceinline__ int live_uid(const DevCfg &cfg, const DevState &st, int s, int lane, int T)
+{
+    return lane < T ? st.trk[(size_t)s * cfg.t_cap + live_slot(cfg, st, s, lane)].uid : -1;
 }
 // The update lists (track-wise Kalman kernels).  A scene's workgroup of k_track appends its T tracks to the list of its SHARD
 // (workgroup index mod shards: eight counters instead of one word that every workgroup of the launch adds to) with one atomicAdd;

@@ -59,21 +59,22 @@ void launch_probe_set(int32_t *w, hipStream_t st);
 void launch_pop_frame(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st);
 void launch_clear_errors(const DevCfg &cfg, const DevState &s, const int32_t *flags, int bits, hipStream_t st);
 void launch_set_batch_size(const DevCfg &cfg, const DevState &s, const int32_t *flags, int new_size, hipStream_t st);
-// k_scan.hip: the scan step of the three live-track exports below -- two count arrays to offsets, totals and the capacity decision
+// k_scan.hip: the scan step of the live-track exports below -- two count arrays to offsets, totals and the capacity decision
 void launch_pair_scan(int S, int32_t *off, int32_t *totals, int cap0, int cap1, hipStream_t st);
+// ... and the generation bump of those that remember uids (report, zones, trails): every non-null word, for the scenes flagged
+// (flags: dev [S] or nullptr = every scene)
+struct UidGens { static constexpr int kMax = 3; int32_t *gen[kMax]; };
+void launch_uid_rebase(int n_scenes, const int32_t *flags, const UidGens &gens, hipStream_t st);
 // k_report.hip: the live-track report
 void launch_report_baseline(const DevCfg &cfg, const DevState &s, const ReportState &rp, hipStream_t st);
-void launch_report_rebase(const DevCfg &cfg, const ReportState &rp, const int32_t *flags, hipStream_t st);
 void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const ReportState &rp, mmw_track_report *rows, int cap_rows, mmw_track_event *events, int cap_events, int scene_base, hipStream_t st);
 // k_cloud.hip: the live tracks' point clouds (mode: MMW_CLOUD_POINTS / MMW_CLOUD_ROWS, | MMW_CLOUD_UNASSIGNED)
 void launch_clouds(const DevCfg &cfg, const DevState &s, const ExportScratch &sc, mmw_cloud_track *dir, int cap_tracks, void *out, int cap_points, int mode, int scene_base, hipStream_t st);
 // k_skeleton.hip: the live tracks' room-frame skeletons (mode: MMW_SKEL_ALL / MMW_SKEL_DRAWN)
 void launch_skeletons(const DevCfg &cfg, const DevState &s, const ExportScratch &sc, mmw_skeleton *out, int cap, int mode, int scene_base, hipStream_t st);
-// k_zone.hip: zone occupancy (flags of the rebase: dev [S] or nullptr = every scene)
-void launch_zone_rebase(const DevCfg &cfg, const ZoneState &zs, const int32_t *flags, hipStream_t st);
+// k_zone.hip: zone occupancy
 void launch_zones(const DevCfg &cfg, const DevState &s, const ZoneState &zs, mmw_zone_row *rows, int cap_rows, mmw_zone_event *events, int cap_events, int scene_base, hipStream_t st);
 // k_trail.hip: track trails (flags: dev [S] or nullptr = every scene; t: dev [S] or nullptr = the scenes' call ordinals)
-void launch_trail_rebase(const DevCfg &cfg, const TrailState &ts, const int32_t *flags, hipStream_t st);
 void launch_trail_sample(const DevCfg &cfg, const DevState &s, const TrailState &ts, const int32_t *flags, const double *t, hipStream_t st);
 void launch_trails(const DevCfg &cfg, const DevState &s, const TrailState &ts, mmw_trail_track *dir, int cap_tracks, mmw_trail_point *points, int cap_points, int max_per_track, int scene_base, hipStream_t st);
 // k_uart.hip: the device-resident radar readers (log: the radar log while it is enabled -- the k_uart_read*_log twins --, else nullptr)

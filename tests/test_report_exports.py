@@ -40,10 +40,10 @@ def test_report_kernels_use_no_scratch_and_store_rows_in_16_byte_pieces():
     rep, asm = _device_isa(("k_report",))["k_report"]
     rows = _kernel_report(rep)
     names = [k[0] for k in rows]
-    for k in ("k_report_baseline", "k_report_rebase", "k_report_count"):
+    for k in ("k_report_baseline", "k_report_count"):
         assert sum(k in n for n in names) == 1, (k, names)
     assert sum("k_report_write" in n for n in names) == 2, names   # the context's window, and each scene's own site
-    assert len(names) == 5, names                                   # (the scan is k_pair_scan of k_scan.hip)
+    assert len(names) == 4, names                                   # (the scan and the generation bump are k_scan.hip's)
     assert_clean(rows)
     for name, scratch, vspill, vgprs, occ, sspill in rows:
         body = kernel_body(asm, name)
@@ -56,12 +56,15 @@ def test_report_kernels_use_no_scratch_and_store_rows_in_16_byte_pieces():
 
 def test_the_exports_share_one_scan_kernel_without_scratch():
     """k_scan.hip holds the one two-array offset scan of the library, k_pair_scan: no scratch, no spilled register.  The three
-    kernels it replaced are in no export's device code, and its launcher is declared once and defined once."""
+    kernels it replaced are in no export's device code, and its launcher is declared once and defined once.  (Its second kernel
+    is k_uid_rebase: test_one_generation_bump_and_one_uid_match_for_report_zones_and_trails.)"""
     from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
     isa = _device_isa(("k_scan", "k_report", "k_cloud", "k_skeleton"))
     rep, asm = isa["k_scan"]
     rows = _kernel_report(rep)
-    assert len(rows) == 1 and "k_pair_scan" in rows[0][0], rows
+    assert len(rows) == 2 and sum("k_uid_rebase" in r[0] for r in rows) == 1, rows
+    rows = [r for r in rows if "k_pair_scan" in r[0]]
+    assert len(rows) == 1, rows
     name, scratch, vspill, vgprs, occ, sspill = rows[0]
     assert_clean(rows)
     body = kernel_body(asm, name, ".Lfunc_end")
@@ -83,6 +86,42 @@ def test_the_exports_share_one_scan_kernel_without_scratch():
     assert holders == ["mmw_scan.hpp"] and open(os.path.join(csrc, "mmw_scan.hpp")).read().count(loop) == 1, holders
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "k_scan.hip" in mk and "mmw_scan.hpp" in mk and "api_export.hip" in mk
+
+
+def test_one_generation_bump_and_one_uid_match_for_report_zones_and_trails():
+    """k_uid_rebase (k_scan.hip) is the one kernel that bumps a generation word -- no scratch, no LDS, no spilled register -- with
+    one launcher and one host entry; the three kernels and the three host wrappers it replaced are gone.  The match of two uid
+    lists, uid_find, is written once, in the header the three by-uid consumers include."""
+    from tests._isa import _device_isa, _kernel_report, assert_clean, kernel_body
+    isa = _device_isa(("k_scan", "k_report", "k_zone", "k_trail"))
+    rep, asm = isa["k_scan"]
+    rows = [r for r in _kernel_report(rep) if "k_uid_rebase" in r[0]]
+    assert len(rows) == 1, rows
+    assert_clean(rows)
+    body = kernel_body(asm, rows[0][0], ".Lfunc_end")
+    assert "scratch_" not in body and not re.search(r"\bds_(read|write)", body), rows[0][0]
+    assert re.search(r"LDS Size \[bytes/block\]: (\d+)", rep.split("remark: Function Name: " + rows[0][0])[1]).group(1) == "0"
+    olds = ("k_report_rebase", "k_zone_rebase", "k_trail_rebase")
+    for f, (_, a) in isa.items():
+        for old in olds:
+            assert old not in a, (f, old)
+        assert ("k_uid_rebase" in a) == (f == "k_scan"), f
+    csrc = os.path.join(ROOT, "mmwave_msc_amd", "csrc")
+    src = {fn: open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".hpp"))}
+    for fn, txt in src.items():
+        for old in olds:
+            assert old not in txt, (fn, old)
+        for old in ("report_rebase", "zone_rebase", "trail_rebase"):   # (the host wrappers, and the launchers' names with them)
+            assert old not in txt, (fn, old)
+    launcher = r"\bvoid\s+launch_uid_rebase\s*\("
+    assert {fn: len(re.findall(launcher, txt)) for fn, txt in src.items() if re.search(launcher, txt)} == {"k_scan.hip": 1, "mmw_kernels.hpp": 1}
+    entry = r"\bint\s+uid_rebase\s*\("
+    assert {fn: len(re.findall(entry, txt)) for fn, txt in src.items() if re.search(entry, txt)} == {"api_export.hip": 1, "mmw_ctx.hpp": 1}
+    find = r"\bint\s+uid_find\s*\("
+    assert {fn: len(re.findall(find, txt)) for fn, txt in src.items() if re.search(find, txt)} == {"mmw_uidlist.hpp": 1}
+    for fn in ("k_report.hip", "k_zone.hip", "k_trail.hip"):
+        assert '#include "mmw_uidlist.hpp"' in src[fn] and "uid_find(" in src[fn], fn
+    assert "mmw_uidlist.hpp" in open(os.path.join(csrc, "Makefile")).read()
 
 
 def test_table_kernels_still_compile_without_scratch_after_sharing_their_body():
