@@ -781,6 +781,102 @@ int mmw_trails_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_tracks, int32_t *n_
 int mmw_trails(mmw_ctx *ctx, mmw_trail_track *dir, int32_t cap_tracks, mmw_trail_point *points, int32_t cap_points,
                int32_t max_per_track, int32_t scene_base, int32_t *n_tracks, int32_t *n_points);   /* async + wait */
 
+/* ---- tripwires ----
+ * How many people walked through a door, and which way: per scene up to MMW_TRIPWIRES_MAX directed segments A -> B in the scene's
+ * normalised frame, per wire the number of tracks that went across it either way, and every crossing as an event with the track's
+ * uid.  The zones are a difference of states -- a track that walks through a doorway zone between two exports appears in neither
+ * -- and the trails hold positions, not passages.  This is a LOG: the sides are decided on the device by mmw_tripwires_sample,
+ * normally once behind each mmw_step, nothing is lost between two exports, and the export is read when the caller likes.  No step
+ * kernel reads or writes any of this: a context that never enables tripwires launches exactly what it did before they existed.
+ *
+ * mmw_tripwires_enable(log_depth), log_depth in 1 .. MMW_TRIPWIRE_LOG_MAX, allocates the wire table (every scene at 0 wires) and per
+ * scene: t_cap uid SLOTS of {owner uid or -1 = free, side word: two bits per wire, 0 unknown, 1 negative, 2 positive}; per wire the
+ * int32 totals `forward` and `backward` and the two MARKS (the totals at the previous successful export); an event ring of
+ * log_depth entries with the words `logged` (events ever appended) and `taken` (events handed out), event number n at n % log_depth;
+ * a generation, the generation seen and a call ordinal.  Every slot starts free, every word at 0; the state is ordered on the
+ * context's stream.  Enabling again, with any depth, starts over (0 wires everywhere).  log_depth == 0 waits for the stream, frees
+ * the state and turns tripwires off (MMW_OK also when they were off).  log_depth outside 0 .. MMW_TRIPWIRE_LOG_MAX: MMW_E_ARG, nothing
+ * changed.  A failed allocation: MMW_E_HIP, nothing changed -- an earlier enablement stays as it is.  Until enabled, every other
+ * entry returns MMW_E_ARG, except mmw_get_tripwires, which reports 0 wires.
+ *
+ * Setting wires follows mmw_set_zones' rules.  mmw_set_tripwires gives scene scenes[i] (scenes == NULL: scene i) the first
+ * n_wires[i] entries of wires[i][MMW_TRIPWIRES_MAX] as its wires 0 .. n_wires[i] - 1; entries past n_wires[i] are not read; scenes
+ * never listed keep what they have.  Every check is made on the host before anything changes, the table travels as ONE copy ordered
+ * on the context's stream, and the call is synchronous.  Refused as a whole (MMW_E_ARG, the message names the entry, no scene's
+ * wires change): n < 0 or n > n_scenes, n_wires or wires NULL with n > 0, a scene index out of range or listed twice, n_wires[i]
+ * outside 0 .. MMW_TRIPWIRES_MAX, a non-zero reserved_, a coordinate that is not finite, a margin that is negative or not finite,
+ * A == B, a len2 or band (below) that is zero (band: with a margin > 0) or not finite.  For each wire the HOST derives, in exactly
+ * this operation order (the library is built with -ffp-contract=off, host side included):
+ *     dx = bx - ax;  dy = by - ay;  len2 = dx * dx + dy * dy;  band = margin * sqrt(len2)
+ * and the device reads only ax, ay, dx, dy, len2, band and id: no device sqrt takes part in a decision.  For the listed scenes
+ * the generation is bumped (their side bits change meaning), and forward, backward and the marks restart at 0, ordered on the
+ * stream; the log and `taken` are kept.  Wires belong to the slot, like zones: mmw_reset* keeps wires, counters and log, a snapshot
+ * blob does not carry them (format version 1 is unchanged) and mmw_restore leaves the destination's wires alone.
+ * mmw_get_tripwires copies the host mirror (no device access; either output may be NULL; entries past a scene's n_wires are zero).
+ *
+ * mmw_tripwires_sample is asynchronous: ONE kernel on the context's stream behind whatever was queued last.  Scene flags and t are
+ * mmw_trails_sample's: scene s is ASKED when scene_flags == NULL or scene_flags[s] != 0 (the frame's n_pts array serves), t == NULL
+ * means the scene's call ordinal as a double -- the number of earlier mmw_tripwires_sample calls that asked this scene since
+ * mmw_tripwires_enable, with or without wires.  An asked scene with 0 wires only sets seen = generation (and counts the call).  For
+ * an asked scene with wires, in this order:
+ *   1. generation != seen: every slot is freed, seen = generation, and ONE MMW_TW_REBASED event is appended (t of this sample);
+ *   2. every slot whose owner is not among the live uids is freed;
+ *   3. every live uid without a slot takes a free one with side word 0 (the trails' rule; which slot is not observable);
+ *   4. for every live track, with p = (x[0], x[1]) of the fp64 state, and every defined wire in ascending order:
+ *          rx = px - ax;  ry = py - ay;
+ *          u = rx * dx + ry * dy;            along the wire
+ *          c = dx * ry - dy * rx;            > 0: left of A -> B
+ *          inside = 0 <= u && u <= len2
+ *          new = !inside ? unknown : c > band ? positive : c < -band ? negative : old
+ *      old = negative and new = positive: one MMW_TW_FORWARD event and forward += 1; old = positive and new = negative:
+ *      MMW_TW_BACKWARD and backward += 1.  Then the side becomes `new`.
+ * So a NaN or infinite coordinate makes `inside` false: the side is forgotten and there is no event.  A track that walks round an
+ * end of the segment passes through `unknown` and is not counted, one that dithers inside the band is counted once at most, one
+ * born beyond the wire is not counted.  Events of one call are appended in this order: REBASED first, then tracks in
+ * effective_tracks order, wires ascending inside a track; each carries slot = the track's position now, t = the sample's t and the
+ * scene.  If one call appends more events than log_depth, only the newest log_depth are written.  A scene that is not asked is not
+ * touched.  Sampling twice without a step changes nothing the second time, except the ordinal.  scene_flags: dev pointer, 4-byte
+ * aligned; t: dev pointer, 8-byte aligned; else MMW_E_ARG.
+ *
+ * mmw_tripwires_async / _wait export rows and events in one call, with the zones' mechanics.  Rows: one per DEFINED wire, in
+ * (scene, wire) order; forward / backward are the totals since the scene's wires were last set, d_forward / d_backward those
+ * totals minus the marks, lost = max(0, logged - log_depth - taken): events of the scene overwritten before an export could take
+ * them, the same in each of the scene's rows -- counters never lose anything.  Events: per scene those numbered
+ * max(taken, logged - log_depth) .. logged - 1, oldest first, scenes ascending; scene is offset by scene_base, as the rows' is.  On
+ * success taken = logged and the marks become the totals.  A uid that crossed forward and back between two exports yields both
+ * events and both counts.  Capacity is decided on the DEVICE against both caps: if anything does not fit, NOTHING is written,
+ * taken and the marks stay as they were, and mmw_tripwires_wait returns MMW_E_CAPACITY with both counts needed: a retry with larger
+ * buffers loses nothing.  mmw_tripwires_async queues its kernels on the context's stream; the counts follow into pinned memory
+ * and mmw_tripwires_wait(ticket) waits for THAT copy only.  ticket in [0,4), ticket 3 is mmw_tripwires' own.  rows / events: dev
+ * pointers, 8-byte aligned.  MMW_E_ARG, nothing touched: a NULL context, tripwires not enabled, a NULL buffer with a positive cap, a
+ * negative cap, a misaligned buffer, a bad ticket, a wait for a ticket with nothing outstanding.
+ *
+ * Life cycle.  mmw_reset, mmw_reset_scenes and mmw_restore bump the generation of the scenes they touch (uids restart there), in
+ * the one launch the report, the zones and the trails share.  mmw_destroy frees the state.  More than INT32_MAX events or crossings
+ * per scene are not supported. */
+#define MMW_TRIPWIRES_MAX 16
+#define MMW_TRIPWIRE_LOG_MAX 4096
+typedef struct mmw_tripwire {      /* 48 bytes */
+    double ax, ay, bx, by;         /* A -> B in the frame of mmw_track_record.x[0], x[1] */
+    double margin;                 /* >= 0, metres: half-width of the band in which a side is kept */
+    int32_t id;                    /* caller's label, copied into rows and events */
+    int32_t reserved_;             /* must be 0 */
+} mmw_tripwire;
+typedef struct mmw_tripwire_row   { int32_t scene, wire, id, forward, backward, d_forward, d_backward, lost; } mmw_tripwire_row;   /* 32 bytes */
+typedef struct mmw_tripwire_event { int32_t scene, uid, kind, wire, id, slot; double t; } mmw_tripwire_event;                       /* 32 bytes */
+#define MMW_TW_FORWARD 1    /* the uid went from the negative side (right of A->B) to the positive side (left) */
+#define MMW_TW_BACKWARD 2
+#define MMW_TW_REBASED 3    /* the scene's uids or wires are new from here on; uid = wire = id = -1, slot = live tracks then */
+int mmw_tripwires_enable(mmw_ctx *ctx, int32_t log_depth);      /* 1 .. MMW_TRIPWIRE_LOG_MAX; 0 = off and freed */
+int mmw_set_tripwires(mmw_ctx *ctx, const int32_t *scenes, int32_t n, const int32_t *n_wires /* host [n] */, const mmw_tripwire *wires /* host [n][MMW_TRIPWIRES_MAX] */);
+int mmw_get_tripwires(mmw_ctx *ctx, int32_t *n_wires /* host [S] */, mmw_tripwire *wires /* host [S][MMW_TRIPWIRES_MAX] */);   /* host mirror, no device access */
+int mmw_tripwires_sample(mmw_ctx *ctx, const int32_t *scene_flags /* dev [S] or NULL */, const double *t /* dev [S] or NULL */);
+int mmw_tripwires_async(mmw_ctx *ctx, mmw_tripwire_row *rows, int32_t cap_rows, mmw_tripwire_event *events, int32_t cap_events,
+                        int32_t scene_base, int32_t ticket);
+int mmw_tripwires_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n_events);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_tripwires(mmw_ctx *ctx, mmw_tripwire_row *rows, int32_t cap_rows, mmw_tripwire_event *events, int32_t cap_events,
+                  int32_t scene_base, int32_t *n_rows, int32_t *n_events);                 /* async + wait */
+
 /* Snapshot / restore of scene state (format version 1).
  *
  * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global

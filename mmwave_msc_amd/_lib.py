@@ -37,7 +37,7 @@ POSTURE_MODELS_MAX = 8             # models one mmw_posture_attach_models call t
 POSTURE_NONE = -1                  # MMW_POSTURE_NONE: the map entry of a scene no model estimates
 EXPORT_TICKETS = 4                 # kTickets (csrc/mmw_ctx.hpp): `*_async` calls of one export that may be outstanding; the
                                    # one-call form of each export (mmw_report, mmw_clouds, ...) uses the last ticket itself
-REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = TRAIL_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
+REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = TRAIL_TICKETS = TRIPWIRE_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
 
 EMPTY_FRAME = -1   # MMW_EMPTY_FRAME (include/mmw.h)
 BAD_FRAME = -3     # MMW_BAD_FRAME: n_out of mmw_normalize_tlv for a TLV body it refused to decode
@@ -188,6 +188,17 @@ TRAIL_TRACK_DTYPE = np.dtype([("scene", "i4"), ("slot", "i4"), ("uid", "i4"), ("
                               ("t_first", "f8"), ("travelled", "f8")], align=True)
 TRAIL_POINT_DTYPE = np.dtype([("t", "f8"), ("x", "f4"), ("y", "f4"), ("z", "f4"), ("flags", "i4")], align=True)
 
+# struct mmw_tripwire / mmw_tripwire_row / mmw_tripwire_event (include/mmw.h): a scene's wires (48 bytes each), and the rows (32 bytes)
+# and events (32 bytes) of mmw_tripwires_*
+TRIPWIRES_MAX = 16                            # MMW_TRIPWIRES_MAX: wires per scene
+TRIPWIRE_LOG_MAX = 4096                       # MMW_TRIPWIRE_LOG_MAX: events a scene's log holds at the most
+TRIPWIRE_FIELDS = ("ax", "ay", "bx", "by", "margin", "id")
+TRIPWIRE_DTYPE = np.dtype([("ax", "f8"), ("ay", "f8"), ("bx", "f8"), ("by", "f8"), ("margin", "f8"), ("id", "i4"), ("reserved_", "i4")], align=True)
+TRIPWIRE_ROW_DTYPE = np.dtype([("scene", "i4"), ("wire", "i4"), ("id", "i4"), ("forward", "i4"), ("backward", "i4"), ("d_forward", "i4"),
+                               ("d_backward", "i4"), ("lost", "i4")], align=True)
+TRIPWIRE_EVENT_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("kind", "i4"), ("wire", "i4"), ("id", "i4"), ("slot", "i4"), ("t", "f8")], align=True)
+TW_FORWARD, TW_BACKWARD, TW_REBASED = 1, 2, 3   # MMW_TW_*: mmw_tripwire_event.kind
+
 
 # C struct name in include/mmw.h -> its Python mirror; every `typedef struct mmw_*` but the opaque mmw_ctx.  Field names are the
 # header's own throughout, so a mirror needs no second spelling beside it.
@@ -197,6 +208,7 @@ ABI_STRUCTS = {
     "mmw_cloud_track": CLOUD_TRACK_DTYPE, "mmw_cloud_point": CLOUD_POINT_DTYPE, "mmw_skeleton": SKELETON_DTYPE,
     "mmw_zone": ZONE_DTYPE, "mmw_zone_row": ZONE_ROW_DTYPE, "mmw_zone_event": ZONE_EVENT_DTYPE,
     "mmw_trail_track": TRAIL_TRACK_DTYPE, "mmw_trail_point": TRAIL_POINT_DTYPE,
+    "mmw_tripwire": TRIPWIRE_DTYPE, "mmw_tripwire_row": TRIPWIRE_ROW_DTYPE, "mmw_tripwire_event": TRIPWIRE_EVENT_DTYPE,
     "mmw_snapshot_header": MmwSnapshotHeader, "mmw_snapshot_entry": MmwSnapshotEntry, "mmw_snapshot_info": MmwSnapshotInfo,
     "mmw_uart_cfg": MmwUartCfg, "mmw_uart_frame": UART_FRAME_DTYPE, "mmw_uart_object": UART_OBJECT_DTYPE,
     "mmw_sample_entry": SAMPLE_ENTRY_DTYPE,
@@ -313,6 +325,13 @@ def _signatures():
         "mmw_trails_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32]),
         "mmw_trails_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_trails": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32p, i32p]),
+        "mmw_tripwires_enable": (C.c_int, [vp, i32]),
+        "mmw_set_tripwires": (C.c_int, [vp, vp, i32, vp, vp]),
+        "mmw_get_tripwires": (C.c_int, [vp, vp, vp]),
+        "mmw_tripwires_sample": (C.c_int, [vp, vp, vp]),
+        "mmw_tripwires_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
+        "mmw_tripwires_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_tripwires": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
         "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
         "mmw_uart_close": (C.c_int, [vp]),
         "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),
@@ -547,3 +566,31 @@ def make_zones(per_scene):
             for f, v in zip(ZONE_FIELDS, vals):
                 zones[i, k][f] = v
     return n_zones, zones
+
+
+def make_tripwires(per_scene):
+    """(n_wires int32[n], wires TRIPWIRE_DTYPE[n, TRIPWIRES_MAX]) for `mmw_set_tripwires` from one list per scene of up to
+    TRIPWIRES_MAX wires, each a dict with keys of TRIPWIRE_FIELDS (`margin` and `id` may be left out: 0, and the wire's index) or a
+    tuple (ax, ay, bx, by[, margin[, id]]).  Entries past a scene's wires stay zero."""
+    per_scene = list(per_scene)
+    n_wires = np.zeros(len(per_scene), np.int32)
+    wires = np.zeros((len(per_scene), TRIPWIRES_MAX), TRIPWIRE_DTYPE)
+    for i, ws in enumerate(per_scene):
+        ws = list(ws)
+        if len(ws) > TRIPWIRES_MAX:
+            raise ValueError(f"make_tripwires: scene entry {i} has {len(ws)} wires, at most {TRIPWIRES_MAX} fit")
+        n_wires[i] = len(ws)
+        for k, w in enumerate(ws):
+            if isinstance(w, dict):
+                unknown = set(w) - set(TRIPWIRE_FIELDS)
+                if unknown:
+                    raise AttributeError(f"mmw_tripwire has no field {sorted(unknown)[0]!r}")
+                vals = [w[f] for f in TRIPWIRE_FIELDS[:4]] + [w.get("margin", 0.0), w.get("id", k)]
+            else:
+                w = tuple(w)
+                if not 4 <= len(w) <= 6:
+                    raise ValueError(f"make_tripwires: a wire is (ax, ay, bx, by[, margin[, id]]), not {len(w)} values")
+                vals = list(w) + [0.0, k][len(w) - 4:]
+            for f, v in zip(TRIPWIRE_FIELDS, vals):
+                wires[i, k][f] = v
+    return n_wires, wires

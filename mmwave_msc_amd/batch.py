@@ -973,6 +973,80 @@ class SceneBatch:
         return self._export_host("trails", lambda *a: self.trails_dev(*a[:4], last, a[4], scene_base), self.L.mmw_trails_wait,
                                  ("trail_dir", _lib.TRAIL_TRACK_DTYPE), ("trail_points", _lib.TRAIL_POINT_DTYPE))
 
+    # -- tripwires ------------------------------------------------------------
+    def enable_tripwires(self, log_depth: int = 256):
+        """mmw_tripwires_enable: per scene a wire table (0 wires to begin with), per-uid sides, per-wire crossing counters and a log
+        of `log_depth` (1 .. `_lib.TRIPWIRE_LOG_MAX`) events; everything starts over, also when tripwires were enabled before.
+        log_depth=0 frees them.  Until enabled, the tripwire calls are refused (E_ARG) -- `tripwires()` reports 0 wires -- and the
+        context launches nothing of them."""
+        self._chk(self.L.mmw_tripwires_enable(self.h, int(log_depth)))
+
+    def set_tripwires(self, wires, scenes=None):
+        """mmw_set_tripwires: give `scenes` (default: scenes 0 .. len(wires)-1) their wires -- `wires` is what
+        `_lib.make_tripwires` takes (a list per scene of dicts or tuples) or its result, the pair (n_wires, TRIPWIRE_DTYPE[n, 16]).
+        Scenes never listed keep what they have; the listed scenes' counters restart at 0 and their sides are void (their next
+        sample logs a TW_REBASED).  Refused (MmwError, E_ARG) with nothing changed for an index out of range or listed twice, more
+        entries than scenes, a coordinate that is not finite, A == B, a margin that is negative or not finite, a squared length or
+        band that is zero or not finite, or a non-zero `reserved_`."""
+        if isinstance(wires, tuple) and len(wires) == 2 and isinstance(wires[1], np.ndarray) and wires[1].dtype == _lib.TRIPWIRE_DTYPE:
+            nw, wt = wires
+        else:
+            nw, wt = _lib.make_tripwires(wires)
+        nw = np.ascontiguousarray(np.asarray(nw, dtype=np.int32).reshape(-1))
+        wt = np.ascontiguousarray(wt.reshape(-1, _lib.TRIPWIRES_MAX))
+        if len(nw) != len(wt):
+            raise ValueError(f"set_tripwires: {len(nw)} counts for {len(wt)} scenes' wires")
+        idx = None
+        if scenes is not None:
+            idx = np.ascontiguousarray(np.asarray(scenes, dtype=np.int32).reshape(-1))
+            if len(idx) != len(nw):
+                raise ValueError(f"set_tripwires: {len(nw)} entries for {len(idx)} scenes")
+        self._chk(self.L.mmw_set_tripwires(self.h, idx.ctypes.data if idx is not None else None, len(nw), nw.ctypes.data if len(nw) else None,
+                                           wt.ctypes.data if len(nw) else None))
+
+    def tripwires(self):
+        """mmw_get_tripwires: (n_wires int32[S], wires TRIPWIRE_DTYPE[S, 16]) of every scene, from the host mirror; zero past a
+        scene's wires."""
+        nw = np.zeros(self.S, dtype=np.int32)
+        wt = np.zeros((self.S, _lib.TRIPWIRES_MAX), dtype=_lib.TRIPWIRE_DTYPE)
+        self._chk(self.L.mmw_get_tripwires(self.h, nw.ctypes.data, wt.ctypes.data))
+        return nw, wt
+
+    def sample_tripwires_dev(self, flags_ptr=None, t_ptr=None):
+        """mmw_tripwires_sample: every live track's side of every wire of the asked scenes, crossings counted and logged, queued
+        behind the last step on the context's stream -- no host wait.  `flags_ptr`: device int32[S], non-zero = asked (the step's
+        n_pts array serves; None = every scene); `t_ptr`: device float64[S], the events' time (None = each scene's count of earlier
+        sample calls)."""
+        self._chk(self.L.mmw_tripwires_sample(self.h, flags_ptr, t_ptr))
+
+    def sample_tripwires(self, t=None, scenes=None):
+        """`sample_tripwires_dev` from host arrays: `t` float64[S] or a scalar for every scene (None = the call ordinals), `scenes`
+        the scenes to sample (default all)."""
+        t_ptr = None
+        if t is not None:
+            t_ptr = self.buf("tripwire_t", self.S * 8).upload(np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (self.S,)))).ptr
+        self.sample_tripwires_dev(self._scene_flags(scenes, "tripwire_flags"), t_ptr)
+
+    def tripwires_async(self, rows_ptr, cap_rows: int, events_ptr, cap_events: int, scene_base: int = 0, ticket: int = 0):
+        """mmw_tripwires_async: one `_lib.TRIPWIRE_ROW_DTYPE` row per defined wire in (scene, wire) order and the
+        `_lib.TRIPWIRE_EVENT_DTYPE` events logged since the previous successful export into device buffers, queued on the context's
+        stream -- no host wait.  Tickets 0 .. 3 (`tripwires_host` uses 3).  Both pointers 8-byte aligned."""
+        self._chk(self.L.mmw_tripwires_async(self.h, rows_ptr, int(cap_rows), events_ptr, int(cap_events), int(scene_base), int(ticket)))
+
+    def tripwires_wait(self, ticket: int = 0):
+        """(n_rows, n_events) of the `tripwires_async` call with this ticket: waits for its counts only, not for the stream.  Buffers
+        too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written and nothing was taken, so
+        the same export can be asked for again with room."""
+        return self._export_wait(self.L.mmw_tripwires_wait, ticket)
+
+    def tripwires_host(self, scene_base: int = 0):
+        """The tripwire export as two structured arrays: (rows[n_rows] TRIPWIRE_ROW_DTYPE, events[n_events] TRIPWIRE_EVENT_DTYPE);
+        fold the events with `tripwires.Tally`.  The buffers grow to what the device says it needs (a refused export loses
+        nothing)."""
+        self._export_caps.setdefault("tripwires", (64, 256))   # (its entry exists from the first call on, as the zones')
+        return self._export_host("tripwires", lambda *a: self.tripwires_async(*a[:4], scene_base, a[4]), self.L.mmw_tripwires_wait,
+                                 ("tripwire_rows", _lib.TRIPWIRE_ROW_DTYPE), ("tripwire_events", _lib.TRIPWIRE_EVENT_DTYPE))
+
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):
         if scenes is None:

@@ -47,12 +47,13 @@ int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const ch
 }
 
 // mmw_reset / mmw_reset_scenes / mmw_restore: uids restart in the scenes flagged in dev_flags (device, [n_scenes]; nullptr = every
-// scene), so the report's baseline, the zones' memberships and the trails of those scenes are void.  One launch for the consumers
+// scene), so the report's baseline, the zones' memberships, the trails and the tripwires' sides of those scenes are void.  One launch for the consumers
 // that are on, queued on the context's stream behind the kernel that emptied or refilled the scenes; nothing at all while none is.
 int uid_rebase(mmw_ctx *c, const int32_t *dev_flags)
 {
-    const UidGens g = {{c->rep.d_block ? c->rs.base.ug.gen : nullptr, c->zone.d_block ? c->zs.base.ug.gen : nullptr, c->trail.d_block ? c->ts.ug.gen : nullptr}};
-    if (!g.gen[0] && !g.gen[1] && !g.gen[2]) return MMW_OK;
+    const UidGens g = {{c->rep.d_block ? c->rs.base.ug.gen : nullptr, c->zone.d_block ? c->zs.base.ug.gen : nullptr, c->trail.d_block ? c->ts.ug.gen : nullptr,
+                       c->trip.d_block ? c->tw.ug.gen : nullptr}};
+    if (!g.gen[0] && !g.gen[1] && !g.gen[2] && !g.gen[3]) return MMW_OK;
     launch_uid_rebase(c->dc.n_scenes, dev_flags, g, c->stream);
     HIPCHK(c, hipGetLastError());
     return MMW_OK;

@@ -1,0 +1,211 @@
+// api_tripwire.hip -- the C-ABI (include/mmw.h): tripwires.  mmw_tripwires_enable owns the table, the uid slots, the counters and
+// the event rings, mmw_set_tripwires derives the table on the host, mmw_tripwires_sample queues the one kernel that decides the
+// sides, mmw_tripwires_async queues the export kernels of k_tripwire.hip and the copy of the two counts, mmw_tripwires_wait waits
+// for that copy.
+#include <cmath>
+#include "mmw_ctx.hpp"
+
+static_assert(sizeof(mmw_tripwire) == 48, "mmw_tripwire: the numpy layout of mmwave_msc_amd/_lib.py");
+static_assert(sizeof(mmw_tripwire_row) == 32, "mmw_tripwire_row: the numpy layout of mmwave_msc_amd/_lib.py");
+static_assert(sizeof(mmw_tripwire_event) == 32, "mmw_tripwire_event: the numpy layout of mmwave_msc_amd/_lib.py");
+
+void tripwire_free(mmw_ctx *c)
+{
+    export_free(c->trip);
+    if (c->d_twtab) hipFree(c->d_twtab);
+    c->d_twtab = nullptr;
+    c->tw = TripState();
+    c->h_wires.clear();
+    c->h_nwires.clear();
+}
+
+// the table's allocation: [S][MMW_TRIPWIRES_MAX] TripWire | [S] n_wires | [S] scene flags of the mmw_set_tripwires call that wrote it
+static size_t twtab_bytes(size_t S) { return S * MMW_TRIPWIRES_MAX * sizeof(TripWire) + 2 * S * sizeof(int32_t); }
+
+int mmw_tripwires_enable(mmw_ctx *c, int32_t log_depth)
+{
+    if (!c) return fail(nullptr, MMW_E_ARG, "mmw_tripwires_enable: null context");
+    if (log_depth < 0 || log_depth > MMW_TRIPWIRE_LOG_MAX)
+        return fail(c, MMW_E_ARG, "mmw_tripwires_enable: log_depth = %d outside 0 .. %d", log_depth, MMW_TRIPWIRE_LOG_MAX);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (log_depth == 0) {
+        if (!c->trip.d_block) return MMW_OK;
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (a sample, an export or a rebase may still be queued on what is freed here)
+        tripwire_free(c);
+        return MMW_OK;
+    }
+    // The new state is allocated and cleared BEFORE the old one goes: a failure leaves an earlier enablement as it was.  One block, the
+    // state in front of the scratch: [S][depth] events | [S][16] counters | [S][t_cap] owner | side | [S] logged | taken | gen | seen | ordinal
+    const size_t S = c->dc.n_scenes, n = S * c->dc.t_cap;
+    const size_t ring_bytes = S * (size_t)log_depth * sizeof(mmw_tripwire_event), count_bytes = S * MMW_TRIPWIRES_MAX * sizeof(TripCount);
+    const size_t words = (ring_bytes + count_bytes) / sizeof(int32_t) + 2 * n + 5 * S;
+    ExportCtx nx;
+    MMW_TRY(export_alloc(c, nx, words, "mmw_tripwires_enable"));
+    char *tab = nullptr;
+    if (hipMalloc((void **)&tab, twtab_bytes(S)) != hipSuccess) {
+        export_free(nx);
+        return fail(c, MMW_E_HIP, "mmw_tripwires_enable: hipMalloc(%zu B) failed", twtab_bytes(S));
+    }
+    TripState tw = {};
+    tw.depth = log_depth;
+    tw.wires = reinterpret_cast<const TripWire *>(tab);
+    tw.n_wires = reinterpret_cast<const int32_t *>(tab + S * MMW_TRIPWIRES_MAX * sizeof(TripWire));
+    tw.ring = reinterpret_cast<mmw_tripwire_event *>(nx.d_block);
+    tw.count = reinterpret_cast<TripCount *>(nx.d_block + ring_bytes);
+    int32_t *p = reinterpret_cast<int32_t *>(nx.d_block + ring_bytes + count_bytes);
+    tw.owner = p; p += n;
+    tw.side = p; p += n;
+    tw.logged = p; p += S;
+    tw.taken = p; p += S;
+    tw.ug.gen = p; p += S;
+    tw.ug.seen = p; p += S;
+    tw.ordinal = p;
+    tw.sc = nx.sc;
+    // every scene at 0 wires, every slot free, every word 0 (the rings need no clearing: an entry is written before `logged` lets anybody read it)
+    hipError_t e = hipMemsetAsync(tab, 0, twtab_bytes(S), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(tw.count, 0, count_bytes, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(tw.owner, 0xff, n * sizeof(int32_t), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(tw.side, 0, (n + 5 * S) * sizeof(int32_t), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (... and whatever was queued on an earlier enablement's state has run)
+    if (e != hipSuccess) {
+        export_free(nx);
+        hipFree(tab);
+        return fail(c, MMW_E_HIP, "mmw_tripwires_enable: %s", hipGetErrorString(e));
+    }
+    tripwire_free(c);
+    c->trip = nx;
+    c->tw = tw;
+    c->d_twtab = tab;
+    c->h_wires.assign(S * MMW_TRIPWIRES_MAX, mmw_tripwire{});
+    c->h_nwires.assign(S, 0);
+    return MMW_OK;
+}
+
+// what the device reads of a wire, in the header's operation order (this file is compiled with -ffp-contract=off like the kernels)
+static TripWire derive(const mmw_tripwire &w)
+{
+    TripWire d = {};
+    d.ax = w.ax;
+    d.ay = w.ay;
+    d.dx = w.bx - w.ax;
+    d.dy = w.by - w.ay;
+    d.len2 = d.dx * d.dx + d.dy * d.dy;
+    d.band = w.margin * std::sqrt(d.len2);
+    d.id = w.id;
+    return d;
+}
+
+int mmw_set_tripwires(mmw_ctx *c, const int32_t *scenes, int32_t n, const int32_t *n_wires, const mmw_tripwire *wires)
+{
+    if (!c) return fail(nullptr, MMW_E_ARG, "mmw_set_tripwires: null context");
+    if (!c->trip.d_block) return fail(c, MMW_E_ARG, "mmw_set_tripwires: tripwires are not enabled (mmw_tripwires_enable)");
+    const int S = c->dc.n_scenes;
+    // every check first: a refused call changes no scene's wires
+    if (n < 0 || n > S) return fail(c, MMW_E_ARG, "mmw_set_tripwires: n = %d, the context has %d scenes", n, S);
+    if (n > 0 && (!n_wires || !wires)) return fail(c, MMW_E_ARG, "mmw_set_tripwires: %s is NULL with n = %d", !n_wires ? "n_wires" : "wires", n);
+    std::vector<char> listed((size_t)S, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = scenes ? scenes[i] : i;
+        if (s < 0 || s >= S) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d names scene %d, the context has %d scenes", i, s, S);
+        if (listed[s]) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d names scene %d a second time", i, s);
+        listed[s] = 1;
+        if (n_wires[i] < 0 || n_wires[i] > MMW_TRIPWIRES_MAX)
+            return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) has n_wires = %d, outside 0 .. %d", i, s, n_wires[i], MMW_TRIPWIRES_MAX);
+        for (int z = 0; z < n_wires[i]; z++) {
+            const mmw_tripwire &q = wires[(size_t)i * MMW_TRIPWIRES_MAX + z];
+            if (q.reserved_ != 0) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a non-zero reserved_", i, s, z);
+            if (!std::isfinite(q.ax) || !std::isfinite(q.ay) || !std::isfinite(q.bx) || !std::isfinite(q.by))
+                return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a coordinate that is not finite", i, s, z);
+            if (!(q.margin >= 0.0) || !std::isfinite(q.margin))
+                return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a margin that is negative or not finite", i, s, z);
+            if (q.ax == q.bx && q.ay == q.by) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has A == B", i, s, z);
+            const TripWire d = derive(q);
+            if (!(d.len2 > 0.0) || !std::isfinite(d.len2)) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a squared length that is zero or not finite", i, s, z);
+            if (!std::isfinite(d.band) || (q.margin > 0.0 && !(d.band > 0.0)))
+                return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a band (margin x length) that is zero or not finite", i, s, z);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // The new table is put together on the host (from a copy of the mirror: a failure below leaves the mirror as it was) and travels
+    // as ONE copy, ordered on the context's stream: what was queued before this call reads the old table.  The listed scenes' flags
+    // ride behind it, for the generation bump -- of the tripwires' word alone -- and the restart of their counters.
+    std::vector<mmw_tripwire> next = c->h_wires;
+    std::vector<int32_t> next_n = c->h_nwires;
+    for (int i = 0; i < n; i++) {
+        const size_t s = scenes ? scenes[i] : i;
+        next_n[s] = n_wires[i];
+        for (int z = 0; z < MMW_TRIPWIRES_MAX; z++) next[s * MMW_TRIPWIRES_MAX + z] = z < n_wires[i] ? wires[(size_t)i * MMW_TRIPWIRES_MAX + z] : mmw_tripwire{};
+    }
+    const size_t tb = (size_t)S * MMW_TRIPWIRES_MAX * sizeof(TripWire);
+    std::vector<char> stage(twtab_bytes((size_t)S), 0);
+    TripWire *dev = reinterpret_cast<TripWire *>(stage.data());
+    for (size_t s = 0; s < (size_t)S; s++)
+        for (int z = 0; z < next_n[s]; z++) dev[s * MMW_TRIPWIRES_MAX + z] = derive(next[s * MMW_TRIPWIRES_MAX + z]);
+    memcpy(stage.data() + tb, next_n.data(), sizeof(int32_t) * (size_t)S);
+    int32_t *flags = reinterpret_cast<int32_t *>(stage.data() + tb) + S;
+    for (int s = 0; s < S; s++) flags[s] = listed[s];
+    hipError_t e = hipMemcpyAsync(c->d_twtab, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_uid_rebase(S, c->tw.n_wires + S, UidGens{{c->tw.ug.gen, nullptr, nullptr, nullptr}}, c->stream);
+        launch_tripwire_zero(S, c->tw.n_wires + S, c->tw, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (`stage` is pageable and goes away)
+    if (e != hipSuccess) return fail(c, MMW_E_HIP, "mmw_set_tripwires: %s", hipGetErrorString(e));
+    c->h_wires.swap(next);
+    c->h_nwires.swap(next_n);
+    return MMW_OK;
+}
+
+int mmw_get_tripwires(mmw_ctx *c, int32_t *n_wires, mmw_tripwire *wires)
+{
+    if (!c) return fail(nullptr, MMW_E_ARG, "mmw_get_tripwires: null context");
+    const size_t S = (size_t)c->dc.n_scenes;
+    const bool have = c->trip.d_block != nullptr;
+    if (n_wires) { if (have) memcpy(n_wires, c->h_nwires.data(), S * sizeof(int32_t)); else memset(n_wires, 0, S * sizeof(int32_t)); }
+    if (wires) { if (have) memcpy(wires, c->h_wires.data(), S * MMW_TRIPWIRES_MAX * sizeof(mmw_tripwire)); else memset(wires, 0, S * MMW_TRIPWIRES_MAX * sizeof(mmw_tripwire)); }
+    return MMW_OK;
+}
+
+int mmw_tripwires_sample(mmw_ctx *c, const int32_t *scene_flags, const double *t)
+{
+    if (!c) return MMW_E_ARG;
+    if (!c->trip.d_block) return fail(c, MMW_E_ARG, "mmw_tripwires_sample: tripwires are not enabled (mmw_tripwires_enable)");
+    if (((uintptr_t)scene_flags & 3) != 0 || ((uintptr_t)t & 7) != 0) return fail(c, MMW_E_ARG, "mmw_tripwires_sample: scene_flags must be 4-byte aligned, t 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_tripwire_sample(c->dc, c->st, c->tw, scene_flags, t, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MMW_OK;
+}
+
+int mmw_tripwires_async(mmw_ctx *c, mmw_tripwire_row *rows, int32_t cap_rows, mmw_tripwire_event *events, int32_t cap_events, int32_t scene_base, int32_t ticket)
+{
+    if (!c) return MMW_E_ARG;
+    if (!c->trip.d_block) return fail(c, MMW_E_ARG, "mmw_tripwires: tripwires are not enabled (mmw_tripwires_enable)");
+    if (cap_rows < 0 || cap_events < 0 || (cap_rows > 0 && !rows) || (cap_events > 0 && !events))
+        return fail(c, MMW_E_ARG, "mmw_tripwires: cap_rows = %d, cap_events = %d with rows %s, events %s", cap_rows, cap_events, rows ? "set" : "NULL", events ? "set" : "NULL");
+    if (((uintptr_t)rows & 7) != 0 || ((uintptr_t)events & 7) != 0) return fail(c, MMW_E_ARG, "mmw_tripwires: the buffers must be 8-byte aligned");
+    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_tripwires: ticket %d outside [0, %d)", ticket, kTickets);
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_tripwires(c->dc, c->tw, rows, cap_rows, events, cap_events, scene_base, c->stream);
+    return export_issue(c, c->trip, ticket);
+}
+
+int mmw_tripwires_wait(mmw_ctx *c, int32_t ticket, int32_t *n_rows, int32_t *n_events)
+{
+    if (!c) return MMW_E_ARG;
+    if (!c->trip.d_block) return fail(c, MMW_E_ARG, "mmw_tripwires_wait: tripwires are not enabled (mmw_tripwires_enable)");
+    const int32_t *h;
+    MMW_TRY(export_wait(c, c->trip, ticket, "mmw_tripwires_wait", "no tripwire export", &h));
+    if (n_rows) *n_rows = h[0];
+    if (n_events) *n_events = h[1];
+    if (!h[2]) return fail(c, MMW_E_CAPACITY, "mmw_tripwires: %d rows and %d events do not fit the buffers: nothing was written, nothing was taken", h[0], h[1]);
+    return MMW_OK;
+}
+
+int mmw_tripwires(mmw_ctx *c, mmw_tripwire_row *rows, int32_t cap_rows, mmw_tripwire_event *events, int32_t cap_events, int32_t scene_base, int32_t *n_rows,
+                  int32_t *n_events)
+{
+    const int rc = mmw_tripwires_async(c, rows, cap_rows, events, cap_events, scene_base, kTickets - 1);
+    return rc ? rc : mmw_tripwires_wait(c, kTickets - 1, n_rows, n_events);
+}

@@ -129,6 +129,11 @@ struct mmw_ctx {
     std::vector<int32_t> h_nzones;    // ... and of n_zones [S] (mmw_get_zones reads both)
     ExportCtx trail;                  // mmw_trails_enable allocates it (depth 0 frees it); not allocated = trails are off, nothing of them is launched
     TrailState ts = {};               // ... the trail slots and rings, in front of trail's scratch in trail.d_block (ts.sc = trail.sc)
+    ExportCtx trip;                   // mmw_tripwires_enable allocates it (log_depth 0 frees it); not allocated = tripwires are off, nothing of them is launched
+    TripState tw = {};                // ... the uid slots, counters and event rings, in front of trip's scratch in trip.d_block (tw.sc = trip.sc)
+    char *d_twtab = nullptr;          // ... the table as ONE copy lands in it: [S][MMW_TRIPWIRES_MAX] TripWire | [S] n_wires | [S] the call's scene flags
+    std::vector<mmw_tripwire> h_wires;   // host mirror of the table as the caller gave it ([S][MMW_TRIPWIRES_MAX], zero past a scene's n_wires) ...
+    std::vector<int32_t> h_nwires;    // ... and of n_wires [S] (mmw_get_tripwires reads both)
     ExportCtx ulog_x;                 // mmw_uart_log_enable; not allocated = the radar log is off and mmw_uart_read launches what it always did
     UartLog ulog = {};                // ... the staged frames, in front of ulog_x's scratch in ulog_x.d_block
     std::vector<double> uart_range;   // [S] rangeIdxToMeters of the open readers (the log's range column)
@@ -149,6 +154,7 @@ int read_headers(mmw_ctx *c, std::vector<SceneHdr> &h);            // api_query.
 int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q);   // api_query.hip
 void posture_batch_free(PostureBatch *b);                          // api_posture.hip
 void zone_free(mmw_ctx *c);                                        // api_zone.hip: table, baseline and mirrors (the caller has waited for the stream)
+void tripwire_free(mmw_ctx *c);                                    // api_tripwire.hip: table, slots, counters, rings and mirrors (the caller has waited for the stream)
 void trail_free(mmw_ctx *c);                                       // api_trail.hip: slots, rings and scratch (the caller has waited for the stream)
 int uart_log_rearm(mmw_ctx *c);                                    // api_uart_log.hip: every scene's log word as new, with its range scale (no-op while the log is off)
 void uart_log_free(mmw_ctx *c);                                    // api_uart_log.hip: ... and the log is off (the caller has waited for the stream)
@@ -157,7 +163,7 @@ int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name)
 void export_free(ExportCtx &x);                                    // ... and x is as never allocated
 int export_issue(mmw_ctx *c, ExportCtx &x, int ticket);           // behind the launch: its error, the totals into the ticket's pinned slot, the event
 int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const char *none, const int32_t **counts);   // -> the ticket's four words
-int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones and trails, none while all three are off
+int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones, trails and tripwires, none while all four are off
 #pragma GCC visibility pop
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)

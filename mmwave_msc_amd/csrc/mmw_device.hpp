@@ -223,6 +223,23 @@ struct TrailState {
     int32_t *ordinal;          // [S] sample calls that asked the scene since mmw_trails_enable
     ExportScratch sc;          // entries / points of the export in flight
 };
+// mmw_tripwires_enable: the wire table and what the tripwires keep from one mmw_tripwires_sample to the next (k_tripwire.hip).  All
+// device memory.  A table entry is what the HOST derived of an mmw_tripwire (mmw_set_tripwires): the device takes no sqrt.
+struct TripWire { double ax, ay, dx, dy, len2, band; int32_t id, pad_; };   // 56 bytes
+struct TripCount { int32_t forward, backward, mark_forward, mark_backward; };   // totals since the wires were set; ... at the previous successful export
+struct TripState {
+    int32_t depth;             // log entries per scene, 1 .. MMW_TRIPWIRE_LOG_MAX
+    const TripWire *wires;     // [S][MMW_TRIPWIRES_MAX] the table (one copy of mmw_set_tripwires; read with scalar loads)
+    const int32_t *n_wires;    // [S] wires defined per scene, behind the table in the same allocation
+    int32_t *owner;            // [S][t_cap] the slot's uid, -1 = free (the trails' slots: lane j of a scene's wave holds slot j)
+    int32_t *side;             // [S][t_cap] two bits per wire: 0 unknown, 1 negative, 2 positive
+    TripCount *count;          // [S][MMW_TRIPWIRES_MAX] lane z of a scene's wave owns wire z's
+    mmw_tripwire_event *ring;  // [S][depth] event n (0-based) of a scene lies at n % depth, with the LOCAL scene index
+    int32_t *logged, *taken;   // [S] events ever appended / handed out
+    UidGen ug;                 // the generation the scene's slots belong to (settled by a sample call that asked the scene)
+    int32_t *ordinal;          // [S] sample calls that asked the scene since mmw_tripwires_enable
+    ExportScratch sc;          // rows / events of the export in flight
+};
 
 // The live list of scene s, as every export walks it: T = live_tracks lanes, lane -> live_slot -> the scene's TrackRec.  Both are
 // clamped into range, so a damaged state gives the same list -- report row i, cloud entry i, skeleton i -- in every export.
