@@ -11,6 +11,9 @@ ValueError, and for a decoded packet numObj, the TLV body as the reference read 
 object -- stale bytes of its 2^15-byte buffer included), x, y, z, doppler, peakVal, range (fp64) and rangeIdx, dopplerIdx.
 
 Data only: the arrays are concatenations, `*_off` are offsets into them (one per read, one past the end).
+
+`--buffer [out.npz]` writes the second recording instead, tests/golden/uart_buffer.npz: the same read() at the full size of its
+2^15-byte buffer (see `buffer_streams` below).  The first recording does not change by it.
 """
 import json
 import os
@@ -317,8 +320,170 @@ def generate(path):
     return out
 
 
+# ---- the second recording: the buffer mechanics at full size (tests/golden/uart_buffer.npz; `--buffer [out.npz]`) ----------
+# Packets of up to 1024 objects, several per buffer, split across chunks, with totalPacketLen on either side of the bytes
+# received, and the 2^15-byte rule at its edge.  Every byte that is not a header is FILLER: position-distinguishing (a move by a
+# wrong shift, pass or mask lands on other values), never 2 (no filler forms a magic word), with a period of 247 = 13 * 19 that
+# is coprime to the 16-byte pieces and the 4096-byte passes of the device's byte mover, and compressible.  Per read the file
+# keeps the chunk, dataOK, frameNumber, raised, byteBufferLength, the SHA-256 of all 2^15 buffer bytes after the call and, when
+# it decoded, numObj and the detObj columns.
+OUT_BUFFER = os.path.join(ROOT, "tests", "golden", "uart_buffer.npz")
+CFG_B = {"rangeIdxToMeters": 0.0872, "dopplerResolutionMps": 0.0626, "numDopplerBins": 32.0}
+SEED_BUFFER = 2015
+
+
+def filler(n, phase):
+    return (9 + (131 * (np.arange(n, dtype=np.int64) + phase)) % 247).astype(np.uint8).tobytes()
+
+
+def big_packet(frame, n, phase, q=15, num_obj=None, total=None, pad=True):
+    """A packet whose n objects are filler bytes (Q 15: x, y, z within +-1 m, so that about half the rows pass normalize_data); padded with filler to a multiple of 32 bytes as the sensor sends it
+    (totalPacketLen counts the padding) unless `total` says otherwise or pad is off."""
+    p = packet(frame, np.frombuffer(filler(12 * n, phase), "<u2").reshape(-1, 6), q=q, num_obj=num_obj, total=total)
+    if total is None and pad:
+        tot = (len(p) + 31) // 32 * 32
+        p = p[:12] + struct.pack("<I", tot) + p[16:] + filler(tot - len(p), phase + 7)
+    return p
+
+
+def bstream_several_per_buffer():
+    """Several packets in one chunk behind a little garbage: the LAST magic word wins, at a position past 4096, 8192, 16384
+    with more than 4096 bytes behind it -- the cut moves them by 1, 2, 3 and 0 modulo 4."""
+    P = big_packet
+    return CFG_A, [filler(37, 1) + P(1, 1024, 11) + P(2, 600, 12) + P(3, 342, 13),
+                   filler(2, 2) + P(4, 600, 14, q=7) + P(5, 1024, 15, q=7),
+                   filler(3, 3) + P(6, 341, 16) + P(7, 337, 17) + P(8, 1024, 18, q=12),
+                   P(9, 338, 19) + P(10, 600, 20),
+                   filler(4099, 4) + P(11, 341, 21, q=0) + filler(5, 5),
+                   P(12, 337, 22) + filler(3, 6), P(13, 338, 23), filler(1, 7) + P(14, 342, 24) + filler(11, 8)]
+
+
+def bstream_split_across_chunks():
+    """Packets that arrive in pieces behind garbage: appends of 1 to 4097 bytes and more onto every length, the head of the next
+    packet behind a decoded one (the drop moves it to the front)."""
+    a, b, c = big_packet(21, 1024, 31), big_packet(22, 600, 32, q=10), big_packet(23, 341, 33)
+    d = big_packet(24, 342, 34, q=8)
+    return CFG_B, [filler(1001, 9) + a[:1], a[1:4096], a[4096:8193], a[8193:] + b[:8], b[8:5000], b[5000:] + filler(13, 10),
+                   filler(4097, 11), c[:3], c[3:19], c[19:4115], c[4115:] + d[:7], d[7:8], d[8:4104], d[4104:], filler(9, 12)]
+
+
+def bstream_total_packet_len():
+    """totalPacketLen shorter than the bytes received (decoded, and only that many bytes dropped: moves to the front of more than
+    4096 bytes by 1, 3, 2 and 0 modulo 4, and by a large odd length) and longer (pending until the bytes are there)."""
+    P = big_packet
+    return CFG_A, [P(31, 1024, 41, total=4097) + filler(6000, 13), P(32, 600, 42, total=7251) + filler(5000, 14),
+                   P(33, 342, 43, total=4098) + filler(4500, 15), P(34, 600, 44, total=20000), filler(9000, 16), filler(3760, 17),
+                   P(35, 1024, 45, total=12001, q=11) + filler(9000, 18), P(36, 341, 46) + filler(2, 19),
+                   P(37, 600, 47, total=2000) + filler(100, 41)]
+
+
+def bstream_fill_to_the_rule():
+    """byteBufferLength + byteCount = 32 767 (kept) and 32 768 (dropped), with chunks of 1, 2, 12 000 and 12 001 bytes and with a
+    pending packet that announces 32 767 bytes: the fill-up that completes it is dropped at one byte more, kept at the byte, and the
+    whole buffer is then dropped by that odd totalPacketLen."""
+    return CFG_A, [big_packet(41, 600, 51, total=32767), filler(13519, 20), filler(12001, 21), filler(12000, 22),
+                   filler(20000, 23), filler(12766, 24), filler(2, 25), filler(1, 26), filler(1, 27), b"", filler(12000, 28)]
+
+
+def bstream_fill_from_empty():
+    """An empty buffer and one chunk of 32 768 bytes (dropped), then of 32 767 (kept; nothing can follow it)."""
+    return CFG_B, [filler(CAP, 29), filler(CAP - 1, 30), filler(1, 31)]
+
+
+def bstream_announced_bounds():
+    """A buffer full of stale filler, then 3 objects sent with 2726 announced (the last object ends at byte 32 760: decoded from
+    the stale bytes) and with 2727 (it ends at 32 772: ValueError), then an honest packet."""
+    P = big_packet
+    return CFG_A, [filler(32000, 32), P(51, 3, 61, num_obj=2726, pad=False) + filler(9, 33), P(52, 3, 62, num_obj=2727, pad=False) + filler(9, 34),
+                   P(53, 2, 63) + filler(4, 35)]
+
+
+def bstream_stale_after_long():
+    """A 1024-object packet decoded and dropped leaves its bytes behind; then 3 objects sent and 900, 300 and 257 announced."""
+    P = big_packet
+    return CFG_B, [P(61, 1024, 71) + filler(8, 36), P(62, 3, 72, num_obj=900, pad=False) + filler(5, 37),
+                   P(63, 3, 73, num_obj=300, q=6, pad=False) + filler(5, 38), P(64, 3, 74, num_obj=257, pad=False) + filler(5, 39),
+                   P(65, 2, 75) + filler(3, 40)]
+
+
+def bstream_random_big():
+    """A seeded run of 1024-, 600-, 342-, 341-, 338- and 337-object packets with garbage between, cut into random chunks."""
+    rng = np.random.default_rng(SEED_BUFFER)
+    data = b""
+    for i, n in enumerate((1024, 341, 600, 342, 1024, 337, 600, 338, 1024, 600)):
+        data += filler(int(rng.integers(0, 40)), 100 + i) + big_packet(80 + i, n, 80 + i, q=int(rng.integers(0, 16)))
+    cuts, at = [0], 0
+    while at < len(data):
+        at = min(at + int(rng.choice([1, 3, 17, 500, 4095, 4097, 6000, 9000])), len(data))
+        cuts.append(at)
+    return CFG_A, [data[a:b] for a, b in zip(cuts, cuts[1:])]
+
+
+def buffer_streams():
+    return [("several_per_buffer",) + bstream_several_per_buffer(), ("split_across_chunks",) + bstream_split_across_chunks(),
+            ("total_packet_len",) + bstream_total_packet_len(), ("fill_to_the_rule",) + bstream_fill_to_the_rule(),
+            ("fill_from_empty",) + bstream_fill_from_empty(), ("announced_bounds",) + bstream_announced_bounds(),
+            ("stale_after_long",) + bstream_stale_after_long(), ("random_big",) + bstream_random_big()]
+
+
+def generate_buffer(path):
+    import hashlib
+    import importlib
+    from oracle.ref_import import REFERENCE_SRC
+    sys.dont_write_bytecode = True
+    for p in (os.path.join(HERE, "serial_shim"), REFERENCE_SRC):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    mod = importlib.import_module("ReadDataIWR1443")
+    acc = {k: [] for k in ("chunk", "ok", "frame", "raised", "buflen", "digest", "num_obj", "det")}
+    names, cfgs, s_reads = [], [], [0]
+    for name, cfgp, chunks in buffer_streams():
+        rd = _reader(mod, cfgp)
+        for ch in chunks:
+            rd.Dataport.q = ch
+            raised = 0
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                try:
+                    ok, fn, det = rd.read()
+                except ValueError:
+                    ok, fn, det, raised = 0, 0, {}, 1
+            acc["chunk"].append(np.frombuffer(ch, dtype=np.uint8))
+            acc["ok"].append(int(ok))
+            acc["frame"].append(int(fn))
+            acc["raised"].append(raised)
+            acc["buflen"].append(int(rd.byteBufferLength))
+            assert rd.byteBuffer.shape == (CAP,) and rd.byteBuffer.dtype == np.uint8
+            acc["digest"].append(np.frombuffer(hashlib.sha256(rd.byteBuffer.tobytes()).digest(), dtype=np.uint8))
+            n = int(det["numObj"]) if ok else -1
+            acc["num_obj"].append(n)
+            acc["det"].append(np.stack([np.asarray(det[k], dtype=np.float64).reshape(n) for k in ("x", "y", "z", "doppler", "peakVal", "range")], axis=1)
+                              if ok else np.zeros((0, 6)))
+        names.append(name)
+        cfgs.append([cfgp["rangeIdxToMeters"], cfgp["dopplerResolutionMps"], cfgp["numDopplerBins"]])
+        s_reads.append(len(acc["ok"]))
+    meta = {"numpy": np.__version__, "python": sys.version.split()[0], "seed": SEED_BUFFER, "filler": "9 + (131 * (i + phase)) % 247",
+            "reference": "src/ReadDataIWR1443.py ReadIWR14xx.read (the reference pins numpy 1.26.3)"}
+    out = {
+        "meta": np.array(json.dumps(meta, sort_keys=True)), "names": np.array(names), "cfg": np.array(cfgs, np.float64),
+        "stream_reads": np.array(s_reads, np.int64),
+        "chunk": np.concatenate(acc["chunk"]), "chunk_off": _offsets(acc["chunk"]),
+        "ok": np.array(acc["ok"], np.int8), "frame": np.array(acc["frame"], np.int64), "raised": np.array(acc["raised"], np.int8),
+        "buflen": np.array(acc["buflen"], np.int64), "digest": np.stack(acc["digest"]),
+        "num_obj": np.array(acc["num_obj"], np.int64), "det": np.concatenate(acc["det"]), "det_off": _offsets(acc["det"]),
+    }
+    np.savez_compressed(path, **out)
+    return out
+
+
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
+    if len(sys.argv) > 1 and sys.argv[1] == "--buffer":
+        path = sys.argv[2] if len(sys.argv) > 2 else OUT_BUFFER
+        o = generate_buffer(path)
+        print(f"{path}: {len(o['names'])} streams, {len(o['ok'])} reads, {int(o['ok'].sum())} decoded, {int(o['raised'].sum())} raised, "
+              f"{len(o['det'])} objects, largest {int(o['num_obj'].max())}, numpy {np.__version__}, {os.path.getsize(path)} bytes")
+        sys.exit(0)
     path = sys.argv[1] if len(sys.argv) > 1 else OUT
     o = generate(path)
     print(f"{path}: {len(o['names'])} streams, {len(o['ok'])} reads, {int(o['ok'].sum())} decoded, {int(o['raised'].sum())} raised, "

@@ -50,6 +50,39 @@ def load(path=GOLD):
     return out
 
 
+GOLD_BUFFER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "uart_buffer.npz")
+
+
+@dataclass
+class BufferRead:
+    """A read of tests/golden/uart_buffer.npz (oracle/gen_uart_golden.py --buffer): the same reference under the same numpy, with
+    packets of up to 1024 objects and buffers filled to the 2^15-byte rule; of the buffer it keeps the SHA-256 of all 2^15 bytes."""
+    index: int
+    chunk: bytes
+    ok: int
+    frame: int
+    raised: bool
+    buflen: int
+    digest: bytes         # hashlib.sha256(byteBuffer.tobytes()).digest() after the call
+    num_obj: int          # -1 unless ok
+    det: np.ndarray       # [num_obj, 6] fp64: x, y, z, doppler, peakVal, range
+
+
+def load_buffer(path=GOLD_BUFFER):
+    g = np.load(path)
+    sl = lambda key, off, i: g[key][g[off][i]: g[off][i + 1]]
+    out = []
+    sr = g["stream_reads"]
+    for s, name in enumerate(g["names"]):
+        c = g["cfg"][s]
+        cfg = {"rangeIdxToMeters": float(c[0]), "dopplerResolutionMps": float(c[1]), "numDopplerBins": float(c[2])}
+        reads = [BufferRead(k, sl("chunk", "chunk_off", r).tobytes(), int(g["ok"][r]), int(g["frame"][r]), bool(g["raised"][r]),
+                            int(g["buflen"][r]), g["digest"][r].tobytes(), int(g["num_obj"][r]), sl("det", "det_off", r))
+                 for k, r in enumerate(range(int(sr[s]), int(sr[s + 1])))]
+        out.append(Stream(str(name), cfg, reads))
+    return out
+
+
 def meta(path=GOLD):
     return json.loads(str(np.load(path)["meta"]))
 
