@@ -872,6 +872,39 @@ class SceneBatch:
         return self._export_host("skeletons", lambda ptr, cap, ticket: self.skeletons_dev(ptr, cap, mode, ticket, scene_base),
                                  self.L.mmw_skeletons_wait, ("skeletons", _lib.SKELETON_DTYPE))[0]
 
+    # -- per-scene tables and by-uid samplers (zones, trails, tripwires) --------
+    def _set_scene_table(self, name, noun, setter, make, dtype, per_scene, table, scenes):
+        """One mmw_set_* call of a per-scene table: `table` is what `make` takes or its result, the pair (counts, dtype[n, per_scene])."""
+        if isinstance(table, tuple) and len(table) == 2 and isinstance(table[1], np.ndarray) and table[1].dtype == dtype:
+            cnt, tab = table
+        else:
+            cnt, tab = make(table)
+        cnt = np.ascontiguousarray(np.asarray(cnt, dtype=np.int32).reshape(-1))
+        tab = np.ascontiguousarray(tab.reshape(-1, per_scene))
+        if len(cnt) != len(tab):
+            raise ValueError(f"{name}: {len(cnt)} counts for {len(tab)} scenes' {noun}")
+        idx = None
+        if scenes is not None:
+            idx = np.ascontiguousarray(np.asarray(scenes, dtype=np.int32).reshape(-1))
+            if len(idx) != len(cnt):
+                raise ValueError(f"{name}: {len(cnt)} entries for {len(idx)} scenes")
+        self._chk(setter(self.h, idx.ctypes.data if idx is not None else None, len(cnt), cnt.ctypes.data if len(cnt) else None,
+                         tab.ctypes.data if len(cnt) else None))
+
+    def _get_scene_table(self, getter, dtype, per_scene):
+        """One mmw_get_* call: (counts int32[S], table dtype[S, per_scene]) from the host mirror."""
+        cnt = np.zeros(self.S, dtype=np.int32)
+        tab = np.zeros((self.S, per_scene), dtype=dtype)
+        self._chk(getter(self.h, cnt.ctypes.data, tab.ctypes.data))
+        return cnt, tab
+
+    def _sample(self, sample_dev, prefix, t, scenes):
+        """A sample call from host arrays: `t` and the scene flags go up through the kept buffers `<prefix>_t` and `<prefix>_flags`."""
+        t_ptr = None
+        if t is not None:
+            t_ptr = self.buf(prefix + "_t", self.S * 8).upload(np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (self.S,)))).ptr
+        sample_dev(self._scene_flags(scenes, prefix + "_flags"), t_ptr)
+
     # -- zone occupancy -------------------------------------------------------
     def set_zones(self, zones, scenes=None):
         """mmw_set_zones: give `scenes` (default: scenes 0 .. len(zones)-1) their zones -- `zones` is what `_lib.make_zones` takes (a
@@ -879,28 +912,11 @@ class SceneBatch:
         have; the listed scenes' memberships are void (their next export starts with a ZEV_REBASED).  Refused (MmwError, E_ARG) with
         nothing changed for an index out of range or listed twice, more entries than scenes, a NaN bound, x0 > x1 or y0 > y1, a
         margin that is negative or not finite, or a non-zero `reserved_`."""
-        if isinstance(zones, tuple) and len(zones) == 2 and isinstance(zones[1], np.ndarray) and zones[1].dtype == _lib.ZONE_DTYPE:
-            nz, zt = zones
-        else:
-            nz, zt = _lib.make_zones(zones)
-        nz = np.ascontiguousarray(np.asarray(nz, dtype=np.int32).reshape(-1))
-        zt = np.ascontiguousarray(zt.reshape(-1, _lib.ZONES_MAX))
-        if len(nz) != len(zt):
-            raise ValueError(f"set_zones: {len(nz)} counts for {len(zt)} scenes' zones")
-        idx = None
-        if scenes is not None:
-            idx = np.ascontiguousarray(np.asarray(scenes, dtype=np.int32).reshape(-1))
-            if len(idx) != len(nz):
-                raise ValueError(f"set_zones: {len(nz)} entries for {len(idx)} scenes")
-        self._chk(self.L.mmw_set_zones(self.h, idx.ctypes.data if idx is not None else None, len(nz), nz.ctypes.data if len(nz) else None,
-                                       zt.ctypes.data if len(nz) else None))
+        self._set_scene_table("set_zones", "zones", self.L.mmw_set_zones, _lib.make_zones, _lib.ZONE_DTYPE, _lib.ZONES_MAX, zones, scenes)
 
     def zones(self):
         """mmw_get_zones: (n_zones int32[S], zones ZONE_DTYPE[S, 16]) of every scene, from the host mirror; zero past a scene's zones."""
-        nz = np.zeros(self.S, dtype=np.int32)
-        zt = np.zeros((self.S, _lib.ZONES_MAX), dtype=_lib.ZONE_DTYPE)
-        self._chk(self.L.mmw_get_zones(self.h, nz.ctypes.data, zt.ctypes.data))
-        return nz, zt
+        return self._get_scene_table(self.L.mmw_get_zones, _lib.ZONE_DTYPE, _lib.ZONES_MAX)
 
     def clear_zones(self):
         """mmw_clear_zones: waits for the stream and frees table and baseline; the context launches what one without zones does."""
@@ -948,10 +964,7 @@ class SceneBatch:
     def sample_trails(self, t=None, scenes=None):
         """`sample_trails_dev` from host arrays: `t` float64[S] or a scalar for every scene (None = the call ordinals), `scenes` the
         scenes to sample (default all)."""
-        t_ptr = None
-        if t is not None:
-            t_ptr = self.buf("trail_t", self.S * 8).upload(np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (self.S,)))).ptr
-        self.sample_trails_dev(self._scene_flags(scenes, "trail_flags"), t_ptr)
+        self._sample(self.sample_trails_dev, "trail", t, scenes)
 
     def trails_dev(self, dir_ptr, cap_tracks: int, points_ptr, cap_points: int, last: int = 0, ticket: int = 0, scene_base: int = 0):
         """mmw_trails_async: every live track's trail into device buffers -- a `_lib.TRAIL_TRACK_DTYPE` directory entry per track in
@@ -988,29 +1001,12 @@ class SceneBatch:
         sample logs a TW_REBASED).  Refused (MmwError, E_ARG) with nothing changed for an index out of range or listed twice, more
         entries than scenes, a coordinate that is not finite, A == B, a margin that is negative or not finite, a squared length or
         band that is zero or not finite, or a non-zero `reserved_`."""
-        if isinstance(wires, tuple) and len(wires) == 2 and isinstance(wires[1], np.ndarray) and wires[1].dtype == _lib.TRIPWIRE_DTYPE:
-            nw, wt = wires
-        else:
-            nw, wt = _lib.make_tripwires(wires)
-        nw = np.ascontiguousarray(np.asarray(nw, dtype=np.int32).reshape(-1))
-        wt = np.ascontiguousarray(wt.reshape(-1, _lib.TRIPWIRES_MAX))
-        if len(nw) != len(wt):
-            raise ValueError(f"set_tripwires: {len(nw)} counts for {len(wt)} scenes' wires")
-        idx = None
-        if scenes is not None:
-            idx = np.ascontiguousarray(np.asarray(scenes, dtype=np.int32).reshape(-1))
-            if len(idx) != len(nw):
-                raise ValueError(f"set_tripwires: {len(nw)} entries for {len(idx)} scenes")
-        self._chk(self.L.mmw_set_tripwires(self.h, idx.ctypes.data if idx is not None else None, len(nw), nw.ctypes.data if len(nw) else None,
-                                           wt.ctypes.data if len(nw) else None))
+        self._set_scene_table("set_tripwires", "wires", self.L.mmw_set_tripwires, _lib.make_tripwires, _lib.TRIPWIRE_DTYPE, _lib.TRIPWIRES_MAX, wires, scenes)
 
     def tripwires(self):
         """mmw_get_tripwires: (n_wires int32[S], wires TRIPWIRE_DTYPE[S, 16]) of every scene, from the host mirror; zero past a
         scene's wires."""
-        nw = np.zeros(self.S, dtype=np.int32)
-        wt = np.zeros((self.S, _lib.TRIPWIRES_MAX), dtype=_lib.TRIPWIRE_DTYPE)
-        self._chk(self.L.mmw_get_tripwires(self.h, nw.ctypes.data, wt.ctypes.data))
-        return nw, wt
+        return self._get_scene_table(self.L.mmw_get_tripwires, _lib.TRIPWIRE_DTYPE, _lib.TRIPWIRES_MAX)
 
     def sample_tripwires_dev(self, flags_ptr=None, t_ptr=None):
         """mmw_tripwires_sample: every live track's side of every wire of the asked scenes, crossings counted and logged, queued
@@ -1022,10 +1018,7 @@ class SceneBatch:
     def sample_tripwires(self, t=None, scenes=None):
         """`sample_tripwires_dev` from host arrays: `t` float64[S] or a scalar for every scene (None = the call ordinals), `scenes`
         the scenes to sample (default all)."""
-        t_ptr = None
-        if t is not None:
-            t_ptr = self.buf("tripwire_t", self.S * 8).upload(np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (self.S,)))).ptr
-        self.sample_tripwires_dev(self._scene_flags(scenes, "tripwire_flags"), t_ptr)
+        self._sample(self.sample_tripwires_dev, "tripwire", t, scenes)
 
     def tripwires_async(self, rows_ptr, cap_rows: int, events_ptr, cap_events: int, scene_base: int = 0, ticket: int = 0):
         """mmw_tripwires_async: one `_lib.TRIPWIRE_ROW_DTYPE` row per defined wire in (scene, wire) order and the

@@ -46,6 +46,16 @@ int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const ch
     return MMW_OK;
 }
 
+// What mmw_trails_sample and mmw_tripwires_sample check before they launch: `entry` ("mmw_trails") is enabled -- x is its export
+// state, `what` its noun in the message -- and the two optional device arrays are aligned.  Leaves the context's device current.
+int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t)
+{
+    if (!x.d_block) return fail(c, MMW_E_ARG, "%s_sample: %s are not enabled (%s_enable)", entry, what, entry);
+    if (((uintptr_t)scene_flags & 3) != 0 || ((uintptr_t)t & 7) != 0) return fail(c, MMW_E_ARG, "%s_sample: scene_flags must be 4-byte aligned, t 8-byte aligned", entry);
+    HIPCHK(c, hipSetDevice(c->device));
+    return MMW_OK;
+}
+
 // mmw_reset / mmw_reset_scenes / mmw_restore: uids restart in the scenes flagged in dev_flags (device, [n_scenes]; nullptr = every
 // scene), so the report's baseline, the zones' memberships, the trails and the tripwires' sides of those scenes are void.  One launch for the consumers
 // that are on, queued on the context's stream behind the kernel that emptied or refilled the scenes; nothing at all while none is.

@@ -39,15 +39,15 @@ int mmw_trails_enable(mmw_ctx *c, int32_t depth)
     ts.last_y = d; d += n;
     ts.ring = reinterpret_cast<mmw_trail_point *>(d);
     int32_t *p = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d) + ring_bytes);
-    ts.owner = p; p += n;
+    ts.ug.owner = p; p += n;
     ts.total = p; p += n;
     ts.ug.gen = p; p += S;
     ts.ug.seen = p; p += S;
-    ts.ordinal = p;
+    ts.ug.ordinal = p;
     ts.sc = nx.sc;
     // every slot free, every word 0 (the rings need no clearing: an entry is written before `total` lets anybody read it)
     hipError_t e = hipMemsetAsync(ts.t_first, 0, 4 * n * sizeof(double), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ts.owner, 0xff, n * sizeof(int32_t), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ts.ug.owner, 0xff, n * sizeof(int32_t), c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(ts.total, 0, (n + 3 * S) * sizeof(int32_t), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (... and whatever was queued on an earlier enablement's state has run)
     if (e != hipSuccess) {
@@ -63,9 +63,7 @@ int mmw_trails_enable(mmw_ctx *c, int32_t depth)
 int mmw_trails_sample(mmw_ctx *c, const int32_t *scene_flags, const double *t)
 {
     if (!c) return MMW_E_ARG;
-    if (!c->trail.d_block) return fail(c, MMW_E_ARG, "mmw_trails_sample: trails are not enabled (mmw_trails_enable)");
-    if (((uintptr_t)scene_flags & 3) != 0 || ((uintptr_t)t & 7) != 0) return fail(c, MMW_E_ARG, "mmw_trails_sample: scene_flags must be 4-byte aligned, t 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
+    MMW_TRY(sample_begin(c, c->trail, "mmw_trails", "trails", scene_flags, t));
     launch_trail_sample(c->dc, c->st, c->ts, scene_flags, t, c->stream);
     HIPCHK(c, hipGetLastError());
     return MMW_OK;

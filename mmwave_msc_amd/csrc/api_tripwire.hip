@@ -3,7 +3,7 @@
 // sides, mmw_tripwires_async queues the export kernels of k_tripwire.hip and the copy of the two counts, mmw_tripwires_wait waits
 // for that copy.
 #include <cmath>
-#include "mmw_ctx.hpp"
+#include "mmw_scene_table.hpp"
 
 static_assert(sizeof(mmw_tripwire) == 48, "mmw_tripwire: the numpy layout of mmwave_msc_amd/_lib.py");
 static_assert(sizeof(mmw_tripwire_row) == 32, "mmw_tripwire_row: the numpy layout of mmwave_msc_amd/_lib.py");
@@ -12,15 +12,9 @@ static_assert(sizeof(mmw_tripwire_event) == 32, "mmw_tripwire_event: the numpy l
 void tripwire_free(mmw_ctx *c)
 {
     export_free(c->trip);
-    if (c->d_twtab) hipFree(c->d_twtab);
-    c->d_twtab = nullptr;
+    scene_table_free(c->twtab);
     c->tw = TripState();
-    c->h_wires.clear();
-    c->h_nwires.clear();
 }
-
-// the table's allocation: [S][MMW_TRIPWIRES_MAX] TripWire | [S] n_wires | [S] scene flags of the mmw_set_tripwires call that wrote it
-static size_t twtab_bytes(size_t S) { return S * MMW_TRIPWIRES_MAX * sizeof(TripWire) + 2 * S * sizeof(int32_t); }
 
 int mmw_tripwires_enable(mmw_ctx *c, int32_t log_depth)
 {
@@ -41,43 +35,41 @@ int mmw_tripwires_enable(mmw_ctx *c, int32_t log_depth)
     const size_t words = (ring_bytes + count_bytes) / sizeof(int32_t) + 2 * n + 5 * S;
     ExportCtx nx;
     MMW_TRY(export_alloc(c, nx, words, "mmw_tripwires_enable"));
-    char *tab = nullptr;
-    if (hipMalloc((void **)&tab, twtab_bytes(S)) != hipSuccess) {
+    decltype(c->twtab) tab;
+    if (const int rc = scene_table_alloc(c, tab, "mmw_tripwires_enable")) {
         export_free(nx);
-        return fail(c, MMW_E_HIP, "mmw_tripwires_enable: hipMalloc(%zu B) failed", twtab_bytes(S));
+        return rc;
     }
     TripState tw = {};
     tw.depth = log_depth;
-    tw.wires = reinterpret_cast<const TripWire *>(tab);
-    tw.n_wires = reinterpret_cast<const int32_t *>(tab + S * MMW_TRIPWIRES_MAX * sizeof(TripWire));
+    tw.wires = tab.entries();
+    tw.n_wires = tab.counts(S);
     tw.ring = reinterpret_cast<mmw_tripwire_event *>(nx.d_block);
     tw.count = reinterpret_cast<TripCount *>(nx.d_block + ring_bytes);
     int32_t *p = reinterpret_cast<int32_t *>(nx.d_block + ring_bytes + count_bytes);
-    tw.owner = p; p += n;
+    tw.ug.owner = p; p += n;
     tw.side = p; p += n;
     tw.logged = p; p += S;
     tw.taken = p; p += S;
     tw.ug.gen = p; p += S;
     tw.ug.seen = p; p += S;
-    tw.ordinal = p;
+    tw.ug.ordinal = p;
     tw.sc = nx.sc;
     // every scene at 0 wires, every slot free, every word 0 (the rings need no clearing: an entry is written before `logged` lets anybody read it)
-    hipError_t e = hipMemsetAsync(tab, 0, twtab_bytes(S), c->stream);
+    hipError_t e = hipMemsetAsync(tab.d_tab, 0, tab.bytes(S), c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(tw.count, 0, count_bytes, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(tw.owner, 0xff, n * sizeof(int32_t), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(tw.ug.owner, 0xff, n * sizeof(int32_t), c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(tw.side, 0, (n + 5 * S) * sizeof(int32_t), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (... and whatever was queued on an earlier enablement's state has run)
     if (e != hipSuccess) {
         export_free(nx);
-        hipFree(tab);
+        scene_table_free(tab);
         return fail(c, MMW_E_HIP, "mmw_tripwires_enable: %s", hipGetErrorString(e));
     }
     tripwire_free(c);
     c->trip = nx;
     c->tw = tw;
-    c->d_twtab = tab;
-    c->h_wires.assign(S * MMW_TRIPWIRES_MAX, mmw_tripwire{});
-    c->h_nwires.assign(S, 0);
+    c->twtab = std::move(tab);
     return MMW_OK;
 }
 
@@ -99,80 +91,37 @@ int mmw_set_tripwires(mmw_ctx *c, const int32_t *scenes, int32_t n, const int32_
 {
     if (!c) return fail(nullptr, MMW_E_ARG, "mmw_set_tripwires: null context");
     if (!c->trip.d_block) return fail(c, MMW_E_ARG, "mmw_set_tripwires: tripwires are not enabled (mmw_tripwires_enable)");
-    const int S = c->dc.n_scenes;
     // every check first: a refused call changes no scene's wires
-    if (n < 0 || n > S) return fail(c, MMW_E_ARG, "mmw_set_tripwires: n = %d, the context has %d scenes", n, S);
-    if (n > 0 && (!n_wires || !wires)) return fail(c, MMW_E_ARG, "mmw_set_tripwires: %s is NULL with n = %d", !n_wires ? "n_wires" : "wires", n);
-    std::vector<char> listed((size_t)S, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = scenes ? scenes[i] : i;
-        if (s < 0 || s >= S) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d names scene %d, the context has %d scenes", i, s, S);
-        if (listed[s]) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d names scene %d a second time", i, s);
-        listed[s] = 1;
-        if (n_wires[i] < 0 || n_wires[i] > MMW_TRIPWIRES_MAX)
-            return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) has n_wires = %d, outside 0 .. %d", i, s, n_wires[i], MMW_TRIPWIRES_MAX);
-        for (int z = 0; z < n_wires[i]; z++) {
-            const mmw_tripwire &q = wires[(size_t)i * MMW_TRIPWIRES_MAX + z];
-            if (q.reserved_ != 0) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a non-zero reserved_", i, s, z);
-            if (!std::isfinite(q.ax) || !std::isfinite(q.ay) || !std::isfinite(q.bx) || !std::isfinite(q.by))
-                return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a coordinate that is not finite", i, s, z);
-            if (!(q.margin >= 0.0) || !std::isfinite(q.margin))
-                return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a margin that is negative or not finite", i, s, z);
-            if (q.ax == q.bx && q.ay == q.by) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has A == B", i, s, z);
-            const TripWire d = derive(q);
-            if (!(d.len2 > 0.0) || !std::isfinite(d.len2)) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a squared length that is zero or not finite", i, s, z);
-            if (!std::isfinite(d.band) || (q.margin > 0.0 && !(d.band > 0.0)))
-                return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a band (margin x length) that is zero or not finite", i, s, z);
-        }
-    }
+    MMW_TRY(scene_table_check<decltype(c->twtab)>(c, {"mmw_set_tripwires", "n_wires", "wires"}, scenes, n, n_wires, wires, [c](int i, int s, int z, const mmw_tripwire &q) {
+        if (q.reserved_ != 0) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a non-zero reserved_", i, s, z);
+        if (!std::isfinite(q.ax) || !std::isfinite(q.ay) || !std::isfinite(q.bx) || !std::isfinite(q.by))
+            return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a coordinate that is not finite", i, s, z);
+        if (!(q.margin >= 0.0) || !std::isfinite(q.margin))
+            return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a margin that is negative or not finite", i, s, z);
+        if (q.ax == q.bx && q.ay == q.by) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has A == B", i, s, z);
+        const TripWire d = derive(q);
+        if (!(d.len2 > 0.0) || !std::isfinite(d.len2)) return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a squared length that is zero or not finite", i, s, z);
+        if (!std::isfinite(d.band) || (q.margin > 0.0 && !(d.band > 0.0)))
+            return fail(c, MMW_E_ARG, "mmw_set_tripwires: entry %d (scene %d) wire %d has a band (margin x length) that is zero or not finite", i, s, z);
+        return MMW_OK;
+    }));
     HIPCHK(c, hipSetDevice(c->device));
-    // The new table is put together on the host (from a copy of the mirror: a failure below leaves the mirror as it was) and travels
-    // as ONE copy, ordered on the context's stream: what was queued before this call reads the old table.  The listed scenes' flags
-    // ride behind it, for the generation bump -- of the tripwires' word alone -- and the restart of their counters.
-    std::vector<mmw_tripwire> next = c->h_wires;
-    std::vector<int32_t> next_n = c->h_nwires;
-    for (int i = 0; i < n; i++) {
-        const size_t s = scenes ? scenes[i] : i;
-        next_n[s] = n_wires[i];
-        for (int z = 0; z < MMW_TRIPWIRES_MAX; z++) next[s * MMW_TRIPWIRES_MAX + z] = z < n_wires[i] ? wires[(size_t)i * MMW_TRIPWIRES_MAX + z] : mmw_tripwire{};
-    }
-    const size_t tb = (size_t)S * MMW_TRIPWIRES_MAX * sizeof(TripWire);
-    std::vector<char> stage(twtab_bytes((size_t)S), 0);
-    TripWire *dev = reinterpret_cast<TripWire *>(stage.data());
-    for (size_t s = 0; s < (size_t)S; s++)
-        for (int z = 0; z < next_n[s]; z++) dev[s * MMW_TRIPWIRES_MAX + z] = derive(next[s * MMW_TRIPWIRES_MAX + z]);
-    memcpy(stage.data() + tb, next_n.data(), sizeof(int32_t) * (size_t)S);
-    int32_t *flags = reinterpret_cast<int32_t *>(stage.data() + tb) + S;
-    for (int s = 0; s < S; s++) flags[s] = listed[s];
-    hipError_t e = hipMemcpyAsync(c->d_twtab, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_uid_rebase(S, c->tw.n_wires + S, UidGens{{c->tw.ug.gen, nullptr, nullptr, nullptr}}, c->stream);
-        launch_tripwire_zero(S, c->tw.n_wires + S, c->tw, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (`stage` is pageable and goes away)
-    if (e != hipSuccess) return fail(c, MMW_E_HIP, "mmw_set_tripwires: %s", hipGetErrorString(e));
-    c->h_wires.swap(next);
-    c->h_nwires.swap(next_n);
-    return MMW_OK;
+    // the generation bump is of the tripwires' word alone; the listed scenes' counters restart behind it
+    return scene_table_send(c, c->twtab, "mmw_set_tripwires", scenes, n, n_wires, wires, derive, c->tw.ug.gen,
+                            [c](const int32_t *flags) { launch_tripwire_zero(c->dc.n_scenes, flags, c->tw, c->stream); });
 }
 
 int mmw_get_tripwires(mmw_ctx *c, int32_t *n_wires, mmw_tripwire *wires)
 {
     if (!c) return fail(nullptr, MMW_E_ARG, "mmw_get_tripwires: null context");
-    const size_t S = (size_t)c->dc.n_scenes;
-    const bool have = c->trip.d_block != nullptr;
-    if (n_wires) { if (have) memcpy(n_wires, c->h_nwires.data(), S * sizeof(int32_t)); else memset(n_wires, 0, S * sizeof(int32_t)); }
-    if (wires) { if (have) memcpy(wires, c->h_wires.data(), S * MMW_TRIPWIRES_MAX * sizeof(mmw_tripwire)); else memset(wires, 0, S * MMW_TRIPWIRES_MAX * sizeof(mmw_tripwire)); }
+    scene_table_get(c->twtab, (size_t)c->dc.n_scenes, n_wires, wires);
     return MMW_OK;
 }
 
 int mmw_tripwires_sample(mmw_ctx *c, const int32_t *scene_flags, const double *t)
 {
     if (!c) return MMW_E_ARG;
-    if (!c->trip.d_block) return fail(c, MMW_E_ARG, "mmw_tripwires_sample: tripwires are not enabled (mmw_tripwires_enable)");
-    if (((uintptr_t)scene_flags & 3) != 0 || ((uintptr_t)t & 7) != 0) return fail(c, MMW_E_ARG, "mmw_tripwires_sample: scene_flags must be 4-byte aligned, t 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
+    MMW_TRY(sample_begin(c, c->trip, "mmw_tripwires", "tripwires", scene_flags, t));
     launch_tripwire_sample(c->dc, c->st, c->tw, scene_flags, t, c->stream);
     HIPCHK(c, hipGetLastError());
     return MMW_OK;

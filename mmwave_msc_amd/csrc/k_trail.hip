@@ -2,7 +2,7 @@
 // sample and the distance walked.  The one state of the exports that outlives a call: mmw_trails_sample appends to it, the export
 // reads it.  Reads SceneHdr, order and two lines of each live TrackRec after the step; nothing of the step is touched.  No LDS, no
 // atomics: a wave per scene, four scenes per workgroup, a lane per track AND per trail slot (t_cap <= 64) -- lane i holds track i's
-// uid, lane j slot j's words, and uid -> slot is uid_find (mmw_uidlist.hpp).
+// uid, lane j slot j's words, and uid -> slot is the one slot table's uid_slots_pick(), which is uid_find() both ways (mmw_uidlist.hpp).
 //   k_uid_rebase    (k_scan.hip) mmw_reset / mmw_reset_scenes / mmw_restore: the touched scenes' generation word
 //   k_trail_sample  free the slots of uids that are gone, hand free slots to the newcomers, append one sample per live track
 //   k_trail_count   entries (= live tracks) and points per scene
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void k_trail_sample(DevCfg cfg, DevState st, T
     if (flags && !flags[s]) return;    // (wave-uniform) not asked: not touched
     const int cap = cfg.t_cap, T = live_tracks(cfg, st, s);
     const size_t base = (size_t)s * cap;
-    const int ord = ts.ordinal[s];
+    const int ord = ts.ug.ordinal[s];
     const bool rebased = ts.ug.rebased(s);
     const double tt = t ? t[s] : (double)ord;
 
@@ -46,33 +46,16 @@ __global__ __launch_bounds__(256) void k_trail_sample(DevCfg cfg, DevState st, T
     int raw_owner = -1, s_total = 0;
     double s_first = 0.0, s_trav = 0.0, s_lx = 0.0, s_ly = 0.0;
     if (lane < cap) {
-        raw_owner = ts.owner[base + lane];
+        raw_owner = ts.ug.owner[base + lane];
         s_total = ts.total[base + lane];
         s_first = ts.t_first[base + lane];
         s_trav = ts.travelled[base + lane];
         s_lx = ts.last_x[base + lane];
         s_ly = ts.last_y[base + lane];
     }
-    const int owner = rebased ? -1 : raw_owner;   // (1.: a uid of another generation owns nothing)
+    const auto [slot, fresh, release] = uid_slots_pick(cuid, raw_owner, rebased, T, cap, lane);   // (all 64 lanes)
 
-    // the two lists of the wave -- lane i's track's uid (-1 past the live list), lane j's slot's owner (-1: free, or past t_cap) --
-    // matched both ways: the slot of this lane's track or -1, and whether this lane's slot belongs to a live uid
-    int slot = uid_find(cuid, owner, cap);
-    const bool kept = uid_find(owner, cuid, T) >= 0;
-    // 2. + 3.: the r-th newcomer, in live order, takes the r-th free slot
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const unsigned long long free_b = __ballot(lane < cap && !kept);
-    const bool fresh = lane < T && slot < 0;
-    const unsigned long long new_b = __ballot(fresh);
-    const int n_new = __popcll(new_b);
-    if (fresh) {
-        unsigned long long f = free_b;
-        for (int r = __popcll(new_b & below); r > 0; r--) f &= f - 1ull;   // (divergent: drop the r lowest set bits)
-        slot = f ? __ffsll((long long)f) - 1 : -1;   // (never -1: live tracks <= t_cap, so free slots >= newcomers)
-    }
-    const bool taken = lane < cap && !kept && __popcll(free_b & below) < n_new;
-
-    // 4.: the words of this lane's TRACK's slot come out of that slot's lane
+    // the words of this lane's TRACK's slot come out of that slot's lane
     const int src = slot < 0 ? lane : slot;
     int total = __shfl(s_total, src);
     double t_first = __shfl(s_first, src), trav = __shfl(s_trav, src);
@@ -88,7 +71,7 @@ __global__ __launch_bounds__(256) void k_trail_sample(DevCfg cfg, DevState st, T
 
     if (lane < T && slot >= 0) {   // (a track writes its own slot, all of it: no word has two writers)
         const size_t at = base + slot;
-        ts.owner[at] = cuid;
+        ts.ug.owner[at] = cuid;
         ts.total[at] = total;
         ts.t_first[at] = t_first;
         ts.travelled[at] = trav;
@@ -96,9 +79,7 @@ __global__ __launch_bounds__(256) void k_trail_sample(DevCfg cfg, DevState st, T
         ts.last_y[at] = y;
         ts.ring[at * (size_t)ts.depth + (unsigned)(total - 1) % (unsigned)ts.depth] = mmw_trail_point{tt, (float)x, (float)y, (float)z, pflags};
     }
-    if (lane < cap && !kept && !taken && raw_owner != -1) ts.owner[base + lane] = -1;   // (freed and not handed on)
-    ts.ug.settle(s, lane);
-    if (lane == 0) ts.ordinal[s] = ord + 1;
+    uid_slots_done(ts.ug, s, lane, base + lane, release, ord);
 }
 
 // What the export says of this lane's track.  All 64 lanes call.
@@ -115,7 +96,7 @@ __device__ __forceinline__ TrailView trail_view(const DevCfg &cfg, const DevStat
     const size_t base = (size_t)s * cap;
     v.T = live_tracks(cfg, st, s);
     v.uid = live_uid(cfg, st, s, lane, v.T);
-    const int owner = (lane < cap && !ts.ug.rebased(s)) ? ts.owner[base + lane] : -1;
+    const int owner = (lane < cap && !ts.ug.rebased(s)) ? ts.ug.owner[base + lane] : -1;
     v.slot = uid_find(v.uid, owner, cap);
     v.count = v.total = 0;
     v.t_first = v.travelled = 0.0;

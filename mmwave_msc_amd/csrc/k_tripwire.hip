@@ -2,8 +2,9 @@
 // across it either way, and every crossing as an event with the track's uid in a per-scene ring.  A LOG: mmw_tripwires_sample
 // appends behind every step, the export drains.  Reads SceneHdr, order and two lines of each live TrackRec after the step; nothing
 // of the step is touched.  No LDS, no atomics: a wave per scene, four scenes per workgroup, a lane per track AND per uid slot
-// (t_cap <= 64) AND per wire -- lane i holds track i's uid, lane j slot j's words, lane z wire z's counters; uid -> slot is uid_find
-// (mmw_uidlist.hpp), the scene's wires are walked with the wave -- s is wave-uniform, so the table comes through scalar loads.
+// (t_cap <= 64) AND per wire -- lane i holds track i's uid, lane j slot j's words, lane z wire z's counters; uid -> slot is the one
+// slot table's uid_slots_pick(), which is uid_find() both ways (mmw_uidlist.hpp); the scene's wires are walked with the wave -- s is
+// wave-uniform, so the table comes through scalar loads.
 //   k_uid_rebase       (k_scan.hip) mmw_reset / mmw_reset_scenes / mmw_restore / mmw_set_tripwires: the touched scenes' generation word
 //   k_tripwire_zero    mmw_set_tripwires: the listed scenes' counters and marks
 //   k_tripwire_sample  free the slots of uids that are gone, hand free slots to the newcomers, every track's side of every wire
@@ -42,11 +43,10 @@ __global__ __launch_bounds__(256) void k_tripwire_sample(DevCfg cfg, DevState st
     const auto [s, lane] = wave_scene();
     if (s >= cfg.n_scenes) return;     // (wave-uniform)
     if (flags && !flags[s]) return;    // (wave-uniform) not asked: not touched
-    const int ord = ts.ordinal[s];
+    const int ord = ts.ug.ordinal[s];
     const int nw = scene_wires(ts, s);
     if (nw == 0) {                     // (wave-uniform) nothing to decide: the scene's slots are void until it has wires, and then rebased
-        ts.ug.settle(s, lane);
-        if (lane == 0) ts.ordinal[s] = ord + 1;
+        uid_slots_done(ts.ug, s, lane, 0, false, ord);
         return;
     }
     const int cap = cfg.t_cap, T = live_tracks(cfg, st, s);
@@ -66,27 +66,12 @@ __global__ __launch_bounds__(256) void k_tripwire_sample(DevCfg cfg, DevState st
     // ... and this lane's slot: both old words are in registers before anything is stored
     int raw_owner = -1, s_side = 0;
     if (lane < cap) {
-        raw_owner = ts.owner[base + lane];
+        raw_owner = ts.ug.owner[base + lane];
         s_side = ts.side[base + lane];
     }
-    const int owner = rebased ? -1 : raw_owner;   // (1.: a uid of another generation owns nothing)
+    const auto [slot, fresh, release] = uid_slots_pick(cuid, raw_owner, rebased, T, cap, lane);   // (all 64 lanes)
 
-    // 2. + 3., the trails' rule: the r-th newcomer, in live order, takes the r-th free slot
-    int slot = uid_find(cuid, owner, cap);
-    const bool kept = uid_find(owner, cuid, T) >= 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const unsigned long long free_b = __ballot(lane < cap && !kept);
-    const bool fresh = lane < T && slot < 0;
-    const unsigned long long new_b = __ballot(fresh);
-    const int n_new = __popcll(new_b);
-    if (fresh) {
-        unsigned long long f = free_b;
-        for (int r = __popcll(new_b & below); r > 0; r--) f &= f - 1ull;   // (divergent: drop the r lowest set bits)
-        slot = f ? __ffsll((long long)f) - 1 : -1;   // (never -1: live tracks <= t_cap, so free slots >= newcomers)
-    }
-    const bool taken = lane < cap && !kept && __popcll(free_b & below) < n_new;
-
-    // 4.: the side word of this lane's TRACK comes out of its slot's lane
+    // the side word of this lane's TRACK comes out of its slot's lane
     const unsigned slot_w = (unsigned)__shfl(s_side, slot < 0 ? lane : slot);   // (all 64 lanes, ahead of the condition)
     const unsigned old_w = fresh ? 0u : slot_w;
     const TripWire *wt = ts.wires + (size_t)s * MMW_TRIPWIRES_MAX;
@@ -150,15 +135,11 @@ __global__ __launch_bounds__(256) void k_tripwire_sample(DevCfg cfg, DevState st
     }
 
     if (lane < T && slot >= 0) {   // (a track writes its own slot, both words: no word has two writers)
-        ts.owner[base + slot] = cuid;
+        ts.ug.owner[base + slot] = cuid;
         ts.side[base + slot] = (int32_t)new_w;
     }
-    if (lane < cap && !kept && !taken && raw_owner != -1) ts.owner[base + lane] = -1;   // (freed and not handed on)
-    ts.ug.settle(s, lane);
-    if (lane == 0) {
-        ts.ordinal[s] = ord + 1;
-        if (total) ts.logged[s] = log0 + total;
-    }
+    uid_slots_done(ts.ug, s, lane, base + lane, release, ord);
+    if (lane == 0 && total) ts.logged[s] = log0 + total;
 }
 
 // What the export hands out of a scene's log: events first .. first + n - 1, and how many were overwritten before it came.

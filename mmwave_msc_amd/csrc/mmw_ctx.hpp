@@ -69,6 +69,24 @@ struct ExportCtx {
     bool issued[kTickets] = {false, false, false, false};
 };
 
+// A per-scene table of up to MAX caller entries E a scene (mmw_set_zones, mmw_set_tripwires; mmw_scene_table.hpp has the code): the
+// device allocation, which holds the table as the kernels read it (entries D) and in which every set call lands as ONE copy, and
+// the host mirrors of what the caller gave.  d_tab == nullptr: not allocated.
+template <class E, class D, int MAX>
+struct SceneTable {
+    using entry = E;
+    using dev_entry = D;
+    static constexpr int kMax = MAX;
+    char *d_tab = nullptr;            // [S][MAX] D | [S] counts | [S] the scene flags of the set call that wrote it
+    std::vector<E> h_entries;         // [S][MAX] as the caller gave them, zero past a scene's count ...
+    std::vector<int32_t> h_counts;    // [S] ... and the counts (the getter reads both)
+    static size_t table_bytes(size_t S) { return S * MAX * sizeof(D); }
+    static size_t bytes(size_t S) { return table_bytes(S) + 2 * S * sizeof(int32_t); }
+    const D *entries() const { return reinterpret_cast<const D *>(d_tab); }
+    const int32_t *counts(size_t S) const { return reinterpret_cast<const int32_t *>(d_tab + table_bytes(S)); }
+    const int32_t *flags(size_t S) const { return counts(S) + S; }
+};
+
 struct mmw_ctx {
     mmw_config cfg;
     DevCfg dc;
@@ -124,16 +142,12 @@ struct mmw_ctx {
     ExportCtx sample;                 // mmw_samples_*: allocated by the first call; not allocated = never called, nothing of it exists
     ExportCtx zone;                   // mmw_set_zones allocates it, mmw_clear_zones frees it; not allocated = no zone table, nothing of it is launched
     ZoneState zs = {};                // ... the zones' baseline, in front of zone's scratch in zone.d_block (zs.sc = zone.sc)
-    char *d_ztab = nullptr;           // ... the table as ONE copy lands in it: [S][MMW_ZONES_MAX] mmw_zone | [S] n_zones | [S] the call's scene flags
-    std::vector<mmw_zone> h_zones;    // host mirror of the table ([S][MMW_ZONES_MAX], zero past a scene's n_zones) ...
-    std::vector<int32_t> h_nzones;    // ... and of n_zones [S] (mmw_get_zones reads both)
+    SceneTable<mmw_zone, mmw_zone, MMW_ZONES_MAX> ztab;   // ... the zone table: what the kernels read is what the caller gave (mmw_get_zones reads the mirrors)
     ExportCtx trail;                  // mmw_trails_enable allocates it (depth 0 frees it); not allocated = trails are off, nothing of them is launched
     TrailState ts = {};               // ... the trail slots and rings, in front of trail's scratch in trail.d_block (ts.sc = trail.sc)
     ExportCtx trip;                   // mmw_tripwires_enable allocates it (log_depth 0 frees it); not allocated = tripwires are off, nothing of them is launched
     TripState tw = {};                // ... the uid slots, counters and event rings, in front of trip's scratch in trip.d_block (tw.sc = trip.sc)
-    char *d_twtab = nullptr;          // ... the table as ONE copy lands in it: [S][MMW_TRIPWIRES_MAX] TripWire | [S] n_wires | [S] the call's scene flags
-    std::vector<mmw_tripwire> h_wires;   // host mirror of the table as the caller gave it ([S][MMW_TRIPWIRES_MAX], zero past a scene's n_wires) ...
-    std::vector<int32_t> h_nwires;    // ... and of n_wires [S] (mmw_get_tripwires reads both)
+    SceneTable<mmw_tripwire, TripWire, MMW_TRIPWIRES_MAX> twtab;   // ... the wire table: what the kernels read is derived on the host (mmw_get_tripwires reads the mirrors)
     ExportCtx ulog_x;                 // mmw_uart_log_enable; not allocated = the radar log is off and mmw_uart_read launches what it always did
     UartLog ulog = {};                // ... the staged frames, in front of ulog_x's scratch in ulog_x.d_block
     std::vector<double> uart_range;   // [S] rangeIdxToMeters of the open readers (the log's range column)
@@ -163,6 +177,7 @@ int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name)
 void export_free(ExportCtx &x);                                    // ... and x is as never allocated
 int export_issue(mmw_ctx *c, ExportCtx &x, int ticket);           // behind the launch: its error, the totals into the ticket's pinned slot, the event
 int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const char *none, const int32_t **counts);   // -> the ticket's four words
+int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t);   // mmw_trails_sample / mmw_tripwires_sample: enabled, aligned, device set
 int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones, trails and tripwires, none while all four are off
 #pragma GCC visibility pop
 

@@ -209,35 +209,32 @@ struct ZoneState {
     ExportScratch sc;          // rows / events of the export in flight
 };
 // mmw_trails_enable: what the track trails keep from one mmw_trails_sample to the next (k_trail.hip).  All device memory.  A scene
-// has t_cap trail SLOTS; a slot belongs to one uid or is free, and which slot a uid has is not visible outside.  The slot words
-// are arrays over [S][t_cap] (lane j of a scene's wave holds slot j), 40 bytes a slot together.
+// has t_cap trail SLOTS, handed out by the one slot table (UidSlots, mmw_uidlist.hpp).  The slot words are arrays over [S][t_cap]
+// (lane j of a scene's wave holds slot j), 40 bytes a slot together.
 struct TrailState {
     int32_t depth;             // ring entries per slot, 1 .. MMW_TRAIL_DEPTH_MAX
-    int32_t *owner;            // [S][t_cap] the slot's uid, -1 = free
-    int32_t *total;            // [S][t_cap] samples ever taken of that uid
+    mmw_trail_point *ring;     // [S][t_cap][depth] sample n (0-based) of a uid lies at n % depth
+    UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
+    int32_t *total;            // [S][t_cap] samples ever taken of the slot's uid
     double *t_first;           // [S][t_cap] t of its first sample
     double *travelled;         // [S][t_cap] path length in the x/y plane over all its samples
     double *last_x, *last_y;   // [S][t_cap] the fp64 position of its newest sample
-    mmw_trail_point *ring;     // [S][t_cap][depth] sample n (0-based) of a uid lies at n % depth
-    UidGen ug;                 // the generation the scene's slots belong to (settled by a sample call that asked the scene)
-    int32_t *ordinal;          // [S] sample calls that asked the scene since mmw_trails_enable
     ExportScratch sc;          // entries / points of the export in flight
 };
 // mmw_tripwires_enable: the wire table and what the tripwires keep from one mmw_tripwires_sample to the next (k_tripwire.hip).  All
-// device memory.  A table entry is what the HOST derived of an mmw_tripwire (mmw_set_tripwires): the device takes no sqrt.
+// device memory.  A table entry is what the HOST derived of an mmw_tripwire (mmw_set_tripwires): the device takes no sqrt.  A uid's
+// side word lies in the slot that the one slot table (UidSlots, mmw_uidlist.hpp) gives it.
 struct TripWire { double ax, ay, dx, dy, len2, band; int32_t id, pad_; };   // 56 bytes
 struct TripCount { int32_t forward, backward, mark_forward, mark_backward; };   // totals since the wires were set; ... at the previous successful export
 struct TripState {
     int32_t depth;             // log entries per scene, 1 .. MMW_TRIPWIRE_LOG_MAX
     const TripWire *wires;     // [S][MMW_TRIPWIRES_MAX] the table (one copy of mmw_set_tripwires; read with scalar loads)
     const int32_t *n_wires;    // [S] wires defined per scene, behind the table in the same allocation
-    int32_t *owner;            // [S][t_cap] the slot's uid, -1 = free (the trails' slots: lane j of a scene's wave holds slot j)
-    int32_t *side;             // [S][t_cap] two bits per wire: 0 unknown, 1 negative, 2 positive
+    int32_t *side;             // [S][t_cap] the slot's uid's sides, two bits per wire: 0 unknown, 1 negative, 2 positive
     TripCount *count;          // [S][MMW_TRIPWIRES_MAX] lane z of a scene's wave owns wire z's
     mmw_tripwire_event *ring;  // [S][depth] event n (0-based) of a scene lies at n % depth, with the LOCAL scene index
     int32_t *logged, *taken;   // [S] events ever appended / handed out
-    UidGen ug;                 // the generation the scene's slots belong to (settled by a sample call that asked the scene)
-    int32_t *ordinal;          // [S] sample calls that asked the scene since mmw_tripwires_enable
+    UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
     ExportScratch sc;          // rows / events of the export in flight
 };
 

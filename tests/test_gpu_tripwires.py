@@ -698,3 +698,43 @@ def test_nothing_else_moves():
     assert all(x == y for x, y in counts) and sum(y for _, y in counts) > 0, counts
     a.check(); b.check()
     a.close(); b.close()
+
+
+# 11 -----------------------------------------------------------------------------------------------------------------------
+def test_trails_and_tripwires_keep_separate_slot_tables():
+    """Both samplers run the one slot code (UidSlots, csrc/mmw_uidlist.hpp), each on a table of its own; a mix-up of the two shows
+    only when both are enabled and the tables differ.  The report scenario cut to 6 scenes, trails of depth 4 beside 16 wires a
+    scene and a log of 64: tripwires are sampled in every scene after every frame, trails in every scene after the even frames and
+    in the even scenes only after the odd ones, and scene 1 is reset in front of frame 6.  Both exports are compared after every
+    frame as tests/test_gpu_trails.py and this file compare them.  Driven from the C oracle on the same cut (identities by
+    continuity), the restatements see 6 trail slots reused, 8 forward and 2 backward crossings, and 6 scene-frames after which the
+    two consumers hold different uid sets; the run counts as not vacuous with one of each."""
+    from mmwave_msc_amd import _lib
+    from tests.test_gpu_trails import _Run as _TrailRun
+    Sn = 6
+    data = _cut(Sn)
+    sb = make_checked(Sn, N, "per_scene", **CFG_KW)
+    trails = _TrailRun(sb, 4, data)
+    wires = _Run(sb, 64, data)
+    wires.set_wires(_wires16(Sn))
+    even = [s for s in range(Sn) if s % 2 == 0]
+    n_crossings = n_differ = 0
+    for f in range(F):
+        if f == 6:
+            sb.reset_scenes(np.arange(Sn) == 1)
+            trails.ref.rebase([1])
+            wires.ref.rebase([1])
+        wires.step(f)
+        clock = np.full(Sn, 0.25 * f)
+        trails.sample(t=clock, scenes=even if f % 2 else None)
+        wires.sample(t=clock)
+        trails.compare(("trails", f))
+        _, events = wires.compare(("tripwires", f))
+        n_crossings += _n_kind(events, _lib.TW_FORWARD) + _n_kind(events, _lib.TW_BACKWARD)
+        n_differ += sum(set(trails.ref.trails[s]) != set(wires.ref.sides[s]) for s in range(Sn))
+    sb.check()
+    sb.close()
+    figures = dict(reused=trails.ref.reused, crossings=n_crossings, differ=n_differ)
+    print("two slot tables", figures, "travelled bit-equal", trails.equal, "of", trails.seen)
+    assert n_crossings == wires.ref.n_forward + wires.ref.n_backward
+    assert figures["reused"] >= 1 and figures["crossings"] >= 1 and figures["differ"] >= 1, figures
