@@ -877,6 +877,118 @@ int mmw_tripwires_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n
 int mmw_tripwires(mmw_ctx *ctx, mmw_tripwire_row *rows, int32_t cap_rows, mmw_tripwire_event *events, int32_t cap_events,
                   int32_t scene_base, int32_t *n_rows, int32_t *n_events);                 /* async + wait */
 
+/* ---- stance ----
+ * Who is on the floor, since when, and did they fall: per live uid one of four classes -- MMW_STANCE_UNKNOWN, _UPRIGHT, _LOW
+ * (sitting or crouched), _LYING -- decided from the head height of the posture keypoints (kp[22]: Head, row 1 = height in metres
+ * above the floor), with falls and long lies as events.  The first by-uid consumer that reads mmw_track_record.kp: without it a
+ * caller reads every skeleton back every frame and keeps the per-uid state on the host.  A LOG with the tripwires' mechanics: the
+ * classes are decided on the device by mmw_stance_sample, normally once behind each mmw_estimate_posture, nothing is lost between
+ * two exports.  No step kernel reads or writes any of this: a context that never enables stance launches exactly what it did before.
+ *
+ * Each scene has zero or one RULE (MMW_STANCE_RULES_MAX = 1); a scene without a rule is not watched.  mmw_stance_enable(log_depth),
+ * log_depth in 1 .. MMW_STANCE_LOG_MAX, allocates the rule table (every scene at 0 rules) and per scene: t_cap uid SLOTS of {owner
+ * uid or -1 = free; word: bits 0-1 the class, bit 2 "LONG_LIE given in this episode"; t_since (double): the t of the sample that
+ * entered the current class; t_upright (double): the t of the newest sample that classed the uid UPRIGHT, -inf if never}; the int32
+ * totals `falls` and `long_lies` and their two MARKS (the totals at the previous successful export); an event ring of log_depth
+ * entries with the words `logged` and `taken`, event number n at n % log_depth; a generation, the generation seen and a call
+ * ordinal.  Every slot starts free, every word at 0; the state is ordered on the context's stream.  Enabling again, with any depth,
+ * starts over (0 rules everywhere).  log_depth == 0 waits for the stream, frees the state and turns stance off (MMW_OK also when it
+ * was off).  log_depth outside 0 .. MMW_STANCE_LOG_MAX: MMW_E_ARG, nothing changed.  A failed allocation: MMW_E_HIP, nothing changed
+ * -- an earlier enablement stays as it is.  Until enabled, every other entry returns MMW_E_ARG, except mmw_get_stance_rules, which
+ * reports 0 rules.
+ *
+ * Setting rules follows mmw_set_tripwires' rules: mmw_set_stance_rules gives scene scenes[i] (scenes == NULL: scene i) the first
+ * n_rules[i] (0 or 1) entries of rules[i][MMW_STANCE_RULES_MAX]; scenes never listed keep what they have.  Every check is made on
+ * the host before anything changes, the table travels as ONE copy ordered on the context's stream, and the call is synchronous.
+ * Refused as a whole (MMW_E_ARG, the message names the entry, no scene's rule changes): n < 0 or n > n_scenes, n_rules or rules NULL
+ * with n > 0, a scene index out of range or listed twice, n_rules[i] outside 0 .. 1, a non-zero reserved_, an h_stand, h_lie,
+ * margin, fall_window or max_gap that is not finite, a negative margin, fall_window or long_lie, a long_lie that is NaN (+inf is
+ * allowed: never), max_gap <= 0, or !(lie_hi < up_lo) (below).  pad_ is not read.  For each rule the HOST derives, one fp64
+ * operation each (the library is built with -ffp-contract=off, host side included):
+ *     up_hi = h_stand + margin;  up_lo = h_stand - margin;  lie_hi = h_lie + margin;  lie_lo = h_lie - margin;  gap2 = max_gap * max_gap
+ * and the device reads only these five and h_stand, h_lie, fall_window, long_lie and id: it takes no sqrt and does no arithmetic on
+ * a threshold.  lie_hi < up_lo makes "above the upper boundary" imply "above the lower boundary" whatever the old class was.  For
+ * the listed scenes the generation is bumped, and falls, long_lies and the marks restart at 0, ordered on the stream; the log and
+ * `taken` are kept.  Rules belong to the slot, as wires do: mmw_reset* keeps rules, counters and log, a snapshot blob does not carry
+ * them (format version 1 is unchanged) and mmw_restore leaves the destination's rules alone.  mmw_get_stance_rules copies the host
+ * mirror (no device access; either output may be NULL; entries past a scene's n_rules are zero).
+ *
+ * mmw_stance_sample is asynchronous: ONE kernel on the context's stream behind whatever was queued last -- normally the frame's
+ * mmw_estimate_posture or mmw_set_keypoints*, whose keypoints it reads.  Scene flags, t and the ordinal are mmw_tripwires_sample's.
+ * An asked scene without a rule only sets seen = generation (and counts the call).  For an asked scene with a rule, in this order:
+ *   1. generation != seen: every slot is freed, seen = generation, and ONE MMW_SEV_REBASED event is appended (t of this sample);
+ *   2. every slot whose owner is not among the live uids is freed;
+ *   3. every live uid without a slot takes a free one with word 0 and t_upright = -inf (which slot is not observable);
+ *   4. for every live track, with kp[] the record's 57 fp32 keypoints, tt the sample's t and old = the slot's class:
+ *          head = (double)kp[22]
+ *          g_c  = fp32(kp[19c + 1] - kp[19c + 2]), c = 0, 1, 2;  s = (g_0^2 + g_1^2) + g_2^2 in fp64     (mmw_skeletons' check)
+ *          plausible = (head - head == 0.0) && !(s > gap2)
+ *          not plausible: nothing of the uid changes and it gets no event
+ *          a1  = head > (old == UPRIGHT ? up_lo  : old == UNKNOWN ? h_stand : up_hi)
+ *          a0  = head > (old == LYING   ? lie_hi : old == UNKNOWN ? h_lie   : lie_lo)
+ *          new = a1 ? UPRIGHT : a0 ? LOW : LYING
+ *          if new != old:
+ *              kind = (new == LYING && old != UNKNOWN && tt - t_upright <= fall_window) ? FALL : CHANGE
+ *              event {kind, from = old, to = new};  t_since = tt;  bit 2 cleared;  FALL: falls += 1
+ *          if new == UPRIGHT: t_upright = tt
+ *          if new == LYING && bit 2 clear && tt - t_since >= long_lie:
+ *              event LONG_LIE {from = to = LYING};  bit 2 set;  long_lies += 1
+ * So a NaN or infinite head is not plausible, a NaN s is (the reference's `nan > 0.5` is false).  The first classification of a
+ * uid is a CHANGE with from = 0 and never a FALL.  A fall seen passing through LOW for a sample or two is still a FALL if the uid
+ * was UPRIGHT within fall_window; a person who lies down slowly produces a CHANGE.  long_lie == 0 gives CHANGE or FALL and
+ * LONG_LIE in the same sample, in that order; there is ONE LONG_LIE per episode of lying.  Events of one call are appended in this
+ * order: REBASED first, then tracks in effective_tracks order, CHANGE or FALL before LONG_LIE; each carries slot = the track's
+ * position now, t = the sample's t and the scene.  If one call appends more events than log_depth, only the newest log_depth are
+ * written.  A scene that is not asked is not touched.  A second sample without a step changes only the ordinal -- and gives a
+ * LONG_LIE if t moved on far enough.  scene_flags: dev pointer, 4-byte aligned; t: dev pointer, 8-byte aligned; else MMW_E_ARG.
+ *
+ * mmw_stance_async / _wait export rows and events in one call, with the tripwires' mechanics.  Rows: one per scene WITH a rule,
+ * scenes ascending; upright, low, lying and unknown count the scene's owned slots by class as of the last sample (all 0 while the
+ * scene is rebased and not yet sampled); falls / long_lies are the totals since the scene's rule was last set, d_falls /
+ * d_long_lies those totals minus the marks, lost = max(0, logged - log_depth - taken).  Events: per scene those numbered
+ * max(taken, logged - log_depth) .. logged - 1, oldest first, scenes ascending; scene is offset by scene_base, as the rows' is.  On
+ * success taken = logged and the marks become the totals.  Capacity is decided on the DEVICE against both caps: if anything does
+ * not fit, NOTHING is written, taken and the marks stay as they were, and mmw_stance_wait returns MMW_E_CAPACITY with both counts
+ * needed: a retry with larger buffers loses nothing.  ticket in [0,4), ticket 3 is mmw_stance's own.  rows / events: dev pointers,
+ * 8-byte aligned.  MMW_E_ARG, nothing touched: a NULL context, stance not enabled, a NULL buffer with a positive cap, a negative
+ * cap, a misaligned buffer, a bad ticket, a wait for a ticket with nothing outstanding.
+ *
+ * Life cycle.  mmw_reset, mmw_reset_scenes and mmw_restore bump the generation of the scenes they touch, in the one launch the
+ * report, the zones, the trails and the tripwires share.  mmw_destroy frees the state.  More than INT32_MAX events per scene are
+ * not supported. */
+#define MMW_STANCE_UNKNOWN 0
+#define MMW_STANCE_UPRIGHT 1
+#define MMW_STANCE_LOW 2        /* sitting or crouched */
+#define MMW_STANCE_LYING 3
+#define MMW_STANCE_RULES_MAX 1
+#define MMW_STANCE_LOG_MAX 4096
+typedef struct mmw_stance_rule {   /* 64 bytes */
+    double h_stand;                /* head above this: UPRIGHT (metres, room height = kp[22]) */
+    double h_lie;                  /* head not above this: LYING */
+    double margin;                 /* >= 0: hysteresis on both heights */
+    double fall_window;            /* >= 0 s: reaching LYING within this of having been UPRIGHT is a FALL */
+    double long_lie;               /* >= 0 s, +inf = never: LYING this long gives ONE LONG_LIE per episode */
+    double max_gap;                /* > 0: the reference's skeleton check (Visualizer.py:277 uses 0.5) */
+    int32_t id;                    /* caller's label, copied into rows */
+    int32_t reserved_;             /* must be 0 */
+    int32_t pad_[2];               /* not read */
+} mmw_stance_rule;
+typedef struct mmw_stance_event { int32_t scene, uid, kind, from, to, slot; double t; } mmw_stance_event;   /* 32 bytes */
+#define MMW_SEV_CHANGE 1
+#define MMW_SEV_FALL 2
+#define MMW_SEV_LONG_LIE 3
+#define MMW_SEV_REBASED 4       /* the scene's uids or rule are new from here on; uid = -1, from = to = 0, slot = live tracks then */
+typedef struct mmw_stance_row { int32_t scene, id, upright, low, lying, unknown, falls, d_falls, long_lies, d_long_lies, lost, reserved_; } mmw_stance_row;   /* 48 bytes */
+int mmw_stance_enable(mmw_ctx *ctx, int32_t log_depth);         /* 1 .. MMW_STANCE_LOG_MAX; 0 = off and freed */
+int mmw_set_stance_rules(mmw_ctx *ctx, const int32_t *scenes, int32_t n, const int32_t *n_rules /* host [n] */, const mmw_stance_rule *rules /* host [n][MMW_STANCE_RULES_MAX] */);
+int mmw_get_stance_rules(mmw_ctx *ctx, int32_t *n_rules /* host [S] */, mmw_stance_rule *rules /* host [S][MMW_STANCE_RULES_MAX] */);   /* host mirror, no device access */
+int mmw_stance_sample(mmw_ctx *ctx, const int32_t *scene_flags /* dev [S] or NULL */, const double *t /* dev [S] or NULL */);
+int mmw_stance_async(mmw_ctx *ctx, mmw_stance_row *rows, int32_t cap_rows, mmw_stance_event *events, int32_t cap_events,
+                     int32_t scene_base, int32_t ticket);
+int mmw_stance_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n_events);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_stance(mmw_ctx *ctx, mmw_stance_row *rows, int32_t cap_rows, mmw_stance_event *events, int32_t cap_events,
+               int32_t scene_base, int32_t *n_rows, int32_t *n_events);                 /* async + wait */
+
 /* Snapshot / restore of scene state (format version 1).
  *
  * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global

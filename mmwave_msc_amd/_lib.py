@@ -37,7 +37,7 @@ POSTURE_MODELS_MAX = 8             # models one mmw_posture_attach_models call t
 POSTURE_NONE = -1                  # MMW_POSTURE_NONE: the map entry of a scene no model estimates
 EXPORT_TICKETS = 4                 # kTickets (csrc/mmw_ctx.hpp): `*_async` calls of one export that may be outstanding; the
                                    # one-call form of each export (mmw_report, mmw_clouds, ...) uses the last ticket itself
-REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = TRAIL_TICKETS = TRIPWIRE_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
+REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = TRAIL_TICKETS = TRIPWIRE_TICKETS = STANCE_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
 
 EMPTY_FRAME = -1   # MMW_EMPTY_FRAME (include/mmw.h)
 BAD_FRAME = -3     # MMW_BAD_FRAME: n_out of mmw_normalize_tlv for a TLV body it refused to decode
@@ -199,6 +199,21 @@ TRIPWIRE_ROW_DTYPE = np.dtype([("scene", "i4"), ("wire", "i4"), ("id", "i4"), ("
 TRIPWIRE_EVENT_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("kind", "i4"), ("wire", "i4"), ("id", "i4"), ("slot", "i4"), ("t", "f8")], align=True)
 TW_FORWARD, TW_BACKWARD, TW_REBASED = 1, 2, 3   # MMW_TW_*: mmw_tripwire_event.kind
 
+# struct mmw_stance_rule / mmw_stance_row / mmw_stance_event (include/mmw.h): a scene's rule (64 bytes), and the rows (48 bytes) and
+# events (32 bytes) of mmw_stance_*
+STANCE_RULES_MAX = 1                          # MMW_STANCE_RULES_MAX: rules per scene
+STANCE_LOG_MAX = 4096                         # MMW_STANCE_LOG_MAX: events a scene's log holds at the most
+STANCE_UNKNOWN, STANCE_UPRIGHT, STANCE_LOW, STANCE_LYING = 0, 1, 2, 3   # MMW_STANCE_*: the classes (mmw_stance_event.from / .to)
+STANCE_CLASS_NAMES = ("unknown", "upright", "low", "lying")
+STANCE_FIELDS = ("h_stand", "h_lie", "margin", "fall_window", "long_lie", "max_gap", "id")
+STANCE_DEFAULTS = dict(h_stand=1.2, h_lie=0.5, margin=0.1, fall_window=1.5, long_lie=30.0, max_gap=0.5, id=0)
+STANCE_RULE_DTYPE = np.dtype([("h_stand", "f8"), ("h_lie", "f8"), ("margin", "f8"), ("fall_window", "f8"), ("long_lie", "f8"), ("max_gap", "f8"),
+                              ("id", "i4"), ("reserved_", "i4"), ("pad_", "i4", (2,))], align=True)
+STANCE_ROW_DTYPE = np.dtype([("scene", "i4"), ("id", "i4"), ("upright", "i4"), ("low", "i4"), ("lying", "i4"), ("unknown", "i4"), ("falls", "i4"),
+                             ("d_falls", "i4"), ("long_lies", "i4"), ("d_long_lies", "i4"), ("lost", "i4"), ("reserved_", "i4")], align=True)
+STANCE_EVENT_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("kind", "i4"), ("from", "i4"), ("to", "i4"), ("slot", "i4"), ("t", "f8")], align=True)
+SEV_CHANGE, SEV_FALL, SEV_LONG_LIE, SEV_REBASED = 1, 2, 3, 4   # MMW_SEV_*: mmw_stance_event.kind
+
 
 # C struct name in include/mmw.h -> its Python mirror; every `typedef struct mmw_*` but the opaque mmw_ctx.  Field names are the
 # header's own throughout, so a mirror needs no second spelling beside it.
@@ -209,6 +224,7 @@ ABI_STRUCTS = {
     "mmw_zone": ZONE_DTYPE, "mmw_zone_row": ZONE_ROW_DTYPE, "mmw_zone_event": ZONE_EVENT_DTYPE,
     "mmw_trail_track": TRAIL_TRACK_DTYPE, "mmw_trail_point": TRAIL_POINT_DTYPE,
     "mmw_tripwire": TRIPWIRE_DTYPE, "mmw_tripwire_row": TRIPWIRE_ROW_DTYPE, "mmw_tripwire_event": TRIPWIRE_EVENT_DTYPE,
+    "mmw_stance_rule": STANCE_RULE_DTYPE, "mmw_stance_row": STANCE_ROW_DTYPE, "mmw_stance_event": STANCE_EVENT_DTYPE,
     "mmw_snapshot_header": MmwSnapshotHeader, "mmw_snapshot_entry": MmwSnapshotEntry, "mmw_snapshot_info": MmwSnapshotInfo,
     "mmw_uart_cfg": MmwUartCfg, "mmw_uart_frame": UART_FRAME_DTYPE, "mmw_uart_object": UART_OBJECT_DTYPE,
     "mmw_sample_entry": SAMPLE_ENTRY_DTYPE,
@@ -332,6 +348,13 @@ def _signatures():
         "mmw_tripwires_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
         "mmw_tripwires_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_tripwires": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
+        "mmw_stance_enable": (C.c_int, [vp, i32]),
+        "mmw_set_stance_rules": (C.c_int, [vp, vp, i32, vp, vp]),
+        "mmw_get_stance_rules": (C.c_int, [vp, vp, vp]),
+        "mmw_stance_sample": (C.c_int, [vp, vp, vp]),
+        "mmw_stance_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
+        "mmw_stance_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_stance": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
         "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
         "mmw_uart_close": (C.c_int, [vp]),
         "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),
@@ -594,3 +617,31 @@ def make_tripwires(per_scene):
             for f, v in zip(TRIPWIRE_FIELDS, vals):
                 wires[i, k][f] = v
     return n_wires, wires
+
+
+def make_stance_rules(per_scene):
+    """(n_rules int32[n], rules STANCE_RULE_DTYPE[n, STANCE_RULES_MAX]) for `mmw_set_stance_rules` from one list per scene of zero or
+    one rule, a dict with keys of STANCE_FIELDS or a tuple (h_stand, h_lie, margin, fall_window, long_lie, max_gap, id) cut short
+    anywhere; what is left out is STANCE_DEFAULTS' (`id`: 0).  An entry without a rule stays zero."""
+    per_scene = list(per_scene)
+    n_rules = np.zeros(len(per_scene), np.int32)
+    rules = np.zeros((len(per_scene), STANCE_RULES_MAX), STANCE_RULE_DTYPE)
+    for i, rs in enumerate(per_scene):
+        rs = list(rs)
+        if len(rs) > STANCE_RULES_MAX:
+            raise ValueError(f"make_stance_rules: scene entry {i} has {len(rs)} rules, at most {STANCE_RULES_MAX} fits")
+        n_rules[i] = len(rs)
+        for k, r in enumerate(rs):
+            if isinstance(r, dict):
+                unknown = set(r) - set(STANCE_FIELDS)
+                if unknown:
+                    raise AttributeError(f"mmw_stance_rule has no field {sorted(unknown)[0]!r}")
+                vals = [r.get(f, STANCE_DEFAULTS[f]) for f in STANCE_FIELDS]
+            else:
+                r = tuple(r)
+                if len(r) > len(STANCE_FIELDS):
+                    raise ValueError(f"make_stance_rules: a rule is (h_stand, h_lie, margin, fall_window, long_lie, max_gap, id) or its head, not {len(r)} values")
+                vals = list(r) + [STANCE_DEFAULTS[f] for f in STANCE_FIELDS[len(r):]]
+            for f, v in zip(STANCE_FIELDS, vals):
+                rules[i, k][f] = v
+    return n_rules, rules

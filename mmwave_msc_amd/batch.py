@@ -1040,6 +1040,60 @@ class SceneBatch:
         return self._export_host("tripwires", lambda *a: self.tripwires_async(*a[:4], scene_base, a[4]), self.L.mmw_tripwires_wait,
                                  ("tripwire_rows", _lib.TRIPWIRE_ROW_DTYPE), ("tripwire_events", _lib.TRIPWIRE_EVENT_DTYPE))
 
+    # -- stance watch ---------------------------------------------------------
+    def enable_stance(self, log_depth: int = 256):
+        """mmw_stance_enable: per scene a rule table (no rule to begin with), per-uid stance classes, the fall and long-lie counters
+        and a log of `log_depth` (1 .. `_lib.STANCE_LOG_MAX`) events; everything starts over, also when stance was enabled before.
+        log_depth=0 frees it.  Until enabled, the stance calls are refused (E_ARG) -- `stance_rules()` reports 0 rules -- and the
+        context launches nothing of them."""
+        self._chk(self.L.mmw_stance_enable(self.h, int(log_depth)))
+
+    def set_stance_rules(self, rules, scenes=None):
+        """mmw_set_stance_rules: give `scenes` (default: scenes 0 .. len(rules)-1) their rule -- `rules` is what
+        `_lib.make_stance_rules` takes (a list per scene of zero or one dict or tuple) or its result, the pair (n_rules,
+        STANCE_RULE_DTYPE[n, 1]).  Scenes never listed keep what they have; the listed scenes' counters restart at 0 and their
+        classes are void (their next sample logs a SEV_REBASED).  Refused (MmwError, E_ARG) with nothing changed for an index out of
+        range or listed twice, more entries than scenes, a height, margin, window or gap that is not finite, a negative margin,
+        window or long_lie, max_gap <= 0, h_lie + margin not below h_stand - margin, or a non-zero `reserved_`."""
+        self._set_scene_table("set_stance_rules", "rules", self.L.mmw_set_stance_rules, _lib.make_stance_rules, _lib.STANCE_RULE_DTYPE,
+                              _lib.STANCE_RULES_MAX, rules, scenes)
+
+    def stance_rules(self):
+        """mmw_get_stance_rules: (n_rules int32[S], rules STANCE_RULE_DTYPE[S, 1]) of every scene, from the host mirror; zero where a
+        scene has no rule."""
+        return self._get_scene_table(self.L.mmw_get_stance_rules, _lib.STANCE_RULE_DTYPE, _lib.STANCE_RULES_MAX)
+
+    def sample_stance_dev(self, flags_ptr=None, t_ptr=None):
+        """mmw_stance_sample: every live track's stance class of the asked scenes from the keypoints its record holds now, changes,
+        falls and long lies counted and logged, queued behind `estimate_posture` / `set_keypoints*` on the context's stream -- no
+        host wait.  `flags_ptr`: device int32[S], non-zero = asked (None = every scene); `t_ptr`: device float64[S], the events' time
+        (None = each scene's count of earlier sample calls)."""
+        self._chk(self.L.mmw_stance_sample(self.h, flags_ptr, t_ptr))
+
+    def sample_stance(self, t=None, scenes=None):
+        """`sample_stance_dev` from host arrays: `t` float64[S] or a scalar for every scene (None = the call ordinals), `scenes` the
+        scenes to sample (default all)."""
+        self._sample(self.sample_stance_dev, "stance", t, scenes)
+
+    def stance_async(self, rows_ptr, cap_rows: int, events_ptr, cap_events: int, scene_base: int = 0, ticket: int = 0):
+        """mmw_stance_async: one `_lib.STANCE_ROW_DTYPE` row per scene with a rule and the `_lib.STANCE_EVENT_DTYPE` events logged
+        since the previous successful export into device buffers, queued on the context's stream -- no host wait.  Tickets 0 .. 3
+        (`stance_host` uses 3).  Both pointers 8-byte aligned."""
+        self._chk(self.L.mmw_stance_async(self.h, rows_ptr, int(cap_rows), events_ptr, int(cap_events), int(scene_base), int(ticket)))
+
+    def stance_wait(self, ticket: int = 0):
+        """(n_rows, n_events) of the `stance_async` call with this ticket: waits for its counts only, not for the stream.  Buffers
+        too small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written and nothing was taken, so
+        the same export can be asked for again with room."""
+        return self._export_wait(self.L.mmw_stance_wait, ticket)
+
+    def stance_host(self, scene_base: int = 0):
+        """The stance export as two structured arrays: (rows[n_rows] STANCE_ROW_DTYPE, events[n_events] STANCE_EVENT_DTYPE); fold the
+        events with `stance.Watch`.  The buffers grow to what the device says it needs (a refused export loses nothing)."""
+        self._export_caps.setdefault("stance", (64, 256))   # (its entry exists from the first call on, as the zones')
+        return self._export_host("stance", lambda *a: self.stance_async(*a[:4], scene_base, a[4]), self.L.mmw_stance_wait,
+                                 ("stance_rows", _lib.STANCE_ROW_DTYPE), ("stance_events", _lib.STANCE_EVENT_DTYPE))
+
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):
         if scenes is None:

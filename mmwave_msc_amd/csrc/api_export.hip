@@ -46,7 +46,7 @@ int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const ch
     return MMW_OK;
 }
 
-// What mmw_trails_sample and mmw_tripwires_sample check before they launch: `entry` ("mmw_trails") is enabled -- x is its export
+// What mmw_trails_sample, mmw_tripwires_sample and mmw_stance_sample check before they launch: `entry` ("mmw_trails") is enabled -- x is its export
 // state, `what` its noun in the message -- and the two optional device arrays are aligned.  Leaves the context's device current.
 int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t)
 {
@@ -57,13 +57,13 @@ int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *
 }
 
 // mmw_reset / mmw_reset_scenes / mmw_restore: uids restart in the scenes flagged in dev_flags (device, [n_scenes]; nullptr = every
-// scene), so the report's baseline, the zones' memberships, the trails and the tripwires' sides of those scenes are void.  One launch for the consumers
+// scene), so the report's baseline, the zones' memberships, the trails, the tripwires' sides and the stance classes of those scenes are void.  One launch for the consumers
 // that are on, queued on the context's stream behind the kernel that emptied or refilled the scenes; nothing at all while none is.
 int uid_rebase(mmw_ctx *c, const int32_t *dev_flags)
 {
     const UidGens g = {{c->rep.d_block ? c->rs.base.ug.gen : nullptr, c->zone.d_block ? c->zs.base.ug.gen : nullptr, c->trail.d_block ? c->ts.ug.gen : nullptr,
-                       c->trip.d_block ? c->tw.ug.gen : nullptr}};
-    if (!g.gen[0] && !g.gen[1] && !g.gen[2] && !g.gen[3]) return MMW_OK;
+                       c->trip.d_block ? c->tw.ug.gen : nullptr, c->stance.d_block ? c->ss.ug.gen : nullptr}};
+    if (!g.gen[0] && !g.gen[1] && !g.gen[2] && !g.gen[3] && !g.gen[4]) return MMW_OK;
     launch_uid_rebase(c->dc.n_scenes, dev_flags, g, c->stream);
     HIPCHK(c, hipGetLastError());
     return MMW_OK;

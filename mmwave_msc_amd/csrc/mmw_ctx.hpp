@@ -69,7 +69,7 @@ struct ExportCtx {
     bool issued[kTickets] = {false, false, false, false};
 };
 
-// A per-scene table of up to MAX caller entries E a scene (mmw_set_zones, mmw_set_tripwires; mmw_scene_table.hpp has the code): the
+// A per-scene table of up to MAX caller entries E a scene (mmw_set_zones, mmw_set_tripwires, mmw_set_stance_rules; mmw_scene_table.hpp has the code): the
 // device allocation, which holds the table as the kernels read it (entries D) and in which every set call lands as ONE copy, and
 // the host mirrors of what the caller gave.  d_tab == nullptr: not allocated.
 template <class E, class D, int MAX>
@@ -148,6 +148,9 @@ struct mmw_ctx {
     ExportCtx trip;                   // mmw_tripwires_enable allocates it (log_depth 0 frees it); not allocated = tripwires are off, nothing of them is launched
     TripState tw = {};                // ... the uid slots, counters and event rings, in front of trip's scratch in trip.d_block (tw.sc = trip.sc)
     SceneTable<mmw_tripwire, TripWire, MMW_TRIPWIRES_MAX> twtab;   // ... the wire table: what the kernels read is derived on the host (mmw_get_tripwires reads the mirrors)
+    ExportCtx stance;                 // mmw_stance_enable allocates it (log_depth 0 frees it); not allocated = stance is off, nothing of it is launched
+    StanceState ss = {};              // ... the uid slots, counters and event rings, in front of stance's scratch in stance.d_block (ss.sc = stance.sc)
+    SceneTable<mmw_stance_rule, StanceRule, MMW_STANCE_RULES_MAX> sttab;   // ... the rule table: what the kernels read is derived on the host (mmw_get_stance_rules reads the mirrors)
     ExportCtx ulog_x;                 // mmw_uart_log_enable; not allocated = the radar log is off and mmw_uart_read launches what it always did
     UartLog ulog = {};                // ... the staged frames, in front of ulog_x's scratch in ulog_x.d_block
     std::vector<double> uart_range;   // [S] rangeIdxToMeters of the open readers (the log's range column)
@@ -169,7 +172,8 @@ int first_scene_error(mmw_ctx *c, const SceneHdr *h, size_t n, const int32_t *q)
 void posture_batch_free(PostureBatch *b);                          // api_posture.hip
 void zone_free(mmw_ctx *c);                                        // api_zone.hip: table, baseline and mirrors (the caller has waited for the stream)
 void tripwire_free(mmw_ctx *c);                                    // api_tripwire.hip: table, slots, counters, rings and mirrors (the caller has waited for the stream)
-void trail_free(mmw_ctx *c);                                       // api_trail.hip: slots, rings and scratch (the caller has waited for the stream)
+void stance_free(mmw_ctx *c);                                      // api_stance.hip: table, slots, counters, rings and mirrors (the caller has waited for the stream)
+void trail_free(mmw_ctx *c);                                     // api_trail.hip: slots, rings and scratch (the caller has waited for the stream)
 int uart_log_rearm(mmw_ctx *c);                                    // api_uart_log.hip: every scene's log word as new, with its range scale (no-op while the log is off)
 void uart_log_free(mmw_ctx *c);                                    // api_uart_log.hip: ... and the log is off (the caller has waited for the stream)
 // api_export.hip: the ticketed counts of the three live-track exports (`name`: the entry the messages speak for)
@@ -177,8 +181,8 @@ int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name)
 void export_free(ExportCtx &x);                                    // ... and x is as never allocated
 int export_issue(mmw_ctx *c, ExportCtx &x, int ticket);           // behind the launch: its error, the totals into the ticket's pinned slot, the event
 int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const char *none, const int32_t **counts);   // -> the ticket's four words
-int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t);   // mmw_trails_sample / mmw_tripwires_sample: enabled, aligned, device set
-int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones, trails and tripwires, none while all four are off
+int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t);   // mmw_trails_sample / mmw_tripwires_sample / mmw_stance_sample: enabled, aligned, device set
+int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones, trails, tripwires and stance, none while all five are off
 #pragma GCC visibility pop
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)

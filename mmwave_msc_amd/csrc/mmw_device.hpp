@@ -237,6 +237,25 @@ struct TripState {
     UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
     ExportScratch sc;          // rows / events of the export in flight
 };
+// mmw_stance_enable: the rule table and what the stance watch keeps from one mmw_stance_sample to the next (k_stance.hip).  All
+// device memory.  A table entry is what the HOST derived of an mmw_stance_rule (mmw_set_stance_rules): the device does no arithmetic
+// on a threshold.  A uid's words lie in the slot that the one slot table (UidSlots, mmw_uidlist.hpp) gives it.
+struct StanceRule { double h_stand, h_lie, up_hi, up_lo, lie_hi, lie_lo, gap2, fall_window, long_lie; int32_t id, pad_; };   // 80 bytes
+struct StanceCount { int32_t falls, long_lies, mark_falls, mark_long_lies; };   // totals since the rule was set; ... at the previous successful export
+constexpr int kStanceClassMask = 3, kStanceLongLie = 4;   // a slot's word: bits 0-1 the class, bit 2 "LONG_LIE given in this episode"
+struct StanceState {
+    int32_t depth;             // log entries per scene, 1 .. MMW_STANCE_LOG_MAX
+    const StanceRule *rules;   // [S][MMW_STANCE_RULES_MAX] the table (one copy of mmw_set_stance_rules; read with scalar loads)
+    const int32_t *n_rules;    // [S] 0 or 1, behind the table in the same allocation
+    int32_t *word;             // [S][t_cap] the slot's uid's class and episode bit
+    double *t_since;           // [S][t_cap] t of the sample that entered the current class
+    double *t_upright;         // [S][t_cap] t of the newest sample that classed the uid UPRIGHT, -inf if never
+    StanceCount *count;        // [S] lane 0 of a scene's wave owns it
+    mmw_stance_event *ring;    // [S][depth] event n (0-based) of a scene lies at n % depth, with the LOCAL scene index
+    int32_t *logged, *taken;   // [S] events ever appended / handed out
+    UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
+    ExportScratch sc;          // rows / events of the export in flight
+};
 
 // The live list of scene s, as every export walks it: T = live_tracks lanes, lane -> live_slot -> the scene's TrackRec.  Both are
 // clamped into range, so a damaged state gives the same list -- report row i, cloud entry i, skeleton i -- in every export.

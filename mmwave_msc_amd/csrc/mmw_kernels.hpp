@@ -14,6 +14,7 @@ struct ReportState;
 struct ZoneState;
 struct TrailState;
 struct TripState;
+struct StanceState;
 struct UartState;
 struct UartLog;
 struct ExportScratch;
@@ -62,9 +63,9 @@ void launch_clear_errors(const DevCfg &cfg, const DevState &s, const int32_t *fl
 void launch_set_batch_size(const DevCfg &cfg, const DevState &s, const int32_t *flags, int new_size, hipStream_t st);
 // k_scan.hip: the scan step of the live-track exports below -- two count arrays to offsets, totals and the capacity decision
 void launch_pair_scan(int S, int32_t *off, int32_t *totals, int cap0, int cap1, hipStream_t st);
-// ... and the generation bump of those that remember uids (report, zones, trails, tripwires): every non-null word, for the scenes flagged
+// ... and the generation bump of those that remember uids (report, zones, trails, tripwires, stance): every non-null word, for the scenes flagged
 // (flags: dev [S] or nullptr = every scene)
-struct UidGens { static constexpr int kMax = 4; int32_t *gen[kMax]; };
+struct UidGens { static constexpr int kMax = 5; int32_t *gen[kMax]; };
 void launch_uid_rebase(int n_scenes, const int32_t *flags, const UidGens &gens, hipStream_t st);
 // k_report.hip: the live-track report
 void launch_report_baseline(const DevCfg &cfg, const DevState &s, const ReportState &rp, hipStream_t st);
@@ -82,6 +83,10 @@ void launch_trails(const DevCfg &cfg, const DevState &s, const TrailState &ts, m
 void launch_tripwire_zero(int n_scenes, const int32_t *flags, const TripState &ts, hipStream_t st);
 void launch_tripwire_sample(const DevCfg &cfg, const DevState &s, const TripState &ts, const int32_t *flags, const double *t, hipStream_t st);
 void launch_tripwires(const DevCfg &cfg, const TripState &ts, mmw_tripwire_row *rows, int cap_rows, mmw_tripwire_event *events, int cap_events, int scene_base, hipStream_t st);
+// k_stance.hip: the stance watch (flags, t as launch_trail_sample's; launch_stance_zero: the flagged scenes' counters and marks, flags: dev [S])
+void launch_stance_zero(int n_scenes, const int32_t *flags, const StanceState &ss, hipStream_t st);
+void launch_stance_sample(const DevCfg &cfg, const DevState &s, const StanceState &ss, const int32_t *flags, const double *t, hipStream_t st);
+void launch_stance(const DevCfg &cfg, const StanceState &ss, mmw_stance_row *rows, int cap_rows, mmw_stance_event *events, int cap_events, int scene_base, hipStream_t st);
 // k_uart.hip: the device-resident radar readers (log: the radar log while it is enabled -- the k_uart_read*_log twins --, else nullptr)
 void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const UartLog *log, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);
