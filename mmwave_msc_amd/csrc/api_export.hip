@@ -1,6 +1,7 @@
 // api_export.hip -- what mmw_report_*, mmw_clouds_* and mmw_skeletons_* share on the host (not part of the ABI): the device scratch
 // that k_pair_scan works on, and the tickets -- the totals of every call follow its kernels into a pinned slot of their own, and a
-// wait is for that copy only.  And the generation bump of the exports that remember uids.
+// wait is for that copy only.  The argument check and the wait of the exports with a rows and an events buffer (report, zones,
+// tripwires, stance).  And the generation bump of the exports that remember uids.
 #include "mmw_ctx.hpp"
 
 void export_free(ExportCtx &x)
@@ -43,6 +44,29 @@ int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const ch
     HIPCHK(c, hipEventSynchronize(x.ev[ticket]));
     x.issued[ticket] = false;
     *counts = x.h_counts + ticket * 4;
+    return MMW_OK;
+}
+
+int pair_export_begin(mmw_ctx *c, const ExportCtx &x, const PairExport &d, const void *rows, int cap_rows, const void *events, int cap_events, int ticket)
+{
+    if (!x.d_block) return fail(c, MMW_E_ARG, "%s: %s", d.entry, d.off);
+    if (cap_rows < 0 || cap_events < 0 || (cap_rows > 0 && !rows) || (cap_events > 0 && !events))
+        return fail(c, MMW_E_ARG, "%s: cap_rows = %d, cap_events = %d with rows %s, events %s", d.entry, cap_rows, cap_events, rows ? "set" : "NULL", events ? "set" : "NULL");
+    if (d.align && (((uintptr_t)rows | (uintptr_t)events) & (uintptr_t)(d.align - 1)) != 0) return fail(c, MMW_E_ARG, "%s: the buffers must be %d-byte aligned", d.entry, d.align);
+    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "%s: ticket %d outside [0, %d)", d.entry, ticket, kTickets);
+    HIPCHK(c, hipSetDevice(c->device));
+    return MMW_OK;
+}
+
+int pair_export_wait(mmw_ctx *c, ExportCtx &x, const PairExport &d, int ticket, int32_t *n_rows, int32_t *n_events)
+{
+    const std::string name = std::string(d.entry) + "_wait";
+    if (!x.d_block) return fail(c, MMW_E_ARG, "%s: %s", name.c_str(), d.off);
+    const int32_t *h;
+    MMW_TRY(export_wait(c, x, ticket, name.c_str(), d.none, &h));
+    if (n_rows) *n_rows = h[0];
+    if (n_events) *n_events = h[1];
+    if (!h[2]) return fail(c, MMW_E_CAPACITY, "%s: %d %s and %d events %s", d.entry, h[0], d.rows, h[1], d.unfit);
     return MMW_OK;
 }
 

@@ -37,30 +37,20 @@ int mmw_report_enable(mmw_ctx *c, int32_t on)
     return MMW_OK;
 }
 
+static const PairExport kExport = {"mmw_report", "reports are not enabled (mmw_report_enable)", "no report", "live rows", kUnfitBaseline, 4};
+
 int mmw_report_async(mmw_ctx *c, mmw_track_report *rows, int32_t cap_rows, mmw_track_event *events, int32_t cap_events, int32_t scene_base,
                      int32_t ticket)
 {
     if (!c) return MMW_E_ARG;
-    if (!c->rep.d_block) return fail(c, MMW_E_ARG, "mmw_report: reports are not enabled (mmw_report_enable)");
-    if (cap_rows < 0 || cap_events < 0 || (cap_rows > 0 && !rows) || (cap_events > 0 && !events))
-        return fail(c, MMW_E_ARG, "mmw_report: cap_rows = %d, cap_events = %d with rows %s, events %s", cap_rows, cap_events, rows ? "set" : "NULL", events ? "set" : "NULL");
-    if (((uintptr_t)rows & 3) != 0 || ((uintptr_t)events & 3) != 0) return fail(c, MMW_E_ARG, "mmw_report: the buffers must be 4-byte aligned");
-    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_report: ticket %d outside [0, %d)", ticket, kTickets);
-    HIPCHK(c, hipSetDevice(c->device));
+    MMW_TRY(pair_export_begin(c, c->rep, kExport, rows, cap_rows, events, cap_events, ticket));
     launch_report(c->dc, sites_or_null(c), c->st, c->rs, rows, cap_rows, events, cap_events, scene_base, c->stream);
     return export_issue(c, c->rep, ticket);
 }
 
 int mmw_report_wait(mmw_ctx *c, int32_t ticket, int32_t *n_rows, int32_t *n_events)
 {
-    if (!c) return MMW_E_ARG;
-    if (!c->rep.d_block) return fail(c, MMW_E_ARG, "mmw_report_wait: reports are not enabled (mmw_report_enable)");
-    const int32_t *h;
-    MMW_TRY(export_wait(c, c->rep, ticket, "mmw_report_wait", "no report", &h));
-    if (n_rows) *n_rows = h[0];
-    if (n_events) *n_events = h[1];
-    if (!h[2]) return fail(c, MMW_E_CAPACITY, "mmw_report: %d live rows and %d events do not fit the buffers: nothing was written, the baseline is unchanged", h[0], h[1]);
-    return MMW_OK;
+    return c ? pair_export_wait(c, c->rep, kExport, ticket, n_rows, n_events) : MMW_E_ARG;
 }
 
 int mmw_report(mmw_ctx *c, mmw_track_report *rows, int32_t cap_rows, mmw_track_event *events, int32_t cap_events, int32_t scene_base,

@@ -43,21 +43,15 @@ int mmw_stance_enable(mmw_ctx *c, int32_t log_depth)
         return rc;
     }
     StanceState ss = {};
-    ss.depth = log_depth;
     ss.rules = tab.entries();
     ss.n_rules = tab.counts(S);
-    ss.ring = reinterpret_cast<mmw_stance_event *>(nx.d_block);
     ss.t_since = reinterpret_cast<double *>(nx.d_block + ring_bytes);
     ss.t_upright = ss.t_since + n;
     ss.count = reinterpret_cast<StanceCount *>(nx.d_block + ring_bytes + time_bytes);
     int32_t *p = reinterpret_cast<int32_t *>(nx.d_block + ring_bytes + time_bytes + count_bytes);
     ss.ug.owner = p; p += n;
     ss.word = p; p += n;
-    ss.logged = p; p += S;
-    ss.taken = p; p += S;
-    ss.ug.gen = p; p += S;
-    ss.ug.seen = p; p += S;
-    ss.ug.ordinal = p;
+    evlog_carve(ss.log, ss.ug, log_depth, nx.d_block, p, S);
     ss.sc = nx.sc;
     // every scene at 0 rules, every slot free, every word 0 (the rings need no clearing: an entry is written before `logged` lets anybody
     // read it; a newcomer's t_upright = -inf is the sample kernel's)
@@ -135,29 +129,19 @@ int mmw_stance_sample(mmw_ctx *c, const int32_t *scene_flags, const double *t)
     return MMW_OK;
 }
 
+static const PairExport kExport = {"mmw_stance", "stance is not enabled (mmw_stance_enable)", "no stance export", "rows", kUnfitLog, 8};
+
 int mmw_stance_async(mmw_ctx *c, mmw_stance_row *rows, int32_t cap_rows, mmw_stance_event *events, int32_t cap_events, int32_t scene_base, int32_t ticket)
 {
     if (!c) return MMW_E_ARG;
-    if (!c->stance.d_block) return fail(c, MMW_E_ARG, "mmw_stance: stance is not enabled (mmw_stance_enable)");
-    if (cap_rows < 0 || cap_events < 0 || (cap_rows > 0 && !rows) || (cap_events > 0 && !events))
-        return fail(c, MMW_E_ARG, "mmw_stance: cap_rows = %d, cap_events = %d with rows %s, events %s", cap_rows, cap_events, rows ? "set" : "NULL", events ? "set" : "NULL");
-    if (((uintptr_t)rows & 7) != 0 || ((uintptr_t)events & 7) != 0) return fail(c, MMW_E_ARG, "mmw_stance: the buffers must be 8-byte aligned");
-    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_stance: ticket %d outside [0, %d)", ticket, kTickets);
-    HIPCHK(c, hipSetDevice(c->device));
+    MMW_TRY(pair_export_begin(c, c->stance, kExport, rows, cap_rows, events, cap_events, ticket));
     launch_stance(c->dc, c->ss, rows, cap_rows, events, cap_events, scene_base, c->stream);
     return export_issue(c, c->stance, ticket);
 }
 
 int mmw_stance_wait(mmw_ctx *c, int32_t ticket, int32_t *n_rows, int32_t *n_events)
 {
-    if (!c) return MMW_E_ARG;
-    if (!c->stance.d_block) return fail(c, MMW_E_ARG, "mmw_stance_wait: stance is not enabled (mmw_stance_enable)");
-    const int32_t *h;
-    MMW_TRY(export_wait(c, c->stance, ticket, "mmw_stance_wait", "no stance export", &h));
-    if (n_rows) *n_rows = h[0];
-    if (n_events) *n_events = h[1];
-    if (!h[2]) return fail(c, MMW_E_CAPACITY, "mmw_stance: %d rows and %d events do not fit the buffers: nothing was written, nothing was taken", h[0], h[1]);
-    return MMW_OK;
+    return c ? pair_export_wait(c, c->stance, kExport, ticket, n_rows, n_events) : MMW_E_ARG;
 }
 
 int mmw_stance(mmw_ctx *c, mmw_stance_row *rows, int32_t cap_rows, mmw_stance_event *events, int32_t cap_events, int32_t scene_base, int32_t *n_rows,

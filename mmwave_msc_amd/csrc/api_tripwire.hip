@@ -41,19 +41,13 @@ int mmw_tripwires_enable(mmw_ctx *c, int32_t log_depth)
         return rc;
     }
     TripState tw = {};
-    tw.depth = log_depth;
     tw.wires = tab.entries();
     tw.n_wires = tab.counts(S);
-    tw.ring = reinterpret_cast<mmw_tripwire_event *>(nx.d_block);
     tw.count = reinterpret_cast<TripCount *>(nx.d_block + ring_bytes);
     int32_t *p = reinterpret_cast<int32_t *>(nx.d_block + ring_bytes + count_bytes);
     tw.ug.owner = p; p += n;
     tw.side = p; p += n;
-    tw.logged = p; p += S;
-    tw.taken = p; p += S;
-    tw.ug.gen = p; p += S;
-    tw.ug.seen = p; p += S;
-    tw.ug.ordinal = p;
+    evlog_carve(tw.log, tw.ug, log_depth, nx.d_block, p, S);
     tw.sc = nx.sc;
     // every scene at 0 wires, every slot free, every word 0 (the rings need no clearing: an entry is written before `logged` lets anybody read it)
     hipError_t e = hipMemsetAsync(tab.d_tab, 0, tab.bytes(S), c->stream);
@@ -127,29 +121,19 @@ int mmw_tripwires_sample(mmw_ctx *c, const int32_t *scene_flags, const double *t
     return MMW_OK;
 }
 
+static const PairExport kExport = {"mmw_tripwires", "tripwires are not enabled (mmw_tripwires_enable)", "no tripwire export", "rows", kUnfitLog, 8};
+
 int mmw_tripwires_async(mmw_ctx *c, mmw_tripwire_row *rows, int32_t cap_rows, mmw_tripwire_event *events, int32_t cap_events, int32_t scene_base, int32_t ticket)
 {
     if (!c) return MMW_E_ARG;
-    if (!c->trip.d_block) return fail(c, MMW_E_ARG, "mmw_tripwires: tripwires are not enabled (mmw_tripwires_enable)");
-    if (cap_rows < 0 || cap_events < 0 || (cap_rows > 0 && !rows) || (cap_events > 0 && !events))
-        return fail(c, MMW_E_ARG, "mmw_tripwires: cap_rows = %d, cap_events = %d with rows %s, events %s", cap_rows, cap_events, rows ? "set" : "NULL", events ? "set" : "NULL");
-    if (((uintptr_t)rows & 7) != 0 || ((uintptr_t)events & 7) != 0) return fail(c, MMW_E_ARG, "mmw_tripwires: the buffers must be 8-byte aligned");
-    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_tripwires: ticket %d outside [0, %d)", ticket, kTickets);
-    HIPCHK(c, hipSetDevice(c->device));
+    MMW_TRY(pair_export_begin(c, c->trip, kExport, rows, cap_rows, events, cap_events, ticket));
     launch_tripwires(c->dc, c->tw, rows, cap_rows, events, cap_events, scene_base, c->stream);
     return export_issue(c, c->trip, ticket);
 }
 
 int mmw_tripwires_wait(mmw_ctx *c, int32_t ticket, int32_t *n_rows, int32_t *n_events)
 {
-    if (!c) return MMW_E_ARG;
-    if (!c->trip.d_block) return fail(c, MMW_E_ARG, "mmw_tripwires_wait: tripwires are not enabled (mmw_tripwires_enable)");
-    const int32_t *h;
-    MMW_TRY(export_wait(c, c->trip, ticket, "mmw_tripwires_wait", "no tripwire export", &h));
-    if (n_rows) *n_rows = h[0];
-    if (n_events) *n_events = h[1];
-    if (!h[2]) return fail(c, MMW_E_CAPACITY, "mmw_tripwires: %d rows and %d events do not fit the buffers: nothing was written, nothing was taken", h[0], h[1]);
-    return MMW_OK;
+    return c ? pair_export_wait(c, c->trip, kExport, ticket, n_rows, n_events) : MMW_E_ARG;
 }
 
 int mmw_tripwires(mmw_ctx *c, mmw_tripwire_row *rows, int32_t cap_rows, mmw_tripwire_event *events, int32_t cap_events, int32_t scene_base, int32_t *n_rows,

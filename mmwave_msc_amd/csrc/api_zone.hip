@@ -83,29 +83,19 @@ int mmw_has_zones(mmw_ctx *c)
     return c->zone.d_block ? 1 : 0;
 }
 
+static const PairExport kExport = {"mmw_zones", "no zone is defined (mmw_set_zones)", "no zone export", "rows", kUnfitBaseline, 4};
+
 int mmw_zones_async(mmw_ctx *c, mmw_zone_row *rows, int32_t cap_rows, mmw_zone_event *events, int32_t cap_events, int32_t scene_base, int32_t ticket)
 {
     if (!c) return MMW_E_ARG;
-    if (!c->zone.d_block) return fail(c, MMW_E_ARG, "mmw_zones: no zone is defined (mmw_set_zones)");
-    if (cap_rows < 0 || cap_events < 0 || (cap_rows > 0 && !rows) || (cap_events > 0 && !events))
-        return fail(c, MMW_E_ARG, "mmw_zones: cap_rows = %d, cap_events = %d with rows %s, events %s", cap_rows, cap_events, rows ? "set" : "NULL", events ? "set" : "NULL");
-    if (((uintptr_t)rows & 3) != 0 || ((uintptr_t)events & 3) != 0) return fail(c, MMW_E_ARG, "mmw_zones: the buffers must be 4-byte aligned");
-    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_zones: ticket %d outside [0, %d)", ticket, kTickets);
-    HIPCHK(c, hipSetDevice(c->device));
+    MMW_TRY(pair_export_begin(c, c->zone, kExport, rows, cap_rows, events, cap_events, ticket));
     launch_zones(c->dc, c->st, c->zs, rows, cap_rows, events, cap_events, scene_base, c->stream);
     return export_issue(c, c->zone, ticket);
 }
 
 int mmw_zones_wait(mmw_ctx *c, int32_t ticket, int32_t *n_rows, int32_t *n_events)
 {
-    if (!c) return MMW_E_ARG;
-    if (!c->zone.d_block) return fail(c, MMW_E_ARG, "mmw_zones_wait: no zone is defined (mmw_set_zones)");
-    const int32_t *h;
-    MMW_TRY(export_wait(c, c->zone, ticket, "mmw_zones_wait", "no zone export", &h));
-    if (n_rows) *n_rows = h[0];
-    if (n_events) *n_events = h[1];
-    if (!h[2]) return fail(c, MMW_E_CAPACITY, "mmw_zones: %d rows and %d events do not fit the buffers: nothing was written, the baseline is unchanged", h[0], h[1]);
-    return MMW_OK;
+    return c ? pair_export_wait(c, c->zone, kExport, ticket, n_rows, n_events) : MMW_E_ARG;
 }
 
 int mmw_zones(mmw_ctx *c, mmw_zone_row *rows, int32_t cap_rows, mmw_zone_event *events, int32_t cap_events, int32_t scene_base, int32_t *n_rows,

@@ -14,6 +14,7 @@
 #include <cstddef>
 #include "mmw_device.hpp"
 #include "mmw_uidlist.hpp"
+#include "mmw_evlog.hpp"
 #include "mmw_wave.hpp"
 #include "mmw_kernels.hpp"
 
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(256) void k_stance_sample(DevCfg cfg, DevState st, 
     const size_t base = (size_t)s * cap;
     const bool rebased = ss.ug.rebased(s);
     const double tt = t ? t[s] : (double)ord;
-    const int log0 = ss.logged[s];
+    const int log0 = ss.log.logged[s];
     // the rule: the same address in every lane, so ten scalar loads
     const StanceRule *q = ss.rules + s;
     const double h_stand = q->h_stand, h_lie = q->h_lie, up_hi = q->up_hi, up_lo = q->up_lo, lie_hi = q->lie_hi, lie_lo = q->lie_lo;
@@ -110,21 +111,18 @@ __global__ __launch_bounds__(256) void k_stance_sample(DevCfg cfg, DevState st, 
     if (longlie) new_w |= kStanceLongLie;
 
     // the events: REBASED, then tracks in live order, CHANGE or FALL before LONG_LIE -- each lane's from the wave-exclusive prefix of
-    // its count on.  Event n lies at n % depth; of more than `depth` in one call only the newest are written: one writer per entry.
+    // its count on, by the log's append rule (mmw_evlog.hpp)
     int n_ev;
     const int at = wave_excl_sum((changed ? 1 : 0) + (longlie ? 1 : 0), lane, n_ev);
-    const int head_ev = rebased ? 1 : 0, total = head_ev + n_ev;
-    const int keep_from = log0 + max(total - ss.depth, 0);
-    const unsigned depth = (unsigned)ss.depth;
-    mmw_stance_event *ring = ss.ring + (size_t)s * depth;
-    if (rebased && lane == 0 && log0 >= keep_from) ring[(unsigned)log0 % depth] = mmw_stance_event{s, -1, MMW_SEV_REBASED, 0, 0, T, tt};
+    const auto ap = evlog_append(ss.log, s, log0, rebased ? 1 : 0, n_ev);
+    if (rebased && lane == 0 && ap.keeps(log0)) ap.at(log0) = mmw_stance_event{s, -1, MMW_SEV_REBASED, 0, 0, T, tt};
     {
-        int n = log0 + head_ev + at;
+        int n = ap.first(at);
         if (changed) {
-            if (n >= keep_from) ring[(unsigned)n % depth] = mmw_stance_event{s, cuid, fall ? MMW_SEV_FALL : MMW_SEV_CHANGE, old, now, lane, tt};
+            if (ap.keeps(n)) ap.at(n) = mmw_stance_event{s, cuid, fall ? MMW_SEV_FALL : MMW_SEV_CHANGE, old, now, lane, tt};
             n++;
         }
-        if (longlie && n >= keep_from) ring[(unsigned)n % depth] = mmw_stance_event{s, cuid, MMW_SEV_LONG_LIE, MMW_STANCE_LYING, MMW_STANCE_LYING, lane, tt};
+        if (longlie && ap.keeps(n)) ap.at(n) = mmw_stance_event{s, cuid, MMW_SEV_LONG_LIE, MMW_STANCE_LYING, MMW_STANCE_LYING, lane, tt};
     }
     // the counters: lane 0 takes the ballots' popcounts
     const int n_fall = __popcll(__ballot(fall)), n_long = __popcll(__ballot(longlie));
@@ -141,39 +139,23 @@ __global__ __launch_bounds__(256) void k_stance_sample(DevCfg cfg, DevState st, 
         ss.t_upright[base + slot] = t_upright;
     }
     uid_slots_done(ss.ug, s, lane, base + lane, release, ord);
-    if (lane == 0 && total) ss.logged[s] = log0 + total;
-}
-
-// What the export hands out of a scene's log: events first .. first + n - 1, and how many were overwritten before it came.
-struct StanceLog { int first, n, lost, logged; };
-__device__ __forceinline__ StanceLog stance_log(const StanceState &ss, int s)
-{
-    StanceLog g;
-    g.logged = ss.logged[s];
-    const int taken = ss.taken[s];
-    g.first = max(taken, g.logged - ss.depth);
-    g.n = g.logged - g.first;
-    g.lost = max(0, g.logged - ss.depth - taken);
-    return g;
+    evlog_commit(ss.log, s, lane, ap);
 }
 
 __global__ __launch_bounds__(256) void k_stance_count(DevCfg cfg, StanceState ss)
 {
     const auto [s, lane] = wave_scene();
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
-    if (lane == 0) {
-        ss.sc.off[s] = scene_rules(ss, s);
-        ss.sc.off[cfg.n_scenes + 1 + s] = stance_log(ss, s).n;
-    }
+    evlog_count(ss.log, ss.sc.off, cfg.n_scenes, s, lane, scene_rules(ss, s));
 }
 
 __global__ __launch_bounds__(256) void k_stance_write(DevCfg cfg, StanceState ss, mmw_stance_row *__restrict__ rows, mmw_stance_event *__restrict__ events, int scene_base)
 {
-    if (!ss.sc.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer, taken nor a mark is written
+    if (!evlog_fits(ss.sc.totals)) return;   // (uniform over the launch) something does not fit: neither buffer, taken nor a mark is written
     const auto [s, lane] = wave_scene();
     const int S = cfg.n_scenes;
     if (s >= S) return;             // (wave-uniform)
-    const StanceLog g = stance_log(ss, s);
+    const LogWindow g = evlog_window(ss.log, s);
     const int row0 = ss.sc.off[s], ev0 = ss.sc.off[S + 1 + s];
     if (scene_rules(ss, s)) {       // (wave-uniform) lane j: slot j's owner and class; the row from four ballots
         const int cap = cfg.t_cap;
@@ -191,15 +173,7 @@ __global__ __launch_bounds__(256) void k_stance_write(DevCfg cfg, StanceState ss
             kp->mark_long_lies = k.long_lies;
         }
     }
-    // the lanes stride over the ring, oldest first
-    const unsigned depth = (unsigned)ss.depth;
-    const mmw_stance_event *ring = ss.ring + (size_t)s * depth;
-    for (int k = lane; k < g.n; k += 64) {
-        mmw_stance_event e = ring[(unsigned)(g.first + k) % depth];
-        e.scene += scene_base;
-        events[ev0 + k] = e;
-    }
-    if (lane == 0) ss.taken[s] = g.logged;
+    evlog_drain(ss.log, s, lane, g, events, ev0, scene_base);
 }
 
 void launch_stance_zero(int n_scenes, const int32_t *flags, const StanceState &ss, hipStream_t st)

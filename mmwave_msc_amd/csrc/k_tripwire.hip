@@ -14,6 +14,7 @@
 #include <cstddef>
 #include "mmw_device.hpp"
 #include "mmw_uidlist.hpp"
+#include "mmw_evlog.hpp"
 #include "mmw_wave.hpp"
 #include "mmw_kernels.hpp"
 
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(256) void k_tripwire_sample(DevCfg cfg, DevState st
     const size_t base = (size_t)s * cap;
     const bool rebased = ts.ug.rebased(s);
     const double tt = t ? t[s] : (double)ord;
-    const int log0 = ts.logged[s];
+    const int log0 = ts.log.logged[s];
 
     // this lane's track ...
     int cuid = -1;
@@ -102,21 +103,18 @@ __global__ __launch_bounds__(256) void k_tripwire_sample(DevCfg cfg, DevState st
     if (lane >= T) new_w = fwd = bwd = 0u;
 
     // the events: REBASED, then tracks in live order, wires ascending inside a track -- each lane's from the wave-exclusive prefix of
-    // the popcounts on.  Event n lies at n % depth; of more than `depth` in one call only the newest are written: one writer per entry.
+    // the popcounts on, by the log's append rule (mmw_evlog.hpp)
     int n_ev;
     const int at = wave_excl_sum(__popc(fwd | bwd), lane, n_ev);
-    const int head = rebased ? 1 : 0, total = head + n_ev;
-    const int keep_from = log0 + max(total - ts.depth, 0);
-    const unsigned depth = (unsigned)ts.depth;
-    mmw_tripwire_event *ring = ts.ring + (size_t)s * depth;
-    if (rebased && lane == 0 && log0 >= keep_from) ring[(unsigned)log0 % depth] = mmw_tripwire_event{s, -1, MMW_TW_REBASED, -1, -1, T, tt};
+    const auto ap = evlog_append(ts.log, s, log0, rebased ? 1 : 0, n_ev);
+    if (rebased && lane == 0 && ap.keeps(log0)) ap.at(log0) = mmw_tripwire_event{s, -1, MMW_TW_REBASED, -1, -1, T, tt};
     {
         unsigned mask = fwd | bwd;
-        int n = log0 + head + at;
+        int n = ap.first(at);
         while (mask) {   // (divergent: as many stores as the lane's track has crossings)
             const int z = __ffs((int)mask) - 1;
             mask &= mask - 1u;
-            if (n >= keep_from) ring[(unsigned)n % depth] = mmw_tripwire_event{s, cuid, ((fwd >> z) & 1u) ? MMW_TW_FORWARD : MMW_TW_BACKWARD, z, wt[z].id, lane, tt};
+            if (ap.keeps(n)) ap.at(n) = mmw_tripwire_event{s, cuid, ((fwd >> z) & 1u) ? MMW_TW_FORWARD : MMW_TW_BACKWARD, z, wt[z].id, lane, tt};
             n++;
         }
     }
@@ -139,41 +137,25 @@ __global__ __launch_bounds__(256) void k_tripwire_sample(DevCfg cfg, DevState st
         ts.side[base + slot] = (int32_t)new_w;
     }
     uid_slots_done(ts.ug, s, lane, base + lane, release, ord);
-    if (lane == 0 && total) ts.logged[s] = log0 + total;
-}
-
-// What the export hands out of a scene's log: events first .. first + n - 1, and how many were overwritten before it came.
-struct TripLog { int first, n, lost, logged; };
-__device__ __forceinline__ TripLog trip_log(const TripState &ts, int s)
-{
-    TripLog g;
-    g.logged = ts.logged[s];
-    const int taken = ts.taken[s];
-    g.first = max(taken, g.logged - ts.depth);
-    g.n = g.logged - g.first;
-    g.lost = max(0, g.logged - ts.depth - taken);
-    return g;
+    evlog_commit(ts.log, s, lane, ap);
 }
 
 __global__ __launch_bounds__(256) void k_tripwire_count(DevCfg cfg, TripState ts)
 {
     const auto [s, lane] = wave_scene();
     if (s >= cfg.n_scenes) return;   // (wave-uniform)
-    if (lane == 0) {
-        ts.sc.off[s] = scene_wires(ts, s);
-        ts.sc.off[cfg.n_scenes + 1 + s] = trip_log(ts, s).n;
-    }
+    evlog_count(ts.log, ts.sc.off, cfg.n_scenes, s, lane, scene_wires(ts, s));
 }
 
 __global__ __launch_bounds__(256) void k_tripwire_write(DevCfg cfg, TripState ts, mmw_tripwire_row *__restrict__ rows, mmw_tripwire_event *__restrict__ events,
                                                         int scene_base)
 {
-    if (!ts.sc.totals[2]) return;   // (uniform over the launch) something does not fit: neither buffer, taken nor a mark is written
+    if (!evlog_fits(ts.sc.totals)) return;   // (uniform over the launch) something does not fit: neither buffer, taken nor a mark is written
     const auto [s, lane] = wave_scene();
     const int S = cfg.n_scenes;
     if (s >= S) return;             // (wave-uniform)
     const int nw = scene_wires(ts, s);
-    const TripLog g = trip_log(ts, s);
+    const LogWindow g = evlog_window(ts.log, s);
     const int row0 = ts.sc.off[s], ev0 = ts.sc.off[S + 1 + s];
     if (lane < nw) {   // lane z: wire z's row, and its totals become the marks
         TripCount *kp = ts.count + (size_t)s * MMW_TRIPWIRES_MAX + lane;
@@ -183,15 +165,7 @@ __global__ __launch_bounds__(256) void k_tripwire_write(DevCfg cfg, TripState ts
         kp->mark_forward = k.forward;
         kp->mark_backward = k.backward;
     }
-    // the lanes stride over the ring, oldest first
-    const unsigned depth = (unsigned)ts.depth;
-    const mmw_tripwire_event *ring = ts.ring + (size_t)s * depth;
-    for (int k = lane; k < g.n; k += 64) {
-        mmw_tripwire_event e = ring[(unsigned)(g.first + k) % depth];
-        e.scene += scene_base;
-        events[ev0 + k] = e;
-    }
-    if (lane == 0) ts.taken[s] = g.logged;
+    evlog_drain(ts.log, s, lane, g, events, ev0, scene_base);
 }
 
 void launch_tripwire_zero(int n_scenes, const int32_t *flags, const TripState &ts, hipStream_t st)

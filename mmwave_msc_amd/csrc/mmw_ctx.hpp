@@ -181,6 +181,14 @@ int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name)
 void export_free(ExportCtx &x);                                    // ... and x is as never allocated
 int export_issue(mmw_ctx *c, ExportCtx &x, int ticket);           // behind the launch: its error, the totals into the ticket's pinned slot, the event
 int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const char *none, const int32_t **counts);   // -> the ticket's four words
+// ... and the front end of the exports with two caller buffers, rows and events (mmw_report_*, mmw_zones_*, mmw_tripwires_*, mmw_stance_*).
+// The messages are built from the entry's words: "<entry>: <off>" while x is not allocated, "<entry>_wait: <none> outstanding under
+// ticket k", and for MMW_E_CAPACITY "<entry>: n <rows> and m events <unfit>".  align: what both buffers must be aligned to, 0 = anything.
+struct PairExport { const char *entry, *off, *none, *rows, *unfit; int align; };
+constexpr const char *kUnfitLog = "do not fit the buffers: nothing was written, nothing was taken";               // a log is drained: tripwires, stance
+constexpr const char *kUnfitBaseline = "do not fit the buffers: nothing was written, the baseline is unchanged";   // two states are compared: report, zones
+int pair_export_begin(mmw_ctx *c, const ExportCtx &x, const PairExport &d, const void *rows, int cap_rows, const void *events, int cap_events, int ticket);   // before the launch: enabled, capacities, pointers, alignment, ticket; device set
+int pair_export_wait(mmw_ctx *c, ExportCtx &x, const PairExport &d, int ticket, int32_t *n_rows, int32_t *n_events);   // export_wait, the two counts out (either may be NULL), MMW_E_CAPACITY if the device decided so
 int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t);   // mmw_trails_sample / mmw_tripwires_sample / mmw_stance_sample: enabled, aligned, device set
 int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones, trails, tripwires and stance, none while all five are off
 #pragma GCC visibility pop
@@ -228,6 +236,20 @@ static inline void prof_end(mmw_ctx *c, EventPair &ep)
     hipEventRecord(ep.b, c->stream);
     c->pending.push_back(ep);
     if (c->pending.size() >= 2048) prof_fold(c);
+}
+
+// mmw_tripwires_enable / mmw_stance_enable: what the state blocks of the log consumers have in common -- the ring at the block's head,
+// and behind the consumer's own int32 words, at p, the five [S] words logged | taken | gen | seen | ordinal
+template <class E>
+static inline void evlog_carve(EventLog<E> &log, UidSlots &ug, int32_t depth, char *block, int32_t *p, size_t S)
+{
+    log.depth = depth;
+    log.ring = reinterpret_cast<E *>(block);
+    log.logged = p;
+    log.taken = p + S;
+    ug.gen = p + 2 * S;
+    ug.seen = p + 3 * S;
+    ug.ordinal = p + 4 * S;
 }
 
 // the context's site table while one is in use (the k_*_site kernels), else nullptr

@@ -7,6 +7,7 @@
 
 #include "../../include/mmw.h"
 #include "mmw_uidlist.hpp"
+#include "mmw_evlog.hpp"
 
 namespace mmw {
 
@@ -223,19 +224,19 @@ struct TrailState {
 };
 // mmw_tripwires_enable: the wire table and what the tripwires keep from one mmw_tripwires_sample to the next (k_tripwire.hip).  All
 // device memory.  A table entry is what the HOST derived of an mmw_tripwire (mmw_set_tripwires): the device takes no sqrt.  A uid's
-// side word lies in the slot that the one slot table (UidSlots, mmw_uidlist.hpp) gives it.
+// side word lies in the slot that the one slot table (UidSlots, mmw_uidlist.hpp) gives it.  (The member order -- the log in front,
+// `side` behind `count`, the scratch in front of the slot table -- is the one that leaves the kernels' registers and the sampler's
+// kernarg loads as they were, profiles/evlog_isa.txt and DESIGN.md 8m; likewise StanceState's.)
 struct TripWire { double ax, ay, dx, dy, len2, band; int32_t id, pad_; };   // 56 bytes
 struct TripCount { int32_t forward, backward, mark_forward, mark_backward; };   // totals since the wires were set; ... at the previous successful export
 struct TripState {
-    int32_t depth;             // log entries per scene, 1 .. MMW_TRIPWIRE_LOG_MAX
+    EventLog<mmw_tripwire_event> log;   // the crossings (mmw_evlog.hpp), depth 1 .. MMW_TRIPWIRE_LOG_MAX
     const TripWire *wires;     // [S][MMW_TRIPWIRES_MAX] the table (one copy of mmw_set_tripwires; read with scalar loads)
     const int32_t *n_wires;    // [S] wires defined per scene, behind the table in the same allocation
-    int32_t *side;             // [S][t_cap] the slot's uid's sides, two bits per wire: 0 unknown, 1 negative, 2 positive
     TripCount *count;          // [S][MMW_TRIPWIRES_MAX] lane z of a scene's wave owns wire z's
-    mmw_tripwire_event *ring;  // [S][depth] event n (0-based) of a scene lies at n % depth, with the LOCAL scene index
-    int32_t *logged, *taken;   // [S] events ever appended / handed out
-    UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
+    int32_t *side;             // [S][t_cap] the slot's uid's sides, two bits per wire: 0 unknown, 1 negative, 2 positive
     ExportScratch sc;          // rows / events of the export in flight
+    UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
 };
 // mmw_stance_enable: the rule table and what the stance watch keeps from one mmw_stance_sample to the next (k_stance.hip).  All
 // device memory.  A table entry is what the HOST derived of an mmw_stance_rule (mmw_set_stance_rules): the device does no arithmetic
@@ -244,15 +245,13 @@ struct StanceRule { double h_stand, h_lie, up_hi, up_lo, lie_hi, lie_lo, gap2, f
 struct StanceCount { int32_t falls, long_lies, mark_falls, mark_long_lies; };   // totals since the rule was set; ... at the previous successful export
 constexpr int kStanceClassMask = 3, kStanceLongLie = 4;   // a slot's word: bits 0-1 the class, bit 2 "LONG_LIE given in this episode"
 struct StanceState {
-    int32_t depth;             // log entries per scene, 1 .. MMW_STANCE_LOG_MAX
+    EventLog<mmw_stance_event> log;   // the changes, falls and long lies (mmw_evlog.hpp), depth 1 .. MMW_STANCE_LOG_MAX
+    int32_t *word;             // [S][t_cap] the slot's uid's class and episode bit
     const StanceRule *rules;   // [S][MMW_STANCE_RULES_MAX] the table (one copy of mmw_set_stance_rules; read with scalar loads)
     const int32_t *n_rules;    // [S] 0 or 1, behind the table in the same allocation
-    int32_t *word;             // [S][t_cap] the slot's uid's class and episode bit
     double *t_since;           // [S][t_cap] t of the sample that entered the current class
     double *t_upright;         // [S][t_cap] t of the newest sample that classed the uid UPRIGHT, -inf if never
     StanceCount *count;        // [S] lane 0 of a scene's wave owns it
-    mmw_stance_event *ring;    // [S][depth] event n (0-based) of a scene lies at n % depth, with the LOCAL scene index
-    int32_t *logged, *taken;   // [S] events ever appended / handed out
     UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
     ExportScratch sc;          // rows / events of the export in flight
 };

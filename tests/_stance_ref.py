@@ -14,6 +14,7 @@ import collections
 import numpy as np
 
 from mmwave_msc_amd import _lib
+from tests._evlog_ref import EventLogRef
 
 UNKNOWN, UPRIGHT, LOW, LYING = 0, 1, 2, 3
 NKP, HEAD = 57, 22
@@ -37,7 +38,6 @@ def gap_s(kp):
 
 class StanceRef:
     def __init__(self, n_scenes, t_cap, depth):
-        assert 1 <= depth <= _lib.STANCE_LOG_MAX
         self.S, self.t_cap, self.depth = n_scenes, t_cap, depth
         self.rules = [None] * n_scenes
         self.owner = np.full((n_scenes, t_cap), -1, np.int64)
@@ -49,9 +49,8 @@ class StanceRef:
         self.long_lies = np.zeros(n_scenes, np.int64)
         self.mark_f = np.zeros(n_scenes, np.int64)
         self.mark_l = np.zeros(n_scenes, np.int64)
-        self.log = [[] for _ in range(n_scenes)]                # the newest `depth` events, oldest first
-        self.logged = np.zeros(n_scenes, np.int64)
-        self.taken = np.zeros(n_scenes, np.int64)
+        self.evlog = EventLogRef(n_scenes, depth, _lib.STANCE_LOG_MAX)
+        self.logged = self.evlog.logged                         # (the same array: the tests read it)
         self.bumped = np.zeros(n_scenes, bool)
         self.ordinal = np.zeros(n_scenes, np.int64)
         self.tally = collections.Counter()
@@ -65,12 +64,6 @@ class StanceRef:
 
     def rebase(self, scenes=None):
         self.bumped[slice(None) if scenes is None else list(scenes)] = True
-
-    def _append(self, s, ev):
-        self.log[s].append(ev)
-        if len(self.log[s]) > self.depth:
-            self.log[s].pop(0)
-        self.logged[s] += 1
 
     def cls(self, s, uid):
         """The class of a live uid as of the last sample."""
@@ -95,7 +88,7 @@ class StanceRef:
                 owner[:] = -1
                 self.lay_expired[s] = False
                 self.bumped[s] = False
-                self._append(s, (s, -1, _lib.SEV_REBASED, 0, 0, T, tt))
+                self.evlog.append(s, (s, -1, _lib.SEV_REBASED, 0, 0, T, tt))
             live = [int(tracks[s, j]["uid"]) for j in range(T)]
             for j in range(self.t_cap):                                          # 2.
                 if owner[j] != -1 and int(owner[j]) not in live:
@@ -135,7 +128,7 @@ class StanceRef:
                     self.tally["kept_above_lying_by_margin"] += 1
                 if new != old:
                     fall = new == LYING and old != UNKNOWN and tt - self.t_upright[s, j] <= q["fall_window"]
-                    self._append(s, (s, uid, _lib.SEV_FALL if fall else _lib.SEV_CHANGE, old, new, i, tt))
+                    self.evlog.append(s, (s, uid, _lib.SEV_FALL if fall else _lib.SEV_CHANGE, old, new, i, tt))
                     self.t_since[s, j] = tt
                     bit = 0
                     if fall:
@@ -149,7 +142,7 @@ class StanceRef:
                 if new == UPRIGHT:
                     self.t_upright[s, j] = tt
                 if new == LYING and not bit and tt - self.t_since[s, j] >= q["long_lie"]:
-                    self._append(s, (s, uid, _lib.SEV_LONG_LIE, LYING, LYING, i, tt))
+                    self.evlog.append(s, (s, uid, _lib.SEV_LONG_LIE, LYING, LYING, i, tt))
                     bit = 4
                     self.long_lies[s] += 1
                     self.tally["long_lie"] += 1
@@ -162,22 +155,19 @@ class StanceRef:
         rows, events = [], []
         for s in range(self.S):
             q = self.rules[s]
+            ev, lost = self.evlog.window(s, scene_base)
             if q is not None:
-                lost = max(0, int(self.logged[s]) - self.depth - int(self.taken[s]))
                 owned = (self.owner[s] != -1) & (not self.bumped[s])
                 n = [int((owned & ((self.word[s] & 3) == c)).sum()) for c in (UPRIGHT, LOW, LYING, UNKNOWN)]
                 f, l = int(self.falls[s]), int(self.long_lies[s])
                 rows.append((scene_base + s, q["id"], n[0], n[1], n[2], n[3], f, f - int(self.mark_f[s]), l, l - int(self.mark_l[s]), lost, 0))
-            first = max(int(self.taken[s]), int(self.logged[s]) - self.depth)
-            n = int(self.logged[s]) - first
-            for e in self.log[s][len(self.log[s]) - n:] if n else []:
-                events.append((scene_base + e[0],) + e[1:])
+            events += ev
         return np.array(rows, _lib.STANCE_ROW_DTYPE).reshape(-1), np.array(events, _lib.STANCE_EVENT_DTYPE).reshape(-1)
 
     def export(self, scene_base=0):
         """... and a successful one: taken = logged, the marks become the totals."""
         out = self.peek(scene_base)
-        self.taken[:] = self.logged
+        self.evlog.commit()
         self.mark_f[:], self.mark_l[:] = self.falls, self.long_lies
         return out
 

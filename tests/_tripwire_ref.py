@@ -7,6 +7,7 @@ import math
 import numpy as np
 
 from mmwave_msc_amd import _lib
+from tests._evlog_ref import EventLogRef
 
 UNKNOWN, NEGATIVE, POSITIVE = 0, 1, 2
 
@@ -26,7 +27,6 @@ class TripRef:
     kept (inside, a known old side, c within [-band, band]), and passages through `unknown` that ended on the other side."""
 
     def __init__(self, n_scenes, t_cap, depth):
-        assert 1 <= depth <= _lib.TRIPWIRE_LOG_MAX
         self.S, self.t_cap, self.depth = n_scenes, t_cap, depth
         self.wires = [[] for _ in range(n_scenes)]
         self.sides = [dict() for _ in range(n_scenes)]          # uid -> [side] * 16
@@ -34,9 +34,8 @@ class TripRef:
         self.backward = np.zeros((n_scenes, 16), np.int64)
         self.mark_f = np.zeros((n_scenes, 16), np.int64)
         self.mark_b = np.zeros((n_scenes, 16), np.int64)
-        self.log = [[] for _ in range(n_scenes)]                # the newest `depth` events, oldest first
-        self.logged = np.zeros(n_scenes, np.int64)
-        self.taken = np.zeros(n_scenes, np.int64)
+        self.evlog = EventLogRef(n_scenes, depth, _lib.TRIPWIRE_LOG_MAX)
+        self.logged = self.evlog.logged                         # (the same array: the tests read it)
         self.bumped = np.zeros(n_scenes, bool)
         self.ordinal = np.zeros(n_scenes, np.int64)
         self.n_forward = self.n_backward = self.n_kept = 0
@@ -50,12 +49,6 @@ class TripRef:
 
     def rebase(self, scenes=None):
         self.bumped[slice(None) if scenes is None else list(scenes)] = True
-
-    def _append(self, s, ev):
-        self.log[s].append(ev)
-        if len(self.log[s]) > self.depth:
-            self.log[s].pop(0)
-        self.logged[s] += 1
 
     def sample(self, tracks, ntr, flags=None, t=None):
         for s in range(self.S):
@@ -71,7 +64,7 @@ class TripRef:
             if self.bumped[s]:                                                   # 1.
                 self.sides[s] = {}
                 self.bumped[s] = False
-                self._append(s, (s, -1, _lib.TW_REBASED, -1, -1, T, tt))
+                self.evlog.append(s, (s, -1, _lib.TW_REBASED, -1, -1, T, tt))
             live = [int(tracks[s, j]["uid"]) for j in range(T)]
             for uid in [u for u in self.sides[s] if u not in live]:              # 2.
                 del self.sides[s][uid]
@@ -100,11 +93,11 @@ class TripRef:
                     if old == NEGATIVE and new == POSITIVE:
                         self.forward[s, z] += 1
                         self.n_forward += 1
-                        self._append(s, (s, int(rec["uid"]), _lib.TW_FORWARD, z, wid, j, tt))
+                        self.evlog.append(s, (s, int(rec["uid"]), _lib.TW_FORWARD, z, wid, j, tt))
                     elif old == POSITIVE and new == NEGATIVE:
                         self.backward[s, z] += 1
                         self.n_backward += 1
-                        self._append(s, (s, int(rec["uid"]), _lib.TW_BACKWARD, z, wid, j, tt))
+                        self.evlog.append(s, (s, int(rec["uid"]), _lib.TW_BACKWARD, z, wid, j, tt))
                     side[z] = new
                 for z in range(len(self.wires[s]), 16):
                     side[z] = UNKNOWN
@@ -113,19 +106,16 @@ class TripRef:
         """(rows TRIPWIRE_ROW_DTYPE, events TRIPWIRE_EVENT_DTYPE) of an export of this state; it changes nothing."""
         rows, events = [], []
         for s in range(self.S):
-            lost = max(0, int(self.logged[s]) - self.depth - int(self.taken[s]))
+            ev, lost = self.evlog.window(s, scene_base)
             for z, w in enumerate(self.wires[s]):
                 f, b = int(self.forward[s, z]), int(self.backward[s, z])
                 rows.append((scene_base + s, z, w[6], f, b, f - int(self.mark_f[s, z]), b - int(self.mark_b[s, z]), lost))
-            first = max(int(self.taken[s]), int(self.logged[s]) - self.depth)
-            n = int(self.logged[s]) - first
-            for e in self.log[s][len(self.log[s]) - n:] if n else []:
-                events.append((scene_base + e[0],) + e[1:])
+            events += ev
         return np.array(rows, _lib.TRIPWIRE_ROW_DTYPE).reshape(-1), np.array(events, _lib.TRIPWIRE_EVENT_DTYPE).reshape(-1)
 
     def export(self, scene_base=0):
         """... and a successful one: taken = logged, the marks become the totals."""
         out = self.peek(scene_base)
-        self.taken[:] = self.logged
+        self.evlog.commit()
         self.mark_f[:], self.mark_b[:] = self.forward, self.backward
         return out

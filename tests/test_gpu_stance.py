@@ -566,3 +566,94 @@ def test_trails_tripwires_and_stance_keep_separate_slot_tables_and_generations()
     assert len(d) == int(ntr.sum())
     sb.check()
     sb.close()
+
+
+def test_tripwire_log_of_depth_3_and_stance_log_of_depth_5_in_one_context():
+    """Both event logs in one context of three scenes, at depths that are odd, differ and are no power of two, so a swapped depth or
+    ring shows: tripwires at 3, stance at 5; scene 1 has neither wires nor a rule.  Track 0 of scenes 0 and 2 is planted half a metre
+    in front of five parallel wires one metre apart with a velocity of one metre per second, so an empty frame whose predict multiplier
+    is five crosses five wires in ONE sample call (more than the log holds) and multipliers of two cross two; every live track's head is planted LYING and UPRIGHT
+    in turn under a rule with long_lie 0, so a call logs CHANGE and LONG_LIE of three tracks (six events, more than the log holds)
+    or three CHANGEs.  The two consumers export at different frames, with more than two turns of their ring in between, and one stance
+    export is first asked with one event too few.  Rows, events and `lost` are the reference model's, byte for byte."""
+    from mmwave_msc_amd import _lib
+    from tests._tripwire_ref import TripRef
+    from tests.test_gpu_tripwires import FAR, _plant
+    S3 = 3
+    kw = {k: v for k, v in CFG_KW.items() if k != "tr_max_tracks"}     # (the default track cap)
+    sb = make_checked(S3, N, "per_scene", **dict(kw, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0, kf_q_std=0.0))
+    data = _cut(S3)
+    for f in range(9):                                       # (the C oracle: three tracks in each of the three scenes from frame 8 on)
+        sb.step_host(data[0][f].astype(np.float64), data[1][f], data[2][f])
+    assert sb.num_tracks().tolist() == [3, 3, 3]
+    blob = bytearray(sb.snapshot())
+    hdr = _lib.MmwSnapshotHeader.from_buffer_copy(bytes(blob[: C.sizeof(_lib.MmwSnapshotHeader)]))
+    for sc in (0, 2):
+        ent = _lib.MmwSnapshotEntry.from_buffer_copy(bytes(blob[hdr.header_bytes + sc * hdr.entry_bytes: hdr.header_bytes + (sc + 1) * hdr.entry_bytes]))
+        _plant(blob, ent.offset, [FAR - 0.5, 0.0, 1.0, 1.0, 0.0, 0.0])
+    sb.restore(bytes(blob))
+    run = _Run(sb, 5, data)                                  # stance, log depth 5
+    sb.enable_tripwires(3)
+    trip = TripRef(S3, sb.track_cap, 3)
+    nw, wt = _lib.make_tripwires([[(FAR + k, -4.0, FAR + k, 4.0, 0.0, 60 + k) for k in range(5)]] * 2)
+    sb.set_tripwires((nw, wt), scenes=[0, 2])
+    trip.set_wires([0, 2], nw, wt)
+    run.set_rules(_rules(2, long_lie=0.0), scenes=[0, 2])
+
+    def frame(k, at, head):
+        """Move the planted tracks to FAR - 0.5 + at, plant every head, sample both consumers at t = k."""
+        if k:                                                # (an empty frame moves a track by velocity x the running sum of dt: that sum becomes the move)
+            mult = float(at - frame.at)
+            sb.step_host(np.zeros((S3, N, 8)), np.full(S3, _lib.EMPTY_FRAME, np.int32), np.full(S3, mult - frame.mult), check=False)
+            frame.mult = mult
+        frame.at = at
+        assert [float(sb.tracks()["x"][sc, 0, 0]) for sc in (0, 2)] == [FAR - 0.5 + at] * 2
+        run.plant_heads([head] * S3)
+        run.sample(t=float(k))
+        sb.sample_tripwires(t=float(k))
+        trip.sample(sb.tracks(), sb.num_tracks(), t=np.full(S3, float(k)))
+
+    def compare_trip(ctx):
+        got = sb.tripwires_host(scene_base=BASE)
+        _same(got, trip.export(BASE), ctx)
+        return got
+
+    frame.mult = 0.0
+    frame(0, 0, L)                                           # stance: REBASED, 3 CHANGE, 3 LONG_LIE in one call -- 7 > 5; tripwires: REBASED
+    assert run.ref.logged.tolist() == [7, 0, 7] and trip.logged.tolist() == [1, 0, 1]
+    rows, events = run.compare("stance at 0")
+    assert rows["lost"].tolist() == [2, 2] and len(events) == 10 and _n_kind(events, _lib.SEV_REBASED) == 0
+    frame(1, 5, U)                                           # tripwires: five wires in one call -- 5 > 3
+    assert trip.logged.tolist() == [6, 0, 6]
+    rows, events = compare_trip("tripwires at 1")
+    assert rows["lost"].tolist() == [3] * 10 and rows["backward"].tolist() == [1] * 10
+    assert [(int(e["scene"]) - BASE, int(e["wire"])) for e in events] == [(0, 2), (0, 3), (0, 4), (2, 2), (2, 3), (2, 4)]
+    frame(2, 3, L)
+    frame(3, 5, U)                                           # stance since its export: 3 + 6 + 3 events, the ring of 5 turned twice
+    assert run.ref.logged.tolist() == [19, 0, 19]
+    # one event too few: MMW_E_CAPACITY with both counts, nothing is written, nothing is taken
+    b_r, b_e = sb.alloc(2 * 48), sb.alloc(10 * 32)
+    sent = np.full(10 * 32, 0x5A, np.uint8)
+    b_e.upload(sent)
+    sb.stance_async(b_r.ptr, 2, b_e.ptr, 9, BASE, 1)
+    with pytest.raises(_lib.MmwError) as ei:
+        sb.stance_wait(1)
+    assert ei.value.code == _lib.E_CAPACITY and ei.value.needed == (2, 10)
+    assert b_e.download((10 * 32,), np.uint8).tobytes() == sent.tobytes()
+    for b in (b_r, b_e):
+        b.free()
+    rows, events = run.compare("stance at 3")
+    assert rows["lost"].tolist() == [7, 7] and len(events) == 10
+    frame(4, 3, L)
+    frame(5, 5, U)                                           # tripwires since their export: 4 x 2 events, the ring of 3 turned twice
+    assert trip.logged.tolist() == [14, 0, 14]
+    rows, events = compare_trip("tripwires at 5")
+    assert rows["lost"].tolist() == [5] * 10 and len(events) == 6
+    assert rows["forward"].tolist() == [0, 0, 0, 2, 2] * 2 and rows["backward"].tolist() == [1, 1, 1, 3, 3] * 2
+    frame(6, 3, L)
+    rows, events = run.compare("stance at 6")
+    assert rows["lost"].tolist() == [10, 10] and len(events) == 10
+    rows, events = compare_trip("tripwires at 6")
+    assert not rows["lost"].any() and [int(e["wire"]) for e in events] == [3, 4, 3, 4]
+    sb.check()
+    sb.close()
