@@ -458,8 +458,16 @@ int mmw_set_keypoints(mmw_ctx *ctx, const float *kp, const int32_t *owner, int32
 
 /* The same assignment when later frames have been tracked since mmw_features_async took the rows (list positions are
  * stale then): row i goes to the track of scene owner[i][0] whose creation ordinal is uid[i]; rows of tracks that
- * have expired meanwhile are dropped, as `track.keypoints = ...` on an object no list refers to any more would be. */
+ * have expired meanwhile are dropped, as `track.keypoints = ...` on an object no list refers to any more would be.
+ * It cannot tell a uid that restarted -- mmw_reset, mmw_reset_scenes and mmw_restore start a scene's ordinals over -- from the
+ * old one: rows taken before such a call go through mmw_set_keypoints_ticket. */
 int mmw_set_keypoints_uid(mmw_ctx *ctx, const float *kp, const int32_t *owner, const int32_t *uid, int32_t n_rows);
+/* The same for the rows mmw_features_async(ticket) wrote, with one addition: a row whose scene mmw_reset, mmw_reset_scenes or
+ * mmw_restore has touched since that call is dropped -- no list refers to any track of before, whatever uid the new ones carry.
+ * Every scene has a generation word that those three bump; mmw_features_async records it per ticket when uid is not NULL, and
+ * the scatter compares the two.  All on the context's stream, no host wait.  MMW_E_ARG, and nothing is written: ticket outside
+ * [0,4), or a ticket whose last mmw_features_async passed uid == NULL (mmw_features does), or one that was never used. */
+int mmw_set_keypoints_ticket(mmw_ctx *ctx, const float *kp, const int32_t *owner, const int32_t *uid, int32_t n_rows, int32_t ticket);
 
 /* Read-back (sync; host pointers).  Also surfaces per-scene errors recorded by
  * the kernels (returns the first one and sets the message). */

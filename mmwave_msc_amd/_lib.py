@@ -267,6 +267,7 @@ def _signatures():
         "mmw_features_async": (C.c_int, [vp, vp, vp, vp, i32, i32]),
         "mmw_features_wait": (C.c_int, [vp, i32, i32p]),
         "mmw_set_keypoints_uid": (C.c_int, [vp, vp, vp, vp, i32]),
+        "mmw_set_keypoints_ticket": (C.c_int, [vp, vp, vp, vp, i32, i32]),
         "mmw_get_inner": (C.c_int, [vp, vp, vp, vp, i32]),
         "mmw_set_batch_size": (C.c_int, [vp, vp, i32]),
         "mmw_set_batch_frame": (C.c_int, [vp, i32, vp, i32]),

@@ -650,6 +650,11 @@ class SceneBatch:
         """Keypoint scatter matched by track creation ordinal (rows taken one or more frames ago)."""
         self._chk(self.L.mmw_set_keypoints_uid(self.h, kp_ptr, owner_ptr, uid_ptr, int(n_rows)))
 
+    def set_keypoints_ticket_dev(self, kp_ptr, owner_ptr, uid_ptr, n_rows: int, ticket: int):
+        """The same for the rows `features_async(ticket=ticket)` wrote: rows of a scene that `reset`, `reset_scenes` or `restore`
+        touched since then are dropped -- its uids start over, and a uid of before must not alias one of after."""
+        self._chk(self.L.mmw_set_keypoints_ticket(self.h, kp_ptr, owner_ptr, uid_ptr, int(n_rows), int(ticket)))
+
     def features_host(self, cap_rows=None):
         """Returns (feat[B,ring,8,8,5] float32 (or [B,8,8,5] when ring == 1), owner[B,2])."""
         cap = int(cap_rows if cap_rows is not None else self.S * self.track_cap)

@@ -164,6 +164,7 @@ static int derive_dev_cfg(const mmw_config *cfg, int32_t n_scenes, int32_t max_p
 
 // sizes of the buffers that are allocated in one part of mmw_create and zero-filled in the next
 static size_t trk_bytes(const DevCfg &d) { return (size_t)d.n_scenes * d.t_cap * sizeof(TrackRec); }
+static size_t kp_gen_bytes(const DevCfg &d) { return (size_t)(1 + kTickets) * d.n_scenes * sizeof(int32_t); }
 static size_t db_list_bytes(const DevCfg &d) { return 4 * (size_t)d.n_scenes * sizeof(int32_t); }
 static size_t upd_list_bytes(const DevCfg &d) { return 2 * (size_t)kUpdShards * upd_region(d.n_scenes, d.t_cap) * sizeof(int32_t); }
 static size_t inner_buf_bytes(const mmw_ctx *c) { return (size_t)c->dc.n_scenes * (size_t)(kInnerHdr + c->st.inner_cap) * sizeof(int32_t); }
@@ -203,6 +204,7 @@ static int create_alloc(mmw_ctx *c)
     ALLOC(c->st.g_ring, S * (size_t)d.ring * d.max_pts * 8 * sizeof(double));
     ALLOC(c->d_posture, MMW_NKP * sizeof(float));
     ALLOC(c->d_row_off, (S + 1) * sizeof(int32_t));
+    ALLOC(c->d_kp_gen, kp_gen_bytes(d));
     ALLOC(c->st.stats, kStatAllocBytes);
     ALLOC(c->st.db_list, db_list_bytes(d));
     ALLOC(c->st.db_count, kDbCountBytes);
@@ -240,6 +242,7 @@ static int create_init_device(mmw_ctx *c, int32_t n_scenes)
         MMW_FILL0(c->st.q, kQBytes) != hipSuccess || MMW_FILL0(c->st.db_list, db_list_bytes(d)) != hipSuccess ||
         MMW_FILL0(c->st.upd_count, kUpdCountBytes) != hipSuccess || MMW_FILL0(c->st.upd_list, upd_list_bytes(d)) != hipSuccess ||
         MMW_FILL0(c->st.spc_count, kSpcCountBytes) != hipSuccess || MMW_FILL0(c->st.trk, trk_bytes(d)) != hipSuccess ||
+        MMW_FILL0(c->d_kp_gen, kp_gen_bytes(d)) != hipSuccess ||
         hipStreamSynchronize(c->own_stream) != hipSuccess) CREATE_FAIL(c, MMW_E_HIP, "device init failed");   // (the source of the posture copy is the context's own cfg)
     if (hipHostMalloc((void **)&c->h_rows, kTickets * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) CREATE_FAIL(c, MMW_E_HIP, "hipHostMalloc failed");
     for (int k = 0; k < kTickets; k++) {
@@ -265,7 +268,7 @@ static int create_init_device(mmw_ctx *c, int32_t n_scenes)
         const size_t slabs = c->st.huge_stride * (size_t)dbscan_huge_workers(n_scenes);
         if (hipMalloc((void **)&c->st.huge_scratch, slabs) != hipSuccess) CREATE_FAIL(c, MMW_E_HIP, "hipMalloc(%zu B of BallTree slabs) failed", slabs);
     }
-    launch_reset(d, c->st, nullptr, c->stream);
+    launch_reset(d, c->st, nullptr, c->d_kp_gen, c->stream);
     // every fill above and the reset kernel have finished before the caller sees the context
     if (hipStreamSynchronize(c->stream) != hipSuccess) CREATE_FAIL(c, MMW_E_HIP, "reset kernel failed: %s", hipGetErrorString(hipGetLastError()));
     return MMW_OK;
@@ -392,7 +395,7 @@ int mmw_destroy(mmw_ctx *c)
     if (c->side_stream) hipStreamSynchronize(c->side_stream);
     prof_fold(c);
     for (auto &ep : c->pool) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
-    void *ptrs[] = {c->st.hdr, c->st.order, c->st.trk, c->st.trk_ring, c->st.g_ring, c->d_posture, c->d_row_off, c->st.stats, c->st.db_list, c->st.db_count, c->st.q, c->d_probe, c->st.gate_buf, c->st.perm, c->st.upd_count, c->st.upd_list, c->st.spc_count, c->st.spc_list, c->st.inner_buf, c->d_in, c->d_out, c->d_raw, c->d_pchain,
+    void *ptrs[] = {c->st.hdr, c->st.order, c->st.trk, c->st.trk_ring, c->st.g_ring, c->d_posture, c->d_row_off, c->d_kp_gen, c->st.stats, c->st.db_list, c->st.db_count, c->st.q, c->d_probe, c->st.gate_buf, c->st.perm, c->st.upd_count, c->st.upd_list, c->st.spc_count, c->st.spc_list, c->st.inner_buf, c->d_in, c->d_out, c->d_raw, c->d_pchain,
                     c->d_export, c->st.huge_scratch, c->d_snap, c->d_sites, c->uart.buf};
     for (void *p : ptrs) if (p) hipFree(p);
     void *pinned[] = {c->h_in, c->h_out, c->h_hdr, c->h_q};
@@ -422,7 +425,7 @@ int mmw_reset(mmw_ctx *c)
 {
     if (!c) return MMW_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    launch_reset(c->dc, c->st, nullptr, c->stream);
+    launch_reset(c->dc, c->st, nullptr, c->d_kp_gen, c->stream);
     HIPCHK(c, hipGetLastError());
     MMW_TRY(uid_rebase(c, nullptr));   // (report, zones, trails -- whichever is on: every scene's uids restart)
     c->dc.var_ring = 0;   // fresh BatchedData objects: default sizes again
@@ -437,7 +440,7 @@ int mmw_reset_scenes(mmw_ctx *c, const int32_t *scene_flags)
     HIPCHK(c, hipSetDevice(c->device));
     int rebase_rc = MMW_OK;
     MMW_TRY(with_scene_flags(c, scene_flags, [&](const int32_t *f) {
-        launch_reset(c->dc, c->st, f, c->stream);
+        launch_reset(c->dc, c->st, f, c->d_kp_gen, c->stream);
         rebase_rc = uid_rebase(c, f);   // (report, zones, trails -- whichever is on: the reset scenes' uids restart)
     }));
     return rebase_rc;

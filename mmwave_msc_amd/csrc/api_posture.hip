@@ -35,14 +35,19 @@ static bool posture_model_ok(const mmw_posture_model *m, const CnnDims &d, bool 
            (!dense2_aligned || ((uintptr_t)m->dense2_w & 15) == 0);
 }
 
+// the keypoint generation words as ticket k's k_features recorded them (mmw_ctx::d_kp_gen: [S] now | [kTickets][S])
+static int32_t *kp_gen_snap(mmw_ctx *c, int ticket) { return c->d_kp_gen + (size_t)(1 + ticket) * c->dc.n_scenes; }
+
 // The eligible tracks' feature tensors (scan, then k_features) and, behind the kernels, their total into pinned host memory with
 // an event: whoever needs the total waits for the event, not for the stream
-static int features_and_total(mmw_ctx *c, float *feat, int32_t *owner, int32_t *uid, int32_t cap_rows, int32_t *h_total, hipEvent_t ev)
+// (gen_snap: the [S] words that receive the scenes' keypoint generation, or nullptr)
+static int features_and_total(mmw_ctx *c, float *feat, int32_t *owner, int32_t *uid, int32_t cap_rows, int32_t *h_total, hipEvent_t ev,
+                              int32_t *gen_snap = nullptr)
 {
     EventPair ep;
     launch_feat_scan(c->dc, c->st, c->d_row_off, c->stream);
     prof_begin(c, MMW_K_FEATURES, ep);
-    launch_features(c->dc, sites_or_null(c), c->st, c->d_row_off, feat, owner, uid, cap_rows, c->stream);
+    launch_features(c->dc, sites_or_null(c), c->st, c->d_row_off, feat, owner, uid, cap_rows, c->stream, nullptr, nullptr, c->d_kp_gen, gen_snap);
     prof_end(c, ep);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_total, c->d_row_off + c->dc.n_scenes, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -62,8 +67,10 @@ int mmw_features_async(mmw_ctx *c, float *feat, int32_t *owner, int32_t *uid, in
     if (!c || !feat || !owner || cap_rows < 0 || ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_features_async: bad argument");
     HIPCHK(c, hipSetDevice(c->device));
     // only mmw_features_wait(ticket) waits for the total
-    MMW_TRY(features_and_total(c, feat, owner, uid, cap_rows, c->h_rows + ticket, c->feat_ev[ticket]));
+    c->feat_uid[ticket] = false;   // (a call that fails half way leaves no ticket to scatter by)
+    MMW_TRY(features_and_total(c, feat, owner, uid, cap_rows, c->h_rows + ticket, c->feat_ev[ticket], uid ? kp_gen_snap(c, ticket) : nullptr));
     c->feat_cap[ticket] = cap_rows;
+    c->feat_uid[ticket] = uid != nullptr;
     return MMW_OK;
 }
 
@@ -108,6 +115,18 @@ int mmw_set_keypoints_uid(mmw_ctx *c, const float *kp, const int32_t *owner, con
     if (!c || (n_rows > 0 && (!kp || !owner || !uid)) || n_rows < 0) return fail(c, MMW_E_ARG, "mmw_set_keypoints_uid: bad argument");
     HIPCHK(c, hipSetDevice(c->device));
     launch_set_kp_uid(c->dc, c->st, kp, owner, uid, n_rows, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MMW_OK;
+}
+
+int mmw_set_keypoints_ticket(mmw_ctx *c, const float *kp, const int32_t *owner, const int32_t *uid, int32_t n_rows, int32_t ticket)
+{
+    if (!c || (n_rows > 0 && (!kp || !owner || !uid)) || n_rows < 0) return fail(c, MMW_E_ARG, "mmw_set_keypoints_ticket: bad argument");
+    if (ticket < 0 || ticket >= kTickets) return fail(c, MMW_E_ARG, "mmw_set_keypoints_ticket: ticket %d outside [0, %d)", ticket, kTickets);
+    if (!c->feat_uid[ticket])
+        return fail(c, MMW_E_ARG, "mmw_set_keypoints_ticket: ticket %d holds no rows with uids (its last mmw_features_async passed uid = NULL, or there was none)", ticket);
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_set_kp_uid(c->dc, c->st, kp, owner, uid, n_rows, c->stream, c->d_kp_gen, kp_gen_snap(c, ticket));
     HIPCHK(c, hipGetLastError());
     return MMW_OK;
 }

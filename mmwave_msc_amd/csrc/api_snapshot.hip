@@ -225,7 +225,7 @@ int mmw_restore(mmw_ctx *c, const void *dev_blob, size_t bytes, const int32_t *s
         HIPCHK(c, hipMemcpyAsync(x.sel, dst.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(x.flags, flags.data(), sizeof(int32_t) * flags.size(), hipMemcpyHostToDevice, c->stream));
         launch_snap_restore(c->dc, c->st, blob, reinterpret_cast<const mmw_snapshot_entry *>(blob + sizeof(h)), x.sel, x.flags, ns, max_tracks, h.ring_rows,
-                            c->stream);
+                            c->d_kp_gen, c->stream);
         HIPCHK(c, hipGetLastError());
         MMW_TRY(uid_rebase(c, x.flags));              // (report, zones, trails -- whichever is on: the restored scenes carry another recording's uids)
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (the host vectors above go away)

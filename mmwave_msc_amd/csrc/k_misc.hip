@@ -178,7 +178,8 @@ __global__ __launch_bounds__(1024) void k_feat_scan(DevCfg cfg, int32_t *__restr
 // this kernel took 120 us for 18 k tracks: 0.27 of the HBM rate for 290 MB.)
 __device__ __forceinline__ void features_scene(const DevCfg &cfg, const DevState &st, const int32_t *__restrict__ row_off,
                                                float *__restrict__ feat, int32_t *__restrict__ owner, int32_t *__restrict__ uid,
-                                               int cap_rows, const int32_t *__restrict__ n_in, int32_t *__restrict__ total_out)
+                                               int cap_rows, const int32_t *__restrict__ n_in, int32_t *__restrict__ total_out,
+                                               const int32_t *__restrict__ gen, int32_t *__restrict__ gen_snap)
 {
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const SceneHdr *hdr = st.hdr + s;
@@ -213,6 +214,7 @@ __device__ __forceinline__ void features_scene(const DevCfg &cfg, const DevState
     }
     const int ne = __popcll(um);
     if (total_out && tid == 0) *total_out = ne;
+    if (gen_snap && tid == 0) gen_snap[s] = gen[s];   // (mmw_features_async: the scene's generation these rows were taken in, for mmw_set_keypoints_ticket)
     for (int item = wave; item < ne * ring; item += 4) {   // (uniform per wave; the next item's rows requested ahead of this item's sort: 135 us against 106 -- registers)
         const int i = item / ring, k = item - i * ring;
         unsigned long long m = um;
@@ -248,16 +250,18 @@ __device__ __forceinline__ void features_scene(const DevCfg &cfg, const DevState
 }
 __global__ __launch_bounds__(256) void k_features(DevCfg cfg, DevState st, const int32_t *__restrict__ row_off,
                                                   float *__restrict__ feat, int32_t *__restrict__ owner, int32_t *__restrict__ uid,
-                                                  int cap_rows, const int32_t *__restrict__ n_in, int32_t *__restrict__ total_out)
+                                                  int cap_rows, const int32_t *__restrict__ n_in, int32_t *__restrict__ total_out,
+                                                  const int32_t *__restrict__ gen, int32_t *__restrict__ gen_snap)
 {
-    features_scene(cfg, st, row_off, feat, owner, uid, cap_rows, n_in, total_out);
+    features_scene(cfg, st, row_off, feat, owner, uid, cap_rows, n_in, total_out, gen, gen_snap);
 }
 __global__ __launch_bounds__(256) void k_features_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, DevState st,
                                                        const int32_t *__restrict__ row_off, float *__restrict__ feat, int32_t *__restrict__ owner,
                                                        int32_t *__restrict__ uid, int cap_rows, const int32_t *__restrict__ n_in,
-                                                       int32_t *__restrict__ total_out)
+                                                       int32_t *__restrict__ total_out, const int32_t *__restrict__ gen,
+                                                       int32_t *__restrict__ gen_snap)
 {
-    features_scene(cfg_with_intensity(cfg, sites + blockIdx.x), st, row_off, feat, owner, uid, cap_rows, n_in, total_out);
+    features_scene(cfg_with_intensity(cfg, sites + blockIdx.x), st, row_off, feat, owner, uid, cap_rows, n_in, total_out, gen, gen_snap);
 }
 
 // Utils.format_single_frame (+ relative_coordinates) on caller-provided frames:
@@ -301,14 +305,18 @@ __global__ void k_set_kp(DevCfg cfg, DevState st, const float *__restrict__ kp, 
 // The same assignment one or more frames LATER (the CNN of frame f runs beside the tracker of frame f+1): the track
 // list may have been re-ordered or shortened by _maintain_tracks since the features were taken, so a row is matched
 // by the track's creation ordinal instead of its list position; a track that has expired meanwhile drops its row.
+// gen / gen_snap (mmw_set_keypoints_ticket; both nullptr for mmw_set_keypoints_uid): the scenes' generation words now and as the
+// ticket's k_features recorded them -- a scene that was reset or restored in between drops its rows, whatever uids it holds now.
 __global__ void k_set_kp_uid(DevCfg cfg, DevState st, const float *__restrict__ kp, const int32_t *__restrict__ owner,
-                             const int32_t *__restrict__ uid, int n_rows)
+                             const int32_t *__restrict__ uid, int n_rows, const int32_t *__restrict__ gen,
+                             const int32_t *__restrict__ gen_snap)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int row = g / 64, e = g % 64;
     if (row >= n_rows) return;
     const int s = owner[row * 2], u = uid[row];
     if (s < 0 || s >= cfg.n_scenes) return;
+    if (gen && gen[s] != gen_snap[s]) return;
     const int T = min(st.hdr[s].n_tracks, cfg.t_cap);
     const int32_t *order = st.order + (size_t)s * cfg.t_cap;
     TrackRec *trk = st.trk + (size_t)s * cfg.t_cap;
@@ -402,11 +410,13 @@ __global__ void k_table_site(DevCfg cfg, const mmw_scene_site *__restrict__ site
 
 // flags == nullptr: every scene (mmw_reset); else only the scenes whose flag is non-zero (mmw_reset_scenes), and nothing of the
 // context-wide schedules
-__global__ void k_reset(DevCfg cfg, DevState st, const int32_t *__restrict__ flags)
+// kp_gen [S]: the generation word of the deferred keypoint scatter (mmw_set_keypoints_ticket), bumped for every scene reset here
+__global__ void k_reset(DevCfg cfg, DevState st, const int32_t *__restrict__ flags, int32_t *__restrict__ kp_gen)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g < cfg.n_scenes && (!flags || flags[g])) {
         SceneHdr *h = st.hdr + g;
+        kp_gen[g] += 1;
         h->n_tracks = 0;
         h->g_len = 1;  // BatchedData() starts with ONE empty frame (Utils.py:35-41, Tracking.py:38-41)
         for (int k = 0; k < MMW_RING_MAX; k++) { h->g_n[k] = 0; h->g_slot[k] = k; }
@@ -485,10 +495,10 @@ void launch_feat_count(const DevCfg &cfg, const DevState &s, int32_t *row_off, h
     hipLaunchKernelGGL(k_feat_count, dim3((cfg.n_scenes + 3) / 4), dim3(256), 0, st, cfg, s, row_off);
 }
 void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner,
-                     int32_t *uid, int cap, hipStream_t st, const int32_t *n_in, int32_t *total_out)
+                     int32_t *uid, int cap, hipStream_t st, const int32_t *n_in, int32_t *total_out, const int32_t *gen, int32_t *gen_snap)
 {
-    if (sites) hipLaunchKernelGGL(k_features_site, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, s, row_off, feat, owner, uid, cap, n_in, total_out);
-    else hipLaunchKernelGGL(k_features, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, row_off, feat, owner, uid, cap, n_in, total_out);
+    if (sites) hipLaunchKernelGGL(k_features_site, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, s, row_off, feat, owner, uid, cap, n_in, total_out, gen, gen_snap);
+    else hipLaunchKernelGGL(k_features, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, row_off, feat, owner, uid, cap, n_in, total_out, gen, gen_snap);
 }
 void launch_format_frames(const DevCfg &cfg, const double *frames, const int32_t *counts, const double *ref, float *feat, int B, hipStream_t st)
 {
@@ -501,10 +511,10 @@ void launch_set_kp(const DevCfg &cfg, const DevState &s, const float *kp, const 
     hipLaunchKernelGGL(k_set_kp, dim3((n_rows * 64 + 255) / 256), dim3(256), 0, st, cfg, s, kp, owner, n_rows, dev_rows);
 }
 void launch_set_kp_uid(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, const int32_t *uid, int n_rows,
-                       hipStream_t st)
+                       hipStream_t st, const int32_t *gen, const int32_t *gen_snap)
 {
     if (n_rows <= 0) return;
-    hipLaunchKernelGGL(k_set_kp_uid, dim3((n_rows * 64 + 255) / 256), dim3(256), 0, st, cfg, s, kp, owner, uid, n_rows);
+    hipLaunchKernelGGL(k_set_kp_uid, dim3((n_rows * 64 + 255) / 256), dim3(256), 0, st, cfg, s, kp, owner, uid, n_rows, gen, gen_snap);
 }
 void launch_export(const DevCfg &cfg, const DevState &s, mmw_track_record *out, int cap, hipStream_t st)
 {
@@ -561,9 +571,9 @@ void launch_pop_frame(const DevCfg &cfg, const DevState &s, const int32_t *flags
     hipLaunchKernelGGL(k_pop_frame, dim3((cfg.n_scenes + 255) / 256), dim3(256), 0, st, cfg, s, flags);
 }
 
-void launch_reset(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st)
+void launch_reset(const DevCfg &cfg, const DevState &s, const int32_t *flags, int32_t *kp_gen, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_reset, dim3((cfg.n_scenes + 255) / 256 > 0 ? (cfg.n_scenes + 255) / 256 : 1), dim3(256), 0, st, cfg, s, flags);
+    hipLaunchKernelGGL(k_reset, dim3((cfg.n_scenes + 255) / 256 > 0 ? (cfg.n_scenes + 255) / 256 : 1), dim3(256), 0, st, cfg, s, flags, kp_gen);
 }
 
 // Do kernels of stream B run while a kernel of stream A is spinning?  Streams are multiplexed onto a few hardware queues, and

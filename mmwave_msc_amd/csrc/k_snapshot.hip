@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256) void k_snap_scrub(DevCfg cfg, DevState st, con
 
 // restore, third: blob scene i -> scene dst[i] (grid as k_snap_pack's)
 __global__ __launch_bounds__(256) void k_snap_unpack(DevCfg cfg, DevState st, const char *__restrict__ blob, const mmw_snapshot_entry *__restrict__ dir,
-                                                     const int32_t *__restrict__ dst, int src_ring_rows)
+                                                     const int32_t *__restrict__ dst, int src_ring_rows, int32_t *__restrict__ kp_gen)
 {
     __shared__ int pre[65];
     const int i = blockIdx.x, y = blockIdx.y, tid = threadIdx.x;
@@ -356,6 +356,7 @@ __global__ __launch_bounds__(256) void k_snap_unpack(DevCfg cfg, DevState st, co
             h.n_upd = 0;
             h.skipped = (h.skipped & ~255) | 1;   // in no update list: the next _predict_all takes its tracks from this header
             st.hdr[s] = h;
+            kp_gen[s] += 1;   // (the deferred keypoint scatter's generation, as k_reset bumps it: rows taken of the scene before this are dropped)
         }
         for (int k = tid; k < cfg.t_cap; k += blockDim.x) st.order[(size_t)s * cfg.t_cap + k] = k;
         unsigned long long *out = reinterpret_cast<unsigned long long *>(trk);
@@ -425,14 +426,14 @@ void launch_snap_check(const DevCfg &cfg, const char *blob, const mmw_snapshot_e
     hipLaunchKernelGGL(k_snap_check, dim3((n + 3) / 4), dim3(256), 0, stream, cfg, blob, dir, n, src_ring_rows, bad);
 }
 void launch_snap_restore(const DevCfg &cfg, const DevState &st, const char *blob, const mmw_snapshot_entry *dir, const int32_t *dst, const int32_t *flags,
-                         int n, int max_tracks, int src_ring_rows, hipStream_t stream)
+                         int n, int max_tracks, int src_ring_rows, int32_t *kp_gen, hipStream_t stream)
 {
     if (n <= 0) return;
 #ifndef MMW_MUTANT_NO_SCRUB   // (diagnostic build `make DIAG=noscrub DIAGFLAGS=-DMMW_MUTANT_NO_SCRUB`, never the product: what
                               //  tests/test_gpu_snapshot.py's live-slot test must catch)
     hipLaunchKernelGGL(k_snap_scrub, dim3(2 * kUpdShards + 2), dim3(256), 0, stream, cfg, st, flags);
 #endif
-    hipLaunchKernelGGL(k_snap_unpack, dim3(n, snap_parts_y(max_tracks)), dim3(256), 0, stream, cfg, st, blob, dir, dst, src_ring_rows);
+    hipLaunchKernelGGL(k_snap_unpack, dim3(n, snap_parts_y(max_tracks)), dim3(256), 0, stream, cfg, st, blob, dir, dst, src_ring_rows, kp_gen);
 }
 
 }  // namespace mmw

@@ -111,6 +111,10 @@ struct mmw_ctx {
     hipEvent_t handoff_ev = nullptr;     // mmw_stream_wait: recorded on the context's stream, waited for by the caller's
     hipEvent_t handback_ev = nullptr;    // mmw_wait_stream: recorded on the caller's stream, waited for by the context's
     int32_t feat_cap[kTickets] = {0, 0, 0, 0};
+    // mmw_set_keypoints_ticket: [S] every scene's generation word (k_reset and k_snap_unpack bump it) | [kTickets][S] the words as
+    // the ticket's k_features found them; feat_uid: the ticket's last mmw_features_async wrote uids, and so that snapshot
+    int32_t *d_kp_gen = nullptr;
+    bool feat_uid[kTickets] = {false, false, false, false};
     float *d_posture = nullptr;
     int step_parity = 0;
     int ring_frames_bound = 0;   // no scene's global ring holds more frames than this (host-side knowledge: steps since the last reset)

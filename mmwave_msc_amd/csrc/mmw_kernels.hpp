@@ -49,13 +49,13 @@ void launch_feat_scan(const DevCfg &cfg, const DevState &s, int32_t *row_off, hi
 void launch_feat_count(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st);
 // k_feat_models.hip: behind launch_feat_count, the offsets model by model (map: dev [S]; groups: dev [16] = totals[8] | bases[8])
 void launch_feat_scan_models(int S, int n_models, int none_off, const int32_t *map, int32_t *row_off, int32_t *groups, hipStream_t st);
-void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner, int32_t *uid, int cap, hipStream_t st, const int32_t *n_in = nullptr, int32_t *total_out = nullptr);
-void launch_set_kp_uid(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, const int32_t *uid, int n_rows, hipStream_t st);
+void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner, int32_t *uid, int cap, hipStream_t st, const int32_t *n_in = nullptr, int32_t *total_out = nullptr, const int32_t *gen = nullptr, int32_t *gen_snap = nullptr);
+void launch_set_kp_uid(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, const int32_t *uid, int n_rows, hipStream_t st, const int32_t *gen = nullptr, const int32_t *gen_snap = nullptr);
 void launch_format_frames(const DevCfg &cfg, const double *frames, const int32_t *counts, const double *ref, float *feat, int B, hipStream_t st);
 void launch_set_kp(const DevCfg &cfg, const DevState &s, const float *kp, const int32_t *owner, int n_rows, hipStream_t st, const int32_t *dev_rows = nullptr);
 void launch_export(const DevCfg &cfg, const DevState &s, mmw_track_record *out, int cap, hipStream_t st);
 void launch_table(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, mmw_track_summary *out, int slots, int base, hipStream_t st);
-void launch_reset(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st);
+void launch_reset(const DevCfg &cfg, const DevState &s, const int32_t *flags, int32_t *kp_gen, hipStream_t st);
 void launch_probe_wait(int32_t *w, int slot, int polls, hipStream_t st);
 void launch_probe_set(int32_t *w, hipStream_t st);
 void launch_pop_frame(const DevCfg &cfg, const DevState &s, const int32_t *flags, hipStream_t st);
@@ -116,5 +116,5 @@ void launch_range_check(const float *a, long long count, int32_t *range_flag, hi
 void launch_snap_size(const DevCfg &cfg, const DevState &st, const int32_t *sel, int n, mmw_snapshot_entry *dir, unsigned long long *bytes, unsigned long long base, hipStream_t stream);
 void launch_snap_pack(const DevCfg &cfg, const DevState &st, const int32_t *sel, int n, const mmw_snapshot_entry *dir, char *blob, int max_tracks, hipStream_t stream);
 void launch_snap_check(const DevCfg &cfg, const char *blob, const mmw_snapshot_entry *dir, int n, int src_ring_rows, int32_t *bad, hipStream_t stream);
-void launch_snap_restore(const DevCfg &cfg, const DevState &st, const char *blob, const mmw_snapshot_entry *dir, const int32_t *dst, const int32_t *flags, int n, int max_tracks, int src_ring_rows, hipStream_t stream);
+void launch_snap_restore(const DevCfg &cfg, const DevState &st, const char *blob, const mmw_snapshot_entry *dir, const int32_t *dst, const int32_t *flags, int n, int max_tracks, int src_ring_rows, int32_t *kp_gen, hipStream_t stream);
 }  // namespace mmw

@@ -17,7 +17,8 @@ frame f+1 is tracked:
   queued behind `wait cnn(f-2)`, the host got its count only after that CNN had ended, and every step paid tracker +
   features + CNN in sequence (1.72 ms at 4096 scenes where the CNN alone is 1.34).
 * The scatter of frame f-2 runs after frame f was tracked, when list positions may have moved
-  (`_maintain_tracks`), so it matches tracks by creation ordinal (`mmw_set_keypoints_uid`);
+  (`_maintain_tracks`), so it matches tracks by creation ordinal, and drops the rows of a scene that was reset or
+  restored meanwhile -- its ordinals start over (`mmw_set_keypoints_ticket`, the buffer's ticket);
   it runs on the TRACKER stream, so it cannot race a spawn re-using a record.
 * The tracker never reads keypoints, so after `drain()` every live track holds exactly what the
   frame-by-frame reference loop would have left in it.
@@ -137,7 +138,7 @@ class PosturePipeline:
         if self._defer_fixup:
             with torch.cuda.stream(self.A), torch.no_grad():
                 self.model.range_fixup(self.feat[d][:n], self.kp[d], self.sflags[d])
-        self.sb.set_keypoints_uid_dev(self.kp[d].data_ptr(), self.owner[d].data_ptr(), self.uid[d].data_ptr(), n)
+        self.sb.set_keypoints_ticket_dev(self.kp[d].data_ptr(), self.owner[d].data_ptr(), self.uid[d].data_ptr(), n, d)
 
     def after_step(self):
         """Call once after every `sb.step_dev(...)` (issued on the tracker stream)."""

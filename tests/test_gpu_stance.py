@@ -379,9 +379,9 @@ def test_reset_restore_and_set_rules_rebase_their_scenes_only():
 
 def test_one_scene_with_64_tracks_every_lane_a_track_and_a_slot():
     """track_cap = 64 and a scene of 64 live tracks, planted through a snapshot blob: the section of a real scene with its first record
-    repeated 64 times under uids 63 .. 0 and no ring rows (x[k] of track t of a section is at offset + 64 + 1504 t + 8 k; uid at
-    + 1228, ring_len at + 1224, ring_n[4] behind uid, the keypoints at + 1264)."""
+    repeated 64 times under uids 63 .. 0 and no ring rows (tests/_snap_plant.py has the offsets)."""
     from mmwave_msc_amd import _lib
+    from tests._snap_plant import plant_tracks
     from mmwave_msc_amd.batch import SceneBatch
     sb = SceneBatch(_lib.default_config(tr_max_tracks=64, db_min_samples=12, track_cap=64, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0), 2, N)
     assert sb.track_cap == 64
@@ -389,28 +389,7 @@ def test_one_scene_with_64_tracks_every_lane_a_track_and_a_slot():
     for f in range(4):
         sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
     assert (sb.num_tracks() >= 1).all()
-    blob = sb.snapshot(scenes=[0])
-    hb = C.sizeof(_lib.MmwSnapshotHeader)
-    hdr = _lib.MmwSnapshotHeader.from_buffer_copy(blob[:hb])
-    ent = _lib.MmwSnapshotEntry.from_buffer_copy(blob[hdr.header_bytes: hdr.header_bytes + hdr.entry_bytes])
-    off = ent.offset
-    shdr = np.frombuffer(blob[off: off + 64], np.int32).copy()
-    rec0 = bytearray(blob[off + 64: off + 64 + _lib.SNAP_TRACK_BYTES])
-    shdr[0], shdr[1], shdr[2:6], shdr[13] = 64, 0, 0, 64     # n_tracks, g_len, g_n, next_uid
-    shdr[15] &= 0xFF00                                       # (no frame of the global ring is left to hold a NaN)
-    rec0[1224:1228] = np.int32(1).tobytes()                  # ring_len 1 ...
-    rec0[1232:1248] = bytes(16)                              # ... of no rows
-    recs = []
-    for k in range(64):
-        r = bytearray(rec0)
-        r[0:8] = np.float64(0.25 * k).tobytes()              # x[0]
-        r[1228:1232] = np.int32(63 - k).tobytes()
-        recs.append(bytes(r))
-    sec = shdr.tobytes() + b"".join(recs)
-    ent.bytes, ent.n_tracks, ent.g_len, ent.max_g_rows, ent.max_trk_rows = len(sec), 64, 0, 0, 0
-    hdr.total_bytes = off + len(sec)
-    new = bytes(memoryview(hdr)) + bytes(memoryview(ent)) + bytes(off - hb - C.sizeof(ent)) + sec
-    sb.restore(new, scenes=[0])
+    plant_tracks(sb, 0, list(range(63, -1, -1)))
     assert sb.num_tracks()[0] == 64 and sb.tracks()[0]["uid"].tolist() == list(range(63, -1, -1))
     sb.enable_stance(256)
     ref = StanceRef(2, 64, 256)
