@@ -11,10 +11,10 @@
 // The queue protocol and every worker's LDS plan: mmw_dbqueue.hpp.  Behind the step's kernels: seek_inner's per-track clustering
 // (k_inner) and mmw_dbscan's caller-provided clouds (k_dbscan_only, k_dbscan_only_huge).
 #include <cstdlib>
-#include <initializer_list>
 #include "mmw_dbqueue.hpp"
 #include "mmw_kalman.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_dispatch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -629,15 +629,6 @@ static size_t chain_lds_bytes(int um, int t_cap, int min_samples) { return chain
 
 size_t dbscan_only_lds_bytes(int UM) { return only_plan(UM < kClassUM[2] ? UM : kClassUM[2]).bytes; }
 
-struct KernelLds { const void *kernel; size_t bytes; };
-static hipError_t set_dynamic_lds(std::initializer_list<KernelLds> table)
-{
-    for (const KernelLds &t : table) {
-        const hipError_t e = hipFuncSetAttribute(t.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
 hipError_t prepare_dbscan(int UM, int t_cap, int min_samples)
 {
     const int bum = big_um(UM, UM);
@@ -712,14 +703,16 @@ void launch_post(const DevCfg &cfg, const DevState &st, const int32_t *n_pts, in
             const size_t b5 = big_lds_bytes(umb, clb, false);
             if (b5 > lds) lds = b5;
         }
-        if (cfg.dx == 9) mmw_launch(k_post<9, 512>, dim3(G0), dim3(512), lds, stream, cfg, st, n_pts, nq, G0, umc5, cl5, umb, clb, UM, parity, epoch, labels, db_n);
-        else mmw_launch(k_post<6, 512>, dim3(G0), dim3(512), lds, stream, cfg, st, n_pts, nq, G0, umc5, cl5, umb, clb, UM, parity, epoch, labels, db_n);
+        with_dx(cfg.dx, [&](auto DX) {
+            mmw_launch(k_post<decltype(DX)::value, 512>, dim3(G0), dim3(512), lds, stream, cfg, st, n_pts, nq, G0, umc5, cl5, umb, clb, UM, parity, epoch, labels, db_n);
+        });
         return;
     }
     const int upd_blocks = (units + 3) / 4;
     const dim3 grid(G0 + 1 + upd_blocks);  // workers | the schedule sort | _update_all
-    if (cfg.dx == 9) mmw_launch(k_post<9, 256>, grid, dim3(256), lds, stream, cfg, st, n_pts, nq, G0, umc, cl, umb, clb, UM, parity, epoch, labels, db_n);
-    else mmw_launch(k_post<6, 256>, grid, dim3(256), lds, stream, cfg, st, n_pts, nq, G0, umc, cl, umb, clb, UM, parity, epoch, labels, db_n);
+    with_dx(cfg.dx, [&](auto DX) {
+        mmw_launch(k_post<decltype(DX)::value, 256>, grid, dim3(256), lds, stream, cfg, st, n_pts, nq, G0, umc, cl, umb, clb, UM, parity, epoch, labels, db_n);
+    });
 }
 
 // The chain workers beside k_track and k_post (a second stream; see k_chain)

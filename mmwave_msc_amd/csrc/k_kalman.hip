@@ -17,6 +17,7 @@
 // The arithmetic per matrix element is unchanged (same operations in the same order as the CPU oracle).
 #include "mmw_kalman.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_dispatch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -180,8 +181,7 @@ void launch_predict(const DevCfg &cfg, const DevState &st, const int32_t *n_pts,
         if (resident >= kUpdShards && resident < grid) grid = resident;
         grid += kSpecialUnits;
     }
-    if (cfg.dx == 9) mmw_launch(k_predict<9>, dim3(grid), dim3(64), 0, stream, cfg, st, n_pts, dt, nq, parity);
-    else mmw_launch(k_predict<6>, dim3(grid), dim3(64), 0, stream, cfg, st, n_pts, dt, nq, parity);
+    with_dx(cfg.dx, [&](auto DX) { mmw_launch(k_predict<decltype(DX)::value>, dim3(grid), dim3(64), 0, stream, cfg, st, n_pts, dt, nq, parity); });
 }
 
 }  // namespace mmw

@@ -6,9 +6,11 @@
 //   k_pop_frame   BatchedData.pop_frame on the global ring         (Tracking.py:66-71)
 //   k_export      flatten effective_tracks for read-back
 //   k_table       fixed-size track summaries for the RCCL all-gather
-//   k_*_site      k_normalize / k_normalize_tlv / k_features / k_table with each scene's own site (mmw_set_sites) in place of the
-//                 context's: the same bodies, launched only while a site table is in use
+//   SITE          a template flag of k_normalize / k_normalize_tlv / k_features / k_table: true = each scene's own site
+//                 (mmw_set_sites) in place of the context's, launched only while a site table is in use; false = the plain kernel,
+//                 which never looks at its `sites` argument
 #include <cstddef>
+#include <type_traits>
 #include "mmw_device.hpp"
 #include "mmw_math.hpp"
 #include "mmw_normalize.hpp"
@@ -16,6 +18,7 @@
 #include "mmw_sort.hpp"
 #include "mmw_summary.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_dispatch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -56,19 +59,13 @@ __device__ __forceinline__ void normalize_scene(const DevCfg &cfg, const RT *__r
     }
     normalize_rows<R>(cfg, s, n, v, out, n_out, wcnt);
 }
-template <typename RT, int R>
-__global__ __launch_bounds__(256) void k_normalize(DevCfg cfg, const RT *__restrict__ raw, const int32_t *__restrict__ n_raw,
-                                                   double *__restrict__ out, int32_t *__restrict__ n_out)
+template <typename RT, int R, bool SITE>
+__global__ __launch_bounds__(256) void k_normalize(DevCfg cfg, const mmw_scene_site *__restrict__ sites, const RT *__restrict__ raw,
+                                                   const int32_t *__restrict__ n_raw, double *__restrict__ out, int32_t *__restrict__ n_out)
 {
     __shared__ int wcnt[R * 4];
-    normalize_scene<RT, R>(cfg, raw, n_raw, out, n_out, wcnt);
-}
-template <typename RT, int R>
-__global__ __launch_bounds__(256) void k_normalize_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, const RT *__restrict__ raw,
-                                                        const int32_t *__restrict__ n_raw, double *__restrict__ out, int32_t *__restrict__ n_out)
-{
-    __shared__ int wcnt[R * 4];
-    normalize_scene<RT, R>(cfg_with_mounting(cfg, sites + blockIdx.x), raw, n_raw, out, n_out, wcnt);
+    if constexpr (SITE) normalize_scene<RT, R>(cfg_with_mounting(cfg, sites + blockIdx.x), raw, n_raw, out, n_out, wcnt);
+    else normalize_scene<RT, R>(cfg, raw, n_raw, out, n_out, wcnt);
 }
 
 // The radar's own wire format in, ring rows out: per scene the body of the detected-points TLV of an IWR1443 UART packet
@@ -117,21 +114,14 @@ __device__ __forceinline__ void normalize_tlv_scene(const DevCfg &cfg, const uin
     normalize_rows<R>(cfg, s, n, v, out, n_out, wcnt);
     if (bad && tid == 0) n_out[s] = -3;   // MMW_BAD_FRAME (the same thread wrote the 0 above)
 }
-template <int R>
-__global__ __launch_bounds__(256) void k_normalize_tlv(DevCfg cfg, const uint8_t *__restrict__ packets, long long packets_bytes,
-                                                       const long long *__restrict__ tlv_offset, double half_bins, double doppler_res,
-                                                       double *__restrict__ out, int32_t *__restrict__ n_out)
+template <int R, bool SITE>
+__global__ __launch_bounds__(256) void k_normalize_tlv(DevCfg cfg, const mmw_scene_site *__restrict__ sites, const uint8_t *__restrict__ packets,
+                                                       long long packets_bytes, const long long *__restrict__ tlv_offset, double half_bins,
+                                                       double doppler_res, double *__restrict__ out, int32_t *__restrict__ n_out)
 {
     __shared__ int wcnt[R * 4];
-    normalize_tlv_scene<R>(cfg, packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out, wcnt);
-}
-template <int R>
-__global__ __launch_bounds__(256) void k_normalize_tlv_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, const uint8_t *__restrict__ packets,
-                                                            long long packets_bytes, const long long *__restrict__ tlv_offset, double half_bins,
-                                                            double doppler_res, double *__restrict__ out, int32_t *__restrict__ n_out)
-{
-    __shared__ int wcnt[R * 4];
-    normalize_tlv_scene<R>(cfg_with_mounting(cfg, sites + blockIdx.x), packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out, wcnt);
+    if constexpr (SITE) normalize_tlv_scene<R>(cfg_with_mounting(cfg, sites + blockIdx.x), packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out, wcnt);
+    else normalize_tlv_scene<R>(cfg, packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out, wcnt);
 }
 
 // ---------------------------------------------------------------------------
@@ -248,20 +238,15 @@ __device__ __forceinline__ void features_scene(const DevCfg &cfg, const DevState
         }
     }
 }
-__global__ __launch_bounds__(256) void k_features(DevCfg cfg, DevState st, const int32_t *__restrict__ row_off,
-                                                  float *__restrict__ feat, int32_t *__restrict__ owner, int32_t *__restrict__ uid,
-                                                  int cap_rows, const int32_t *__restrict__ n_in, int32_t *__restrict__ total_out,
-                                                  const int32_t *__restrict__ gen, int32_t *__restrict__ gen_snap)
+template <bool SITE>
+__global__ __launch_bounds__(256) void k_features(DevCfg cfg, const mmw_scene_site *__restrict__ sites, DevState st,
+                                                  const int32_t *__restrict__ row_off, float *__restrict__ feat, int32_t *__restrict__ owner,
+                                                  int32_t *__restrict__ uid, int cap_rows, const int32_t *__restrict__ n_in,
+                                                  int32_t *__restrict__ total_out, const int32_t *__restrict__ gen,
+                                                  int32_t *__restrict__ gen_snap)
 {
-    features_scene(cfg, st, row_off, feat, owner, uid, cap_rows, n_in, total_out, gen, gen_snap);
-}
-__global__ __launch_bounds__(256) void k_features_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, DevState st,
-                                                       const int32_t *__restrict__ row_off, float *__restrict__ feat, int32_t *__restrict__ owner,
-                                                       int32_t *__restrict__ uid, int cap_rows, const int32_t *__restrict__ n_in,
-                                                       int32_t *__restrict__ total_out, const int32_t *__restrict__ gen,
-                                                       int32_t *__restrict__ gen_snap)
-{
-    features_scene(cfg_with_intensity(cfg, sites + blockIdx.x), st, row_off, feat, owner, uid, cap_rows, n_in, total_out, gen, gen_snap);
+    if constexpr (SITE) features_scene(cfg_with_intensity(cfg, sites + blockIdx.x), st, row_off, feat, owner, uid, cap_rows, n_in, total_out, gen, gen_snap);
+    else features_scene(cfg, st, row_off, feat, owner, uid, cap_rows, n_in, total_out, gen, gen_snap);
 }
 
 // Utils.format_single_frame (+ relative_coordinates) on caller-provided frames:
@@ -370,8 +355,8 @@ __global__ void k_export(DevCfg cfg, DevState st, mmw_track_record *__restrict__
     if (sizeof(mmw_track_record) > kUsed) reinterpret_cast<int32_t *>(o)[kUsed / 4] = 0;
 }
 
-// One track slot of the table.  The window / monitoring point (m_x .. fade_weight) are the context's for k_table, the scene's own
-// for k_table_site; everything arrives as scalars, so that the plain kernel reads its arguments exactly as it always did.  The
+// One track slot of the table.  The window / monitoring point (m_x .. fade_weight) are the context's for k_table<false>, the scene's
+// own for k_table<true>; everything arrives as scalars, so that the plain kernel reads its arguments exactly as it always did.  The
 // fields a live-track report row shares with the table come from summary_fields (mmw_summary.hpp), which k_report.hip calls too.
 __device__ __forceinline__ void table_slot(const SceneHdr *hdrs, const int32_t *order, const TrackRec *trk, int t_cap, int dx,
                                            mmw_track_summary *out, int slots, int scene_base, int s, int j, double m_x, double m_y,
@@ -387,25 +372,23 @@ __device__ __forceinline__ void table_slot(const SceneHdr *hdrs, const int32_t *
     o->is_static = alive ? rec->is_static : 0;
     summary_fields(o, rec, dx, m_x, m_y, m_z, fade_max, fade_min, fade_weight);
 }
-__global__ void k_table(DevCfg cfg, DevState st, mmw_track_summary *__restrict__ out, int slots, int scene_base)
+// SITE: a thread is one track slot and neighbouring threads may be different scenes: the site is an ordinary per-lane load, behind
+// the bounds check (the table has n_scenes entries)
+template <bool SITE>
+__global__ void k_table(DevCfg cfg, const mmw_scene_site *__restrict__ sites, DevState st, mmw_track_summary *__restrict__ out, int slots,
+                        int scene_base)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int s = g / slots, j = g % slots;
     if (s >= cfg.n_scenes) return;
-    table_slot(st.hdr, st.order, st.trk, cfg.t_cap, cfg.dx, out, slots, scene_base, s, j, cfg.m_x, cfg.m_y, cfg.m_z, cfg.fade_max, cfg.fade_min,
-               cfg.fade_weight);
-}
-// a thread is one track slot and neighbouring threads may be different scenes: the site is an ordinary per-lane load, behind the
-// bounds check (the table has n_scenes entries)
-__global__ void k_table_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, DevState st, mmw_track_summary *__restrict__ out, int slots,
-                             int scene_base)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int s = g / slots, j = g % slots;
-    if (s >= cfg.n_scenes) return;
-    const mmw_scene_site *w = sites + s;
-    table_slot(st.hdr, st.order, st.trk, cfg.t_cap, cfg.dx, out, slots, scene_base, s, j, w->m_x, w->m_y, w->m_z, w->v_screen_fade_size_max,
-               w->v_screen_fade_size_min, w->v_screen_fade_weight);
+    if constexpr (SITE) {
+        const mmw_scene_site *w = sites + s;
+        table_slot(st.hdr, st.order, st.trk, cfg.t_cap, cfg.dx, out, slots, scene_base, s, j, w->m_x, w->m_y, w->m_z, w->v_screen_fade_size_max,
+                   w->v_screen_fade_size_min, w->v_screen_fade_weight);
+    } else {
+        table_slot(st.hdr, st.order, st.trk, cfg.t_cap, cfg.dx, out, slots, scene_base, s, j, cfg.m_x, cfg.m_y, cfg.m_z, cfg.fade_max, cfg.fade_min,
+                   cfg.fade_weight);
+    }
 }
 
 // flags == nullptr: every scene (mmw_reset); else only the scenes whose flag is non-zero (mmw_reset_scenes), and nothing of the
@@ -457,32 +440,23 @@ void launch_poison(hipStream_t stream)
 }
 #endif
 
-// sites: the context's site table (device, [n_scenes]) while one is in use, else nullptr -- the kernels of a context without sites
+// sites: the context's site table (device, [n_scenes]) while one is in use (SITE = true), else nullptr -- the plain kernels
 void launch_normalize(const DevCfg &cfg, const mmw_scene_site *sites, const void *raw, bool f32, const int32_t *n_raw, double *out, int32_t *n_out,
                       hipStream_t st)
 {
-    static_assert(MMW_MAX_PTS_LIMIT <= 4 * 256, "k_normalize (and k_track / k_scene) take at most four rows per thread: a larger limit needs a round loop");
-    const int r = (cfg.max_pts + 255) / 256;   // rows per thread: 1, 2 or 4 (max_pts <= 1024)
-#define MMW_NORM(RT, R) mmw_launch(k_normalize<RT, R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, reinterpret_cast<const RT *>(raw), n_raw, out, n_out)
-#define MMW_NORM_SITE(RT, R) mmw_launch(k_normalize_site<RT, R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, reinterpret_cast<const RT *>(raw), n_raw, out, n_out)
-    if (sites) {
-        if (f32) { if (r <= 1) MMW_NORM_SITE(float, 1); else if (r == 2) MMW_NORM_SITE(float, 2); else MMW_NORM_SITE(float, 4); }
-        else { if (r <= 1) MMW_NORM_SITE(double, 1); else if (r == 2) MMW_NORM_SITE(double, 2); else MMW_NORM_SITE(double, 4); }
-    } else if (f32) { if (r <= 1) MMW_NORM(float, 1); else if (r == 2) MMW_NORM(float, 2); else MMW_NORM(float, 4); }
-    else { if (r <= 1) MMW_NORM(double, 1); else if (r == 2) MMW_NORM(double, 2); else MMW_NORM(double, 4); }
-#undef MMW_NORM
-#undef MMW_NORM_SITE
+    with_flag(f32, [&](auto F32) { with_rows(rows_per_thread(cfg.max_pts), [&](auto R) { with_flag(sites != nullptr, [&](auto SITE) {
+        using RT = std::conditional_t<decltype(F32)::value, float, double>;
+        mmw_launch(k_normalize<RT, decltype(R)::value, decltype(SITE)::value>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites,
+                   reinterpret_cast<const RT *>(raw), n_raw, out, n_out);
+    }); }); });
 }
 void launch_normalize_tlv(const DevCfg &cfg, const mmw_scene_site *sites, const uint8_t *packets, long long packets_bytes, const long long *tlv_offset,
                           double half_bins, double doppler_res, double *out, int32_t *n_out, hipStream_t st)
 {
-    const int r = (cfg.max_pts + 255) / 256;
-#define MMW_NORM_TLV(R) mmw_launch(k_normalize_tlv<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out)
-#define MMW_NORM_TLV_SITE(R) mmw_launch(k_normalize_tlv_site<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, packets, packets_bytes, tlv_offset, half_bins, doppler_res, out, n_out)
-    if (sites) { if (r <= 1) MMW_NORM_TLV_SITE(1); else if (r == 2) MMW_NORM_TLV_SITE(2); else MMW_NORM_TLV_SITE(4); }
-    else if (r <= 1) MMW_NORM_TLV(1); else if (r == 2) MMW_NORM_TLV(2); else MMW_NORM_TLV(4);
-#undef MMW_NORM_TLV
-#undef MMW_NORM_TLV_SITE
+    with_rows(rows_per_thread(cfg.max_pts), [&](auto R) { with_flag(sites != nullptr, [&](auto SITE) {
+        mmw_launch(k_normalize_tlv<decltype(R)::value, decltype(SITE)::value>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, packets, packets_bytes,
+                   tlv_offset, half_bins, doppler_res, out, n_out);
+    }); });
 }
 void launch_feat_scan(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st)
 {
@@ -497,8 +471,10 @@ void launch_feat_count(const DevCfg &cfg, const DevState &s, int32_t *row_off, h
 void launch_features(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, const int32_t *row_off, float *feat, int32_t *owner,
                      int32_t *uid, int cap, hipStream_t st, const int32_t *n_in, int32_t *total_out, const int32_t *gen, int32_t *gen_snap)
 {
-    if (sites) hipLaunchKernelGGL(k_features_site, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, s, row_off, feat, owner, uid, cap, n_in, total_out, gen, gen_snap);
-    else hipLaunchKernelGGL(k_features, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, s, row_off, feat, owner, uid, cap, n_in, total_out, gen, gen_snap);
+    with_flag(sites != nullptr, [&](auto SITE) {
+        hipLaunchKernelGGL(k_features<decltype(SITE)::value>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, s, row_off, feat, owner, uid, cap, n_in,
+                           total_out, gen, gen_snap);
+    });
 }
 void launch_format_frames(const DevCfg &cfg, const double *frames, const int32_t *counts, const double *ref, float *feat, int B, hipStream_t st)
 {
@@ -524,8 +500,9 @@ void launch_export(const DevCfg &cfg, const DevState &s, mmw_track_record *out, 
 void launch_table(const DevCfg &cfg, const mmw_scene_site *sites, const DevState &s, mmw_track_summary *out, int slots, int base, hipStream_t st)
 {
     const int tot = cfg.n_scenes * slots;
-    if (sites) hipLaunchKernelGGL(k_table_site, dim3((tot + 127) / 128), dim3(128), 0, st, cfg, sites, s, out, slots, base);
-    else hipLaunchKernelGGL(k_table, dim3((tot + 127) / 128), dim3(128), 0, st, cfg, s, out, slots, base);
+    with_flag(sites != nullptr, [&](auto SITE) {
+        hipLaunchKernelGGL(k_table<decltype(SITE)::value>, dim3((tot + 127) / 128), dim3(128), 0, st, cfg, sites, s, out, slots, base);
+    });
 }
 // BatchedData.pop_frame() (Tracking.py:66-71) on the global ring of the scenes whose flag is set: the oldest frame
 // goes, its physical slot moves behind the live ones (the same rotation add_frame does when the ring is full).

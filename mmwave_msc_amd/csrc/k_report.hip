@@ -11,6 +11,7 @@
 #include "mmw_uidlist.hpp"
 #include "mmw_math.hpp"
 #include "mmw_summary.hpp"
+#include "mmw_dispatch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -142,8 +143,9 @@ void launch_report(const DevCfg &cfg, const mmw_scene_site *sites, const DevStat
     // (rows <= S * t_cap, events <= 2 * S * t_cap: below 2^31, so the scan's saturation at INT32_MAX never fires for a report)
     static_assert(2LL * kUpdMaxScenes * MMW_TRACK_CAP_LIMIT < (1LL << 31), "a report's totals fit an int32");
     launch_pair_scan(cfg.n_scenes, rp.sc.off, rp.sc.totals, cap_rows, cap_events, st);
-    if (sites) hipLaunchKernelGGL(k_report_write<true>, grid, dim3(256), 0, st, cfg, sites, s, rp, rows, events, scene_base);
-    else hipLaunchKernelGGL(k_report_write<false>, grid, dim3(256), 0, st, cfg, sites, s, rp, rows, events, scene_base);
+    with_flag(sites != nullptr, [&](auto SITE) {
+        hipLaunchKernelGGL(k_report_write<decltype(SITE)::value>, grid, dim3(256), 0, st, cfg, sites, s, rp, rows, events, scene_base);
+    });
 }
 
 }  // namespace mmw

@@ -14,6 +14,7 @@
 #include "mmw_math.hpp"
 #include "mmw_ring.hpp"
 #include "mmw_sort.hpp"
+#include "mmw_dispatch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -103,7 +104,7 @@ __device__ __forceinline__ uint2 bits_of(double d)
 // INPUT: 64 threads.  Every value rounded once to fp32, the intensity normalised by two fp32 operations, rows that are all zero
 //        after that behind the others as true zero rows, then the stable sort on x: ties by (is-all-zero, row position).  The
 //        1280 bytes leave through LDS as 80 16-byte units.
-// SITE:  (INPUT) the scene's own intensity scale, where k_features_site takes it.
+// SITE:  (INPUT) the scene's own intensity scale, where k_features<true> takes it.
 template <int MODE, bool SITE>
 __global__ __launch_bounds__(MODE == MMW_SAMPLE_BLOCK ? 64 * kSampleFrames : 64)
 void k_sample_write(DevCfg cfg, const mmw_scene_site *__restrict__ sites, DevState st, ExportScratch sc, const int32_t *__restrict__ flags,
@@ -173,10 +174,10 @@ void launch_samples(const DevCfg &cfg, const mmw_scene_site *sites, const DevSta
     launch_pair_scan(cfg.n_scenes, sc.off, sc.totals, cap_samples, cap_samples, st);
     if ((mode & 1) == MMW_SAMPLE_BLOCK)
         hipLaunchKernelGGL((k_sample_write<MMW_SAMPLE_BLOCK, false>), dim3(cfg.n_scenes), dim3(64 * kSampleFrames), 0, st, cfg, sites, s, sc, scene_flags, dir, out, absolute, scene_base);
-    else if (sites)
-        hipLaunchKernelGGL((k_sample_write<MMW_SAMPLE_INPUT, true>), dim3(cfg.n_scenes), dim3(64), 0, st, cfg, sites, s, sc, scene_flags, dir, out, absolute, scene_base);
     else
-        hipLaunchKernelGGL((k_sample_write<MMW_SAMPLE_INPUT, false>), dim3(cfg.n_scenes), dim3(64), 0, st, cfg, sites, s, sc, scene_flags, dir, out, absolute, scene_base);
+        with_flag(sites != nullptr, [&](auto SITE) {
+            hipLaunchKernelGGL((k_sample_write<MMW_SAMPLE_INPUT, decltype(SITE)::value>), dim3(cfg.n_scenes), dim3(64), 0, st, cfg, sites, s, sc, scene_flags, dir, out, absolute, scene_base);
+        });
 }
 
 }  // namespace mmw

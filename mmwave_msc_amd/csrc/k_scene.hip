@@ -30,6 +30,7 @@
 #endif
 #include "mmw_assoc.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_dispatch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -809,47 +810,27 @@ __global__ __launch_bounds__(NT, PPT >= 4 ? NT / 256 : NT / 128) void k_scene(De
 
 size_t scene_lds_bytes(const DevCfg &c) { return lds_layout<false>(c, nullptr, nullptr); }
 
-template <int NT, int PPT, bool F32>
-static void launch_scene_t(const DevCfg &cfg, const DevState &st, const void *pts, const int32_t *n_pts, const double *dt, int32_t *assoc,
-                           int32_t *db_n, int32_t *db_labels, int UM, int parity, hipStream_t stream)
-{
-    if (cfg.dx == 9)
-        mmw_launch(k_scene<NT, PPT, 9, F32>, dim3(cfg.n_scenes), dim3(NT), scene_lds_bytes(cfg), stream, cfg, st, pts, n_pts, dt, assoc, db_n, db_labels,
-                   UM, parity);
-    else
-        mmw_launch(k_scene<NT, PPT, 6, F32>, dim3(cfg.n_scenes), dim3(NT), scene_lds_bytes(cfg), stream, cfg, st, pts, n_pts, dt, assoc, db_n, db_labels,
-                   UM, parity);
-}
-
+// The instantiations of k_scene: F32 x DX x PPT = 2 x {9, 6} x {1, 2, 4}, all on NT = 256 threads.  prepare_scene walks all of them,
+// launch_scene picks one: the same three parameters, nested the same way.
 // (NT = 256: eight waves per scene were tried -- one point per thread, a wave per Kalman filter, sums and min / max on different
 //  waves.  Two such workgroups per CU leave 128 VGPRs per lane: the kernel spills 80 of them and ran 57 us instead of 45.)
+hipError_t prepare_scene(const DevCfg &cfg)
+{
+    const size_t lds = scene_lds_bytes(cfg);
+    hipError_t e = hipSuccess;
+    each_flag([&](auto F32) { each_dx([&](auto DX) { each_rows([&](auto PPT) {
+        if (e == hipSuccess) e = set_dynamic_lds({{(const void *)k_scene<256, decltype(PPT)::value, decltype(DX)::value, decltype(F32)::value>, lds}});
+    }); }); });
+    return e;
+}
+
 void launch_scene(const DevCfg &cfg, const DevState &st, const void *pts, bool f32, const int32_t *n_pts, const double *dt, int32_t *assoc,
                   int32_t *db_n, int32_t *db_labels, int UM, int parity, hipStream_t stream)
 {
-    const int ppt = (cfg.max_pts + 255) / 256;
-    if (f32) {
-        if (ppt <= 1) launch_scene_t<256, 1, true>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-        else if (ppt == 2) launch_scene_t<256, 2, true>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-        else launch_scene_t<256, 4, true>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-        return;
-    }
-    if (ppt <= 1) launch_scene_t<256, 1, false>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-    else if (ppt == 2) launch_scene_t<256, 2, false>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-    else launch_scene_t<256, 4, false>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-}
-
-hipError_t prepare_scene(const DevCfg &cfg)
-{
-    const int lds = (int)scene_lds_bytes(cfg);
-    const void *fns[12] = {(const void *)k_scene<256, 1, 9>, (const void *)k_scene<256, 2, 9>, (const void *)k_scene<256, 4, 9>,
-                           (const void *)k_scene<256, 1, 6>, (const void *)k_scene<256, 2, 6>, (const void *)k_scene<256, 4, 6>,
-                           (const void *)k_scene<256, 1, 9, true>, (const void *)k_scene<256, 2, 9, true>, (const void *)k_scene<256, 4, 9, true>,
-                           (const void *)k_scene<256, 1, 6, true>, (const void *)k_scene<256, 2, 6, true>, (const void *)k_scene<256, 4, 6, true>};
-    for (const void *f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    with_flag(f32, [&](auto F32) { with_dx(cfg.dx, [&](auto DX) { with_rows(rows_per_thread(cfg.max_pts), [&](auto PPT) {
+        mmw_launch(k_scene<256, decltype(PPT)::value, decltype(DX)::value, decltype(F32)::value>, dim3(cfg.n_scenes), dim3(256), scene_lds_bytes(cfg), stream,
+                   cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity);
+    }); }); });
 }
 
 }  // namespace mmw

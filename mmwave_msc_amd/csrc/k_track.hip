@@ -17,6 +17,7 @@
 #include "mmw_kalman.hpp"
 #include "mmw_assoc.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_dispatch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -883,63 +884,25 @@ __global__ __launch_bounds__(kThreads, (PRED ? 2 : (PPT == 2 ? 5 : (PPT == 1 ? 4
     WGTIME(1);
 }
 
-template <int PPT, bool F32>
-static void launch_track_t(const DevCfg &cfg, const DevState &st, const void *pts, const int32_t *n_pts, const double *dt,
-                           int32_t *assoc, int32_t *db_n, int32_t *db_labels, int UM, int parity, hipStream_t stream)
-{
-    if (pred_in_track(cfg)) {  // (never with seek_inner)
-        if (cfg.var_ring)
-            mmw_launch(k_track<PPT, true, true, F32>, dim3(cfg.n_scenes), dim3(kThreads), track_lds_bytes(cfg), stream, cfg, st, pts, n_pts, dt, assoc,
-                       db_n, db_labels, UM, parity);
-        else
-            mmw_launch(k_track<PPT, false, true, F32>, dim3(cfg.n_scenes), dim3(kThreads), track_lds_bytes(cfg), stream, cfg, st, pts, n_pts, dt, assoc,
-                       db_n, db_labels, UM, parity);
-        return;
-    }
-    if (cfg.seek_inner || cfg.var_ring)
-        mmw_launch(k_track<PPT, true, false, F32>, dim3(cfg.n_scenes), dim3(kThreads), track_lds_bytes(cfg), stream, cfg, st, pts, n_pts, dt, assoc, db_n,
-                   db_labels, UM, parity);
-    else
-        mmw_launch(k_track<PPT, false, false, F32>, dim3(cfg.n_scenes), dim3(kThreads), track_lds_bytes(cfg), stream, cfg, st, pts, n_pts, dt, assoc, db_n,
-                   db_labels, UM, parity);
-}
-
+// The instantiations of k_track: F32 x PPT x PRED x INNER = 2 x {1, 2, 4} x 2 x 2.  launch_track picks one, prepare_track walks all
+// of them: the same four parameters, nested the same way.
 void launch_track(const DevCfg &cfg, const DevState &st, const void *pts, bool f32, const int32_t *n_pts, const double *dt,
                   int32_t *assoc, int32_t *db_n, int32_t *db_labels, int UM, int parity, hipStream_t stream)
 {
-    const int ppt = (cfg.max_pts + kThreads - 1) / kThreads;
-    if (f32) {
-        if (ppt <= 1) launch_track_t<1, true>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-        else if (ppt == 2) launch_track_t<2, true>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-        else launch_track_t<4, true>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-        return;
-    }
-    if (ppt <= 1) launch_track_t<1, false>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-    else if (ppt == 2) launch_track_t<2, false>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-    else launch_track_t<4, false>(cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity, stream);
-}
-
-template <int PPT, bool F32>
-static hipError_t prepare_track_t(int lds)
-{
-    const void *fns[4] = {(const void *)k_track<PPT, false, false, F32>, (const void *)k_track<PPT, true, false, F32>,
-                          (const void *)k_track<PPT, false, true, F32>, (const void *)k_track<PPT, true, true, F32>};
-    for (const void *f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    const bool pred = pred_in_track(cfg), inner = cfg.seek_inner || cfg.var_ring;   // (pred_in_track: never with seek_inner)
+    with_flag(f32, [&](auto F32) { with_rows(rows_per_thread(cfg.max_pts), [&](auto PPT) { with_flag(pred, [&](auto PRED) { with_flag(inner, [&](auto INNER) {
+        mmw_launch(k_track<decltype(PPT)::value, decltype(INNER)::value, decltype(PRED)::value, decltype(F32)::value>, dim3(cfg.n_scenes), dim3(kThreads),
+                   track_lds_bytes(cfg), stream, cfg, st, pts, n_pts, dt, assoc, db_n, db_labels, UM, parity);
+    }); }); }); });
 }
 
 hipError_t prepare_track(const DevCfg &cfg)
 {
-    const int lds = (int)track_lds_bytes(cfg);
-    hipError_t e = prepare_track_t<1, false>(lds);
-    if (e == hipSuccess) e = prepare_track_t<2, false>(lds);
-    if (e == hipSuccess) e = prepare_track_t<4, false>(lds);
-    if (e == hipSuccess) e = prepare_track_t<1, true>(lds);
-    if (e == hipSuccess) e = prepare_track_t<2, true>(lds);
-    if (e == hipSuccess) e = prepare_track_t<4, true>(lds);
+    const size_t lds = track_lds_bytes(cfg);
+    hipError_t e = hipSuccess;
+    each_flag([&](auto F32) { each_rows([&](auto PPT) { each_flag([&](auto PRED) { each_flag([&](auto INNER) {
+        if (e == hipSuccess) e = set_dynamic_lds({{(const void *)k_track<decltype(PPT)::value, decltype(INNER)::value, decltype(PRED)::value, decltype(F32)::value>, lds}});
+    }); }); }); });
     return e;
 }
 

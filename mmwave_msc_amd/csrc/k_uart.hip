@@ -2,9 +2,10 @@
 //   k_uart_read      ReadIWR14xx.read (ReadDataIWR1443.py:27-201) + Utils.normalize_data for every scene: one workgroup per
 //                    scene keeps that scene's 2^15-byte byteBuffer in global memory, appends the bytes that arrived, cuts to
 //                    the last magic word, decodes one packet into registers, drops it and normalises the rows
-//   k_uart_read_site the same body with each scene's own mounting (mmw_set_sites)
-//   k_uart_read_log, k_uart_read_site_log   the same body again, which also leaves the decoded frame as it came off the wire in
-//                    the scene's radar log (mmw_uart_log_enable; exported by k_uart_log.hip).  Launched only while the log is on.
+//                    SITE = true: the same body with each scene's own mounting (mmw_set_sites)
+//                    LOG = true: the same body again, which also leaves the decoded frame as it came off the wire in the scene's
+//                    radar log (mmw_uart_log_enable; exported by k_uart_log.hip).  Launched only while the log is on.
+//                    Both false: the plain kernel, which looks at neither its `sites` nor its `log` argument.
 //   k_uart_set_time  main.py's `t` restarted
 // The buffer discipline is the reference's to the byte: its two slice assignments (66-69, 191-195) are moves of the buffer
 // onto itself, and what they leave behind past byteBufferLength is read again by a later packet whose objects reach past the
@@ -13,6 +14,7 @@
 #include "mmw_math.hpp"
 #include "mmw_normalize.hpp"
 #include "mmw_launch.hpp"
+#include "mmw_dispatch.hpp"
 #include "mmw_kernels.hpp"
 
 namespace mmw {
@@ -128,12 +130,12 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t *p) { return *reinterpret
 
 // One read() of scene blockIdx.x, then normalize_data on what it decoded.  R = rows per thread, as in k_normalize_tlv.
 // LOG: a read that gives MMW_UART_POINTS also stores its wire objects and the scene's log word (UartLog, mmw_device.hpp).
-template <int R, bool LOG = false>
+template <int R, bool LOG>
 __device__ __forceinline__ void uart_read_scene(const DevCfg &cfg, const UartState &us, const uint8_t *__restrict__ chunks,
                                                 const long long *__restrict__ chunk_off, long long chunks_bytes, const int32_t *__restrict__ flags,
                                                 double now, double *__restrict__ out, int32_t *__restrict__ n_out, double *__restrict__ dt_out,
                                                 int32_t *__restrict__ status, uint32_t *__restrict__ frame_number, int *wcnt /* LDS [R * 4] */,
-                                                int *red /* LDS [4] */, const UartLog &log = UartLog{})
+                                                int *red /* LDS [4] */, const UartLog &log)
 {
     const int s = blockIdx.x, tid = threadIdx.x;
     UartScene *sc = us.scene + s;
@@ -241,48 +243,19 @@ __device__ __forceinline__ void uart_read_scene(const DevCfg &cfg, const UartSta
     }
 }
 
-template <int R>
-__global__ __launch_bounds__(256) void k_uart_read(DevCfg cfg, UartState us, const uint8_t *__restrict__ chunks, const long long *__restrict__ chunk_off,
-                                                   long long chunks_bytes, const int32_t *__restrict__ flags, double now, double *__restrict__ out,
-                                                   int32_t *__restrict__ n_out, double *__restrict__ dt_out, int32_t *__restrict__ status,
-                                                   uint32_t *__restrict__ frame_number)
+template <int R, bool SITE, bool LOG>
+__global__ __launch_bounds__(256) void k_uart_read(DevCfg cfg, const mmw_scene_site *__restrict__ sites, UartState us, UartLog log,
+                                                   const uint8_t *__restrict__ chunks, const long long *__restrict__ chunk_off, long long chunks_bytes,
+                                                   const int32_t *__restrict__ flags, double now, double *__restrict__ out, int32_t *__restrict__ n_out,
+                                                   double *__restrict__ dt_out, int32_t *__restrict__ status, uint32_t *__restrict__ frame_number)
 {
     __shared__ int wcnt[R * 4];
     __shared__ int red[4];
-    uart_read_scene<R>(cfg, us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number, wcnt, red);
-}
-template <int R>
-__global__ __launch_bounds__(256) void k_uart_read_site(DevCfg cfg, const mmw_scene_site *__restrict__ sites, UartState us, const uint8_t *__restrict__ chunks,
-                                                        const long long *__restrict__ chunk_off, long long chunks_bytes, const int32_t *__restrict__ flags,
-                                                        double now, double *__restrict__ out, int32_t *__restrict__ n_out, double *__restrict__ dt_out,
-                                                        int32_t *__restrict__ status, uint32_t *__restrict__ frame_number)
-{
-    __shared__ int wcnt[R * 4];
-    __shared__ int red[4];
-    uart_read_scene<R>(cfg_with_mounting(cfg, sites + blockIdx.x), us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number,
-                       wcnt, red);
-}
-
-template <int R>
-__global__ __launch_bounds__(256) void k_uart_read_log(DevCfg cfg, UartState us, UartLog log, const uint8_t *__restrict__ chunks, const long long *__restrict__ chunk_off,
-                                                       long long chunks_bytes, const int32_t *__restrict__ flags, double now, double *__restrict__ out,
-                                                       int32_t *__restrict__ n_out, double *__restrict__ dt_out, int32_t *__restrict__ status,
-                                                       uint32_t *__restrict__ frame_number)
-{
-    __shared__ int wcnt[R * 4];
-    __shared__ int red[4];
-    uart_read_scene<R, true>(cfg, us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number, wcnt, red, log);
-}
-template <int R>
-__global__ __launch_bounds__(256) void k_uart_read_site_log(DevCfg cfg, const mmw_scene_site *__restrict__ sites, UartState us, UartLog log,
-                                                            const uint8_t *__restrict__ chunks, const long long *__restrict__ chunk_off, long long chunks_bytes,
-                                                            const int32_t *__restrict__ flags, double now, double *__restrict__ out, int32_t *__restrict__ n_out,
-                                                            double *__restrict__ dt_out, int32_t *__restrict__ status, uint32_t *__restrict__ frame_number)
-{
-    __shared__ int wcnt[R * 4];
-    __shared__ int red[4];
-    uart_read_scene<R, true>(cfg_with_mounting(cfg, sites + blockIdx.x), us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status,
-                             frame_number, wcnt, red, log);
+    if constexpr (SITE)
+        uart_read_scene<R, LOG>(cfg_with_mounting(cfg, sites + blockIdx.x), us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status,
+                                frame_number, wcnt, red, log);
+    else
+        uart_read_scene<R, LOG>(cfg, us, chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number, wcnt, red, log);
 }
 
 __global__ __launch_bounds__(256) void k_uart_set_time(UartState us, const int32_t *__restrict__ flags, double t, int n_scenes)
@@ -295,23 +268,11 @@ void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const Uart
                       long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status,
                       uint32_t *frame_number, hipStream_t st)
 {
-    const int r = (cfg.max_pts + 255) / 256;   // rows per thread, as launch_normalize_tlv
-#define MMW_UART_ARGS chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number
-#define MMW_UART_READ(R) mmw_launch(k_uart_read<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, us, MMW_UART_ARGS)
-#define MMW_UART_READ_SITE(R) mmw_launch(k_uart_read_site<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, us, MMW_UART_ARGS)
-#define MMW_UART_READ_LOG(R) mmw_launch(k_uart_read_log<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, us, *log, MMW_UART_ARGS)
-#define MMW_UART_READ_SITE_LOG(R) mmw_launch(k_uart_read_site_log<R>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, us, *log, MMW_UART_ARGS)
-    if (log) {   // the twins, only while the radar log is enabled
-        if (sites) { if (r <= 1) MMW_UART_READ_SITE_LOG(1); else if (r == 2) MMW_UART_READ_SITE_LOG(2); else MMW_UART_READ_SITE_LOG(4); }
-        else if (r <= 1) MMW_UART_READ_LOG(1); else if (r == 2) MMW_UART_READ_LOG(2); else MMW_UART_READ_LOG(4);
-    }
-    else if (sites) { if (r <= 1) MMW_UART_READ_SITE(1); else if (r == 2) MMW_UART_READ_SITE(2); else MMW_UART_READ_SITE(4); }
-    else if (r <= 1) MMW_UART_READ(1); else if (r == 2) MMW_UART_READ(2); else MMW_UART_READ(4);
-#undef MMW_UART_READ
-#undef MMW_UART_READ_SITE
-#undef MMW_UART_READ_LOG
-#undef MMW_UART_READ_SITE_LOG
-#undef MMW_UART_ARGS
+    const UartLog lg = log ? *log : UartLog{};   // (LOG = true only while the radar log is enabled)
+    with_rows(rows_per_thread(cfg.max_pts), [&](auto R) { with_flag(sites != nullptr, [&](auto SITE) { with_flag(log != nullptr, [&](auto LOG) {
+        mmw_launch(k_uart_read<decltype(R)::value, decltype(SITE)::value, decltype(LOG)::value>, dim3(cfg.n_scenes), dim3(256), 0, st, cfg, sites, us, lg,
+                   chunks, chunk_off, chunks_bytes, flags, now, out, n_out, dt_out, status, frame_number);
+    }); }); });
 }
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st)
 {

@@ -1,4 +1,4 @@
-// k_uart_log.hip -- the radar log's export (mmw_uart_log_*): every scene's staged frame -- what k_uart_read_log (k_uart.hip) kept of
+// k_uart_log.hip -- the radar log's export (mmw_uart_log_*): every scene's staged frame -- what k_uart_read<., ., LOG = true> (k_uart.hip) kept of
 // the last read() that decoded one: its wire objects and its log word -- as the reference's `frameNumber, detObj`
 // (DataLogging.py:30-38), compacted into one output in ascending scene order with a directory entry per frame.
 //   k_ulog_count   a lane per scene: is the scene emitted, and with how many objects

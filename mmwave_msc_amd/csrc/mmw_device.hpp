@@ -118,7 +118,7 @@ struct UartState {
     uint8_t *buf;          // [S][kUartBuf], 16-byte aligned
     UartScene *scene;      // [S]
 };
-// The radar log (mmw_uart_log_enable; k_uart_read_log stages, k_uart_log.hip exports): per scene the frame its last read()
+// The radar log (mmw_uart_log_enable; k_uart_read<., ., LOG = true> stages, k_uart_log.hip exports): per scene the frame its last read()
 // decoded, as it came off the wire -- the DataLogging.py recorder's `dataOk, frameNumber, detObj`.  A read that gives
 // MMW_UART_POINTS rewrites the scene's word (all of it but `range_scale`, which the host sets) and its first `count` objects;
 // every other status leaves both alone.

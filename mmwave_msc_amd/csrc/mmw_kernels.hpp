@@ -42,7 +42,7 @@ size_t dbscan_huge_slab_bytes(int UM, int t_cap, int min_samples);
 void launch_dbscan_huge(const DevCfg &cfg, const DevState &st, int UM, int u_bound, int parity, int32_t *labels, int32_t *db_n, hipStream_t stream);
 void launch_dbscan_only(const DevCfg &cfg, const DevState &st, int UM, const double *pts, const int32_t *n, int max_n, double eps, int min_samples, int32_t *labels, int32_t *ncl, hipStream_t stream);
 // k_misc.hip
-// (sites: the context's site table while one is in use -- the k_*_site kernels --, else nullptr)
+// (sites: the context's site table while one is in use -- the kernels' SITE = true instantiations --, else nullptr: the plain kernels)
 void launch_normalize(const DevCfg &cfg, const mmw_scene_site *sites, const void *raw, bool f32, const int32_t *n_raw, double *out, int32_t *n_out, hipStream_t st);
 void launch_normalize_tlv(const DevCfg &cfg, const mmw_scene_site *sites, const uint8_t *packets, long long packets_bytes, const long long *tlv_offset, double half_bins, double doppler_res, double *out, int32_t *n_out, hipStream_t st);
 void launch_feat_scan(const DevCfg &cfg, const DevState &s, int32_t *row_off, hipStream_t st);
@@ -87,7 +87,7 @@ void launch_tripwires(const DevCfg &cfg, const TripState &ts, mmw_tripwire_row *
 void launch_stance_zero(int n_scenes, const int32_t *flags, const StanceState &ss, hipStream_t st);
 void launch_stance_sample(const DevCfg &cfg, const DevState &s, const StanceState &ss, const int32_t *flags, const double *t, hipStream_t st);
 void launch_stance(const DevCfg &cfg, const StanceState &ss, mmw_stance_row *rows, int cap_rows, mmw_stance_event *events, int cap_events, int scene_base, hipStream_t st);
-// k_uart.hip: the device-resident radar readers (log: the radar log while it is enabled -- the k_uart_read*_log twins --, else nullptr)
+// k_uart.hip: the device-resident radar readers (log: the radar log while it is enabled -- k_uart_read's LOG = true instantiations --, else nullptr)
 void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const UartLog *log, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);
 // k_uart_log.hip: the radar log's export (scene_flags: dev [S] or nullptr = every scene)

@@ -77,11 +77,11 @@ __device__ __forceinline__ void decode_tlv_object(const unsigned short (&w)[6], 
     v[4] = (double)(short)w[2];
 }
 
-// Per-scene sites (mmw_set_sites): a kernel's `cfg` with the site's values in place of the context's, so that the site variants
-// below run the SAME bodies -- the operation order of normalize_rows, features_scene and table_slot (which takes the window as scalars) is what pins them to the
+// Per-scene sites (mmw_set_sites): a kernel's `cfg` with the site's values in place of the context's, so that a kernel's SITE = true
+// instantiation runs the SAME body as its SITE = false one, the plain kernel -- the operation order of normalize_rows, features_scene and table_slot (which takes the window as scalars) is what pins them to the
 // reference bit for bit.  The table is written by an earlier call on the same stream, never by the launch that reads it: it
 // may come through the scalar cache, and needs no invalidate (unlike the gate records of k_track).
-// Mounting (k_normalize*): one workgroup is one scene, so the site is wave-uniform -- `site` is sites + blockIdx.x of a
+// Mounting (k_normalize*, k_uart_read): one workgroup is one scene, so the site is wave-uniform -- `site` is sites + blockIdx.x of a
 // const __restrict__ kernel argument and arrives as scalar operands (s_load), like DevCfg itself.
 __device__ __forceinline__ DevCfg cfg_with_mounting(DevCfg cfg, const mmw_scene_site *__restrict__ site)
 {

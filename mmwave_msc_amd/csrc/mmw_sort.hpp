@@ -55,7 +55,7 @@ __device__ __forceinline__ void bitonic_sort64(int lane, double &key, int &src)
 // the wave on (x, row) -- ties ordered by row position -- then 5 fp32 stores per lane.  18 of its 21 steps exchange by DPP (partners inside a row of
 // 16 lanes); with every step three trips through the LDS crossbar the kernel was a chain of ds_bpermute latencies (118 us at 98 k sorts).
 // The keys must not be NaN: bitonic_step's `<` and `==` are both false on a NaN, so both lanes of a pair keep the same element and
-// the result is no permutation.  The callers that feed it from a track's ring (k_features, k_features_site) cannot meet one: the
+// the result is no permutation.  The callers that feed it from a track's ring (k_features<SITE>) cannot meet one: the
 // gate refuses a row whose x is not finite, DBSCAN raises on one, so no ring frame holds such a row, and the centroid subtracted
 // from it is a mean of ring rows.  Caller data (k_format_frames) goes through sort_rows_store_nan_last.
 __device__ inline void sort_rows_store(int lane, double v0, double v1, double v2, double v3, double v4, float *dst)

@@ -1,4 +1,4 @@
-// mmw_summary.hpp -- the per-track output fields that mmw_track_summary (k_table / k_table_site, k_misc.hip) and mmw_track_report
+// mmw_summary.hpp -- the per-track output fields that mmw_track_summary (k_table<SITE>, k_misc.hip) and mmw_track_report
 // (k_report_write, k_report.hip) share, computed in ONE place: a report row equals the table row of its (scene, slot) bit for bit
 // because both are this function's.
 #pragma once
@@ -9,7 +9,7 @@ namespace mmw {
 
 // Row: mmw_track_summary or mmw_track_report (global memory or LDS: the stores follow the pointer).  rec == nullptr: a list
 // position beyond the scene's tracks -- zeros.  The window / monitoring point (m_x .. fade_weight) are the context's or the scene's
-// own site; everything arrives as scalars, so that k_table reads its arguments exactly as it always did.
+// own site; everything arrives as scalars, so that the plain kernel (k_table<false>) reads its arguments exactly as it always did.
 template <typename Row>
 __device__ __forceinline__ void summary_fields(Row *o, const TrackRec *rec, int dx, double m_x, double m_y, double m_z, double fade_max,
                                                double fade_min, double fade_weight)

@@ -9,7 +9,14 @@
 Beside the verdict: VGPRs, SGPRs, scratch bytes per lane, static LDS bytes and occupancy as the compiler's own kernel-info
 comments give them, before -> after.  Exit status 1 if a kernel is missing on one side or a resource figure moved.
 
-    scripts/isa_diff.py before.s after.s [more pairs ...] > profiles/<name>.txt
+In front of the per-kernel verdicts, one line per pair says whether the two FILES are the same text (apart from the lines that
+carry the compilation unit's id, __hip_cuid_<hash of path and options>): same symbols in the same order, same ISA, same metadata.
+
+--twins _site,_log: a kernel of the second file that the first does not have is looked up there under the name its trailing
+bool template arguments spell -- one suffix per argument, appended where it is true: k<4, true, false> is the first file's
+k_site<4>, k<4, true, true> its k_site_log<4>, k<false> its k (template flags that replaced twin kernels).
+
+    scripts/isa_diff.py [--twins SUFFIX[,SUFFIX...]] before.s after.s [more pairs ...] > profiles/<name>.txt
 """
 import collections
 import re
@@ -90,20 +97,50 @@ def demangle(names):
         return {n: n for n in names}
 
 
+def twin_name(pretty, suffixes):
+    """The name the first file has for `pretty`, a kernel whose trailing bool template arguments replaced twin kernels (--twins)."""
+    m = re.match(r"(.*?)<(.*)>$", pretty)
+    if not m:
+        return None
+    args, tail = m.group(2).split(", "), ""
+    flags = []
+    while args and args[-1] in ("true", "false") and len(flags) < len(suffixes):
+        flags.insert(0, args.pop() == "true")
+    if not flags:
+        return None
+    for on, suffix in zip(flags, suffixes[:len(flags)]):
+        tail += suffix if on else ""
+    return m.group(1) + tail + ("<" + ", ".join(args) + ">" if args else "")
+
+
+def same_text(before, after):
+    text = lambda path: [l for l in open(path).read().split("\n") if "__hip_cuid_" not in l]
+    return text(before) == text(after)
+
+
 def main(argv):
+    suffixes = []
+    if len(argv) > 2 and argv[1] == "--twins":
+        suffixes = argv[2].split(",")
+        argv = argv[:1] + argv[3:]
     if len(argv) < 3 or len(argv) % 2 == 0:
         sys.exit(__doc__)
     bad = False
     for before, after in zip(argv[1::2], argv[2::2]):
         a, b = kernels(before), kernels(after)
         pretty = demangle(sorted(set(a) | set(b)))
-        print(f"== {before} -> {after}: {len(a)} / {len(b)} kernels")
-        for name in sorted(set(a) | set(b)):
-            if name not in a or name not in b:
-                print(f"{pretty[name]}: only in {'the first' if name in a else 'the second'} file")
+        print(f"== {before} -> {after}: {len(a)} / {len(b)} kernels; the files are {'the same text' if same_text(before, after) else 'not the same text'}")
+        by_pretty = {pretty[n]: n for n in a}
+        partner = {n: n if n in a else by_pretty.get(twin_name(pretty[n], suffixes)) for n in b}
+        for name in sorted(set(a) - set(partner.values())):
+            print(f"{pretty[name]}: only in the first file")
+            bad = True
+        for name in sorted(b):
+            if partner[name] is None:
+                print(f"{pretty[name]}: only in the second file")
                 bad = True
                 continue
-            (ia, fa), (ib, fb) = a[name], b[name]
+            (ia, fa), (ib, fb) = a[partner[name]], b[name]
             op = lambda seq: collections.Counter(x.split()[0] for x in seq if not x.endswith(":"))
             ca, cb = op(ia), op(ib)
             if ia == ib:
@@ -117,7 +154,8 @@ def main(argv):
             if any(fa.get(key) != fb.get(key) for _, key in INFO):
                 res += "  RESOURCES MOVED"
                 bad = True
-            print(f"{pretty[name]}: {verdict}\n    {res}")
+            was = "" if partner[name] == name else f" (was {pretty[partner[name]]})"
+            print(f"{pretty[name]}{was}: {verdict}\n    {res}")
     return 1 if bad else 0
 
 

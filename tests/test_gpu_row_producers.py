@@ -1,5 +1,5 @@
-"""Every kernel that writes a frame's rows -- k_normalize<double | float, R> and k_normalize_tlv<R> with their _site twins,
-k_uart_read<R> with its _site / _log twins -- ends in normalize_rows<R> (csrc/mmw_normalize.hpp).  Here each of them, at 1, 2 and 4
+"""Every kernel that writes a frame's rows -- k_normalize<double | float, R, SITE> and k_normalize_tlv<R, SITE>, k_uart_read<R, SITE,
+LOG>, each flag false and true -- ends in normalize_rows<R> (csrc/mmw_normalize.hpp).  Here each of them, at 1, 2 and 4
 rows per thread (max_pts 256 | 257, 512 | 513, 768, 1024), against the C oracle.
 
 NO expected value in this file comes from a GPU call: every `want` is tests/_rows_ref.py's expected_rows -- oracle.c_oracle.normalize
@@ -97,7 +97,7 @@ def _check_rows(pts, n_out, want, tags, where):
 @pytest.mark.parametrize("group", ["counts", "edges"])
 @pytest.mark.parametrize("max_pts", rr.MAX_PTS)
 def test_normalize_equals_the_oracle(max_pts, group, f32, sites):
-    """k_normalize<double | float, R> and k_normalize_site<., R>: seam frames, the count list (with the counts normalize_scene
+    """k_normalize<double | float, R, false> and k_normalize<., R, true>: seam frames, the count list (with the counts normalize_scene
     clamps) and the edge rows.  The fp32 entry gets the same values where float32 holds them exactly; the edge rows that need
     5e-324 or 1e+-200 (the smallest double, r == 0 by underflow, r == inf by overflow) exist in no float32 and are left out
     of the fp32 runs, which get float32's own one-ulp neighbours and smallest positive value instead (_rows_ref.edge_rows)."""
@@ -122,7 +122,7 @@ def test_normalize_equals_the_oracle(max_pts, group, f32, sites):
 @pytest.mark.parametrize("sites", [False, True], ids=["ctx", "sites"])
 @pytest.mark.parametrize("max_pts", rr.MAX_PTS)
 def test_normalize_tlv_equals_host_decode_then_the_oracle(max_pts, sites):
-    """k_normalize_tlv<R> / k_normalize_tlv_site<R> on bodies encoded from int16 objects (seam frames in wire format, the count
+    """k_normalize_tlv<R, false> / k_normalize_tlv<R, true> on bodies encoded from int16 objects (seam frames in wire format, the count
     list, y == 0 objects, doppler indices on both sides of the wrap) at 2-byte-aligned offsets.  Expected: the host numpy decode
     of the same bytes, then the oracle."""
     from mmwave_msc_amd import radar
@@ -146,7 +146,7 @@ def test_normalize_tlv_equals_host_decode_then_the_oracle(max_pts, sites):
 @pytest.mark.parametrize("mode", ["plain", "sites", "log", "sites+log"])
 @pytest.mark.parametrize("max_pts", rr.MAX_PTS)
 def test_uart_read_equals_host_decode_then_the_oracle(max_pts, mode):
-    """k_uart_read<R> and its _site / _log / _site_log twins: three reads, each delivering one complete packet to every scene
+    """k_uart_read<R, SITE, LOG>, all four combinations of the flags: three reads, each delivering one complete packet to every scene
     (read k gives scene s the body of scene s + k, so the second and third start from the buffer the one before cut): status
     MMW_UART_POINTS, the frame number, n and the rows against the host decode + the oracle under the scene's mounting.  With the
     log enabled the staged frame is the host decode as well.  A fourth read: max_pts + 1 objects stay MMW_UART_OVERFLOW."""

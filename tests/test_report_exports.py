@@ -125,7 +125,7 @@ def test_one_generation_bump_and_one_uid_match_for_report_zones_and_trails():
 
 
 def test_table_kernels_still_compile_without_scratch_after_sharing_their_body():
-    """k_table / k_table_site call the function the report rows come from (mmw_summary.hpp)."""
+    """k_table<false> / k_table<true> call the function the report rows come from (mmw_summary.hpp)."""
     from tests._isa import _device_isa, _kernel_report, assert_clean
     rep, _ = _device_isa(("k_misc",))["k_misc"]
     rows = [k for k in _kernel_report(rep) if "k_table" in k[0]]

@@ -41,7 +41,11 @@ def test_reader_kernels_use_no_scratch_and_spill_nothing():
     rep, asm = _device_isa(("k_uart",))["k_uart"]
     rows = _kernel_report(rep)
     names = [k[0] for k in rows]
-    assert sum("k_uart_readI" in n for n in names) == 3 and sum("k_uart_read_siteI" in n for n in names) == 3, names   # 1, 2, 4 rows per thread
+    # k_uart_read<R, SITE, LOG>: 1, 2, 4 rows per thread of the plain kernel, of SITE = true, and of either with LOG = true
+    flags = [re.match(r"_ZN3mmw11k_uart_readILi\dELb([01])ELb([01])EEEv", n) for n in names]
+    flags = [m.groups() for m in flags if m]
+    assert flags.count(("0", "0")) == 3 and flags.count(("1", "0")) == 3, names
+    assert flags.count(("0", "1")) == 3 and flags.count(("1", "1")) == 3, names
     assert sum("k_uart_set_time" in n for n in names) == 1, names
     assert_clean(rows)
     for name, scratch, vspill, vgprs, occ, sspill in rows:
