@@ -997,6 +997,101 @@ int mmw_stance_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n_ev
 int mmw_stance(mmw_ctx *ctx, mmw_stance_row *rows, int32_t cap_rows, mmw_stance_event *events, int32_t cap_events,
                int32_t scene_base, int32_t *n_rows, int32_t *n_events);                 /* async + wait */
 
+/* ---- heat ----
+ * Where in the room people spend their time: per scene zero or one GRID of nx x ny square cells in the scene's normalised frame, and
+ * per cell the time live tracks spent in it (`dwell`, fp64), the samples taken in it and the visits that began in it.  The zones are
+ * a few rectangles chosen in advance and the trails forget a uid when its track expires; this is the accumulation over hours, kept
+ * next to the state it reads -- a few words per live track per frame -- and moved only when the caller asks for the map.  The first
+ * consumer whose state is a dense per-scene array, so its export is a stream compaction: only cells with samples > 0 travel.  No step
+ * kernel reads or writes any of this: a context that never enables heat launches exactly what it did before.
+ *
+ * mmw_heat_enable(cells), cells in 1 .. MMW_HEAT_CELLS_MAX, allocates the grid table (every scene at 0 grids) and per scene: `cells`
+ * cells of {dwell fp64, samples int32, visits int32} = 16 bytes; t_cap uid SLOTS of {owner uid or -1 = free, last_cell int32, last_t
+ * fp64} = 16 bytes; the scene words calls, outside (int32), t_first, t_last (fp64); a generation, the generation seen and a call
+ * ordinal -- S * (16 * cells + 16 * t_cap + 36) bytes plus a table of 56 S (4096 scenes x 1024 cells: 16 B x 4 Mi cells = 67 MB, plus
+ * 3.5 MB of slots at t_cap 51).  Every slot starts free, every word at 0; the state is ordered on the context's stream.  Enabling
+ * again, with any capacity, starts over (0 grids everywhere).  cells == 0 waits for the stream, frees the state and turns heat off
+ * (MMW_OK also when it was off).  cells outside 0 .. MMW_HEAT_CELLS_MAX: MMW_E_ARG, nothing changed.  A failed allocation: MMW_E_HIP,
+ * nothing changed -- an earlier enablement stays as it is.  Until enabled, every other entry returns MMW_E_ARG, except
+ * mmw_get_heat_grids, which reports 0 grids.
+ *
+ * Setting grids follows mmw_set_stance_rules' rules: mmw_set_heat_grids gives scene scenes[i] (scenes == NULL: scene i) the first
+ * n_grids[i] (0 or 1) entries of grids[i][MMW_HEAT_GRIDS_MAX]; scenes never listed keep what they have.  Every check is made on the
+ * host before anything changes, the table travels as ONE copy ordered on the context's stream, and the call is synchronous.  Refused
+ * as a whole (MMW_E_ARG, the message names the entry, no scene's grid changes): n < 0 or n > n_scenes, n_grids or grids NULL with
+ * n > 0, a scene index out of range or listed twice, n_grids[i] outside 0 .. 1, a non-zero reserved_, an x0, y0 or cell that is not
+ * finite, cell <= 0, a max_gap that is NaN or <= 0 (+inf is allowed: every interval counts), nx < 1 or ny < 1, nx * ny (formed in 64
+ * bits) above the enabled capacity.  Cell (ix, iy) covers [x0 + ix * cell, x0 + (ix + 1) * cell) x [y0 + iy * cell, ...) and has index
+ * iy * nx + ix.  For the listed scenes the generation is bumped and every cell and calls, outside, t_first and t_last restart at 0,
+ * ordered on the stream: the geometry changed, so old cells mean nothing.  Grids and cells belong to the slot (the room), like a
+ * site: mmw_reset* and mmw_restore keep both and only bump the generation; a snapshot blob carries neither (format version 1 is
+ * unchanged).  mmw_get_heat_grids copies the host mirror (no device access; either output may be NULL; entries past n_grids are zero).
+ *
+ * mmw_heat_sample is asynchronous: ONE kernel on the context's stream behind whatever was queued last, normally once behind each
+ * mmw_step.  Scene flags, t and the ordinal are mmw_tripwires_sample's: scene s is ASKED when scene_flags == NULL or scene_flags[s]
+ * != 0, and t == NULL means the scene's call ordinal as a double -- the number of earlier mmw_heat_sample calls that asked this
+ * scene since mmw_heat_enable, with or without a grid.  An asked scene without a grid only sets seen = generation (and counts the
+ * call).  For an asked scene with a grid, in this order:
+ *   1. generation != seen: every slot is freed and seen = generation;
+ *   2. every slot whose owner is not among the live uids is freed;
+ *   3. every live uid without a slot takes a free one and is FRESH (which slot is not observable);
+ *   4. tt = the sample's t;  calls was 0: t_first = tt;  calls += 1;  t_last = tt;
+ *   5. for every live track, in effective_tracks order, with p = (x[0], x[1]) of the fp64 state:
+ *          fx = (px - x0) / cell;  fy = (py - y0) / cell                  one fp64 subtraction and one fp64 division each
+ *          inside = fx >= 0 && fx < (double)nx && fy >= 0 && fy < (double)ny          (a NaN makes it false)
+ *          c = inside ? (int)fy * nx + (int)fx : -1
+ *          c < 0: outside += 1
+ *          else:  samples[c] += 1
+ *                 visits[c] += 1 iff the track is fresh or last_cell != c
+ *                 not fresh: dt = tt - last_t;  dwell[c] = dwell[c] + dt iff dt > 0 && dt <= max_gap
+ *          last_cell = c;  last_t = tt
+ * The interval since a uid's previous sample is credited to the cell it is in NOW.  Several tracks in one cell add to dwell[c] one
+ * after another in list order: the fp64 sum is one defined sequence of additions (the library is built with -ffp-contract=off).  A
+ * track outside the grid keeps its slot: coming back counts a visit, and the interval it was away is credited like any other.  A
+ * scene that is not asked is not touched.  scene_flags: dev pointer, 4-byte aligned; t: dev pointer, 8-byte aligned; else MMW_E_ARG.
+ *
+ * mmw_heat_async / _wait write two buffers.  Rows: one per scene WITH a grid -- with scene_flags != NULL only those whose flag is
+ * non-zero -- scenes ascending; calls and outside count the samples since the counters last restarted, t_first / t_last are the t of
+ * the first and the newest of those calls (0 while calls == 0).  Cells: one mmw_heat_cell per cell of those scenes with samples > 0,
+ * in (scene, cell index) order; row i owns cells[first .. first + count).  scene is offset by scene_base in both.  With mode
+ * MMW_HEAT_KEEP the export is a pure function of the state: the same state can be exported under several tickets.  With
+ * MMW_HEAT_CLEAR, and only when everything fitted, the exported scenes' cells and their calls, outside, t_first and t_last restart at
+ * 0 behind the copy; the uid slots stay, so the next interval of somebody who is still sitting there is credited in the new window
+ * and counts no new visit -- hourly maps are cut without losing a frame.  Capacity is decided on the DEVICE against both caps, as
+ * the trails': totals are formed in 64 bits, saturate at INT32_MAX and then never fit; if anything does not fit, NOTHING is written,
+ * nothing is cleared and mmw_heat_wait returns MMW_E_CAPACITY with both counts needed.  mmw_heat_async queues its kernels on the
+ * context's stream; the counts follow into pinned memory and mmw_heat_wait(ticket) waits for THAT copy only.  ticket in [0,4),
+ * ticket 3 is mmw_heat's own.  rows / cells: dev pointers, 8-byte aligned; scene_flags: dev pointer, 4-byte aligned.  MMW_E_ARG,
+ * nothing touched: a NULL context, heat not enabled, a NULL buffer with a positive cap, a negative cap, a misaligned pointer, a mode
+ * other than the two, a bad ticket, a wait for a ticket with nothing outstanding.
+ *
+ * Life cycle.  mmw_reset, mmw_reset_scenes and mmw_restore bump the generation of the scenes they touch, with the same kernel as
+ * the report's, the zones', the trails', the tripwires' and stance's, launched only while heat is enabled: no interval is credited across them, no uid of before aliases one
+ * of after, and the cells are kept.  mmw_destroy frees the state.  More than INT32_MAX samples per cell are not supported. */
+#define MMW_HEAT_CELLS_MAX 4096
+#define MMW_HEAT_GRIDS_MAX 1
+typedef struct mmw_heat_grid {     /* 48 bytes */
+    double x0, y0;                 /* corner of cell (0, 0) in the frame of mmw_track_record.x[0], x[1] */
+    double cell;                   /* side of a cell, > 0 and finite */
+    double max_gap;                /* > 0, +inf allowed: an interval longer than this is credited to nobody */
+    int32_t nx, ny;                /* >= 1, nx * ny <= the enabled capacity */
+    int32_t id;                    /* caller's label, copied into the row */
+    int32_t reserved_;             /* must be 0 */
+} mmw_heat_grid;
+typedef struct mmw_heat_row  { int32_t scene, id, nx, ny, first, count, calls, outside; double t_first, t_last; } mmw_heat_row;   /* 48 bytes */
+typedef struct mmw_heat_cell { int32_t scene, cell, samples, visits; double dwell; } mmw_heat_cell;                               /* 24 bytes */
+#define MMW_HEAT_KEEP 0
+#define MMW_HEAT_CLEAR 1
+int mmw_heat_enable(mmw_ctx *ctx, int32_t cells);               /* 1 .. MMW_HEAT_CELLS_MAX per scene; 0 = off and freed */
+int mmw_set_heat_grids(mmw_ctx *ctx, const int32_t *scenes, int32_t n, const int32_t *n_grids /* host [n] */, const mmw_heat_grid *grids /* host [n][MMW_HEAT_GRIDS_MAX] */);
+int mmw_get_heat_grids(mmw_ctx *ctx, int32_t *n_grids /* host [S] */, mmw_heat_grid *grids /* host [S][MMW_HEAT_GRIDS_MAX] */);   /* host mirror, no device access */
+int mmw_heat_sample(mmw_ctx *ctx, const int32_t *scene_flags /* dev [S] or NULL */, const double *t /* dev [S] or NULL */);
+int mmw_heat_async(mmw_ctx *ctx, mmw_heat_row *rows, int32_t cap_rows, mmw_heat_cell *cells, int32_t cap_cells,
+                   const int32_t *scene_flags /* dev [S] or NULL = every scene */, int32_t mode, int32_t scene_base, int32_t ticket);
+int mmw_heat_wait(mmw_ctx *ctx, int32_t ticket, int32_t *n_rows, int32_t *n_cells);   /* waits for that ticket's counts only; either may be NULL */
+int mmw_heat(mmw_ctx *ctx, mmw_heat_row *rows, int32_t cap_rows, mmw_heat_cell *cells, int32_t cap_cells,
+             const int32_t *scene_flags, int32_t mode, int32_t scene_base, int32_t *n_rows, int32_t *n_cells);   /* async + wait */
+
 /* Snapshot / restore of scene state (format version 1).
  *
  * A snapshot is one contiguous blob that holds the state of any subset of a context's scenes (TrackBuffer + global

@@ -37,7 +37,7 @@ POSTURE_MODELS_MAX = 8             # models one mmw_posture_attach_models call t
 POSTURE_NONE = -1                  # MMW_POSTURE_NONE: the map entry of a scene no model estimates
 EXPORT_TICKETS = 4                 # kTickets (csrc/mmw_ctx.hpp): `*_async` calls of one export that may be outstanding; the
                                    # one-call form of each export (mmw_report, mmw_clouds, ...) uses the last ticket itself
-REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = TRAIL_TICKETS = TRIPWIRE_TICKETS = STANCE_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
+REPORT_TICKETS = CLOUD_TICKETS = SKEL_TICKETS = ZONE_TICKETS = TRAIL_TICKETS = TRIPWIRE_TICKETS = STANCE_TICKETS = HEAT_TICKETS = UART_LOG_TICKETS = SAMPLE_TICKETS = EXPORT_TICKETS   # (the names callers know)
 
 EMPTY_FRAME = -1   # MMW_EMPTY_FRAME (include/mmw.h)
 BAD_FRAME = -3     # MMW_BAD_FRAME: n_out of mmw_normalize_tlv for a TLV body it refused to decode
@@ -214,6 +214,18 @@ STANCE_ROW_DTYPE = np.dtype([("scene", "i4"), ("id", "i4"), ("upright", "i4"), (
 STANCE_EVENT_DTYPE = np.dtype([("scene", "i4"), ("uid", "i4"), ("kind", "i4"), ("from", "i4"), ("to", "i4"), ("slot", "i4"), ("t", "f8")], align=True)
 SEV_CHANGE, SEV_FALL, SEV_LONG_LIE, SEV_REBASED = 1, 2, 3, 4   # MMW_SEV_*: mmw_stance_event.kind
 
+# struct mmw_heat_grid / mmw_heat_row / mmw_heat_cell (include/mmw.h): a scene's grid (48 bytes), and the rows (48 bytes) and cells
+# (24 bytes) of mmw_heat_*
+HEAT_CELLS_MAX = 4096                         # MMW_HEAT_CELLS_MAX: cells a scene's grid has at the most
+HEAT_GRIDS_MAX = 1                            # MMW_HEAT_GRIDS_MAX: grids per scene
+HEAT_KEEP, HEAT_CLEAR = 0, 1                  # MMW_HEAT_*: the mode of mmw_heat_*
+HEAT_FIELDS = ("x0", "y0", "cell", "max_gap", "nx", "ny", "id")
+HEAT_GRID_DTYPE = np.dtype([("x0", "f8"), ("y0", "f8"), ("cell", "f8"), ("max_gap", "f8"), ("nx", "i4"), ("ny", "i4"), ("id", "i4"),
+                            ("reserved_", "i4")], align=True)
+HEAT_ROW_DTYPE = np.dtype([("scene", "i4"), ("id", "i4"), ("nx", "i4"), ("ny", "i4"), ("first", "i4"), ("count", "i4"), ("calls", "i4"),
+                           ("outside", "i4"), ("t_first", "f8"), ("t_last", "f8")], align=True)
+HEAT_CELL_DTYPE = np.dtype([("scene", "i4"), ("cell", "i4"), ("samples", "i4"), ("visits", "i4"), ("dwell", "f8")], align=True)
+
 
 # C struct name in include/mmw.h -> its Python mirror; every `typedef struct mmw_*` but the opaque mmw_ctx.  Field names are the
 # header's own throughout, so a mirror needs no second spelling beside it.
@@ -225,6 +237,7 @@ ABI_STRUCTS = {
     "mmw_trail_track": TRAIL_TRACK_DTYPE, "mmw_trail_point": TRAIL_POINT_DTYPE,
     "mmw_tripwire": TRIPWIRE_DTYPE, "mmw_tripwire_row": TRIPWIRE_ROW_DTYPE, "mmw_tripwire_event": TRIPWIRE_EVENT_DTYPE,
     "mmw_stance_rule": STANCE_RULE_DTYPE, "mmw_stance_row": STANCE_ROW_DTYPE, "mmw_stance_event": STANCE_EVENT_DTYPE,
+    "mmw_heat_grid": HEAT_GRID_DTYPE, "mmw_heat_row": HEAT_ROW_DTYPE, "mmw_heat_cell": HEAT_CELL_DTYPE,
     "mmw_snapshot_header": MmwSnapshotHeader, "mmw_snapshot_entry": MmwSnapshotEntry, "mmw_snapshot_info": MmwSnapshotInfo,
     "mmw_uart_cfg": MmwUartCfg, "mmw_uart_frame": UART_FRAME_DTYPE, "mmw_uart_object": UART_OBJECT_DTYPE,
     "mmw_sample_entry": SAMPLE_ENTRY_DTYPE,
@@ -356,6 +369,13 @@ def _signatures():
         "mmw_stance_async": (C.c_int, [vp, vp, i32, vp, i32, i32, i32]),
         "mmw_stance_wait": (C.c_int, [vp, i32, i32p, i32p]),
         "mmw_stance": (C.c_int, [vp, vp, i32, vp, i32, i32, i32p, i32p]),
+        "mmw_heat_enable": (C.c_int, [vp, i32]),
+        "mmw_set_heat_grids": (C.c_int, [vp, vp, i32, vp, vp]),
+        "mmw_get_heat_grids": (C.c_int, [vp, vp, vp]),
+        "mmw_heat_sample": (C.c_int, [vp, vp, vp]),
+        "mmw_heat_async": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32]),
+        "mmw_heat_wait": (C.c_int, [vp, i32, i32p, i32p]),
+        "mmw_heat": (C.c_int, [vp, vp, i32, vp, i32, vp, i32, i32, i32p, i32p]),
         "mmw_uart_open": (C.c_int, [vp, vp, i32, C.c_double]),
         "mmw_uart_close": (C.c_int, [vp]),
         "mmw_uart_read": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_double, vp, vp, vp, vp, vp]),
@@ -646,3 +666,31 @@ def make_stance_rules(per_scene):
             for f, v in zip(STANCE_FIELDS, vals):
                 rules[i, k][f] = v
     return n_rules, rules
+
+
+def make_heat_grids(per_scene):
+    """(n_grids int32[n], grids HEAT_GRID_DTYPE[n, HEAT_GRIDS_MAX]) for `mmw_set_heat_grids` from one list per scene of zero or one
+    grid, a dict with keys of HEAT_FIELDS (`max_gap` and `id` may be left out: +inf, and 0) or a tuple
+    (x0, y0, cell, max_gap, nx, ny[, id]).  An entry without a grid stays zero."""
+    per_scene = list(per_scene)
+    n_grids = np.zeros(len(per_scene), np.int32)
+    grids = np.zeros((len(per_scene), HEAT_GRIDS_MAX), HEAT_GRID_DTYPE)
+    for i, gs in enumerate(per_scene):
+        gs = list(gs)
+        if len(gs) > HEAT_GRIDS_MAX:
+            raise ValueError(f"make_heat_grids: scene entry {i} has {len(gs)} grids, at most {HEAT_GRIDS_MAX} fits")
+        n_grids[i] = len(gs)
+        for k, g in enumerate(gs):
+            if isinstance(g, dict):
+                unknown = set(g) - set(HEAT_FIELDS)
+                if unknown:
+                    raise AttributeError(f"mmw_heat_grid has no field {sorted(unknown)[0]!r}")
+                vals = [g["x0"], g["y0"], g["cell"], g.get("max_gap", float("inf")), g["nx"], g["ny"], g.get("id", 0)]
+            else:
+                g = tuple(g)
+                if not 6 <= len(g) <= 7:
+                    raise ValueError(f"make_heat_grids: a grid is (x0, y0, cell, max_gap, nx, ny[, id]), not {len(g)} values")
+                vals = list(g) + [0][len(g) - 6:]
+            for f, v in zip(HEAT_FIELDS, vals):
+                grids[i, k][f] = v
+    return n_grids, grids

@@ -1099,6 +1099,68 @@ class SceneBatch:
         return self._export_host("stance", lambda *a: self.stance_async(*a[:4], scene_base, a[4]), self.L.mmw_stance_wait,
                                  ("stance_rows", _lib.STANCE_ROW_DTYPE), ("stance_events", _lib.STANCE_EVENT_DTYPE))
 
+    # -- dwell heat maps ------------------------------------------------------
+    def enable_heat(self, cells: int):
+        """mmw_heat_enable: per scene a grid table (no grid to begin with), `cells` (1 .. `_lib.HEAT_CELLS_MAX`) cells of dwell time,
+        samples and visits, and per live uid its last cell and time; everything starts over, also when heat was enabled before.
+        16 bytes a cell and scene: 4096 scenes x 1024 cells are 67 MB.  Until enabled, the heat calls are refused (E_ARG) --
+        `get_heat_grids()` reports 0 grids -- and the context launches nothing of them."""
+        if int(cells) == 0:
+            raise ValueError("enable_heat: cells must be positive (disable_heat() frees the maps)")
+        self._chk(self.L.mmw_heat_enable(self.h, int(cells)))
+
+    def disable_heat(self):
+        """mmw_heat_enable(0): waits for the stream and frees the maps; the context launches what one without heat does."""
+        self._chk(self.L.mmw_heat_enable(self.h, 0))
+
+    def set_heat_grids(self, grids, scenes=None):
+        """mmw_set_heat_grids: give `scenes` (default: scenes 0 .. len(grids)-1) their grid -- `grids` is what `_lib.make_heat_grids`
+        takes (a list per scene of zero or one dict or tuple) or its result, the pair (n_grids, HEAT_GRID_DTYPE[n, 1]).  Scenes never
+        listed keep what they have; the listed scenes' cells and counters restart at 0 and no interval is credited across the call.
+        Refused (MmwError, E_ARG) with nothing changed for an index out of range or listed twice, more entries than scenes, an x0, y0
+        or cell that is not finite, cell <= 0, a max_gap that is NaN or <= 0, nx or ny < 1, more cells than were enabled, or a
+        non-zero `reserved_`."""
+        self._set_scene_table("set_heat_grids", "grids", self.L.mmw_set_heat_grids, _lib.make_heat_grids, _lib.HEAT_GRID_DTYPE,
+                              _lib.HEAT_GRIDS_MAX, grids, scenes)
+
+    def get_heat_grids(self):
+        """mmw_get_heat_grids: (n_grids int32[S], grids HEAT_GRID_DTYPE[S, 1]) of every scene, from the host mirror; zero where a
+        scene has no grid or heat is off."""
+        return self._get_scene_table(self.L.mmw_get_heat_grids, _lib.HEAT_GRID_DTYPE, _lib.HEAT_GRIDS_MAX)
+
+    def sample_heat_dev(self, flags_ptr=None, t_ptr=None):
+        """mmw_heat_sample: every live track of the asked scenes with a grid adds a sample, maybe a visit, and the time since its
+        previous sample to the cell it is in, queued behind the last step on the context's stream -- no host wait.  `flags_ptr`:
+        device int32[S] (None = every scene), `t_ptr`: device float64[S] (None = the scenes' call ordinals)."""
+        self._chk(self.L.mmw_heat_sample(self.h, flags_ptr, t_ptr))
+
+    def sample_heat(self, t=None, scenes=None):
+        """`sample_heat_dev` from host arrays: `t` float64[S] or a scalar for every scene (None = the call ordinals), `scenes` the
+        scenes to sample (default all)."""
+        self._sample(self.sample_heat_dev, "heat", t, scenes)
+
+    def heat_dev(self, rows_ptr, cap_rows: int, cells_ptr, cap_cells: int, clear: bool = False, flags_ptr=None, scene_base: int = 0, ticket: int = 0):
+        """mmw_heat_async: one `_lib.HEAT_ROW_DTYPE` row per scene with a grid (with `flags_ptr`, device int32[S]: of the flagged
+        scenes) and one `_lib.HEAT_CELL_DTYPE` entry per cell of theirs with samples > 0, in (scene, cell) order, into device buffers;
+        row i owns cells[first : first + count].  clear=True restarts what was exported at 0 -- when everything fitted.  Queued on
+        the context's stream -- no host wait.  Tickets 0 .. 3 (`heat_host` uses 3).  Both buffers 8-byte aligned."""
+        self._chk(self.L.mmw_heat_async(self.h, rows_ptr, int(cap_rows), cells_ptr, int(cap_cells), flags_ptr,
+                                        _lib.HEAT_CLEAR if clear else _lib.HEAT_KEEP, int(scene_base), int(ticket)))
+
+    def heat_wait(self, ticket: int = 0):
+        """(n_rows, n_cells) of the `heat_dev` call with this ticket: waits for its counts only, not for the stream.  Buffers too
+        small: MmwError with code E_CAPACITY and the counts needed in `.needed` -- nothing was written and nothing was cleared."""
+        return self._export_wait(self.L.mmw_heat_wait, ticket)
+
+    def heat_host(self, clear: bool = False, scenes=None, scene_base: int = 0):
+        """The heat export as two structured arrays: (rows[n_rows] HEAT_ROW_DTYPE, cells[n_cells] HEAT_CELL_DTYPE); `heat.dense`
+        makes an (ny, nx) map of a scene, `heat.Accumulator` folds clear=True windows.  The buffers grow to what the device says it
+        needs (a refused export clears nothing)."""
+        self._export_caps.setdefault("heat", (64, 4096))   # (its entry exists from the first call on, as the zones')
+        flags_ptr = self._scene_flags(scenes, "heat_export_flags")
+        return self._export_host("heat", lambda *a: self.heat_dev(*a[:4], clear, flags_ptr, scene_base, a[4]), self.L.mmw_heat_wait,
+                                 ("heat_rows", _lib.HEAT_ROW_DTYPE), ("heat_cells", _lib.HEAT_CELL_DTYPE))
+
     # -- snapshot / restore ---------------------------------------------------
     def _scene_list(self, scenes):
         if scenes is None:

@@ -413,6 +413,7 @@ int mmw_destroy(mmw_ctx *c)
     trail_free(c);
     tripwire_free(c);
     stance_free(c);
+    heat_free(c);
     uart_log_free(c);
     if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->side_gate) hipEventDestroy(c->side_gate);

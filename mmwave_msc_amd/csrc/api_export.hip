@@ -66,11 +66,11 @@ int pair_export_wait(mmw_ctx *c, ExportCtx &x, const PairExport &d, int ticket, 
     MMW_TRY(export_wait(c, x, ticket, name.c_str(), d.none, &h));
     if (n_rows) *n_rows = h[0];
     if (n_events) *n_events = h[1];
-    if (!h[2]) return fail(c, MMW_E_CAPACITY, "%s: %d %s and %d events %s", d.entry, h[0], d.rows, h[1], d.unfit);
+    if (!h[2]) return fail(c, MMW_E_CAPACITY, "%s: %d %s and %d %s %s", d.entry, h[0], d.rows, h[1], d.second, d.unfit);
     return MMW_OK;
 }
 
-// What mmw_trails_sample, mmw_tripwires_sample and mmw_stance_sample check before they launch: `entry` ("mmw_trails") is enabled -- x is its export
+// What mmw_trails_sample, mmw_tripwires_sample, mmw_stance_sample and mmw_heat_sample check before they launch: `entry` ("mmw_trails") is enabled -- x is its export
 // state, `what` its noun in the message -- and the two optional device arrays are aligned.  Leaves the context's device current.
 int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t)
 {
@@ -81,14 +81,17 @@ int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *
 }
 
 // mmw_reset / mmw_reset_scenes / mmw_restore: uids restart in the scenes flagged in dev_flags (device, [n_scenes]; nullptr = every
-// scene), so the report's baseline, the zones' memberships, the trails, the tripwires' sides and the stance classes of those scenes are void.  One launch for the consumers
-// that are on, queued on the context's stream behind the kernel that emptied or refilled the scenes; nothing at all while none is.
+// scene), so the report's baseline, the zones' memberships, the trails, the tripwires' sides, the stance classes and the heat maps' last cells of those scenes are void.  One launch for the
+// five consumers of UidGens that are on, queued on the context's stream behind the kernel that emptied or refilled the scenes, and one
+// for the heat maps' word while they are on (a launch takes UidGens::kMax = 5 words, and a reset is rare); nothing at all while none is.
 int uid_rebase(mmw_ctx *c, const int32_t *dev_flags)
 {
     const UidGens g = {{c->rep.d_block ? c->rs.base.ug.gen : nullptr, c->zone.d_block ? c->zs.base.ug.gen : nullptr, c->trail.d_block ? c->ts.ug.gen : nullptr,
                        c->trip.d_block ? c->tw.ug.gen : nullptr, c->stance.d_block ? c->ss.ug.gen : nullptr}};
-    if (!g.gen[0] && !g.gen[1] && !g.gen[2] && !g.gen[3] && !g.gen[4]) return MMW_OK;
-    launch_uid_rebase(c->dc.n_scenes, dev_flags, g, c->stream);
+    const bool five = g.gen[0] || g.gen[1] || g.gen[2] || g.gen[3] || g.gen[4];
+    if (!five && !c->heat.d_block) return MMW_OK;
+    if (five) launch_uid_rebase(c->dc.n_scenes, dev_flags, g, c->stream);
+    if (c->heat.d_block) launch_uid_rebase(c->dc.n_scenes, dev_flags, UidGens{{c->hs.ug.gen, nullptr, nullptr, nullptr, nullptr}}, c->stream);
     HIPCHK(c, hipGetLastError());
     return MMW_OK;
 }

@@ -69,7 +69,7 @@ struct ExportCtx {
     bool issued[kTickets] = {false, false, false, false};
 };
 
-// A per-scene table of up to MAX caller entries E a scene (mmw_set_zones, mmw_set_tripwires, mmw_set_stance_rules; mmw_scene_table.hpp has the code): the
+// A per-scene table of up to MAX caller entries E a scene (mmw_set_zones, mmw_set_tripwires, mmw_set_stance_rules, mmw_set_heat_grids; mmw_scene_table.hpp has the code): the
 // device allocation, which holds the table as the kernels read it (entries D) and in which every set call lands as ONE copy, and
 // the host mirrors of what the caller gave.  d_tab == nullptr: not allocated.
 template <class E, class D, int MAX>
@@ -155,6 +155,9 @@ struct mmw_ctx {
     ExportCtx stance;                 // mmw_stance_enable allocates it (log_depth 0 frees it); not allocated = stance is off, nothing of it is launched
     StanceState ss = {};              // ... the uid slots, counters and event rings, in front of stance's scratch in stance.d_block (ss.sc = stance.sc)
     SceneTable<mmw_stance_rule, StanceRule, MMW_STANCE_RULES_MAX> sttab;   // ... the rule table: what the kernels read is derived on the host (mmw_get_stance_rules reads the mirrors)
+    ExportCtx heat;                   // mmw_heat_enable allocates it (cells 0 frees it); not allocated = heat is off, nothing of it is launched
+    HeatState hs = {};                // ... the cells, uid slots and scene words, in front of heat's scratch in heat.d_block (hs.sc = heat.sc)
+    SceneTable<mmw_heat_grid, HeatGrid, MMW_HEAT_GRIDS_MAX> htab;   // ... the grid table: what the kernels read is what the caller gave (mmw_get_heat_grids reads the mirrors)
     ExportCtx ulog_x;                 // mmw_uart_log_enable; not allocated = the radar log is off and mmw_uart_read launches what it always did
     UartLog ulog = {};                // ... the staged frames, in front of ulog_x's scratch in ulog_x.d_block
     std::vector<double> uart_range;   // [S] rangeIdxToMeters of the open readers (the log's range column)
@@ -177,6 +180,7 @@ void posture_batch_free(PostureBatch *b);                          // api_postur
 void zone_free(mmw_ctx *c);                                        // api_zone.hip: table, baseline and mirrors (the caller has waited for the stream)
 void tripwire_free(mmw_ctx *c);                                    // api_tripwire.hip: table, slots, counters, rings and mirrors (the caller has waited for the stream)
 void stance_free(mmw_ctx *c);                                      // api_stance.hip: table, slots, counters, rings and mirrors (the caller has waited for the stream)
+void heat_free(mmw_ctx *c);                                        // api_heat.hip: table, cells, slots and mirrors (the caller has waited for the stream)
 void trail_free(mmw_ctx *c);                                     // api_trail.hip: slots, rings and scratch (the caller has waited for the stream)
 int uart_log_rearm(mmw_ctx *c);                                    // api_uart_log.hip: every scene's log word as new, with its range scale (no-op while the log is off)
 void uart_log_free(mmw_ctx *c);                                    // api_uart_log.hip: ... and the log is off (the caller has waited for the stream)
@@ -185,16 +189,16 @@ int export_alloc(mmw_ctx *c, ExportCtx &x, size_t extra_words, const char *name)
 void export_free(ExportCtx &x);                                    // ... and x is as never allocated
 int export_issue(mmw_ctx *c, ExportCtx &x, int ticket);           // behind the launch: its error, the totals into the ticket's pinned slot, the event
 int export_wait(mmw_ctx *c, ExportCtx &x, int ticket, const char *name, const char *none, const int32_t **counts);   // -> the ticket's four words
-// ... and the front end of the exports with two caller buffers, rows and events (mmw_report_*, mmw_zones_*, mmw_tripwires_*, mmw_stance_*).
+// ... and the front end of the exports with two caller buffers, rows and events (mmw_report_*, mmw_zones_*, mmw_tripwires_*, mmw_stance_*; mmw_heat_*: rows and cells).
 // The messages are built from the entry's words: "<entry>: <off>" while x is not allocated, "<entry>_wait: <none> outstanding under
-// ticket k", and for MMW_E_CAPACITY "<entry>: n <rows> and m events <unfit>".  align: what both buffers must be aligned to, 0 = anything.
-struct PairExport { const char *entry, *off, *none, *rows, *unfit; int align; };
+// ticket k", and for MMW_E_CAPACITY "<entry>: n <rows> and m <second> <unfit>".  align: what both buffers must be aligned to, 0 = anything.
+struct PairExport { const char *entry, *off, *none, *rows, *unfit; int align; const char *second = "events"; };   // second: the noun of the second buffer's entries
 constexpr const char *kUnfitLog = "do not fit the buffers: nothing was written, nothing was taken";               // a log is drained: tripwires, stance
 constexpr const char *kUnfitBaseline = "do not fit the buffers: nothing was written, the baseline is unchanged";   // two states are compared: report, zones
 int pair_export_begin(mmw_ctx *c, const ExportCtx &x, const PairExport &d, const void *rows, int cap_rows, const void *events, int cap_events, int ticket);   // before the launch: enabled, capacities, pointers, alignment, ticket; device set
 int pair_export_wait(mmw_ctx *c, ExportCtx &x, const PairExport &d, int ticket, int32_t *n_rows, int32_t *n_events);   // export_wait, the two counts out (either may be NULL), MMW_E_CAPACITY if the device decided so
-int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t);   // mmw_trails_sample / mmw_tripwires_sample / mmw_stance_sample: enabled, aligned, device set
-int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones, trails, tripwires and stance, none while all five are off
+int sample_begin(mmw_ctx *c, const ExportCtx &x, const char *entry, const char *what, const int32_t *scene_flags, const double *t);   // mmw_trails_sample / mmw_tripwires_sample / mmw_stance_sample / mmw_heat_sample: enabled, aligned, device set
+int uid_rebase(mmw_ctx *c, const int32_t *dev_flags);             // the flagged scenes' uids restart: one launch for report, zones, trails, tripwires and stance, one for heat, none while all six are off
 #pragma GCC visibility pop
 
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, MMW_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); } while (0)

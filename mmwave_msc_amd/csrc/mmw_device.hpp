@@ -255,6 +255,25 @@ struct StanceState {
     UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
     ExportScratch sc;          // rows / events of the export in flight
 };
+// mmw_heat_enable: the grid table and what the heat maps keep from one mmw_heat_sample to the next (k_heat.hip).  All device memory.
+// A table entry is the caller's mmw_heat_grid as it is (the host only checks it).  The first state here that is a dense per-scene
+// array: `cells` cells a scene, three arrays over [S][cells] (a wave strides over a scene's words).  A uid's last cell and time lie
+// in the slot that the one slot table (UidSlots, mmw_uidlist.hpp) gives it.
+struct HeatGrid { double x0, y0, cell, max_gap; int32_t nx, ny, id, pad_; };   // 48 bytes
+struct HeatScene { int32_t calls, outside; double t_first, t_last; };          // since the counters last restarted (set call, CLEAR export)
+struct HeatState {
+    int32_t cells;             // cell capacity per scene, 1 .. MMW_HEAT_CELLS_MAX
+    const HeatGrid *grids;     // [S][MMW_HEAT_GRIDS_MAX] the table (one copy of mmw_set_heat_grids; read with scalar loads)
+    const int32_t *n_grids;    // [S] 0 or 1, behind the table in the same allocation
+    double *dwell;             // [S][cells] time credited to the cell
+    int32_t *samples;          // [S][cells] samples taken in it ...
+    int32_t *visits;           // [S][cells] ... of which began a stay
+    int32_t *last_cell;        // [S][t_cap] the slot's uid's cell at its newest sample, -1 = outside
+    double *last_t;            // [S][t_cap] ... and that sample's t
+    HeatScene *scene;          // [S] lane 0 of a scene's wave owns it
+    UidSlots ug;               // the scenes' uid generation and the slot table that belongs to it: owner, call ordinal
+    ExportScratch sc;          // rows / cells of the export in flight
+};
 
 // The live list of scene s, as every export walks it: T = live_tracks lanes, lane -> live_slot -> the scene's TrackRec.  Both are
 // clamped into range, so a damaged state gives the same list -- report row i, cloud entry i, skeleton i -- in every export.

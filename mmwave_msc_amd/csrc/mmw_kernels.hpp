@@ -15,6 +15,7 @@ struct ZoneState;
 struct TrailState;
 struct TripState;
 struct StanceState;
+struct HeatState;
 struct UartState;
 struct UartLog;
 struct ExportScratch;
@@ -63,7 +64,7 @@ void launch_clear_errors(const DevCfg &cfg, const DevState &s, const int32_t *fl
 void launch_set_batch_size(const DevCfg &cfg, const DevState &s, const int32_t *flags, int new_size, hipStream_t st);
 // k_scan.hip: the scan step of the live-track exports below -- two count arrays to offsets, totals and the capacity decision
 void launch_pair_scan(int S, int32_t *off, int32_t *totals, int cap0, int cap1, hipStream_t st);
-// ... and the generation bump of those that remember uids (report, zones, trails, tripwires, stance): every non-null word, for the scenes flagged
+// ... and the generation bump of those that remember uids (report, zones, trails, tripwires, stance, heat): every non-null word, for the scenes flagged
 // (flags: dev [S] or nullptr = every scene)
 struct UidGens { static constexpr int kMax = 5; int32_t *gen[kMax]; };
 void launch_uid_rebase(int n_scenes, const int32_t *flags, const UidGens &gens, hipStream_t st);
@@ -87,6 +88,11 @@ void launch_tripwires(const DevCfg &cfg, const TripState &ts, mmw_tripwire_row *
 void launch_stance_zero(int n_scenes, const int32_t *flags, const StanceState &ss, hipStream_t st);
 void launch_stance_sample(const DevCfg &cfg, const DevState &s, const StanceState &ss, const int32_t *flags, const double *t, hipStream_t st);
 void launch_stance(const DevCfg &cfg, const StanceState &ss, mmw_stance_row *rows, int cap_rows, mmw_stance_event *events, int cap_events, int scene_base, hipStream_t st);
+// k_heat.hip: the dwell heat maps (flags, t as launch_trail_sample's; launch_heat_zero: the flagged scenes' cells and scene words, flags: dev [S];
+// launch_heat: scene_flags dev [S] or nullptr = every scene, mode MMW_HEAT_KEEP / MMW_HEAT_CLEAR)
+void launch_heat_zero(int n_scenes, const int32_t *flags, const HeatState &hs, hipStream_t st);
+void launch_heat_sample(const DevCfg &cfg, const DevState &s, const HeatState &hs, const int32_t *flags, const double *t, hipStream_t st);
+void launch_heat(const DevCfg &cfg, const HeatState &hs, mmw_heat_row *rows, int cap_rows, mmw_heat_cell *cells, int cap_cells, const int32_t *scene_flags, int mode, int scene_base, hipStream_t st);
 // k_uart.hip: the device-resident radar readers (log: the radar log while it is enabled -- k_uart_read's LOG = true instantiations --, else nullptr)
 void launch_uart_read(const DevCfg &cfg, const mmw_scene_site *sites, const UartState &us, const UartLog *log, const uint8_t *chunks, const long long *chunk_off, long long chunks_bytes, const int32_t *flags, double now, double *out, int32_t *n_out, double *dt_out, int32_t *status, uint32_t *frame_number, hipStream_t st);
 void launch_uart_set_time(const DevCfg &cfg, const UartState &us, const int32_t *flags, double t, hipStream_t st);

@@ -1,4 +1,5 @@
-// mmw_scene_table.hpp -- the per-scene tables of the C-ABI (mmw_set_zones / mmw_get_zones, mmw_set_tripwires / mmw_get_tripwires, mmw_set_stance_rules / mmw_get_stance_rules):
+// mmw_scene_table.hpp -- the per-scene tables of the C-ABI (mmw_set_zones / mmw_get_zones, mmw_set_tripwires / mmw_get_tripwires, mmw_set_stance_rules / mmw_get_stance_rules,
+// mmw_set_heat_grids / mmw_get_heat_grids):
 // one allocation, one check of a set call's arguments, one way a new table reaches the device, one getter.  Host code only; the
 // state is SceneTable (mmw_ctx.hpp).  What differs between the tables comes from the caller: the names the messages speak with,
 // the check of one entry and what the device reads of it.

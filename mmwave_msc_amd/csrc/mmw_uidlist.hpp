@@ -1,6 +1,6 @@
-// mmw_uidlist.hpp -- what the by-uid consumers of the live-track list share (k_report.hip, k_zone.hip, k_trail.hip, k_tripwire.hip, k_stance.hip):
+// mmw_uidlist.hpp -- what the by-uid consumers of the live-track list share (k_report.hip, k_zone.hip, k_trail.hip, k_tripwire.hip, k_stance.hip, k_heat.hip):
 // the words that say whether a scene's uids are still the ones a consumer remembers, the remembered list itself (report, zones), the
-// SLOT TABLE that keeps a word set per live uid from one sample call to the next (trails, tripwires, stance), and the match of two unsorted
+// SLOT TABLE that keeps a word set per live uid from one sample call to the next (trails, tripwires, stance, heat), and the match of two unsorted
 // uid lists held one entry per lane.  Registers only; a wave per scene, a lane per entry (t_cap <= 64).  (This lane's live uid is
 // live_uid, beside live_tracks and live_slot in mmw_device.hpp, which includes this header for the structs.)
 #pragma once
@@ -62,7 +62,7 @@ __device__ __forceinline__ int uid_find(int key, int other, int n)
 }
 
 // The SLOT TABLE of a consumer that keeps words per live uid between its sample calls (trails: the ring and its totals; tripwires:
-// the side word; stance: the class word and two times).  A scene has t_cap slots; a slot belongs to one uid or is free, and which slot a uid has is not visible outside.
+// the side word; stance: the class word and two times; heat: the last cell and its time).  A scene has t_cap slots; a slot belongs to one uid or is free, and which slot a uid has is not visible outside.
 // Lane j of the scene's wave holds slot j's words, lane i track i's uid.  The slot rule of a sample call:
 //   1. a uid of another generation owns nothing (the scene was rebased: every slot counts as free);
 //   2. a slot whose uid is live is kept, every other slot is free;
