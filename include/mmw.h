@@ -284,6 +284,11 @@ int mmw_normalize_f32(mmw_ctx *ctx, const float *raw, const int32_t *n_raw, doub
  *   A scene with n_pts[s] == 0 is skipped entirely (offline_main.py:56 never calls track() on an empty frame);
  *   n_pts[s] == MMW_EMPTY_FRAME is track() called ON an empty point cloud: tracks are predicted, aged and expired,
  *   _update_all runs, an empty frame enters the ring (what the reference does when a caller does call it).
+ *   dt[s] may be ANY FINITE double, per scene and per frame: zero (two frames with one timestamp) and negative (a clock that
+ *   stepped back) included, as well as minutes and hours.  The predict runs with lifetime + dt (Tracking.py:372-385: F and Q
+ *   are built from that sum, which may itself be zero or negative), an unassigned track's lifetime becomes lifetime + dt and
+ *   the track expires when that is > its limit (Tracking.py:513-528); every layout does this arithmetic in the oracle's order,
+ *   bit for bit (tests/test_gpu_dt.py).  What a NaN or infinite dt does is not pinned.
  * Outputs (dev, each may be NULL):
  *   assoc[S][max_pts]      _calc_dist_fun result: -1 = None, else index into the
  *                          track list as it was BEFORE _maintain_tracks (Tracking.py:530-574)

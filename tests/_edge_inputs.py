@@ -18,6 +18,9 @@ The fuzz scenes see only what track() decided, and a random point sits about 1e1
                   `T < tr_max_tracks`, `total > model_min_input`, 64 | 65 and ring_rows | ring_rows + 1 rows in a frame, each
                   with constants that make the equality exact in binary -- and asserted to be, here, on the oracle; and
                   `feature_ties`: equal x among a track's rows, and x equal to the centroid's, in the feature maps' sort
+  dt_edges        frame intervals that are NOT exact in binary or lie far outside 0.05 .. 0.2 s: 0.1 + 0.2 > 0.3 == 0.15 + 0.15
+                  against a lifetime limit of 0.3, lifetime + dt == 0, five frames of dt = 0, a 60 s predict with rows an ulp
+                  inside and outside its gate (tests/test_gpu_dt.py)
 
 Everything is seeded, fp64, built once, cached and read-only.  Rows of the input buffer at and beyond a frame's count are
 copies of rows that lie well inside a gate: a kernel that gates a row past n changes point_num and the centroid."""
@@ -111,7 +114,7 @@ def replay(scene, upto=None, **cfg_over):
         if c == 0:
             out.append(None)
             continue
-        a, lab = orc.track(scene.pts[f, :c], float(scene.dt[f]))
+        a, lab = orc.track(scene.pts[f, : max(c, 0)], float(scene.dt[f]))      # (c == -1: track() on an empty cloud)
         trk = orc.tracks()
         feat, owner = orc.features()
         rings = [[orc.track_ring_frame(t, k) for k in range(trk[t]["ring_len"])] for t in range(len(trk))]
@@ -673,8 +676,193 @@ def equality_groups():
     return list(groups.values())
 
 
+# ------------------------------------------------------------------------------------------------- frame-interval edges
+def _dt_scene(tag, cfg_kw, frames, dts, filler, max_pts=128):
+    """_scene with an interval per frame; a frame given as None is track() on an empty cloud (cnt == -1, MMW_EMPTY_FRAME)."""
+    assert len(dts) == len(frames)
+    pts = np.stack([_fill(max_pts, np.zeros((0, 8)) if r is None else r, filler) for r in frames])
+    cnt = np.array([-1 if r is None else len(r) for r in frames], np.int32)
+    dts = np.array(dts, dtype=np.float64)
+    _ro(pts, cnt, dts)
+    return Scene(tag, dict(cfg_kw), max_pts, pts, cnt, dts)
+
+
+def _two_clusters(seed):
+    """A dynamic and a static cluster (tr_vel_thres = 0.3125), as _lifetimes: tracks 0 and 1 of the scene."""
+    rng = np.random.default_rng(seed)
+    dyn = _exact_cluster(rng, (-2.0, 2.0, 1.0), 16, (0.5, 0.25, 0.0))
+    sta = _exact_cluster(rng, (1.0, 3.0, 1.0), 16, (0.0, 0.0, 0.0))
+    return np.concatenate([dyn, sta]), sta
+
+
+LIFETIME_SUM = 0.3     # 0.1 + 0.2 > 0.3 == 0.15 + 0.15 in binary64
+
+
+def _lifetime_sums(dim_x, which):
+    """`lifetime > lim` where the sums are NOT exact (Tracking.py:513-528), lim = 0.3 for the `which` ("dynamic" | "static") track
+    and 0.75 for the other; both lose their points after frame 0.  Intervals 0.1, 0.2: 0.30000000000000004 > 0.3, dropped on the
+    second frame.  Intervals 0.15, 0.15: == 0.3, kept; a frame of 2^-60 is absorbed (0.3 + 2^-60 == 0.3: half an ulp of 0.3 is
+    2^-55), kept again; a frame of one ulp, 2^-54, drops it.  The predicts run with lifetime + dt = 0.1, 0.1 + 0.2, 0.15, 0.15 + 0.15."""
+    e = 0 if which == "dynamic" else 1
+    lims = {"tr_lifetime_dynamic": (LIFETIME_SUM, 0.75)[e], "tr_lifetime_static": (0.75, LIFETIME_SUM)[e]}
+    kw = dict(EQ_KW, dim_x=int(dim_x), tr_vel_thres=0.3125, **lims)
+    f0, sta = _two_clusters(21)
+    over = _dt_scene(f"{which} lifetime 0.1 + 0.2", kw, [f0] + [_LONE] * 3, [EQ_DT, 0.1, 0.2, 0.1], sta)
+    equal = _dt_scene(f"{which} lifetime 0.15 + 0.15", kw, [f0] + [_LONE] * 5, [EQ_DT, 0.15, 0.15, 2.0 ** -60, 2.0 ** -54, 0.1], sta)
+    assert 0.1 + 0.2 > LIFETIME_SUM and 0.15 + 0.15 == LIFETIME_SUM
+    assert LIFETIME_SUM + 2.0 ** -60 == LIFETIME_SUM and LIFETIME_SUM + 2.0 ** -54 == np.nextafter(LIFETIME_SUM, 1.0)
+
+    def check_over(fr):
+        assert fr[0].n_tracks == 2 and list(fr[0].tracks["is_static"]) == [0, 1]
+        assert all(np.all(fr[f].assoc == -1) for f in range(1, 4))
+        assert fr[1].n_tracks == 2 and list(fr[1].tracks["lifetime"]) == [0.1, 0.1]
+        assert fr[2].n_tracks == 1 and fr[2].tracks["is_static"][0] == 1 - e and fr[2].tracks["lifetime"][0] == 0.1 + 0.2   # > 0.3: dropped
+        assert fr[3].n_tracks == 1
+
+    def check_equal(fr):
+        assert fr[0].n_tracks == 2 and list(fr[0].tracks["is_static"]) == [0, 1]
+        assert all(np.all(fr[f].assoc == -1) for f in range(1, 6))
+        assert fr[2].n_tracks == 2 and list(fr[2].tracks["lifetime"]) == [LIFETIME_SUM] * 2                     # == 0.3: kept
+        assert fr[3].n_tracks == 2 and list(fr[3].tracks["lifetime"]) == [LIFETIME_SUM] * 2                     # 2^-60: absorbed
+        assert fr[4].n_tracks == 1 and fr[4].tracks["is_static"][0] == 1 - e and fr[4].tracks["lifetime"][0] > LIFETIME_SUM
+        assert fr[5].n_tracks == 1
+    return {f"{which}_sum_over": Equality(over, check_over), f"{which}_sum_equal": Equality(equal, check_equal)}
+
+
+_STILL_KW = dict(EQ_KW, tr_lifetime_dynamic=0.5, tr_lifetime_static=0.75, tr_vel_thres=0.3125)
+
+
+def _dtm_zero(dim_x):
+    """lifetime + dt == 0: both tracks go unassigned for one frame of 0.125, then track() on an empty cloud with dt = -0.125: the
+    predict runs with F = I and Q = Q(0) (kf_q_std on the last diagonal entry of every 3 x 3 block, nothing else), the lifetime is
+    +0.0 again; a frame with the clusters' rows follows.  The twin with dt = +0.125 on the empty frame ends in another state."""
+    kw = dict(_STILL_KW, dim_x=int(dim_x))
+    f0, sta = _two_clusters(22)
+    scene = _dt_scene("lifetime + dt == 0", kw, [f0, _LONE, None, f0], [EQ_DT, 0.125, -0.125, 0.125], sta)
+    twin = _dt_scene("lifetime + dt == 0.25", kw, [f0, _LONE, None, f0], [EQ_DT, 0.125, 0.125, 0.125], sta)
+
+    def check(fr):
+        assert fr[1].n_tracks == 2 and list(fr[1].tracks["lifetime"]) == [0.125, 0.125] and 0.125 + -0.125 == 0.0
+        assert fr[2].n_tracks == 2 and len(fr[2].assoc) == 0
+        assert fr[2].tracks["lifetime"].tobytes() == np.zeros(2).tobytes()                     # +0.0, by its bits
+        assert set(fr[3].assoc.tolist()) == {0, 1}                                             # both take their rows again
+        other = replay(twin)
+        assert list(other[2].tracks["lifetime"]) == [0.25, 0.25]
+        for f in (2, 3):
+            assert not np.array_equal(other[f].tracks["P"], fr[f].tracks["P"]) and not np.array_equal(other[f].tracks["x"], fr[f].tracks["x"])
+    return {"dtm_zero": Equality(scene, check)}
+
+
+def _stands_still(dim_x):
+    """Five empty frames of dt = 0 leave the lifetime (0.125) and both tracks where they were; then a frame of the dynamic limit plus
+    2^-50 drops the dynamic track.  The sharp form: a frame of lim - 0.125 brings the lifetime to == lim, kept, and a frame of 2^-50
+    drops it."""
+    kw = dict(_STILL_KW, dim_x=int(dim_x))
+    lim = kw["tr_lifetime_dynamic"]
+    f0, sta = _two_clusters(23)
+    head, hdt = [f0, _LONE] + [None] * 5, [EQ_DT, 0.125] + [0.0] * 5
+    plain = _dt_scene("lifetime stands still", kw, head + [_LONE, _LONE], hdt + [lim + 2.0 ** -50, 0.0], sta)
+    sharp = _dt_scene("lifetime stands still, then == lim", kw, head + [_LONE, None, _LONE], hdt + [lim - 0.125, 2.0 ** -50, 0.0], sta)
+    assert 0.125 + (lim - 0.125) == lim and lim + 2.0 ** -50 > lim
+
+    def still(fr):
+        for f in range(1, 7):
+            assert fr[f].n_tracks == 2 and list(fr[f].tracks["lifetime"]) == [0.125, 0.125] and np.all(fr[f].assoc == -1), f
+        assert not np.array_equal(fr[5].tracks["P"], fr[6].tracks["P"])                        # (the filter goes on: predict and update)
+
+    def check_plain(fr):
+        still(fr)
+        assert fr[7].n_tracks == 1 and fr[7].tracks["is_static"][0] == 1 and fr[7].tracks["lifetime"][0] == 0.125 + (lim + 2.0 ** -50)
+        assert fr[8].n_tracks == 1
+
+    def check_sharp(fr):
+        still(fr)
+        assert fr[7].n_tracks == 2 and list(fr[7].tracks["lifetime"]) == [lim, lim]               # == lim: kept
+        assert fr[8].n_tracks == 1 and fr[8].tracks["is_static"][0] == 1 and fr[8].tracks["lifetime"][0] == lim + 2.0 ** -50
+        assert fr[9].n_tracks == 1
+    return {"stands_still": Equality(plain, check_plain), "stands_still_sharp": Equality(sharp, check_sharp)}
+
+
+LONG_DT = 60.0
+LONG_RAYS = 12
+
+
+def _long_predict(dim_x):
+    """A predict over 60 s that is then gated.  Frame 0 makes one dynamic track; frame 1 comes 60 s later.  Its rows, per ray from the
+    oracle's predicted position of the track (x + 60 v; P has grown by dtm^2 and Q(60) by dtm^4 / 4): the position itself and the
+    point half-way to the gate surface -- taken --, the last double inside and the first outside (bisection on the oracle, as
+    gate_probes), and the point one gate radius further out -- refused.  tr_gate is the first multiple of 8 under which the
+    predicted position is inside at all, plus 8 (log|det C| alone is beyond the gates track() is used with).  A frame 0.125 s
+    later repeats the taken rows."""
+    f0 = _two_clusters(24)[0][:16]
+    base = dict(EQ_KW, dim_x=int(dim_x), fb_frames_batch=0, tr_vel_thres=0.3125)
+
+    def prober(gate):
+        cfg = co.default_config(**dict(base, tr_gate=float(gate)))
+
+        def probe(rows6):
+            orc = co.OracleScene(cfg, max(len(rows6), len(f0)))
+            orc.track(f0, EQ_DT)
+            rows = np.zeros((len(rows6), 8))
+            rows[:, :6] = rows6
+            return orc.track(rows, LONG_DT)[0]
+        return probe
+
+    orc = co.OracleScene(co.default_config(**base), len(f0))
+    orc.track(f0, EQ_DT)
+    trk = orc.tracks()
+    assert len(trk) == 1 and trk["is_static"][0] == 0
+    centre = trk["x"][:1, :6].copy()
+    centre[:, :3] += LONG_DT * trk["x"][:1, 3:6] + 0.5 * LONG_DT * LONG_DT * trk["x"][:1, 6:9]
+    gate = next(g for g in range(8, 257, 8) if prober(g)(centre)[0] == 0) + 8
+    kw = dict(base, tr_gate=float(gate))
+    rng = np.random.default_rng(25)
+    dirs = rng.normal(0.0, 1.0, size=(LONG_RAYS, 6))
+    dirs[:, 3:] *= 0.3
+    lo, hi = _bisect(prober(gate), centre, dirs, lambda a: a == 0, 1.0e7)
+    rows6 = np.concatenate([centre, centre + 0.5 * lo[:, None] * dirs, centre + lo[:, None] * dirs,
+                            centre + hi[:, None] * dirs, centre + 2.0 * hi[:, None] * dirs])
+    want = np.concatenate([np.zeros(1 + 2 * LONG_RAYS, np.int32), np.full(2 * LONG_RAYS, -1, np.int32)])
+    order = rng.permutation(len(rows6))
+    f1 = np.zeros((len(rows6), 8))
+    f1[:, :6] = rows6[order]
+    f1[:, 6], f1[:, 7] = 0.25, 20.0
+    want = want[order]
+    taken = f1[want >= 0]
+    scene = _dt_scene(f"60 s predict, gate {gate}", kw, [f0, f1, taken], [EQ_DT, LONG_DT, 0.125], taken)
+    _ro(want, lo, hi)
+
+    def check(fr):
+        assert np.array_equal(np.nextafter(lo, np.inf), hi) and np.all(lo > 1.0)
+        assert fr[0].n_tracks == 1 and np.array_equal(fr[1].assoc, want), (fr[1].assoc, want)
+        assert fr[1].tracks["lifetime"][0] == 0.0 and fr[1].tracks["point_num"][0] == 1 + 2 * LONG_RAYS
+        assert fr[1].labels is not None and len(fr[1].labels) == 2 * LONG_RAYS                 # the refused rows go to apply_DBscan
+        assert gate > 16 and np.all(replay(scene, upto=2, tr_gate=float(gate - 16))[1].assoc == -1)   # log|det C| alone is beyond that
+        assert fr[2].n_tracks >= 1 and np.all(np.isfinite(fr[2].tracks["P"])) and np.any(fr[2].assoc == 0)
+    return {"long_predict": Equality(scene, check)}
+
+
+@functools.lru_cache(maxsize=None)
+def dt_edges(dim_x):
+    """name -> Equality: the frame-interval edges, each asserted on the oracle before anything else uses it."""
+    out = {}
+    for part in (_lifetime_sums(dim_x, "dynamic"), _lifetime_sums(dim_x, "static"), _dtm_zero(dim_x), _stands_still(dim_x), _long_predict(dim_x)):
+        out.update(part)
+    for eq in out.values():
+        eq.check(replay(eq.scene))
+    return out
+
+
+def dt_edge_groups(dim_x):
+    """The interval edges grouped by configuration: one context each."""
+    groups = {}
+    for name, eq in dt_edges(dim_x).items():
+        groups.setdefault(cfg_key(eq.scene.cfg), []).append(name)
+    return list(groups.values())
+
+
 # ------------------------------------------------------------------------------------------------- the contexts of the tests
-GATE_SCENES = ((1, 3), (2, 3), (3, 3), (4, 12))      # (seed, tracks) of the four scenes of a gate context: one has 12 tracks
+GATE_SCENES =((1, 3), (2, 3), (3, 3), (4, 12))      # (seed, tracks) of the four scenes of a gate context: one has 12 tracks
 TIE_SCENES = ((1, 3), (2, 3), (4, 12))
 MAX_PTS = (256, 320, 1024)                           # 1, 2 and 4 points per thread of k_track / k_scene
 DIM_X = (6, 9)

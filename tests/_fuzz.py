@@ -135,6 +135,45 @@ def scene_inputs(case: dict):
     return pts, cnt, dts
 
 
+# Frame intervals OUTSIDE the band scene_inputs draws from (0.05 .. 0.2 s), finite: equal timestamps, a reader that was paused, a
+# clock that stepped back.  name -> (kind, ...): "every" = `odd` where f % period == period - 1, else 0.1; "choice" = one of the
+# values per frame.  The order is part of the definition: `per_scene` gives scene s schedule number s % 10.
+DT_BAND = (0.05, 0.2)
+_DT_BASE = 0.1
+_DT_RULES = {
+    "zero": ("every", 3, 0.0), "tiny": ("every", 3, 1e-9), "short": ("choice", (0.001, 0.01, 0.03)),
+    "inexact": ("choice", (0.1, 0.2, 0.3, 0.7, 1.1)), "long1": ("every", 4, 1.0), "long5": ("every", 4, 5.0),
+    "long60": ("every", 5, 60.0), "hour": ("every", 5, 3600.0), "negative": ("every", 4, -0.05),
+    "mixed": ("choice", (0.0, 0.001, 0.05, 0.1, 0.2, 0.5, 2.0)),
+}
+DT_SCHEDULES = tuple(_DT_RULES) + ("per_scene",)
+
+
+def _dt_column(seed: int, name: str, s: int, F: int) -> np.ndarray:
+    rule = _DT_RULES[name]
+    if rule[0] == "every":
+        _, period, odd = rule
+        return np.where(np.arange(F) % period == period - 1, odd, _DT_BASE)
+    # a generator of its own per (seed, schedule, scene): draw_case / scene_inputs keep their draws
+    rng = np.random.default_rng([660000 + int(seed), DT_SCHEDULES.index(name), int(s)])
+    return np.asarray(rule[1])[rng.integers(0, len(rule[1]), size=F)]
+
+
+def dt_schedule(case: dict, name: str) -> np.ndarray:
+    """dts[F, S] float64 of the schedule `name` (DT_SCHEDULES) for a drawn case: a pure function of (case["seed"], name, s) that
+    consumes none of the generators of draw_case / scene_inputs."""
+    assert name in DT_SCHEDULES, name
+    F, S = case["F"], case["S"]
+    dts = np.empty((F, S))
+    for s in range(S):
+        dts[:, s] = _dt_column(case["seed"], DT_SCHEDULES[s % 10] if name == "per_scene" else name, s, F)
+    return dts
+
+
+def dt_out_of_band(dts: np.ndarray) -> np.ndarray:
+    return (dts < DT_BAND[0]) | (dts > DT_BAND[1])
+
+
 def plant_nonfinite(case: dict, pts: np.ndarray, cnt: np.ndarray, rate: float = 0.25):
     """The non-finite arm: NaN / +inf / -inf written into random columns (all 8: x, y, z, vx, vy, vz, doppler, peakVal) of random
     rows of about `rate` of the (frame, scene) pairs -- rows that will be unassigned (start-up frames, clutter) and rows a track

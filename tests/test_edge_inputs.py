@@ -109,6 +109,28 @@ def test_equality_is_met_exactly_and_the_next_frame_behaves(name):
     eq.check(ei.replay(eq.scene))
 
 
+@pytest.mark.parametrize("dim_x", ei.DIM_X)
+@pytest.mark.parametrize("name", list(ei.dt_edges(6)))
+def test_interval_edge_sits_where_it_is_claimed(name, dim_x):
+    """The frame-interval edges (inexact lifetime sums on both sides of `lifetime > lim`, lifetime + dt == 0, a lifetime that stands
+    still, a 60 s predict with rows on both sides of its gate): each scene's own check, on an oracle replay."""
+    eq = ei.dt_edges(dim_x)[name]
+    eq.check(ei.replay(eq.scene))
+
+
+def test_interval_edges_decide_differently_on_one_rounding():
+    """0.1 + 0.2 and 0.15 + 0.15 against the limit 0.3: the first pair drops the track on its second frame, the second keeps it, for
+    the dynamic and for the static track; an interval of 2^-60 is absorbed, one of 2^-54 is not."""
+    assert 0.1 + 0.2 == float.fromhex("0x1.3333333333334p-2") and 0.15 + 0.15 == 0.3 == float.fromhex("0x1.3333333333333p-2")
+    for dim_x in ei.DIM_X:
+        e = ei.dt_edges(dim_x)
+        for which, kept in (("dynamic", 1), ("static", 0)):
+            over, equal = ei.replay(e[f"{which}_sum_over"].scene), ei.replay(e[f"{which}_sum_equal"].scene)
+            assert [fr.n_tracks for fr in over] == [2, 2, 1, 1] and [fr.n_tracks for fr in equal] == [2, 2, 2, 2, 1, 1]
+            assert over[2].tracks["is_static"][0] == equal[4].tracks["is_static"][0] == kept     # the OTHER track is the one left
+        assert len(ei.dt_edge_groups(dim_x)) == 4
+
+
 def test_equality_constants_are_exact_in_binary():
     a, n = ei._n_est_constants()
     assert (1 - a) * float(n) + a * float(n) != float(n)

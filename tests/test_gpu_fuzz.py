@@ -4,7 +4,8 @@
 What a configuration draws (tests/_fuzz.py: draw_case): 1..8 scenes; points per frame anywhere in [1, 1024] (multiples of
 64 are the exception); ring length 1..4; DB_EPS, DB_MIN_SAMPLES_MIN, DB_Z_WEIGHT, DB_RANGE_WEIGHT; TR_GATE,
 TR_MAX_TRACKS, TR_VEL_THRES, the two lifetimes; CONST_ACC / CONST_VEL model; KF_ENABLE_EST and the estimator constants;
-0..12 targets per scene (some appear or vanish half-way); ragged point counts; a different dt every frame; frames that
+0..12 targets per scene (some appear or vanish half-way); ragged point counts; a different dt every frame, drawn from
+0.05 .. 0.2 s (intervals outside that band -- zero, tiny, negative, seconds to an hour: tests/test_gpu_dt.py); frames that
 are skipped (n = 0, offline_main.py:56) and frames on which track() is called with an empty cloud (MMW_EMPTY_FRAME); one
 configuration in eight runs ClusterTrack.seek_inner_clusters (Tracking.py:409-448).
 
@@ -45,12 +46,14 @@ def test_random_small_and_threshold_clouds_vs_oracle(seed, arm, layout):
     assert seen is not None
 
 
-def run_case(case, layout):
+def run_case(case, layout, dts=None):
+    """`dts`[F,S]: frame intervals that replace the generated ones (tests/test_gpu_dt.py)."""
     from mmwave_msc_amd import _lib
     from oracle import c_oracle as co
     seed = case["seed"]
     kw, S, N, F = case["cfg"], case["S"], case["N"], case["F"]
-    pts, cnt, dts = scene_inputs(case)                       # [F,S,N,8] float32, [F,S] (0 = skipped, -1 = empty cloud), [F,S]
+    pts, cnt, gen_dts = scene_inputs(case)                   # [F,S,N,8] float32, [F,S] (0 = skipped, -1 = empty cloud), [F,S]
+    dts = gen_dts if dts is None else np.ascontiguousarray(dts, dtype=np.float64).reshape(gen_dts.shape)
     sb = make_checked(S, N, layout, **kw)
     cfg = co.default_config(**kw)
     scenes = [co.OracleScene(cfg, N) for _ in range(S)]

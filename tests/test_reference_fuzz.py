@@ -54,9 +54,10 @@ def _window():
     return out
 
 
-def run_case(arm: str, seed: int, draw_arm: str = None):
+def run_case(arm: str, seed: int, draw_arm: str = None, dts=None):
     """One configuration, every scene, every frame: the live reference and oracle/c side by side.  Returns what was seen.
-    `draw_arm`: which draw of tests/_fuzz.py the non-finite arm plants into (default: the arm itself, "wide" for nonfinite)."""
+    `draw_arm`: which draw of tests/_fuzz.py the non-finite arm plants into (default: the arm itself, "wide" for nonfinite).
+    `dts`[F,S]: frame intervals that replace the generated ones (tests/test_reference_dt.py)."""
     from oracle import c_oracle as co
     from oracle.ref_import import load_reference
     from oracle.ref_runner import RefScene, _Recorder
@@ -66,7 +67,8 @@ def run_case(arm: str, seed: int, draw_arm: str = None):
     draw_arm = draw_arm or ("wide" if nonfinite else arm)
     case = draw_case(seed, arm=draw_arm, **_SIZES[arm])
     kw, S, N, F = case["cfg"], case["S"], case["N"], case["F"]
-    pts, cnt, dts = scene_inputs(case)
+    pts, cnt, gen_dts = scene_inputs(case)
+    dts = gen_dts if dts is None else np.ascontiguousarray(dts, dtype=np.float64).reshape(gen_dts.shape)
     planted = plant_nonfinite(case, pts, cnt, rate=0.3) if nonfinite else []
     const, utils, _ = load_reference()
     over = reference_overrides(kw)
