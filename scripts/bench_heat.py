@@ -38,7 +38,7 @@ GRID = dict(x0=-4.0, y0=0.0, cell=0.25, max_gap=1.0, nx=NX, ny=NY, id=0)
 
 def planted_blob(sb, first_cell):
     """A snapshot blob of every scene of `sb`: track_cap tracks, track k in the centre of cell first_cell + k of GRID (wrapping)."""
-    from tests._heat_plant import context_blob   # (the one place that builds version-1 sections by hand)
+    from tests._snap_plant import context_blob   # (the one place that builds version-1 sections by hand)
     cells = [(first_cell + k) % (NX * NY) for k in range(sb.track_cap)]
     return context_blob(sb, list(range(sb.track_cap)), [(GRID["x0"] + (c % NX + 0.5) * GRID["cell"], GRID["y0"] + (c // NX + 0.5) * GRID["cell"]) for c in cells])
 

@@ -8,82 +8,27 @@ fp64 division per coordinate, one subtraction per interval and one addition per 
 is built with -ffp-contract=off).
 
 What a sample reads is what the track records hold when its kernel runs, so the edge cases plant positions through an edited
-snapshot blob (tests/_heat_plant.py, on tests/_snap_plant.py's offsets) and sample several times without a step in between: the uids stay, the
+snapshot blob (tests/_snap_plant.py) and sample several times without a step in between: the uids stay, the
 positions and times are chosen."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from tests._heat_plant import FAR, dts as _dts, plant_state as _plant, plant_xy as _plant_xy
+from tests._feature_run import BASE, REPORT, S2, TRACKS, HeatRun, cut, nothing_else_moves, same_pair, settled, step_empty
 from tests._heat_ref import HeatRef, cell_of
 from tests._layouts import make_checked
 from tests._report_scenes import CFG_KW, F, N, S, scenario
+from tests._snap_plant import FAR, directory, dts as _dts, plant_state, plant_tracks, plant_xy as _plant_xy, record_at
 
 pytestmark = pytest.mark.gpu
 
-BASE = 7      # scene_base of the compared exports
-S2 = 5        # a short last workgroup: one wave of four in use
 INF, NAN = float("inf"), float("nan")
 NO_GRID = (5, 17)
-
-
-def _cut(n_scenes, n_frames=F):
-    pts, cnt, dts = scenario()
-    return pts[:n_frames, :n_scenes], cnt[:n_frames, :n_scenes], dts[:n_frames, :n_scenes]
-
-
-def _same(got, want, ctx):
-    for g, w, what in zip(got, want, ("rows", "cells")):
-        assert g.dtype == w.dtype, (ctx, what)
-        assert len(g) == len(w), (ctx, what, len(g), len(w), g.tolist(), w.tolist())
-        for k in g.dtype.names:
-            assert g[k].tobytes() == w[k].tobytes(), (ctx, what, k, g[k].tolist(), w[k].tolist())
-
-
-class _Run:
-    """A context and its restatement, stepped, sampled and compared together."""
-
-    def __init__(self, sb, cells, data=None):
-        self.sb, self.data = sb, data if data is not None else scenario()
-        sb.enable_heat(cells)
-        self.ref = HeatRef(sb.S, sb.track_cap, cells)
-
-    def set_grids(self, grids, scenes=None):
-        from mmwave_msc_amd import _lib
-        ng, gt = grids if isinstance(grids, tuple) else _lib.make_heat_grids(grids)
-        self.sb.set_heat_grids((ng, gt), scenes=scenes)
-        self.ref.set_grids(list(range(len(ng))) if scenes is None else list(scenes), ng, gt)
-
-    def step(self, f):
-        pts, cnt, dts = self.data
-        self.sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
-
-    def sample(self, t=None, scenes=None):
-        self.sb.sample_heat(t=t, scenes=scenes)
-        flags = None
-        if scenes is not None:
-            flags = np.zeros(self.sb.S, np.int32)
-            flags[list(scenes)] = 1
-        t = None if t is None else np.broadcast_to(np.asarray(t, np.float64), (self.sb.S,))
-        self.ref.sample(self.sb.tracks(), self.sb.num_tracks(), flags=flags, t=t)
-
-    def compare(self, ctx, scene_base=BASE, scenes=None, clear=False):
-        got = self.sb.heat_host(clear=clear, scenes=scenes, scene_base=scene_base)
-        _same(got, self.ref.export(scene_base, scenes=scenes, clear=clear), ctx)
-        return got
+NOUNS = HeatRun.nouns
 
 
 def _settled(n_scenes=S2, frames=4, cells=128, **cfg):
     """A context whose scenes hold tracks that stay (lifetimes of 100 s), heat enabled behind them."""
-    kw = dict(CFG_KW, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0, **cfg)
-    sb = make_checked(n_scenes, N, "per_scene", **kw)
-    data = _cut(n_scenes)
-    run = _Run(sb, cells, data)
-    for f in range(frames):
-        run.step(f)
-    assert (sb.num_tracks() >= 1).all()
-    return run
+    return settled(lambda sb, data: HeatRun(sb, cells, data), n_scenes, frames, long_lived=True, **cfg)
 
 
 def _room(s, cap_shape, x0=-4.0, y0=0.0):
@@ -103,7 +48,7 @@ def test_scenario_sampled_and_exported_after_every_step(layout, cells, cap_shape
     """24 scenes x 96 points x 12 frames; scenes 5 and 17 have no grid.  A capacity that is a multiple of 4 and one that is not: both
     load widths of the count pass."""
     sb = make_checked(S, N, layout, **CFG_KW)
-    run = _Run(sb, cells)
+    run = HeatRun(sb, cells)
     run.set_grids([[_room(s, cap_shape)] if s not in NO_GRID else [] for s in range(S)])
     assert {int(g["nx"]) * int(g["ny"]) for g in run.ref.grid if g is not None} == {63, 64, 65, cells}
     rows = cells_ = None
@@ -133,11 +78,10 @@ def test_tracks_that_share_a_cell_add_in_list_order():
     one after another -- 0.1 three times is not 0.3, and behind 2^53 an interval of 2 added 64 times is lost 64 times."""
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.batch import SceneBatch
-    from tests._snap_plant import plant_tracks
     n = 3
     sb = SceneBatch(_lib.default_config(tr_max_tracks=64, db_min_samples=12, track_cap=64, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0), n, N)
     assert sb.track_cap == 64
-    pts, cnt, dts = _cut(n)
+    pts, cnt, dts = cut(n)
     for f in range(4):
         sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
     assert (sb.num_tracks() >= 1).all()
@@ -158,7 +102,7 @@ def test_tracks_that_share_a_cell_add_in_list_order():
         sb.sample_heat(t=t)
         ref.sample(sb.tracks(), sb.num_tracks(), t=np.full(n, t))
         rows, cells = sb.heat_host(scene_base=BASE)
-        _same((rows, cells), ref.export(BASE), ("shared", k))
+        same_pair((rows, cells), ref.export(BASE), ("shared", k), NOUNS)
         if k == 0:
             assert {2, 3, 5, 64} <= set(cells["samples"].tolist()), cells["samples"].tolist()
         if k == 1:                                           # 0.1 added twice, three times, 64 times in a row
@@ -231,31 +175,28 @@ def test_max_gap_at_its_bound_and_intervals_that_are_zero_negative_or_nan():
 # 5 ------------------------------------------------------------------------------------------------------------------------
 def test_visits_across_a_return_a_reset_and_a_restore():
     """Track 0 of each scene is planted alone in a grid far from everybody else, with a velocity of 1 m/s along x and no process noise:
-    an empty frame moves it by its predict multiplier (tests/_heat_plant.py), so it steps into the next cell
+    an empty frame moves it by its predict multiplier (tests/_snap_plant.py: dts), so it steps into the next cell
     and back.  Then one scene is reset and all are restored between samples."""
-    from mmwave_msc_amd import _lib
     n = 3
     run = _settled(n, cells=64, kf_q_std=0.0)
     sb, ref = run.sb, run.ref
     blob = bytearray(sb.snapshot())
-    hdr = _lib.MmwSnapshotHeader.from_buffer_copy(bytes(blob[: C.sizeof(_lib.MmwSnapshotHeader)]))
+    ents = directory(blob)
     for sc in range(n):
-        ent = _lib.MmwSnapshotEntry.from_buffer_copy(bytes(blob[hdr.header_bytes + sc * hdr.entry_bytes: hdr.header_bytes + (sc + 1) * hdr.entry_bytes]))
-        _plant(blob, ent.offset, [FAR + 0.125, 2.125, 1.0, 1.0, 0.0, 0.0])
+        plant_state(blob, record_at(ents, sc), [FAR + 0.125, 2.125, 1.0, 1.0, 0.0, 0.0])
     blob = bytes(blob)
     sb.restore(blob)
     run.set_grids([[dict(x0=FAR, y0=2.0, cell=0.25, max_gap=INF, nx=8, ny=8, id=s)] for s in range(n)])
     dts = _dts([[0.25, -0.25]] * n)
-    empty = (np.zeros((n, N, 8)), np.full(n, _lib.EMPTY_FRAME, np.int32))
 
     def mine(cells, s):
         return [(int(c["cell"]), int(c["samples"]), int(c["visits"]), float(c["dwell"])) for c in cells if c["scene"] == BASE + s]
 
     run.sample(t=0.0)                                        # fresh in cell 0
-    sb.step_host(*empty, dts[0], check=False)
+    step_empty(sb, dts[0])
     assert [float(sb.tracks()["x"][s, 0, 0]) for s in range(n)] == [FAR + 0.375] * n
     run.sample(t=0.5)                                        # cell 1: a visit, and the interval goes to the cell it is in now
-    sb.step_host(*empty, dts[1], check=False)
+    step_empty(sb, dts[1])
     assert [float(sb.tracks()["x"][s, 0, 0]) for s in range(n)] == [FAR + 0.125] * n
     run.sample(t=1.0)                                        # back in cell 0: a second visit
     rows, cells = run.compare("there and back")
@@ -317,7 +258,7 @@ def test_clear_cuts_windows_keeps_the_uid_memory_and_a_refused_export_clears_not
     sb.heat_dev(b_r.ptr + G, n_r, b_c.ptr + G, n_c, clear=True, scene_base=BASE, ticket=1)
     assert sb.heat_wait(1) == (n_r, n_c)
     raw_r, raw_c = b_r.download((sent_r.nbytes,), np.uint8), b_c.download((sent_c.nbytes,), np.uint8)
-    _same((np.frombuffer(raw_r[G:-G].tobytes(), _lib.HEAT_ROW_DTYPE), np.frombuffer(raw_c[G:-G].tobytes(), _lib.HEAT_CELL_DTYPE)), ref.export(BASE, clear=True), "CLEAR")
+    same_pair((np.frombuffer(raw_r[G:-G].tobytes(), _lib.HEAT_ROW_DTYPE), np.frombuffer(raw_c[G:-G].tobytes(), _lib.HEAT_CELL_DTYPE)), ref.export(BASE, clear=True), "CLEAR", NOUNS)
     for raw, sent in ((raw_r, sent_r), (raw_c, sent_c)):
         assert raw[:G].tobytes() == sent[:G].tobytes() and raw[-G:].tobytes() == sent[-G:].tobytes()
     for b in (b_r, b_c):
@@ -337,7 +278,7 @@ def test_clear_cuts_windows_keeps_the_uid_memory_and_a_refused_export_clears_not
 def test_accumulator_over_clear_windows_equals_one_run_that_never_cleared():
     from mmwave_msc_amd import heat
     n = 6
-    a, b = (_Run(make_checked(n, N, "per_scene", **CFG_KW), 1024, _cut(n)) for _ in range(2))
+    a, b = (HeatRun(make_checked(n, N, "per_scene", **CFG_KW), 1024, cut(n)) for _ in range(2))
     for run in (a, b):
         run.set_grids(_whole_room(n))
     acc = heat.Accumulator()
@@ -388,7 +329,7 @@ def test_flags_scene_base_four_tickets_and_a_set_call_zeroes_its_scenes_only():
     for k in (2, 0, 3, 1):
         b_r, b_c, want = bufs[k]
         assert sb.heat_wait(k) == (len(want[0]), len(want[1]))
-        _same((b_r.download((len(want[0]),), _lib.HEAT_ROW_DTYPE), b_c.download((len(want[1]),), _lib.HEAT_CELL_DTYPE)), want, ("ticket", k))
+        same_pair((b_r.download((len(want[0]),), _lib.HEAT_ROW_DTYPE), b_c.download((len(want[1]),), _lib.HEAT_CELL_DTYPE)), want, ("ticket", k), NOUNS)
         b_r.free(); b_c.free()
     with pytest.raises(_lib.MmwError) as ei:
         sb.heat_wait(0)                                      # nothing outstanding under it any more
@@ -399,7 +340,7 @@ def test_flags_scene_base_four_tickets_and_a_set_call_zeroes_its_scenes_only():
     rows, cells = run.compare("set")
     assert (rows["scene"] - BASE).tolist() == [0, 1, 2, 3, 4] and rows["id"].tolist() == [0, 1, 22, 33, 4]
     assert rows["count"][2] == 0 and rows["count"][3] == 0 and rows["calls"][2] == 0 and rows["calls"][3] == 0
-    _same(run.compare("the others", scenes=[0, 1, 4]), before, "untouched by the set call")
+    same_pair(run.compare("the others", scenes=[0, 1, 4]), before, "untouched by the set call", NOUNS)
     run.step(8)
     run.sample(t=1.0)
     rows, cells = run.compare("sampled behind the set call")
@@ -451,7 +392,7 @@ def test_refusals_change_nothing():
     # ... and all of that left the mirrors and the state as they were
     after_tab = sb.get_heat_grids()
     assert before_tab[0].tobytes() == after_tab[0].tobytes() and before_tab[1].tobytes() == after_tab[1].tobytes() and after_tab[0].tolist() == [1] * S2
-    _same(run.compare("after"), before, "state")
+    same_pair(run.compare("after"), before, "state", NOUNS)
     run.step(6)
     run.sample(t=0.75)
     rows, cells = run.compare("goes on")                     # (a refused set call bumped no generation: the intervals across it count)
@@ -495,18 +436,15 @@ def test_nothing_else_moves():
         assert ei.value.code == _lib.E_ARG
     buf.free()
     assert a.get_heat_grids()[0].tolist() == [0] * S
-    run = _Run(a, 1024)
+    run = HeatRun(a, 1024)
     run.set_grids(_whole_room(S, max_gap=0.25))
-    pts, cnt, dts = scenario()
-    for f in range(F):
-        for sb in (a, b):
-            sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
+
+    def drive(f):
         run.sample(t=0.125 * f)
         if f % 4 == 3:
             run.compare(("moves", f), clear=(f == 7))
-    assert a.num_tracks().tobytes() == b.num_tracks().tobytes() and a.tracks().tobytes() == b.tracks().tobytes()
-    for x, y in zip(a.report_host(), b.report_host()):
-        assert x.tobytes() == y.tobytes()
+
+    nothing_else_moves(a, b, scenario(), F, drive, at_end=TRACKS + REPORT)
     for sb in (a, b):
         sb.check()
         sb.close()

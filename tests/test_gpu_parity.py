@@ -15,6 +15,7 @@ from tests._golden import (GOLDEN, assert_feat_equal, assert_feat_identical, ass
 pytestmark = pytest.mark.gpu
 
 
+from tests._grid_scenes import grid_scene as _grid_scene
 from tests._layouts import LAYOUTS, make_checked
 
 _LAYOUT = {"name": "per_scene"}
@@ -269,34 +270,6 @@ def test_dbscan_screen_decisions_vs_oracle(case):
     sb.close()
     # the case is only meaningful if both outcomes occur
     assert n_db > 50 and 0 < n_clustered < n_db, (n_db, n_clustered)
-
-
-def _grid_scene(seed, n_frames, n_pts, n_targets):
-    """Targets on a 1.3 m grid (4 rows in y), 24 points each per frame, the rest clutter; fp32-representable."""
-    rng = np.random.default_rng(seed)
-    cols = (n_targets + 3) // 4
-    centres = np.array([[-0.65 * (cols - 1) + 1.3 * (k // 4), 1.5 + 1.3 * (k % 4)] for k in range(n_targets)])
-    vel = rng.normal(0.0, 0.08, size=(n_targets, 2))
-    out = np.zeros((n_frames, n_pts, 8))
-    per = 24
-    for f in range(n_frames):
-        c = centres + vel * 0.1 * f
-        rows = []
-        for k in range(n_targets):
-            r = np.zeros((per, 8))
-            r[:, 0:2] = c[k] + rng.normal(0.0, 0.08, size=(per, 2))
-            r[:, 2] = rng.uniform(0.3, 1.5, size=per)
-            r[:, 3:5] = vel[k] + rng.normal(0.0, 0.03, size=(per, 2))
-            r[:, 5] = rng.normal(0.0, 0.03, size=per)
-            rows.append(r)
-        ncl = n_pts - per * n_targets
-        cl = np.zeros((ncl, 8))
-        cl[:, 0] = rng.uniform(-6.0, 6.0, size=ncl); cl[:, 1] = rng.uniform(0.3, 7.5, size=ncl); cl[:, 2] = rng.uniform(0.05, 2.4, size=ncl)
-        cl[:, 3:6] = rng.normal(0.0, 0.05, size=(ncl, 3))
-        fr = np.concatenate(rows + [cl])
-        fr[:, 6] = rng.normal(0.0, 0.3, size=n_pts); fr[:, 7] = rng.gamma(1.0, 30.0, size=n_pts)
-        out[f] = fr[rng.permutation(n_pts)]
-    return out.astype(np.float32)
 
 
 def test_many_tracks_vs_oracle():

@@ -8,8 +8,9 @@ loses a track in the same frame; the tests assert positive BORN and GONE counts 
 import numpy as np
 import pytest
 
+from tests._feature_run import step
 from tests._layouts import LAYOUTS, make_checked
-from tests._report_scenes import CFG_KW, F, N, S, scenario
+from tests._report_scenes import CFG_KW, F, N, S, as_tuples, host_events, scenario, uid_lists
 
 pytestmark = pytest.mark.gpu
 
@@ -20,34 +21,6 @@ def _batch(n_scenes=S, max_pts=N, **kw):
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.batch import SceneBatch
     return SceneBatch(_lib.default_config(**{**CFG_KW, **kw}), n_scenes, max_pts)
-
-
-def _step(sb, f, data=None):
-    pts, cnt, dts = data if data is not None else scenario()
-    sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
-
-
-def _uid_lists(sb):
-    """effective_tracks' uids per scene, in list order."""
-    ntr, trk = sb.num_tracks(), sb.tracks()
-    return [[int(u) for u in trk["uid"][s, : ntr[s]]] for s in range(sb.S)]
-
-
-def _host_events(prev, cur, rebased=(), scene_base=0):
-    """What a report must say: per scene GONE in baseline order, then BORN in current order; one REBASED for a rebased scene."""
-    from mmwave_msc_amd import _lib
-    ev = []
-    for s, (p, c) in enumerate(zip(prev, cur)):
-        if s in rebased:
-            ev.append((scene_base + s, -1, _lib.EV_REBASED, len(c)))
-            continue
-        ev += [(scene_base + s, u, _lib.EV_GONE, j) for j, u in enumerate(p) if u not in c]
-        ev += [(scene_base + s, u, _lib.EV_BORN, j) for j, u in enumerate(c) if u not in p]
-    return ev
-
-
-def _as_tuples(events):
-    return [(int(e["scene"]), int(e["uid"]), int(e["kind"]), int(e["slot"])) for e in events]
 
 
 def _check_rows(sb, rows, events, scene_base=0):
@@ -81,11 +54,11 @@ def test_rows_and_events_after_every_step(layout):
     prev = [[] for _ in range(S)]
     n_born = n_gone = n_both = 0
     for f in range(F):
-        _step(sb, f)
+        step(sb, f)
         rows, events = sb.report_host(scene_base=100)
         _check_rows(sb, rows, events, scene_base=100)
-        cur = _uid_lists(sb)
-        assert _as_tuples(events) == _host_events(prev, cur, scene_base=100), f
+        cur = uid_lists(sb)
+        assert as_tuples(events) == host_events(prev, cur, scene_base=100), f
         kinds = {}
         for e in events:
             kinds.setdefault(int(e["scene"]), set()).add(int(e["kind"]))
@@ -105,13 +78,13 @@ def test_a_report_every_third_frame_is_the_net_difference():
     prev = [[] for _ in range(S)]
     n_born = n_gone = 0
     for f in range(F):
-        _step(sb, f)
-        cur = _uid_lists(sb)
+        step(sb, f)
+        cur = uid_lists(sb)
         if f % 3 != 2:
             continue
         rows, events = sb.report_host()
         _check_rows(sb, rows, events)
-        assert _as_tuples(events) == _host_events(prev, cur), f
+        assert as_tuples(events) == host_events(prev, cur), f
         n_born += int((events["kind"] == _lib.EV_BORN).sum())
         n_gone += int((events["kind"] == _lib.EV_GONE).sum())
         prev = cur   # (a difference of states, not a log: a track born and gone between two reports is in neither)
@@ -126,7 +99,7 @@ def test_capacity_is_decided_on_the_device_and_a_retry_loses_nothing():
     for sb in (a, b):
         sb.enable_report()
         for f in range(6):
-            _step(sb, f)
+            step(sb, f)
     b._export_caps["report"] = (S * b.track_cap, 2 * S * b.track_cap)   # (the twin is never refused)
     want_rows, want_events = b.report_host()
     n_r, n_e = len(want_rows), len(want_events)
@@ -153,7 +126,7 @@ def test_capacity_is_decided_on_the_device_and_a_retry_loses_nothing():
     assert b_e.download((n_e,), edt).tobytes() == want_events.tobytes()
     # ... and both carry on alike
     for sb in (a, b):
-        _step(sb, 6)
+        step(sb, 6)
     ra, ea = a.report_host()
     rb, eb = b.report_host()
     assert ra.tobytes() == rb.tobytes() and ea.tobytes() == eb.tobytes() and len(ea) > 0
@@ -167,33 +140,33 @@ def test_reset_and_restore_rebase_their_scenes():
     sb.enable_report()
     blob = None
     for f in range(6):
-        _step(sb, f)
+        step(sb, f)
         if f == 3:
             blob = sb.snapshot([7])
-            snap_uids = _uid_lists(sb)[7]
+            snap_uids = uid_lists(sb)[7]
         sb.report_host()
     assert snap_uids, "scene 7 holds a track at frame 3"
-    before = _uid_lists(sb)
+    before = uid_lists(sb)
     mask = np.zeros(S, bool)
     mask[[2, 5]] = True
     sb.reset_scenes(mask)
     sb.restore(blob, [9])
     rows, events = sb.report_host()
-    cur = _uid_lists(sb)
+    cur = uid_lists(sb)
     assert cur[2] == [] and cur[5] == [] and cur[9] == snap_uids
     _check_rows(sb, rows, events)
     # those three scenes, and only those: exactly one REBASED each (slot = tracks now), no BORN / GONE; nothing else moved
-    assert _as_tuples(events) == [(2, -1, _lib.EV_REBASED, 0), (5, -1, _lib.EV_REBASED, 0), (9, -1, _lib.EV_REBASED, len(snap_uids))]
-    assert _as_tuples(events) == _host_events(before, cur, rebased=(2, 5, 9))
+    assert as_tuples(events) == [(2, -1, _lib.EV_REBASED, 0), (5, -1, _lib.EV_REBASED, 0), (9, -1, _lib.EV_REBASED, len(snap_uids))]
+    assert as_tuples(events) == host_events(before, cur, rebased=(2, 5, 9))
     # the reports after that are ordinary: uids restarted at 0 in the reset scenes, and uid 0 is BORN only where it is a new track
     prev = cur
     born0 = set()
     for f in range(6, F):
-        _step(sb, f)
+        step(sb, f)
         rows, events = sb.report_host()
-        cur = _uid_lists(sb)
+        cur = uid_lists(sb)
         _check_rows(sb, rows, events)
-        assert _as_tuples(events) == _host_events(prev, cur), f
+        assert as_tuples(events) == host_events(prev, cur), f
         assert not (events["kind"] == _lib.EV_REBASED).any()
         born0 |= {int(e["scene"]) for e in events if e["kind"] == _lib.EV_BORN and e["uid"] == 0}
         prev = cur
@@ -201,7 +174,7 @@ def test_reset_and_restore_rebase_their_scenes():
     # mmw_reset: every scene
     sb.reset()
     rows, events = sb.report_host()
-    assert len(rows) == 0 and _as_tuples(events) == [(s, -1, _lib.EV_REBASED, 0) for s in range(S)]
+    assert len(rows) == 0 and as_tuples(events) == [(s, -1, _lib.EV_REBASED, 0) for s in range(S)]
     rows, events = sb.report_host()
     assert len(rows) == 0 and len(events) == 0
     sb.close()
@@ -216,7 +189,7 @@ def test_rows_use_each_scenes_own_site():
                             v_screen_fade_weight=rng.uniform(0.02, 0.2, S))
     sb.enable_report()
     for f in range(6):
-        _step(sb, f)
+        step(sb, f)
     sb.report_host()                    # (takes the events: the reports below carry no BORN flag)
     plain_rows, _ = sb.report_host()
     sb.set_sites(sites)
@@ -240,11 +213,11 @@ def test_two_reports_outstanding_across_two_steps():
     for sb in (a, b):
         sb.enable_report()
         for f in range(4):
-            _step(sb, f)
+            step(sb, f)
         sb.report_host()
     want = []
     for f in (4, 5):
-        _step(b, f)
+        step(b, f)
         want.append(b.report_host())
     rdt, edt = _lib.TRACK_REPORT_DTYPE, _lib.TRACK_EVENT_DTYPE
     cap = S * a.track_cap
@@ -276,7 +249,7 @@ def test_reports_leave_the_scene_state_alone():
     a.enable_report()
     for f in range(8):
         for sb in (a, b):
-            _step(sb, f)
+            step(sb, f)
         a.report_host()
     assert a.snapshot() == b.snapshot()
     a.close(); b.close()
@@ -300,11 +273,11 @@ def test_1027_scenes_the_scan_loop_and_a_short_last_block():
     prev = [[] for _ in range(S2)]
     n_born = 0
     for f in range(F2):
-        _step(sb, f, (pts, cnt, dts))
+        step(sb, f, (pts, cnt, dts))
         rows, events = sb.report_host()
-        cur = _uid_lists(sb)
+        cur = uid_lists(sb)
         _check_rows(sb, rows, events)
-        assert _as_tuples(events) == _host_events(prev, cur), f
+        assert as_tuples(events) == host_events(prev, cur), f
         n_born += int((events["kind"] == _lib.EV_BORN).sum())
         prev = cur
     assert cur[S2 - 1] or cur[S2 - 2] or cur[S2 - 3], "the last, short block holds tracks"
@@ -316,7 +289,7 @@ def test_more_than_32_live_tracks_in_one_scene():
     """track_cap = 64 and 36 targets in scene 0: every lane of the wave's lower half and some of the upper hold a track, and the rows
     of the scene take three staging passes."""
     from mmwave_msc_amd import _lib
-    from tests.test_gpu_parity import _grid_scene
+    from tests._grid_scenes import grid_scene as _grid_scene
     S3, N3, F3 = 2, 1024, 5
     kw = dict(tr_max_tracks=40, db_min_samples=12, track_cap=64)
     from mmwave_msc_amd.batch import SceneBatch
@@ -329,11 +302,11 @@ def test_more_than_32_live_tracks_in_one_scene():
     prev = [[] for _ in range(S3)]
     most = 0
     for f in range(F3):
-        _step(sb, f, (pts, cnt, dts))
+        step(sb, f, (pts, cnt, dts))
         rows, events = sb.report_host()
-        cur = _uid_lists(sb)
+        cur = uid_lists(sb)
         _check_rows(sb, rows, events)
-        assert _as_tuples(events) == _host_events(prev, cur), f
+        assert as_tuples(events) == host_events(prev, cur), f
         most = max(most, len(cur[0]))
         prev = cur
     sb.check()
@@ -351,7 +324,7 @@ def test_not_enabled_is_refused_and_enable_disable_enable_works():
             call()
         assert ei.value.code == _lib.E_ARG
     for f in range(3):
-        _step(sb, f)
+        step(sb, f)
     sb.enable_report()
     for bad in (lambda: sb.report_async(None, 1, buf.ptr, 1), lambda: sb.report_async(buf.ptr, 1, None, 1), lambda: sb.report_async(buf.ptr, -1, buf.ptr, 1),
                 lambda: sb.report_async(buf.ptr, 1, buf.ptr, -1), lambda: sb.report_async(buf.ptr, 1, buf.ptr, 1, 0, 4), lambda: sb.report_async(buf.ptr, 1, buf.ptr, 1, 0, -1),
@@ -365,16 +338,16 @@ def test_not_enabled_is_refused_and_enable_disable_enable_works():
     with pytest.raises(MmwError) as ei:
         sb.report_host()
     assert ei.value.code == _lib.E_ARG
-    _step(sb, 3)
-    _step(sb, 4)
+    step(sb, 3)
+    step(sb, 4)
     sb.enable_report(False)   # (off twice is fine)
     sb.enable_report()
     rows, events = sb.report_host()
     _check_rows(sb, rows, events)
     assert len(events) == 0
-    _step(sb, 5)
+    step(sb, 5)
     prev = [[int(u) for u in rows["uid"][rows["scene"] == s]] for s in range(S)]
     rows, events = sb.report_host()
-    assert _as_tuples(events) == _host_events(prev, _uid_lists(sb))
+    assert as_tuples(events) == host_events(prev, uid_lists(sb))
     buf.free()
     sb.close()

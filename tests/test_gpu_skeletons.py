@@ -140,7 +140,7 @@ def test_drawn_mode_is_the_not_skipped_subset_in_order(dim_x):
 
 # 3 ------------------------------------------------------------------------------------------------------------------------
 def test_many_tracks_lanes_past_16_and_several_stores_per_scene():
-    from tests.test_gpu_parity import _grid_scene
+    from tests._grid_scenes import grid_scene as _grid_scene
     n_s, n_pts, frames = 2, 640, 3
     sb = make_checked(n_s, n_pts, "per_scene", tr_max_tracks=28, db_min_samples=12, track_cap=40)
     assert sb.track_cap == 40
@@ -165,7 +165,7 @@ def test_many_tracks_lanes_past_16_and_several_stores_per_scene():
 # 4 ------------------------------------------------------------------------------------------------------------------------
 def _four_tracks():
     """One scene with four live tracks (four targets of test_gpu_parity._grid_scene)."""
-    from tests.test_gpu_parity import _grid_scene
+    from tests._grid_scenes import grid_scene as _grid_scene
     sb = make_checked(1, 160, "per_scene", tr_max_tracks=4, db_min_samples=12)
     pts = _grid_scene(4400, 2, 160, 4)
     for f in range(2):

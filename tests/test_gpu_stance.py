@@ -10,99 +10,25 @@ difference for each of the two ages, and the squared gap is three products and t
 Keypoints are planted with `set_keypoints_host` behind each frame, from `_stance_ref.planted(scene, uid, frame)` or by hand; the CNN
 runs in one test only.  What a sample reads is what the track records hold when its kernel runs, so the edge cases plant, sample and
 plant again without a step in between: the uids stay, the heads are chosen."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from tests._feature_run import BASE, REPORT, S2, TRACKS, StanceRun, TripRun, cut, head_kp as _kp, n_kind, nothing_else_moves, same_pair, settled, step_empty
 from tests._layouts import make_checked
-from tests._report_scenes import CFG_KW, F, N, S, scenario
-from tests._stance_ref import HEAD, L, LOW, LYING, M, NKP, U, UPRIGHT, StanceRef, planted
+from tests._report_scenes import CFG_KW, F, N, S, scenario, wires16
+from tests._snap_plant import FAR, directory, plant_state, record_at
+from tests._stance_ref import HEAD, L, LOW, LYING, M, U, UPRIGHT, StanceRef, planted
 
 pytestmark = pytest.mark.gpu
 
-BASE = 7      # scene_base of the compared exports
-S2 = 5        # a short last workgroup: one wave of four in use
 RULE = (1.25, 0.5, 0.125, 0.25, 0.5, 0.5)   # h_stand, h_lie, margin, fall_window, long_lie, max_gap: every derived threshold is exact
 UP_HI, UP_LO, LIE_HI, LIE_LO, H_STAND, H_LIE = 1.375, 1.125, 0.625, 0.375, 1.25, 0.5
 F32 = np.float32
 
 
-def _cut(n_scenes, n_frames=F):
-    pts, cnt, dts = scenario()
-    return pts[:n_frames, :n_scenes], cnt[:n_frames, :n_scenes], dts[:n_frames, :n_scenes]
-
-
-def _same(got, want, ctx):
-    for g, w, what in zip(got, want, ("rows", "events")):
-        assert g.dtype == w.dtype, (ctx, what)
-        assert len(g) == len(w), (ctx, what, len(g), len(w), g.tolist(), w.tolist())
-        for k in g.dtype.names:
-            assert g[k].tobytes() == w[k].tobytes(), (ctx, what, k, g[k].tolist(), w[k].tolist())
-
-
-def _kp(head, g=0.0):
-    kp = np.zeros(NKP, F32)
-    kp[HEAD], kp[1] = head, g
-    return kp
-
-
 def _up(x):
     """The next fp32 above x."""
     return np.nextafter(F32(x), F32(np.inf))
-
-
-class _Run:
-    """A context and its restatement, stepped, planted, sampled and compared together."""
-
-    def __init__(self, sb, depth, data=None):
-        self.sb, self.data = sb, data if data is not None else scenario()
-        sb.enable_stance(depth)
-        self.ref = StanceRef(sb.S, sb.track_cap, depth)
-
-    def set_rules(self, rules, scenes=None):
-        from mmwave_msc_amd import _lib
-        nr, rt = rules if isinstance(rules, tuple) else _lib.make_stance_rules(rules)
-        self.sb.set_stance_rules((nr, rt), scenes=scenes)
-        self.ref.set_rules(list(range(len(nr))) if scenes is None else list(scenes), nr, rt)
-
-    def step(self, f):
-        pts, cnt, dts = self.data
-        self.sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
-
-    def plant(self, kp_of):
-        """kp_of(scene, position, uid) -> the 57 keypoints of that live track, or None to leave them."""
-        ntr, trk = self.sb.num_tracks(), self.sb.tracks()
-        kps, own = [], []
-        for s in range(self.sb.S):
-            for j in range(int(ntr[s])):
-                kp = kp_of(s, j, int(trk[s, j]["uid"]))
-                if kp is not None:
-                    kps.append(kp); own.append((s, j))
-        if own:
-            self.sb.set_keypoints_host(np.stack(kps), np.array(own, np.int32))
-
-    def plant_heads(self, heads, g=None):
-        """Every live track of scene s gets head heads[s] (None: left alone) and kp[1] = g[s]."""
-        self.plant(lambda s, j, uid: None if heads[s] is None else _kp(heads[s], 0.0 if g is None else g[s]))
-
-    def sample(self, t=None, scenes=None):
-        self.sb.sample_stance(t=t, scenes=scenes)
-        flags = None
-        if scenes is not None:
-            flags = np.zeros(self.sb.S, np.int32)
-            flags[list(scenes)] = 1
-        t = None if t is None else np.broadcast_to(np.asarray(t, np.float64), (self.sb.S,))
-        self.ref.sample(self.sb.tracks(), self.sb.num_tracks(), flags=flags, t=t)
-
-    def compare(self, ctx, scene_base=BASE):
-        got = self.sb.stance_host(scene_base=scene_base)
-        _same(got, self.ref.export(scene_base), ctx)
-        return got
-
-
-def _n_kind(events, kind):
-    return int((events["kind"] == kind).sum())
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------
@@ -116,7 +42,7 @@ def test_scenario_planted_sampled_every_frame_and_exported_every_third(layout):
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.stance import Watch
     sb = make_checked(S, N, layout, **CFG_KW)
-    run = _Run(sb, 64)
+    run = StanceRun(sb, 64)
     run.set_rules([[RULE + (100 + s,)] if s not in NO_RULE else [] for s in range(S)])
     watch, last_rows = Watch(), None
     for f in range(F):
@@ -148,14 +74,7 @@ def test_scenario_planted_sampled_every_frame_and_exported_every_third(layout):
 # 2 ------------------------------------------------------------------------------------------------------------------------
 def _settled(n_scenes=S2, frames=4, depth=64, **cfg):
     """A context whose scenes hold tracks that stay (lifetimes of 100 s), stance enabled behind them."""
-    kw = dict(CFG_KW, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0, **cfg)
-    sb = make_checked(n_scenes, N, "per_scene", **kw)
-    data = _cut(n_scenes)
-    run = _Run(sb, depth, data)
-    for f in range(frames):
-        run.step(f)
-    assert (sb.num_tracks() >= 1).all()
-    return run
+    return settled(lambda sb, data: StanceRun(sb, depth, data), n_scenes, frames, long_lived=True, **cfg)
 
 
 def _rules(n, **over):
@@ -281,7 +200,7 @@ def test_log_depth_2_capacity_subsets_and_ordinals():
         assert b_e.download((2 * S2 * 32,), np.uint8).tobytes() == sent.tobytes()
     sb.stance_async(b_r.ptr, S2, b_e.ptr, 2 * S2, BASE, 2)
     assert sb.stance_wait(2) == (S2, 2 * S2)
-    _same((b_r.download((S2,), _lib.STANCE_ROW_DTYPE), b_e.download((2 * S2,), _lib.STANCE_EVENT_DTYPE)), ref.export(BASE), "retry")
+    same_pair((b_r.download((S2,), _lib.STANCE_ROW_DTYPE), b_e.download((2 * S2,), _lib.STANCE_EVENT_DTYPE)), ref.export(BASE), "retry")
     for b in (b_r, b_e):
         b.free()
     # a subset of the scenes, t = None: the asked scenes' ordinals move (1), the others' do not
@@ -332,7 +251,7 @@ def test_refused_rules_change_nothing():
     run.plant_heads([U] * S2)
     run.sample(t=0.0)
     rows, events = run.compare("one REBASED only")           # (of the accepted set call; the refused ones bumped nothing)
-    assert _n_kind(events, _lib.SEV_REBASED) == S2
+    assert n_kind(events, _lib.SEV_REBASED) == S2
     run.sb.check()
     run.sb.close()
 
@@ -345,7 +264,7 @@ def test_reset_restore_and_set_rules_rebase_their_scenes_only():
     run.plant_heads([U, M, L, U, M])
     run.sample(t=0.0)
     rows, events = run.compare("first")
-    assert _n_kind(events, _lib.SEV_REBASED) == S2
+    assert n_kind(events, _lib.SEV_REBASED) == S2
     blob = sb.snapshot()
     # a set call on scene 2 alone: its counters restart and it is REBASED; the neighbours keep their classes (no event for them)
     run.set_rules(_rules(1, id=99, long_lie=float("inf")), scenes=[2])
@@ -366,7 +285,7 @@ def test_reset_restore_and_set_rules_rebase_their_scenes_only():
     ref.rebase()
     run.sample(t=3.0)
     rows, events = run.compare("restore")
-    assert _n_kind(events, _lib.SEV_REBASED) == S2 and _n_kind(events, _lib.SEV_CHANGE) == int(sb.num_tracks().sum())
+    assert n_kind(events, _lib.SEV_REBASED) == S2 and n_kind(events, _lib.SEV_CHANGE) == int(sb.num_tracks().sum())
     assert rows["falls"].tolist() == [0] * S2                # the first classification behind a REBASED is never a FALL
     sb.reset()
     ref.rebase()
@@ -385,7 +304,7 @@ def test_one_scene_with_64_tracks_every_lane_a_track_and_a_slot():
     from mmwave_msc_amd.batch import SceneBatch
     sb = SceneBatch(_lib.default_config(tr_max_tracks=64, db_min_samples=12, track_cap=64, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0), 2, N)
     assert sb.track_cap == 64
-    pts, cnt, dts = _cut(2)
+    pts, cnt, dts = cut(2)
     for f in range(4):
         sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
     assert (sb.num_tracks() >= 1).all()
@@ -404,7 +323,7 @@ def test_one_scene_with_64_tracks_every_lane_a_track_and_a_slot():
         sb.sample_stance(t=0.125 * k)
         ref.sample(sb.tracks(), sb.num_tracks(), t=np.full(2, 0.125 * k))
         rows, events = sb.stance_host(scene_base=BASE)
-        _same((rows, events), ref.export(BASE), ("64", k))
+        same_pair((rows, events), ref.export(BASE), ("64", k))
         assert int(rows["upright"][0] + rows["low"][0] + rows["lying"][0] + rows["unknown"][0]) == 64
     assert ref.falls[0] >= 1 and ref.long_lies[0] >= 1 and ref.tally["implausible_gap"] >= 1 and ref.tally["implausible_head"] >= 1, sorted(ref.tally.items())
     sb.check()
@@ -444,7 +363,7 @@ def test_sampled_behind_the_cnn_without_a_host_wait():
             est += sb.estimate_posture()                     # (waits for the row count only: the chain is still queued)
             sb.sample_stance(t=0.125 * f)
             ref.sample(sb.tracks(), sb.num_tracks(), t=np.full(n, 0.125 * f))
-            _same(sb.stance_host(scene_base=BASE), ref.export(BASE), ("cnn", f))
+            same_pair(sb.stance_host(scene_base=BASE), ref.export(BASE), ("cnn", f))
     assert est >= n and ref.logged.sum() > n
     got = {k for k in ref.tally if k.startswith("first_")}
     assert len(got) >= 2, sorted(ref.tally.items())
@@ -469,22 +388,21 @@ def test_nothing_else_moves():
     buf.free()
     nr, rt = a.stance_rules()
     assert nr.tolist() == [0] * S and rt.tobytes() == bytes(S * 64)
-    run = _Run(a, 64)
+    run = StanceRun(a, 64)
     run.set_rules([[RULE]] * S)
-    pts, cnt, dts = scenario()
-    for f in range(F):
-        for sb in (a, b):
-            sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
-            ntr, trk = sb.num_tracks(), sb.tracks()
-            own = [(s, j) for s in range(S) for j in range(int(ntr[s]))]
-            if own:
-                sb.set_keypoints_host(np.stack([planted(s, int(trk[s, j]["uid"]), f) for s, j in own]), np.array(own, np.int32))
+
+    def plant(sb, f):
+        ntr, trk = sb.num_tracks(), sb.tracks()
+        own = [(s, j) for s in range(S) for j in range(int(ntr[s]))]
+        if own:
+            sb.set_keypoints_host(np.stack([planted(s, int(trk[s, j]["uid"]), f) for s, j in own]), np.array(own, np.int32))
+
+    def drive(f):
         run.sample(t=0.125 * f)
         if f % 4 == 3:
             run.compare(("moves", f))
-    assert a.num_tracks().tobytes() == b.num_tracks().tobytes() and a.tracks().tobytes() == b.tracks().tobytes()
-    for x, y in zip(a.report_host(), b.report_host()):
-        assert x.tobytes() == y.tobytes()
+
+    nothing_else_moves(a, b, scenario(), F, drive, both=plant, at_end=TRACKS + REPORT)
     for sb in (a, b):
         sb.check()
         sb.close()
@@ -493,23 +411,14 @@ def test_nothing_else_moves():
 # 5 ------------------------------------------------------------------------------------------------------------------------
 def test_trails_tripwires_and_stance_keep_separate_slot_tables_and_generations():
     from mmwave_msc_amd import _lib
-    from tests._tripwire_ref import TripRef
     S6 = 6
     sb = make_checked(S6, N, "per_scene", **CFG_KW)
-    data = _cut(S6)
-    run = _Run(sb, 64, data)
+    data = cut(S6)
+    run = StanceRun(sb, 64, data)
     sb.enable_trails(8)
-    sb.enable_tripwires(64)
-    trip = TripRef(S6, sb.track_cap, 64)
-    nw, wt = _lib.make_tripwires([[(0.25 * k - 2.0, 8.0, 0.25 * k - 2.0, 0.0, 0.03, 100 + k) for k in range(16)]] * S6)
-    sb.set_tripwires((nw, wt))
-    trip.set_wires(list(range(S6)), nw, wt)
+    trip = TripRun(sb, 64, data)
+    trip.set_wires(wires16(S6))
     run.set_rules([[RULE]] * S6)
-
-    def compare_trip(ctx):
-        got, want = sb.tripwires_host(scene_base=BASE), trip.export(BASE)
-        _same(got, want, ctx)
-        return got
 
     for f in range(F):
         run.step(f)
@@ -517,28 +426,25 @@ def test_trails_tripwires_and_stance_keep_separate_slot_tables_and_generations()
         if f % 2 == 0:                                       # the three are sampled at different times: their slot tables drift apart
             sb.sample_trails(t=0.125 * f)
         if f % 3 != 1:
-            sb.sample_tripwires(t=0.125 * f)
-            trip.sample(sb.tracks(), sb.num_tracks(), t=np.full(S6, 0.125 * f))
+            trip.sample(t=0.125 * f)
         run.sample(t=0.125 * f)
         run.compare(("stance", f))
-        compare_trip(("trip", f))
+        trip.compare(("trip", f))
         if f == 5:                                           # a rule set call: a REBASED for stance alone
             run.set_rules([[RULE + (9,)]] * 2, scenes=[1, 4])
             run.sample(t=0.125 * f + 0.0625)
-            sb.sample_tripwires(t=0.125 * f + 0.0625)
-            trip.sample(sb.tracks(), sb.num_tracks(), t=np.full(S6, 0.125 * f + 0.0625))
+            trip.sample(t=0.125 * f + 0.0625)
             _, ev = run.compare("stance set")
             assert sorted((ev["scene"][ev["kind"] == _lib.SEV_REBASED] - BASE).tolist()) == [1, 4]
-            assert _n_kind(compare_trip("trip after stance set")[1], _lib.TW_REBASED) == 0
+            assert n_kind(trip.compare("trip after stance set")[1], _lib.TW_REBASED) == 0
         if f == 8:                                           # reset_scenes: one REBASED each
             sb.reset_scenes(np.isin(np.arange(S6), (2,)))
-            run.ref.rebase([2]); trip.rebase([2])
+            run.ref.rebase([2]); trip.ref.rebase([2])
             run.sample(t=0.125 * f + 0.0625)
-            sb.sample_tripwires(t=0.125 * f + 0.0625)
-            trip.sample(sb.tracks(), sb.num_tracks(), t=np.full(S6, 0.125 * f + 0.0625))
+            trip.sample(t=0.125 * f + 0.0625)
             _, ev = run.compare("stance reset")
             assert (ev["scene"][ev["kind"] == _lib.SEV_REBASED] - BASE).tolist() == [2]
-            tw = compare_trip("trip reset")[1]
+            tw = trip.compare("trip reset")[1]
             assert (tw["scene"][tw["kind"] == _lib.TW_REBASED] - BASE).tolist() == [2]
     d, p = sb.trails_host()
     ntr = sb.num_tracks()
@@ -556,55 +462,43 @@ def test_tripwire_log_of_depth_3_and_stance_log_of_depth_5_in_one_context():
     or three CHANGEs.  The two consumers export at different frames, with more than two turns of their ring in between, and one stance
     export is first asked with one event too few.  Rows, events and `lost` are the reference model's, byte for byte."""
     from mmwave_msc_amd import _lib
-    from tests._tripwire_ref import TripRef
-    from tests.test_gpu_tripwires import FAR, _plant
     S3 = 3
     kw = {k: v for k, v in CFG_KW.items() if k != "tr_max_tracks"}     # (the default track cap)
     sb = make_checked(S3, N, "per_scene", **dict(kw, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0, kf_q_std=0.0))
-    data = _cut(S3)
+    data = cut(S3)
     for f in range(9):                                       # (the C oracle: three tracks in each of the three scenes from frame 8 on)
         sb.step_host(data[0][f].astype(np.float64), data[1][f], data[2][f])
     assert sb.num_tracks().tolist() == [3, 3, 3]
     blob = bytearray(sb.snapshot())
-    hdr = _lib.MmwSnapshotHeader.from_buffer_copy(bytes(blob[: C.sizeof(_lib.MmwSnapshotHeader)]))
+    ents = directory(blob)
     for sc in (0, 2):
-        ent = _lib.MmwSnapshotEntry.from_buffer_copy(bytes(blob[hdr.header_bytes + sc * hdr.entry_bytes: hdr.header_bytes + (sc + 1) * hdr.entry_bytes]))
-        _plant(blob, ent.offset, [FAR - 0.5, 0.0, 1.0, 1.0, 0.0, 0.0])
+        plant_state(blob, record_at(ents, sc), [FAR - 0.5, 0.0, 1.0, 1.0, 0.0, 0.0])
     sb.restore(bytes(blob))
-    run = _Run(sb, 5, data)                                  # stance, log depth 5
-    sb.enable_tripwires(3)
-    trip = TripRef(S3, sb.track_cap, 3)
-    nw, wt = _lib.make_tripwires([[(FAR + k, -4.0, FAR + k, 4.0, 0.0, 60 + k) for k in range(5)]] * 2)
-    sb.set_tripwires((nw, wt), scenes=[0, 2])
-    trip.set_wires([0, 2], nw, wt)
+    run = StanceRun(sb, 5, data)                             # stance, log depth 5
+    trip = TripRun(sb, 3, data)
+    trip.set_wires([[(FAR + k, -4.0, FAR + k, 4.0, 0.0, 60 + k) for k in range(5)]] * 2, scenes=[0, 2])
     run.set_rules(_rules(2, long_lie=0.0), scenes=[0, 2])
 
     def frame(k, at, head):
         """Move the planted tracks to FAR - 0.5 + at, plant every head, sample both consumers at t = k."""
         if k:                                                # (an empty frame moves a track by velocity x the running sum of dt: that sum becomes the move)
             mult = float(at - frame.at)
-            sb.step_host(np.zeros((S3, N, 8)), np.full(S3, _lib.EMPTY_FRAME, np.int32), np.full(S3, mult - frame.mult), check=False)
+            step_empty(sb, mult - frame.mult)
             frame.mult = mult
         frame.at = at
         assert [float(sb.tracks()["x"][sc, 0, 0]) for sc in (0, 2)] == [FAR - 0.5 + at] * 2
         run.plant_heads([head] * S3)
         run.sample(t=float(k))
-        sb.sample_tripwires(t=float(k))
-        trip.sample(sb.tracks(), sb.num_tracks(), t=np.full(S3, float(k)))
-
-    def compare_trip(ctx):
-        got = sb.tripwires_host(scene_base=BASE)
-        _same(got, trip.export(BASE), ctx)
-        return got
+        trip.sample(t=float(k))
 
     frame.mult = 0.0
     frame(0, 0, L)                                           # stance: REBASED, 3 CHANGE, 3 LONG_LIE in one call -- 7 > 5; tripwires: REBASED
-    assert run.ref.logged.tolist() == [7, 0, 7] and trip.logged.tolist() == [1, 0, 1]
+    assert run.ref.logged.tolist() == [7, 0, 7] and trip.ref.logged.tolist() == [1, 0, 1]
     rows, events = run.compare("stance at 0")
-    assert rows["lost"].tolist() == [2, 2] and len(events) == 10 and _n_kind(events, _lib.SEV_REBASED) == 0
+    assert rows["lost"].tolist() == [2, 2] and len(events) == 10 and n_kind(events, _lib.SEV_REBASED) == 0
     frame(1, 5, U)                                           # tripwires: five wires in one call -- 5 > 3
-    assert trip.logged.tolist() == [6, 0, 6]
-    rows, events = compare_trip("tripwires at 1")
+    assert trip.ref.logged.tolist() == [6, 0, 6]
+    rows, events = trip.compare("tripwires at 1")
     assert rows["lost"].tolist() == [3] * 10 and rows["backward"].tolist() == [1] * 10
     assert [(int(e["scene"]) - BASE, int(e["wire"])) for e in events] == [(0, 2), (0, 3), (0, 4), (2, 2), (2, 3), (2, 4)]
     frame(2, 3, L)
@@ -625,14 +519,14 @@ def test_tripwire_log_of_depth_3_and_stance_log_of_depth_5_in_one_context():
     assert rows["lost"].tolist() == [7, 7] and len(events) == 10
     frame(4, 3, L)
     frame(5, 5, U)                                           # tripwires since their export: 4 x 2 events, the ring of 3 turned twice
-    assert trip.logged.tolist() == [14, 0, 14]
-    rows, events = compare_trip("tripwires at 5")
+    assert trip.ref.logged.tolist() == [14, 0, 14]
+    rows, events = trip.compare("tripwires at 5")
     assert rows["lost"].tolist() == [5] * 10 and len(events) == 6
     assert rows["forward"].tolist() == [0, 0, 0, 2, 2] * 2 and rows["backward"].tolist() == [1, 1, 1, 3, 3] * 2
     frame(6, 3, L)
     rows, events = run.compare("stance at 6")
     assert rows["lost"].tolist() == [10, 10] and len(events) == 10
-    rows, events = compare_trip("tripwires at 6")
+    rows, events = trip.compare("tripwires at 6")
     assert not rows["lost"].any() and [int(e["wire"]) for e in events] == [3, 4, 3, 4]
     sb.check()
     sb.close()

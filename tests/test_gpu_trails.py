@@ -9,76 +9,16 @@ built with -ffp-contract=off) except for sqrt, where the device's may differ fro
 most 2**-52 relative; each of the at most `total` samples adds one such term, every term is non-negative, so the sum only grows and
 each term's error is at most 2**-52 of the final sum.  The tests print how many values were bit-equal.  The scenario is
 tests/_report_scenes.py's (24 scenes x 96 points x 12 frames: tracks are born, walk and expire inside the run)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from tests._feature_run import BASE, S2, TrailRun, cut, nothing_else_moves, same_trails, step, step_empty
 from tests._layouts import make_checked
 from tests._report_scenes import CFG_KW, F, N, S, scenario
+from tests._snap_plant import directory, plant_state, record_at
 from tests._trail_ref import TrailRef
 
 pytestmark = pytest.mark.gpu
-
-BASE = 7      # scene_base of the compared exports
-S2 = 5        # a short last workgroup: one of four waves, one of one
-
-
-def _step(sb, f, data=None):
-    pts, cnt, dts = data if data is not None else scenario()
-    sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
-
-
-def _cut(n_scenes, n_frames=F):
-    pts, cnt, dts = scenario()
-    return pts[:n_frames, :n_scenes], cnt[:n_frames, :n_scenes], dts[:n_frames, :n_scenes]
-
-
-def _same(got, want, ctx):
-    """(dir, points) pairs: everything by its bytes, `travelled` within its bound; -> (bit-equal travelled values, all of them)."""
-    (gd, gp), (wd, wp) = got, want
-    assert gd.dtype == wd.dtype and gp.dtype == wp.dtype, ctx
-    assert len(gd) == len(wd) and len(gp) == len(wp), (ctx, len(gd), len(wd), len(gp), len(wp))
-    for k in gd.dtype.names:
-        if k != "travelled":
-            assert gd[k].tobytes() == wd[k].tobytes(), (ctx, "dir", k, gd[k].tolist(), wd[k].tolist())
-    for k in gp.dtype.names:
-        assert gp[k].tobytes() == wp[k].tobytes(), (ctx, "points", k)
-    g, w = gd["travelled"], wd["travelled"]
-    assert np.array_equal(np.isnan(g), np.isnan(w)), (ctx, "travelled NaN", g.tolist(), w.tolist())
-    ok = ~np.isnan(w)
-    with np.errstate(invalid="ignore"):
-        bound = wd["total"][ok] * 2.0 ** -52 * np.abs(w[ok])
-        assert (np.abs(g[ok] - w[ok]) <= bound).all(), (ctx, "travelled", g.tolist(), w.tolist())
-    return int((g.view(np.uint64) == w.view(np.uint64)).sum()), len(g)
-
-
-class _Run:
-    """A context and its restatement, stepped, sampled and compared together."""
-
-    def __init__(self, sb, depth, data=None):
-        self.sb, self.data = sb, data if data is not None else scenario()
-        sb.enable_trails(depth)
-        self.ref = TrailRef(sb.S, sb.track_cap, depth)
-        self.equal = self.seen = 0
-
-    def step(self, f):
-        _step(self.sb, f, self.data)
-
-    def sample(self, t=None, scenes=None):
-        self.sb.sample_trails(t=t, scenes=scenes)
-        flags = None
-        if scenes is not None:
-            flags = np.zeros(self.sb.S, np.int32)
-            flags[list(scenes)] = 1
-        self.ref.sample(self.sb.tracks(), self.sb.num_tracks(), flags=flags, t=t)
-
-    def compare(self, ctx, last=0, scene_base=BASE):
-        got = self.sb.trails_host(last=last, scene_base=scene_base)
-        want = self.ref.export(self.sb.tracks(), self.sb.num_tracks(), last=last, scene_base=scene_base)
-        e, n = _same(got, want, ctx)
-        self.equal, self.seen = self.equal + e, self.seen + n
-        return got
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------
@@ -86,7 +26,7 @@ class _Run:
 def test_depth_4_sampled_and_exported_after_every_step(layout):
     sb = make_checked(S, N, layout, **CFG_KW)
     sb.enable_report()
-    run = _Run(sb, 4)
+    run = TrailRun(sb, 4)
     pts, cnt, dts = scenario()
     d_flags, d_t = sb.alloc(S * 4), sb.alloc(S * 8)
     clock = np.zeros(S)
@@ -114,7 +54,7 @@ def test_depth_4_sampled_and_exported_after_every_step(layout):
 # 2 ------------------------------------------------------------------------------------------------------------------------
 def test_scene_flags_call_ordinals_and_the_trimmed_export():
     sb = make_checked(S, N, "per_scene", **CFG_KW)
-    run = _Run(sb, 4)
+    run = TrailRun(sb, 4)
     for f in range(F):
         run.step(f)
         run.sample(scenes=[s for s in range(S) if not (f % 2 == 1 and s % 3 == 0)])   # (t = NULL: the scenes' call ordinals)
@@ -140,7 +80,7 @@ def test_capacity_is_decided_on_the_device_and_the_export_consumes_nothing():
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.batch import MmwError
     sb = make_checked(S2, N, "per_scene", **CFG_KW)
-    run = _Run(sb, 4, _cut(S2))
+    run = TrailRun(sb, 4, cut(S2))
     for f in range(8):
         run.step(f)
         run.sample(t=np.full(S2, 0.25 * f))
@@ -159,7 +99,7 @@ def test_capacity_is_decided_on_the_device_and_the_export_consumes_nothing():
     sb.trails_dev(b_d.ptr, n_t, b_p.ptr, n_p, 0, 0)
     assert sb.trails_wait(0) == (n_t, n_p)
     got = (b_d.download((n_t,), _lib.TRAIL_TRACK_DTYPE), b_p.download((n_p,), _lib.TRAIL_POINT_DTYPE))
-    _same(got, (want_d, want_p), "exact caps")
+    same_trails(got, (want_d, want_p), "exact caps")
     assert np.array_equal(b_d.download(sent_d.shape, np.uint8)[n_t * 40:], sent_d[n_t * 40:])
     assert np.array_equal(b_p.download(sent_p.shape, np.uint8)[n_p * 24:], sent_p[n_p * 24:])
     run.compare("after the refusals", scene_base=0)
@@ -171,8 +111,8 @@ def test_capacity_is_decided_on_the_device_and_the_export_consumes_nothing():
         assert sb.trails_wait(t) == (n_t, n_p)
     outs = [bd.download((n_t,), _lib.TRAIL_TRACK_DTYPE).tobytes() + bp.download((n_p,), _lib.TRAIL_POINT_DTYPE).tobytes() for bd, bp in bufs]
     assert outs[0] == outs[1] == outs[2]
-    _same((np.frombuffer(outs[0][: n_t * 40], _lib.TRAIL_TRACK_DTYPE), np.frombuffer(outs[0][n_t * 40:], _lib.TRAIL_POINT_DTYPE)),
-          run.ref.export(sb.tracks(), sb.num_tracks(), scene_base=BASE), "tickets")
+    same_trails((np.frombuffer(outs[0][: n_t * 40], _lib.TRAIL_TRACK_DTYPE), np.frombuffer(outs[0][n_t * 40:], _lib.TRAIL_POINT_DTYPE)),
+                run.ref.export(sb.tracks(), sb.num_tracks(), scene_base=BASE), "tickets")
     # the argument checks: nothing is queued, the message names the entry
     for bad in (lambda: sb.trails_dev(None, 1, b_p.ptr, n_p), lambda: sb.trails_dev(b_d.ptr, -1, b_p.ptr, n_p),
                 lambda: sb.trails_dev(b_d.ptr + 4, n_t, b_p.ptr, n_p), lambda: sb.trails_dev(b_d.ptr, n_t, b_p.ptr + 4, n_p),
@@ -191,7 +131,7 @@ def test_capacity_is_decided_on_the_device_and_the_export_consumes_nothing():
 def test_reset_and_restore_end_the_trails_of_their_scenes_only():
     S4, reset, restored = 8, (1, 5), (2, 6)
     sb = make_checked(S4, N, "per_scene", **CFG_KW)
-    run = _Run(sb, 4, _cut(S4))
+    run = TrailRun(sb, 4, cut(S4))
     blob = None
     for f in range(7):
         run.step(f)
@@ -234,33 +174,25 @@ def test_reset_and_restore_end_the_trails_of_their_scenes_only():
 
 # 5 ------------------------------------------------------------------------------------------------------------------------
 def test_planted_positions_walk_overflow_signed_zero_and_nan():
-    """Four tracks' states written through a snapshot blob (x[k] of track t of a section is at offset + 64 + 1504 t + 8 k, its
-    P behind x, its lifetime at + 8 * 151), ONE restore -- a restore ends the scene's trails --, then the tracker itself moves them: a
+    """Four tracks' states written through a snapshot blob (tests/_snap_plant.py's plant_state: x at REC_X, P at REC_P, the lifetime
+    at REC_LIFETIME of a track's record), ONE restore -- a restore ends the scene's trails --, then the tracker itself moves them: a
     step on an empty frame predicts x += (lifetime + dt) * v, exactly for these values, and its Kalman update (towards the old
     centroid) leaves x alone because the planted covariance is zero and stays zero with kf_q_std = 0: the gain is 0."""
-    from mmwave_msc_amd import _lib
     kw = dict(CFG_KW, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0, kf_q_std=0.0)
     sb = make_checked(S2, N, "per_scene", **kw)
-    data = _cut(S2)
+    data = cut(S2)
     for f in range(4):
-        _step(sb, f, data)
+        step(sb, f, data)
     assert (sb.num_tracks() >= 1).all()
     blob = bytearray(sb.snapshot())
-    hdr = _lib.MmwSnapshotHeader.from_buffer_copy(bytes(blob[: C.sizeof(_lib.MmwSnapshotHeader)]))
-    ents = [_lib.MmwSnapshotEntry.from_buffer_copy(bytes(blob[hdr.header_bytes + i * hdr.entry_bytes: hdr.header_bytes + (i + 1) * hdr.entry_bytes]))
-            for i in range(S2)]
+    ents = directory(blob)
     WALK, BIG, NEG, NAN = 0, 1, 2, 3                  # the scene whose track 0 carries each plant
     plants = {WALK: [0.0, 0.0, 1.0, 3.0, 4.0, 0.0], BIG: [1e39, 2.0, 1.0, 0.0, 0.0, 0.0], NEG: [-0.0, 1.0, -0.0, 0.0, 0.0, 0.0],
               NAN: [0.0, 0.0, 1.0, np.nan, 0.0, 0.0]}
     for sc, x in plants.items():
-        at = ents[sc].offset + _lib.SNAP_SCENE_HDR_BYTES
-        blob[at: at + 72] = np.array(x + [0.0, 0.0, 0.0], np.float64).tobytes()
-        blob[at + 72: at + 72 + 648] = bytes(648)
-        blob[at + 8 * 151: at + 8 * 152] = np.float64(0.0).tobytes()
+        plant_state(blob, record_at(ents, sc), x)
     sb.restore(bytes(blob))
-    run = _Run(sb, 8, data)
-    empty = np.full(S2, _lib.EMPTY_FRAME, np.int32)
-    zeros = np.zeros((S2, N, 8))
+    run = TrailRun(sb, 8, data)
 
     def entry(d, sc):
         return d[(d["scene"] == BASE + sc) & (d["slot"] == 0)][0]
@@ -268,7 +200,7 @@ def test_planted_positions_walk_overflow_signed_zero_and_nan():
     seen = []
     for k, dt in enumerate((None, 1.0, 0.0)):   # sample; step dt = 1; sample; sample again; step dt = 0 (the lifetime is 1 by then); sample
         if dt is not None:
-            sb.step_host(zeros, empty, np.full(S2, dt), check=False)
+            step_empty(sb, dt)
         run.sample(t=np.full(S2, float(k)))
         d, p = run.compare(("planted", k))
         seen.append((d, p))
@@ -296,13 +228,13 @@ def test_planted_positions_walk_overflow_signed_zero_and_nan():
 def test_depth_1_depth_256_and_the_refused_depths():
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.batch import MmwError
-    data = _cut(2)
+    data = cut(2)
     for depth in (1, _lib.TRAIL_DEPTH_MAX):
         sb = make_checked(2, N, "per_scene", **CFG_KW)
         with pytest.raises(MmwError) as ei:       # before enabling, every other entry is refused
             sb.sample_trails()
         assert ei.value.code == _lib.E_ARG
-        run = _Run(sb, depth, data)
+        run = TrailRun(sb, depth, data)
         for f in range(F):
             run.step(f)
             run.sample(t=np.full(2, 0.125 * f))
@@ -330,7 +262,7 @@ def test_depth_1_depth_256_and_the_refused_depths():
                 entry()
             assert ei.value.code == _lib.E_ARG
         sb.enable_trails(0)      # (off already: MMW_OK)
-        _step(sb, 0, data)       # the context steps on, and resets launch nothing of the trails
+        step(sb, 0, data)       # the context steps on, and resets launch nothing of the trails
         sb.reset()
         b.free()
         sb.close()
@@ -341,14 +273,14 @@ def test_depth_1_depth_256_and_the_refused_depths():
 def test_trails_leave_the_tracker_alone():
     a = make_checked(S2, N, "per_scene", **CFG_KW)
     b = make_checked(S2, N, "per_scene", **CFG_KW)
-    data = _cut(S2)
+    data = cut(S2)
     a.enable_trails(4)
-    for f in range(F):
-        for sb in (a, b):
-            _step(sb, f, data)
+
+    def drive(f):
         a.sample_trails()
         a.trails_host()
-    assert a.tracks().tobytes() == b.tracks().tobytes() and np.array_equal(a.num_tracks(), b.num_tracks())
+
+    nothing_else_moves(a, b, data, F, drive)
     a.close(); b.close()
 
 
@@ -356,14 +288,9 @@ def test_trails_leave_the_tracker_alone():
 def test_more_than_32_live_tracks_in_one_scene():
     """track_cap = 64 with 36 targets in scene 0 (lanes and trail slots past 32: the upper half of the 64-bit ballots) and 5 in
     scene 1; depth 2 over 5 frames wraps the rings."""
-    from mmwave_msc_amd import _lib
-    from mmwave_msc_amd.batch import SceneBatch
-    from tests.test_gpu_parity import _grid_scene
-    n_s, n_pts, frames = 2, 1024, 5
-    sb = SceneBatch(_lib.default_config(tr_max_tracks=40, db_min_samples=12, track_cap=64), n_s, n_pts)
-    assert sb.track_cap == 64
-    pts = np.stack([_grid_scene(4700, frames, n_pts, 36), _grid_scene(4701, frames, n_pts, 5)], axis=1)
-    run = _Run(sb, 2)
+    from tests._grid_scenes import many_tracks
+    sb, pts, n_s, n_pts, frames, _ = many_tracks("track_cap_64")
+    run = TrailRun(sb, 2)
     most = 0
     for f in range(frames):
         sb.step_host(pts[f].astype(np.float64), np.full(n_s, n_pts, np.int32), np.full(n_s, 0.1))

@@ -7,91 +7,22 @@ is compared by its bytes -- there is no tolerance anywhere: the device takes no 
 and sums in the same order (the library is built with -ffp-contract=off).  The scenario is tests/_report_scenes.py's (24 scenes x 96
 points x 12 frames: tracks are born, walk and expire inside the run).
 
-The planted tests write track states into a snapshot blob (x[k] of track t of a section is at offset + 64 + 1504 t + 8 k, its P
-behind x, its lifetime at + 8 * 151) and restore it ONCE; then steps on empty frames move the tracks: predict is
+The planted tests write track states into a snapshot blob (tests/_snap_plant.py's plant_state: x at REC_X, P at REC_P, the lifetime
+at REC_LIFETIME of a track's record) and restore it ONCE; then steps on empty frames move the tracks: predict is
 x += (lifetime + dt) * v with lifetime += dt, so the multiplier of step k is the running sum L_k of the dts given so far -- any
 sequence of non-zero L_k, negative ones included, by giving dt_k = L_k - L_(k-1) -- and the Kalman update leaves x alone because
 the planted covariance is zero and stays zero with kf_q_std = 0.  Every planted value is a small dyadic number: each product and
 sum below is exact, and the positions are asserted as read back."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from tests._feature_run import BASE, REPORT, S2, TRACKS, TrailRun, TripRun, cut, n_kind, nothing_else_moves, same_pair, settled, step
 from tests._layouts import make_checked
-from tests._report_scenes import CFG_KW, F, N, S, scenario
+from tests._report_scenes import CFG_KW, F, N, S, coming_and_going, scenario, strips, wires16
+from tests._snap_plant import FAR, directory, dts as _dts, plant_state, record_at
 from tests._tripwire_ref import TripRef
 
 pytestmark = pytest.mark.gpu
-
-BASE = 7      # scene_base of the compared exports
-S2 = 5        # a short last workgroup: one of four waves, one of one
-FAR = 100.0   # x of the wires no track of the scenario comes near (they all stay on its positive side: c = -8 (px - 100) > 0)
-
-
-def _step(sb, f, data=None):
-    pts, cnt, dts = data if data is not None else scenario()
-    sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
-
-
-def _cut(n_scenes, n_frames=F):
-    pts, cnt, dts = scenario()
-    return pts[:n_frames, :n_scenes], cnt[:n_frames, :n_scenes], dts[:n_frames, :n_scenes]
-
-
-def _wires16(n_scenes, margin=0.03, y0=8.0, y1=0.0, x0=-2.0, pitch=0.25):
-    """16 wires per scene from (c, y0) to (c, y1), c = x0 + pitch k; id = 100 + k."""
-    from mmwave_msc_amd import _lib
-    return _lib.make_tripwires([[(x0 + pitch * k, y0, x0 + pitch * k, y1, margin, 100 + k) for k in range(16)] for _ in range(n_scenes)])
-
-
-def _same(got, want, ctx):
-    for g, w, what in zip(got, want, ("rows", "events")):
-        assert g.dtype == w.dtype, (ctx, what)
-        assert len(g) == len(w), (ctx, what, len(g), len(w), g.tolist(), w.tolist())
-        for k in g.dtype.names:
-            assert g[k].tobytes() == w[k].tobytes(), (ctx, what, k, g[k].tolist(), w[k].tolist())
-
-
-class _Run:
-    """A context and its restatement, stepped, sampled and compared together."""
-
-    def __init__(self, sb, depth, data=None):
-        self.sb, self.data = sb, data if data is not None else scenario()
-        sb.enable_tripwires(depth)
-        self.ref = TripRef(sb.S, sb.track_cap, depth)
-
-    def set_wires(self, wires, scenes=None):
-        from mmwave_msc_amd import _lib
-        nw, wt = wires if isinstance(wires, tuple) else _lib.make_tripwires(wires)
-        self.sb.set_tripwires((nw, wt), scenes=scenes)
-        self.ref.set_wires(list(range(len(nw))) if scenes is None else list(scenes), nw, wt)
-
-    def step(self, f):
-        _step(self.sb, f, self.data)
-
-    def step_empty(self, dt):
-        from mmwave_msc_amd import _lib
-        n = self.sb.S
-        self.sb.step_host(np.zeros((n, N, 8)), np.full(n, _lib.EMPTY_FRAME, np.int32), np.asarray(dt, np.float64), check=False)
-
-    def sample(self, t=None, scenes=None):
-        self.sb.sample_tripwires(t=t, scenes=scenes)
-        flags = None
-        if scenes is not None:
-            flags = np.zeros(self.sb.S, np.int32)
-            flags[list(scenes)] = 1
-        t = None if t is None else np.broadcast_to(np.asarray(t, np.float64), (self.sb.S,))
-        self.ref.sample(self.sb.tracks(), self.sb.num_tracks(), flags=flags, t=t)
-
-    def compare(self, ctx, scene_base=BASE):
-        got = self.sb.tripwires_host(scene_base=scene_base)
-        _same(got, self.ref.export(scene_base), ctx)
-        return got
-
-
-def _n_kind(events, kind):
-    return int((events["kind"] == kind).sum())
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------
@@ -102,8 +33,8 @@ def test_scenario_sampled_and_exported_after_every_step(layout):
     scenes (31 / 35 crossings at margin 0): the floors asserted on the restatement are a third of that."""
     from mmwave_msc_amd.tripwires import Tally
     sb = make_checked(S, N, layout, **CFG_KW)
-    run = _Run(sb, 64)
-    run.set_wires(_wires16(S))
+    run = TripRun(sb, 64)
+    run.set_wires(wires16(S))
     pts, cnt, dts = scenario()
     d_flags, d_t = sb.alloc(S * 4), sb.alloc(S * 8)
     clock = np.zeros(S)
@@ -139,36 +70,13 @@ def test_scenario_sampled_and_exported_after_every_step(layout):
 def _planted(plants, n_scenes=S2, depth=8):
     """A context whose scene sc's track 0 is plants[sc] = [px, py, pz, vx, vy, vz] with zero covariance and lifetime 0 (one restore),
     tripwires enabled behind it.  -> (run, blob, entries)"""
-    from mmwave_msc_amd import _lib
-    kw = dict(CFG_KW, tr_lifetime_dynamic=100.0, tr_lifetime_static=100.0, kf_q_std=0.0)
-    sb = make_checked(n_scenes, N, "per_scene", **kw)
-    data = _cut(n_scenes)
-    for f in range(4):
-        _step(sb, f, data)
-    assert (sb.num_tracks() >= 1).all()
+    sb = settled(lambda sb, data: sb, n_scenes, long_lived=True, kf_q_std=0.0)
     blob = bytearray(sb.snapshot())
-    hdr = _lib.MmwSnapshotHeader.from_buffer_copy(bytes(blob[: C.sizeof(_lib.MmwSnapshotHeader)]))
-    ents = [_lib.MmwSnapshotEntry.from_buffer_copy(bytes(blob[hdr.header_bytes + i * hdr.entry_bytes: hdr.header_bytes + (i + 1) * hdr.entry_bytes]))
-            for i in range(n_scenes)]
+    ents = directory(blob)
     for sc, x in plants.items():
-        _plant(blob, ents[sc].offset, x)
+        plant_state(blob, record_at(ents, sc), x)
     sb.restore(bytes(blob))
-    return _Run(sb, depth, data), blob, ents
-
-
-def _plant(blob, offset, x):
-    from mmwave_msc_amd import _lib
-    at = offset + _lib.SNAP_SCENE_HDR_BYTES
-    blob[at: at + 72] = np.array(list(x) + [0.0, 0.0, 0.0], np.float64).tobytes()
-    blob[at + 72: at + 72 + 648] = bytes(648)
-    blob[at + 8 * 151: at + 8 * 152] = np.float64(0.0).tobytes()
-
-
-def _dts(multipliers):
-    """dt[k][scene] from the per-scene multipliers L_k (all non-zero: a lifetime of 0 marks a track as just updated)."""
-    L = np.array(multipliers, np.float64)          # [scene][k]
-    assert (L != 0).all()
-    return np.diff(np.concatenate([np.zeros((len(L), 1)), L], axis=1), axis=1).T
+    return TripRun(sb, depth, cut(n_scenes)), blob, ents
 
 
 def test_planted_positions_band_edges_ends_u_turns_and_non_finite():
@@ -297,11 +205,11 @@ def test_log_depth_1_and_2_three_wires_crossed_in_one_step(depth):
 def test_depth_log_max_the_refused_depths_and_enabling_again():
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.batch import MmwError
-    data = _cut(2)
+    data = cut(2)
     sb = make_checked(2, N, "per_scene", **CFG_KW)
     b = sb.alloc(64)
     entries = (lambda: sb.sample_tripwires(), lambda: sb.tripwires_async(b.ptr, 1, b.ptr, 1), lambda: sb.tripwires_wait(0), lambda: sb.tripwires_host(),
-               lambda: sb.set_tripwires(_wires16(2)))
+               lambda: sb.set_tripwires(wires16(2)))
 
     def all_refused():
         for entry in entries:
@@ -310,8 +218,8 @@ def test_depth_log_max_the_refused_depths_and_enabling_again():
             assert ei.value.code == _lib.E_ARG
         assert not sb.tripwires()[0].any() and sb.tripwires()[1].tobytes() == bytes(2 * 16 * 48)   # (mmw_get_tripwires: 0 wires)
     all_refused()                                  # before enabling
-    run = _Run(sb, _lib.TRIPWIRE_LOG_MAX, data)
-    run.set_wires(_wires16(2))
+    run = TripRun(sb, _lib.TRIPWIRE_LOG_MAX, data)
+    run.set_wires(wires16(2))
     for f in range(F):
         run.step(f)
         run.sample(t=0.125 * f)
@@ -329,14 +237,14 @@ def test_depth_log_max_the_refused_depths_and_enabling_again():
     assert not sb.tripwires()[0].any()
     rows, events = run.compare("enabled again")
     assert len(rows) == 0 and len(events) == 0
-    run.set_wires(_wires16(2))
+    run.set_wires(wires16(2))
     run.sample()
     rows, events = run.compare("enabled again, sampled")
     assert len(rows) == 32 and [int(e["kind"]) for e in events] == [_lib.TW_REBASED] * 2 and not events["t"].any()
     sb.enable_tripwires(0)
     all_refused()
     sb.enable_tripwires(0)      # (off already: MMW_OK)
-    _step(sb, 0, data)          # the context steps on, and resets launch nothing of the tripwires
+    step(sb, 0, data)          # the context steps on, and resets launch nothing of the tripwires
     sb.reset()
     b.free()
     sb.close()
@@ -344,14 +252,11 @@ def test_depth_log_max_the_refused_depths_and_enabling_again():
 
 # 4 ------------------------------------------------------------------------------------------------------------------------
 def _settled(n_scenes=S2, frames=8, depth=64):
-    sb = make_checked(n_scenes, N, "per_scene", **CFG_KW)
-    data = _cut(n_scenes)
-    run = _Run(sb, depth, data)
-    run.set_wires(_wires16(n_scenes))
-    for f in range(frames):
-        run.step(f)
-        run.sample(t=0.25 * f)
-    return run
+    def make(sb, data):
+        run = TripRun(sb, depth, data)
+        run.set_wires(wires16(n_scenes))
+        return run
+    return settled(make, n_scenes, frames, each_frame=lambda run, f: run.sample(t=0.25 * f))
 
 
 def test_capacity_is_decided_on_the_device_and_a_refused_export_takes_nothing():
@@ -373,7 +278,7 @@ def test_capacity_is_decided_on_the_device_and_a_refused_export_takes_nothing():
     # `taken` and the marks stand: the retry returns what the first call would have, and nothing is written past the counts
     sb.tripwires_async(b_r.ptr, n_r, b_e.ptr, n_e, 0, 0)
     assert sb.tripwires_wait(0) == (n_r, n_e)
-    _same((b_r.download((n_r,), _lib.TRIPWIRE_ROW_DTYPE), b_e.download((n_e,), _lib.TRIPWIRE_EVENT_DTYPE)), run.ref.export(), "exact caps")
+    same_pair((b_r.download((n_r,), _lib.TRIPWIRE_ROW_DTYPE), b_e.download((n_e,), _lib.TRIPWIRE_EVENT_DTYPE)), run.ref.export(), "exact caps")
     assert (want_r["d_forward"] + want_r["d_backward"]).sum() > 0
     assert np.array_equal(b_r.download(sent_r.shape, np.uint8)[n_r * 32:], sent_r[n_r * 32:])
     assert np.array_equal(b_e.download(sent_e.shape, np.uint8)[n_e * 32:], sent_e[n_e * 32:])
@@ -390,8 +295,8 @@ def test_reset_restore_and_set_tripwires_rebase_their_scenes_only():
     from mmwave_msc_amd import _lib
     S4, reset, restored, rewired = 8, (1, 5), (2, 6), (3,)
     sb = make_checked(S4, N, "per_scene", **CFG_KW)
-    run = _Run(sb, 64, _cut(S4))
-    run.set_wires(_wires16(S4))
+    run = TripRun(sb, 64, cut(S4))
+    run.set_wires(wires16(S4))
     blob = None
     for f in range(7):
         run.step(f)
@@ -404,7 +309,7 @@ def test_reset_restore_and_set_tripwires_rebase_their_scenes_only():
     sb.reset_scenes(np.isin(np.arange(S4), reset))
     sb.restore(blob, scenes=list(restored))
     run.ref.rebase(reset + restored)
-    nw, wt = _wires16(1, margin=0.125)
+    nw, wt = wires16(1, margin=0.125)
     run.set_wires((nw, wt), scenes=list(rewired))
     rows, events = run.compare("before the next sample")     # nothing is logged until a sample asks the scene; scene 3's counters restarted
     assert len(events) == 0
@@ -429,7 +334,7 @@ def test_reset_restore_and_set_tripwires_rebase_their_scenes_only():
     run.step(0)
     run.sample(t=4.0)
     rows, events = run.compare("after reset")
-    assert _n_kind(events, _lib.TW_REBASED) == S4
+    assert n_kind(events, _lib.TW_REBASED) == S4
     sb.close()
 
 
@@ -444,7 +349,7 @@ def test_a_uid_restored_on_the_other_side_gives_no_crossing():
     run.compare("negative side")
     uid = int(sb.tracks()["uid"][0, 0])
     assert run.ref.sides[0][uid][0] == 1                      # (the restatement's: negative)
-    _plant(blob, ents[0].offset, [FAR - 0.5, 0.0, 1.0, 0.0, 0.0, 0.0])
+    plant_state(blob, record_at(ents, 0), [FAR - 0.5, 0.0, 1.0, 0.0, 0.0, 0.0])
     sb.reset_scenes(np.arange(S2) == 0)
     sb.restore(bytes(blob))                                    # (every scene of the blob: scene 0's track 0 on the other side)
     run.ref.rebase()
@@ -461,20 +366,10 @@ def test_a_uid_restored_on_the_other_side_gives_no_crossing():
 def test_many_tracks_and_all_16_wires(shape):
     """The track_cap = 40 grid scenes of the skeleton tests, and the report's track_cap = 64 scene with 36 targets (lanes and uid
     slots past 32: the upper half of the 64-bit ballots); 16 long wires across the grid."""
-    from mmwave_msc_amd import _lib
-    from tests.test_gpu_parity import _grid_scene
-    if shape == "track_cap_40":
-        n_s, n_pts, frames, floor = 2, 640, 3, 16
-        sb = make_checked(n_s, n_pts, "per_scene", tr_max_tracks=28, db_min_samples=12, track_cap=40)
-        pts = np.stack([_grid_scene(4300 + s, frames, n_pts, 18 + 2 * s) for s in range(n_s)], axis=1)
-    else:
-        from mmwave_msc_amd.batch import SceneBatch
-        n_s, n_pts, frames, floor = 2, 1024, 5, 32
-        sb = SceneBatch(_lib.default_config(tr_max_tracks=40, db_min_samples=12, track_cap=64), n_s, n_pts)
-        assert sb.track_cap == 64
-        pts = np.stack([_grid_scene(4700, frames, n_pts, 36), _grid_scene(4701, frames, n_pts, 5)], axis=1)
-    run = _Run(sb, 256)
-    run.set_wires(_wires16(n_s, margin=0.01, y0=40.0, y1=-40.0, x0=-6.0, pitch=0.75))
+    from tests._grid_scenes import many_tracks
+    sb, pts, n_s, n_pts, frames, floor = many_tracks(shape)
+    run = TripRun(sb, 256)
+    run.set_wires(wires16(n_s, margin=0.01, y0=40.0, y1=-40.0, x0=-6.0, pitch=0.75))
     most = 0
     for f in range(frames):
         sb.step_host(pts[f].astype(np.float64), np.full(n_s, n_pts, np.int32), np.full(n_s, 0.1))
@@ -495,20 +390,12 @@ def test_1027_scenes_the_scan_loop_a_short_last_block_and_scenes_without_wires()
     fourth scene has no wire: no row, no event."""
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.batch import SceneBatch
-    from mmwave_msc_amd.synth import make_scene
     Sn, Nn, Fn = 1027, 32, 5
-    pts = np.zeros((Fn, Sn, Nn, 8), np.float32)
-    cnt = np.zeros((Fn, Sn), np.int32)
-    dts = np.zeros((Fn, Sn))
-    for s in range(Sn):
-        presence = np.ones((Fn, 1), bool)
-        presence[: s % 3] = False            # arrives at frame 0, 1 or 2
-        presence[2 + s % 3:] = s % 5 != 0    # one scene in five: leaves again
-        pts[:, s], cnt[:, s], dts[:, s] = make_scene(7000 + s, Fn, Nn, 1, presence=presence)
+    pts, cnt, dts = coming_and_going(Sn, Nn, Fn)
     sb = SceneBatch(_lib.default_config(**CFG_KW), Sn, Nn)
-    run = _Run(sb, 16, (pts, cnt, dts))
+    run = TripRun(sb, 16, (pts, cnt, dts))
     with_wires = [s for s in range(Sn) if s % 4 != 3]
-    run.set_wires(_wires16(len(with_wires)), scenes=with_wires)
+    run.set_wires(wires16(len(with_wires)), scenes=with_wires)
     for f in range(Fn):
         run.step(f)
         if f == 3:
@@ -519,9 +406,9 @@ def test_1027_scenes_the_scan_loop_a_short_last_block_and_scenes_without_wires()
         assert len(rows) == 16 * len(with_wires) and set((rows["scene"] - BASE).tolist()) == set(with_wires)
         assert not np.isin((events["scene"] - BASE) % 4, (3,)).any()
         if f == 0:
-            assert _n_kind(events, _lib.TW_REBASED) == len(with_wires)
+            assert n_kind(events, _lib.TW_REBASED) == len(with_wires)
         if f == 3:
-            assert _n_kind(events, _lib.TW_REBASED) == len([s for s in with_wires if s % 64 == 1])
+            assert n_kind(events, _lib.TW_REBASED) == len([s for s in with_wires if s % 64 == 1])
     print("1027 scenes: forward, backward, kept", run.ref.n_forward, run.ref.n_backward, run.ref.n_kept)
     assert run.ref.n_forward + run.ref.n_backward > 0
     assert (run.ref.logged[Sn - 3:] > 0).any(), "the last, short block logged something"
@@ -630,7 +517,7 @@ def test_refused_arguments_touch_nothing():
     assert set_raw(None, 1, nw_ok, wt_ok) == 0
     assert sb.tripwires()[0][0] == 1 and sb.tripwires()[1][0, 1:].tobytes() == bytes(15 * 48)
     run.ref.set_wires([0], nw_ok, wt_ok)
-    nw, wt = _wires16(1)
+    nw, wt = wires16(1)
     run.set_wires((nw, wt), scenes=[0])
     # refused sample and export arguments: nothing queued, no ticket left behind, nothing taken
     sent = np.full(4096, 0x3C, np.uint8)
@@ -666,33 +553,29 @@ def test_nothing_else_moves():
     """A context that enables, sets, samples and exports tripwires ends the run with the snapshot bytes, report, zones and trails of
     one that never did, and both launched the same step kernels the same number of times (mmw_profile_get)."""
     from mmwave_msc_amd import _lib
-    from tests.test_gpu_zones import _strips
     a = make_checked(S2, N, "per_scene", **CFG_KW)
     b = make_checked(S2, N, "per_scene", **CFG_KW)
-    data = _cut(S2)
+    data = cut(S2)
     for sb in (a, b):
         sb.profile(True)
         sb.enable_report()
-        sb.set_zones(_strips(S2))
+        sb.set_zones(strips(S2))
         sb.enable_trails(4)
-    run = _Run(a, 64, data)
-    run.set_wires(_wires16(S2))
-    n_events = 0
-    for f in range(8):
-        for sb in (a, b):
-            _step(sb, f, data)
-            sb.sample_trails(t=0.25 * f)
+    run = TripRun(a, 64, data)
+    run.set_wires(wires16(S2))
+    n_events = []
+
+    def drive(f):
         run.sample(t=0.25 * f)
-        n_events += len(run.compare(f)[1])
+        n_events.append(len(run.compare(f)[1]))
         if f == 4:
             for sb in (a, b):
                 sb.reset_scenes(np.arange(S2) == 1)
             run.ref.rebase([1])
-        assert a.tracks().tobytes() == b.tracks().tobytes() and np.array_equal(a.num_tracks(), b.num_tracks()), f
-        for x, y in zip(a.report_host() + a.zones_host() + a.trails_host(), b.report_host() + b.zones_host() + b.trails_host()):
-            assert x.tobytes() == y.tobytes(), f
-    assert a.snapshot() == b.snapshot()
-    assert n_events > S2
+
+    nothing_else_moves(a, b, data, 8, drive, both=lambda sb, f: sb.sample_trails(t=0.25 * f),
+                       each_frame=TRACKS + REPORT + (lambda sb: sb.zones_host(), lambda sb: sb.trails_host()), at_end=(lambda sb: sb.snapshot(),))
+    assert sum(n_events) > S2
     counts = [(a.profile_get(k)[1], b.profile_get(k)[1]) for k in range(_lib.K_COUNT)]
     print("kernel launches (with tripwires, without)", counts)
     assert all(x == y for x, y in counts) and sum(y for _, y in counts) > 0, counts
@@ -710,13 +593,12 @@ def test_trails_and_tripwires_keep_separate_slot_tables():
     continuity), the restatements see 6 trail slots reused, 8 forward and 2 backward crossings, and 6 scene-frames after which the
     two consumers hold different uid sets; the run counts as not vacuous with one of each."""
     from mmwave_msc_amd import _lib
-    from tests.test_gpu_trails import _Run as _TrailRun
     Sn = 6
-    data = _cut(Sn)
+    data = cut(Sn)
     sb = make_checked(Sn, N, "per_scene", **CFG_KW)
-    trails = _TrailRun(sb, 4, data)
-    wires = _Run(sb, 64, data)
-    wires.set_wires(_wires16(Sn))
+    trails = TrailRun(sb, 4, data)
+    wires = TripRun(sb, 64, data)
+    wires.set_wires(wires16(Sn))
     even = [s for s in range(Sn) if s % 2 == 0]
     n_crossings = n_differ = 0
     for f in range(F):
@@ -730,7 +612,7 @@ def test_trails_and_tripwires_keep_separate_slot_tables():
         wires.sample(t=clock)
         trails.compare(("trails", f))
         _, events = wires.compare(("tripwires", f))
-        n_crossings += _n_kind(events, _lib.TW_FORWARD) + _n_kind(events, _lib.TW_BACKWARD)
+        n_crossings += n_kind(events, _lib.TW_FORWARD) + n_kind(events, _lib.TW_BACKWARD)
         n_differ += sum(set(trails.ref.trails[s]) != set(wires.ref.sides[s]) for s in range(Sn))
     sb.check()
     sb.close()

@@ -13,12 +13,10 @@ import itertools
 import numpy as np
 import pytest
 
-from tests._report_scenes import CFG_KW
+from tests._feature_run import export_and_compare, same_trails
+from tests._report_scenes import CFG_KW, as_tuples, host_events, strips, uid_lists
 from tests._trail_ref import TrailRef
 from tests._zone_ref import ZoneRef
-from tests.test_gpu_report import _as_tuples, _host_events, _uid_lists
-from tests.test_gpu_trails import _same as _trails_same
-from tests.test_gpu_zones import _export_and_compare, _strips
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +54,7 @@ class _Ctx:
         if report:
             self.sb.enable_report()
         if zones:
-            nz, zt = _strips(SN)
+            nz, zt = strips(SN)
             self.sb.set_zones((nz, zt))
             self.zref = ZoneRef(SN)
             self.zref.set_zones(nz, zt)
@@ -85,19 +83,19 @@ class _Ctx:
             sb.sample_trails(t=t)
             self.tref.sample(sb.tracks(), sb.num_tracks(), t=t)
             got = sb.trails_host()
-            _trails_same(got, self.tref.export(sb.tracks(), sb.num_tracks()), (ctx, "trails"))
+            same_trails(got, self.tref.export(sb.tracks(), sb.num_tracks()), (ctx, "trails"))
             out[2] = got[0]
         if self.report:
             rows, events = sb.report_host()
-            cur = _uid_lists(sb)
+            cur = uid_lists(sb)
             assert len(rows) == sum(len(c) for c in cur), ctx
             if self.prev is not None:
-                assert _as_tuples(events) == _host_events(self.prev, cur, rebased=rebased), (ctx, "report")
+                assert as_tuples(events) == host_events(self.prev, cur, rebased=rebased), (ctx, "report")
             assert sorted(int(e["scene"]) for e in events if e["kind"] == _lib.EV_REBASED) == sorted(rebased), (ctx, "report REBASED")
             self.prev = cur
             out[0] = events
         if self.zones:
-            _, events = _export_and_compare(sb, self.zref, (ctx, "zones"), scene_base=0)
+            _, events = export_and_compare(sb, self.zref, (ctx, "zones"), scene_base=0)
             assert sorted(int(e["scene"]) for e in events if e["kind"] == _lib.ZEV_REBASED) == sorted(rebased), (ctx, "zones REBASED")
             out[1] = events
         return out
@@ -119,9 +117,9 @@ def test_one_bump_serves_the_consumers_that_are_on(report, zones, trails):
     # the zones' REBASED for every scene (mmw_set_zones voided all it listed) and ENTER for the tracks that stand inside a zone
     if report:
         sb.report_host()
-        c.prev = _uid_lists(sb)
+        c.prev = uid_lists(sb)
     if zones:
-        _, events = _export_and_compare(sb, c.zref, "first zones", scene_base=0)
+        _, events = export_and_compare(sb, c.zref, "first zones", scene_base=0)
         assert len(events) > SN, "memberships exist"
     first = c.sample_and_export("baselines")
 
@@ -156,20 +154,20 @@ def test_one_bump_serves_the_consumers_that_are_on(report, zones, trails):
         # mmw_set_zones for scene 7 alone: the zones' word of scene 7, and no other word of anybody
         c.step()
         _, _, before = c.sample_and_export("settled")
-        nz, zt = _strips(SN, margin=0.125)
+        nz, zt = strips(SN, margin=0.125)
         sb.set_zones((nz[7:8], zt[7:8]), scenes=[7])
         c.zref.set_zones(nz[7:8], zt[7:8], scenes=[7])
         c.step()
         sb.sample_trails(t=np.full(SN, float(c.frame)))
         c.tref.sample(sb.tracks(), sb.num_tracks(), t=np.full(SN, float(c.frame)))
         d, p = sb.trails_host()
-        _trails_same((d, p), c.tref.export(sb.tracks(), sb.num_tracks()), "set_zones: trails")
+        same_trails((d, p), c.tref.export(sb.tracks(), sb.num_tracks()), "set_zones: trails")
         was, now = _totals(before[before["scene"] == 7]), _totals(d[d["scene"] == 7])
         assert was and set(was) <= set(now) and all(now[k] == was[k] + 1 for k in was), (was, now)   # scene 7's trails go on
         from mmwave_msc_amd import _lib
         _, events = sb.report_host()
-        cur = _uid_lists(sb)
-        assert _as_tuples(events) == _host_events(c.prev, cur) and not (events["kind"] == _lib.EV_REBASED).any()
-        _, zev = _export_and_compare(sb, c.zref, "set_zones: zones", scene_base=0)
+        cur = uid_lists(sb)
+        assert as_tuples(events) == host_events(c.prev, cur) and not (events["kind"] == _lib.EV_REBASED).any()
+        _, zev = export_and_compare(sb, c.zref, "set_zones: zones", scene_base=0)
         assert [int(e["scene"]) for e in zev if e["kind"] == _lib.ZEV_REBASED] == [7]
     sb.close()

@@ -5,60 +5,21 @@ Expected values come from tests/_zone_ref.py, a numpy restatement of the header'
 `tracks()` / `num_tracks()` after each step; it carries its own baseline.  Everything is integers: rows and events are compared
 exactly, field by field.  The scenario is tests/_report_scenes.py's (24 scenes x 96 points x 12 frames: tracks are born, walk and
 expire inside the run)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from tests._feature_run import BASE, REPORT, S2, TRACKS, cut, export_and_compare, n_kind, nothing_else_moves, same_records, settled, step
 from tests._layouts import make_checked
-from tests._report_scenes import CFG_KW, F, N, S, scenario
+from tests._report_scenes import CFG_KW, F, N, S, coming_and_going, strips
+from tests._snap_plant import REC_X, directory, plant_word, record_at
 from tests._zone_ref import ZoneRef
 
 pytestmark = pytest.mark.gpu
-
-BASE = 7      # scene_base of the compared exports
-
-
-def _step(sb, f, data=None):
-    pts, cnt, dts = data if data is not None else scenario()
-    sb.step_host(pts[f].astype(np.float64), cnt[f], dts[f])
-
-
-def _cut(n_scenes, n_frames=F):
-    pts, cnt, dts = scenario()
-    return pts[:n_frames, :n_scenes], cnt[:n_frames, :n_scenes], dts[:n_frames, :n_scenes]
-
-
-def _strips(n_scenes, margin=0.05):
-    """16 strips x in [-3 + 0.375 k, -3 + 0.375 (k + 1)), any y, per scene, with ids that differ per scene."""
-    from mmwave_msc_amd import _lib
-    return _lib.make_zones([[(-3.0 + 0.375 * k, -3.0 + 0.375 * (k + 1), -np.inf, np.inf, margin, 1000 * s + k) for k in range(16)]
-                            for s in range(n_scenes)])
-
-
-def _same(got, want, ctx):
-    assert got.dtype == want.dtype, ctx
-    assert len(got) == len(want), (ctx, len(got), len(want), got.tolist(), want.tolist())
-    for k in got.dtype.names:
-        assert np.array_equal(got[k], want[k]), (ctx, k, got.tolist(), want.tolist())
-
-
-def _export_and_compare(sb, ref, ctx, scene_base=BASE):
-    """One export of `sb` against the restatement on the state read back; (rows, events)."""
-    rows, events = sb.zones_host(scene_base=scene_base)
-    want_rows, want_events = ref.export(sb.tracks(), sb.num_tracks(), scene_base=scene_base)
-    _same(events, want_events, (ctx, "events"))
-    _same(rows, want_rows, (ctx, "rows"))
-    return rows, events
 
 
 def _roster_equals(roster, ref, scene_base=BASE):
     want = {(s + scene_base, z): frozenset(u) for (s, z), u in ref.membership().items()}
     assert roster.occupied() == want, (roster.occupied(), want)
-
-
-def _n_kind(events, kind):
-    return int((events["kind"] == kind).sum())
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------
@@ -68,7 +29,7 @@ def test_strips_rows_and_events_after_every_step(layout):
     from mmwave_msc_amd.zones import Roster
     sb = make_checked(S, N, layout, **CFG_KW)
     assert not sb.has_zones
-    nz, zt = _strips(S)
+    nz, zt = strips(S)
     sb.set_zones((nz, zt))
     assert sb.has_zones
     got_n, got_z = sb.zones()
@@ -77,9 +38,9 @@ def test_strips_rows_and_events_after_every_step(layout):
     ref.set_zones(nz, zt)
     tally = dict(enter_live=0, leave_live=0, enter_newborn=0, leave_expired=0, track_frames=0)
     for f in range(F):
-        _step(sb, f)
+        step(sb, f)
         before = [{u for u, _ in b} for b in ref.base]
-        rows, events = _export_and_compare(sb, ref, f)
+        rows, events = export_and_compare(sb, ref, f)
         roster.apply(events)
         _roster_equals(roster, ref)
         now = [{u for u, _ in b} for b in ref.base]
@@ -91,7 +52,7 @@ def test_strips_rows_and_events_after_every_step(layout):
             elif e["kind"] == _lib.ZEV_LEAVE:
                 tally["leave_live" if u in now[s] else "leave_expired"] += 1
         tally["track_frames"] += int(sb.num_tracks().sum())
-        assert _n_kind(events, _lib.ZEV_REBASED) == (S if f == 0 else 0), f   # (mmw_set_zones listed every scene)
+        assert n_kind(events, _lib.ZEV_REBASED) == (S if f == 0 else 0), f   # (mmw_set_zones listed every scene)
         assert len(rows) == 16 * S and int(rows["count"].sum()) == sum(len(v) for v in roster.occupied().values())
     sb.check()
     sb.close()
@@ -102,15 +63,12 @@ def test_strips_rows_and_events_after_every_step(layout):
 
 
 # 2 ------------------------------------------------------------------------------------------------------------------------
-S2 = 5
-
-
 def _record_positions():
     """Pass 1: the first five scenes without zones; per frame (uid[S2][T], x[S2][T][2], num_tracks)."""
     sb = make_checked(S2, N, "per_scene", **CFG_KW)
-    data, rec = _cut(S2), []
+    data, rec = cut(S2), []
     for f in range(F):
-        _step(sb, f, data)
+        step(sb, f, data)
         trk, ntr = sb.tracks(), sb.num_tracks()
         rec.append((trk["uid"].copy(), trk["x"][:, :, :2].copy(), ntr.copy()))
     sb.close()
@@ -173,14 +131,14 @@ def test_exact_bounds_margin_identity_and_non_finite_positions():
     sb.set_zones((nz, zt), scenes=[s])
     ref, roster = ZoneRef(S2), Roster()
     ref.set_zones(nz, zt, scenes=[s])
-    data = _cut(S2)
+    data = cut(S2)
     got = {}
     for k in range(f + 1):
-        _step(sb, k, data)
+        step(sb, k, data)
         if k in (f0, f):
             trk = sb.tracks()
             assert trk["uid"].tobytes() == rec[k][0].tobytes() and trk["x"][:, :, :2].tobytes() == rec[k][1].tobytes(), "the two passes differ"
-            got[k] = _export_and_compare(sb, ref, k)
+            got[k] = export_and_compare(sb, ref, k)
             roster.apply(got[k][1])
     ev0 = [(int(e["uid"]), int(e["kind"]), int(e["zone"])) for e in got[f0][1] if e["scene"] == s + BASE]
     ev1 = [(int(e["uid"]), int(e["kind"]), int(e["zone"])) for e in got[f][1] if e["scene"] == s + BASE]
@@ -189,19 +147,16 @@ def test_exact_bounds_margin_identity_and_non_finite_positions():
     assert roster.zones_of(s + BASE, uid) == [0, 2, 5], roster.zones_of(s + BASE, uid)
     assert ref.held >= 1
 
-    # NaN, +inf and -0.0 positions, planted in a snapshot blob and restored: x[0] of track t of a section is at offset + 64 + 1504 t
+    # NaN, +inf and -0.0 positions, planted in a snapshot blob and restored: x[0] of track t of a section (tests/_snap_plant.py: REC_X)
     ntr = sb.num_tracks()
     spots = [(sc, t) for sc in range(S2) for t in range(int(ntr[sc]))]
     assert len(spots) >= 3, ntr
     blob = bytearray(sb.snapshot())
-    hdr = _lib.MmwSnapshotHeader.from_buffer_copy(bytes(blob[: C.sizeof(_lib.MmwSnapshotHeader)]))
-    assert hdr.n_scenes == S2
-    ents = [_lib.MmwSnapshotEntry.from_buffer_copy(bytes(blob[hdr.header_bytes + i * hdr.entry_bytes: hdr.header_bytes + (i + 1) * hdr.entry_bytes]))
-            for i in range(S2)]
+    ents = directory(blob)
+    assert len(ents) == S2
     planted = dict(zip(spots[:3], (np.nan, np.inf, -0.0)))
     for (sc, t), v in planted.items():
-        at = ents[sc].offset + _lib.SNAP_SCENE_HDR_BYTES + _lib.SNAP_TRACK_BYTES * t
-        blob[at: at + 8] = np.float64(v).tobytes()
+        plant_word(blob, record_at(ents, sc, t) + REC_X, v)
     sb.restore(bytes(blob))
     nz2, zt2 = _lib.make_zones([[(-inf, inf, -inf, inf, 0.0, 60), (0.0, inf, -inf, inf, 0.0, 61), (-inf, 0.0, -inf, inf, 0.0, 62),
                                  (-5.0, 1e300, -inf, inf, 0.5, 63)]] * S2)
@@ -212,9 +167,9 @@ def test_exact_bounds_margin_identity_and_non_finite_positions():
     (s_nan, t_nan), (s_inf, t_inf), (s_neg, t_neg) = spots[:3]
     assert np.isnan(trk["x"][s_nan, t_nan, 0]) and trk["x"][s_inf, t_inf, 0] == np.inf
     assert trk["x"][s_neg, t_neg, 0] == 0.0 and np.signbit(trk["x"][s_neg, t_neg, 0])
-    rows, events = _export_and_compare(sb, ref, "planted")
-    assert _n_kind(events, R) == S2 and _n_kind(events, L) == 0
-    assert _n_kind(events, E) == len(events) - S2 > 0
+    rows, events = export_and_compare(sb, ref, "planted")
+    assert n_kind(events, R) == S2 and n_kind(events, L) == 0
+    assert n_kind(events, E) == len(events) - S2 > 0
     roster = Roster().apply(events)
     assert roster.zones_of(s_nan + BASE, int(trk["uid"][s_nan, t_nan])) == []          # NaN: every comparison is false
     assert roster.zones_of(s_inf + BASE, int(trk["uid"][s_inf, t_inf])) == []          # +inf < x1 is false for x1 = +inf and for a finite x1
@@ -227,17 +182,17 @@ def test_export_every_third_frame_gives_the_net_difference():
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.zones import Roster
     sb = make_checked(S, N, "per_scene", **CFG_KW)
-    nz, zt = _strips(S)
+    nz, zt = strips(S)
     sb.set_zones((nz, zt))
     ref, roster = ZoneRef(S), Roster()
     ref.set_zones(nz, zt)
     seen_uids, event_uids = set(), set()
     for f in range(F):
-        _step(sb, f)
+        step(sb, f)
         ntr, trk = sb.num_tracks(), sb.tracks()
         seen_uids |= {(s, int(trk["uid"][s, j])) for s in range(S) for j in range(int(ntr[s]))}
         if f % 3 == 2:
-            rows, events = _export_and_compare(sb, ref, f)
+            rows, events = export_and_compare(sb, ref, f)
             roster.apply(events)
             _roster_equals(roster, ref)
             event_uids |= {(int(e["scene"]) - BASE, int(e["uid"])) for e in events if e["kind"] != _lib.ZEV_REBASED}
@@ -249,11 +204,9 @@ def test_export_every_third_frame_gives_the_net_difference():
 # 4 ------------------------------------------------------------------------------------------------------------------------
 def _settled(n_scenes=S2, frames=8):
     """A context after `frames` frames with the strips defined and nothing exported yet, and the restatement for it."""
-    sb = make_checked(n_scenes, N, "per_scene", **CFG_KW)
-    data = _cut(n_scenes)
-    for f in range(frames):
-        _step(sb, f, data)
-    nz, zt = _strips(n_scenes)
+    sb = settled(lambda sb, data: sb, n_scenes, frames)
+    data = cut(n_scenes)
+    nz, zt = strips(n_scenes)
     sb.set_zones((nz, zt))
     ref = ZoneRef(n_scenes)
     ref.set_zones(nz, zt)
@@ -280,18 +233,18 @@ def test_capacity_is_decided_on_the_device_and_a_refused_export_loses_nothing():
     sb.zones_async(b_r.ptr, n_rows, b_e.ptr, n_events, 0, 0)
     assert sb.zones_wait(0) == (n_rows, n_events)
     t_rows, t_events = twin.zones_host()
-    _same(t_rows, want_rows, "twin rows")
-    _same(t_events, want_events, "twin events")
+    same_records(t_rows, want_rows, "twin", "rows")
+    same_records(t_events, want_events, "twin", "events")
     assert b_r.download((n_rows,), _lib.ZONE_ROW_DTYPE).tobytes() == t_rows.tobytes()
     assert b_e.download((n_events,), _lib.ZONE_EVENT_DTYPE).tobytes() == t_events.tobytes()
     assert np.array_equal(b_r.download(sent_r.shape, np.uint8)[n_rows * 32:], sent_r[n_rows * 32:])      # nothing past the rows
     assert np.array_equal(b_e.download(sent_e.shape, np.uint8)[n_events * 24:], sent_e[n_events * 24:])  # ... or the events
     for c in (sb, twin):
-        _step(c, 8, data)
+        step(c, 8, data)
     a_rows, a_events = sb.zones_host()
     t_rows, t_events = twin.zones_host()
     assert a_rows.tobytes() == t_rows.tobytes() and a_events.tobytes() == t_events.tobytes()
-    assert _n_kind(a_events, _lib.ZEV_REBASED) == 0
+    assert n_kind(a_events, _lib.ZEV_REBASED) == 0
     for b in (b_r, b_e):
         b.free()
     sb.close(); twin.close()
@@ -302,8 +255,8 @@ def test_reset_restore_and_set_zones_rebase_their_scenes_only():
     from mmwave_msc_amd import _lib
     R = _lib.ZEV_REBASED
     sb = make_checked(S2, N, "per_scene", **CFG_KW)
-    data = _cut(S2)
-    nz, zt = _strips(S2)
+    data = cut(S2)
+    nz, zt = strips(S2)
     sb.set_zones((nz, zt))
     ref = ZoneRef(S2)
     ref.set_zones(nz, zt)
@@ -313,20 +266,20 @@ def test_reset_restore_and_set_zones_rebase_their_scenes_only():
 
     f, elsewhere = 0, 0
     for _ in range(5):
-        _step(sb, f, data); f += 1
-        _export_and_compare(sb, ref, f)
+        step(sb, f, data); f += 1
+        export_and_compare(sb, ref, f)
     # reset_scenes
     sb.reset_scenes(np.isin(np.arange(S2), (1, 3)))
     ref.rebase((1, 3))
-    _step(sb, f, data); f += 1
-    _, events = _export_and_compare(sb, ref, "reset_scenes")
+    step(sb, f, data); f += 1
+    _, events = export_and_compare(sb, ref, "reset_scenes")
     assert rebased_scenes(events) == [1, 3]
     elsewhere += sum(e["kind"] != R and int(e["scene"]) - BASE not in (1, 3) for e in events)
     # restore: scene 0's state into scene 2
     sb.restore(sb.snapshot([0]), scenes=[2])
     ref.rebase((2,))
-    _step(sb, f, data); f += 1
-    _, events = _export_and_compare(sb, ref, "restore")
+    step(sb, f, data); f += 1
+    _, events = export_and_compare(sb, ref, "restore")
     assert rebased_scenes(events) == [2]
     elsewhere += sum(e["kind"] != R and int(e["scene"]) - BASE != 2 for e in events)
     assert np.array_equal(sb.zones()[0], nz) and sb.zones()[1].tobytes() == zt.tobytes()    # zones belong to the slot
@@ -334,19 +287,19 @@ def test_reset_restore_and_set_zones_rebase_their_scenes_only():
     nz4, zt4 = _lib.make_zones([[(-1.0, 1.0, 0.0, 4.0, 0.1, 444), (-3.0, 3.0, 4.0, np.inf, 0.1, 445)]])
     sb.set_zones((nz4, zt4), scenes=[4])
     ref.set_zones(nz4, zt4, scenes=[4])
-    _step(sb, f, data); f += 1
-    rows, events = _export_and_compare(sb, ref, "set_zones")
+    step(sb, f, data); f += 1
+    rows, events = export_and_compare(sb, ref, "set_zones")
     assert rebased_scenes(events) == [4] and len(rows) == 16 * (S2 - 1) + 2
     elsewhere += sum(e["kind"] != R and int(e["scene"]) - BASE != 4 for e in events)
     assert elsewhere > 0   # ... and ordinary events in the scenes that were not rebased
     # reset(): every scene, and the zones stay
     sb.reset()
     ref.rebase()
-    rows, events = _export_and_compare(sb, ref, "reset")
+    rows, events = export_and_compare(sb, ref, "reset")
     assert rebased_scenes(events) == list(range(S2)) and len(events) == S2 and (events["slot"] == 0).all()
     assert len(rows) == 16 * (S2 - 1) + 2 and not rows["count"].any()
-    _step(sb, 0, data)
-    _, events = _export_and_compare(sb, ref, "after reset")
+    step(sb, 0, data)
+    _, events = export_and_compare(sb, ref, "after reset")
     assert rebased_scenes(events) == []
     sb.close()
 
@@ -358,17 +311,8 @@ def test_many_tracks_and_all_16_overlapping_zones(shape):
     targets (lanes past 32); 16 zones that overlap, so that tracks sit in several at once."""
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.zones import Roster
-    from tests.test_gpu_parity import _grid_scene
-    if shape == "track_cap_40":
-        n_s, n_pts, frames, floor = 2, 640, 3, 16
-        sb = make_checked(n_s, n_pts, "per_scene", tr_max_tracks=28, db_min_samples=12, track_cap=40)
-        pts = np.stack([_grid_scene(4300 + s, frames, n_pts, 18 + 2 * s) for s in range(n_s)], axis=1)
-    else:
-        from mmwave_msc_amd.batch import SceneBatch
-        n_s, n_pts, frames, floor = 2, 1024, 5, 32
-        sb = SceneBatch(_lib.default_config(tr_max_tracks=40, db_min_samples=12, track_cap=64), n_s, n_pts)
-        assert sb.track_cap == 64
-        pts = np.stack([_grid_scene(4700, frames, n_pts, 36), _grid_scene(4701, frames, n_pts, 5)], axis=1)
+    from tests._grid_scenes import many_tracks
+    sb, pts, n_s, n_pts, frames, floor = many_tracks(shape)
     nz, zt = _lib.make_zones([[(-6.0 + 0.5 * k, -1.5 + 0.5 * k, 0.5 + 0.25 * k, np.inf, 0.1, 100 * s + k) for k in range(16)] for s in range(n_s)])
     sb.set_zones((nz, zt))
     ref, roster = ZoneRef(n_s), Roster()
@@ -376,7 +320,7 @@ def test_many_tracks_and_all_16_overlapping_zones(shape):
     most = 0
     for f in range(frames):
         sb.step_host(pts[f].astype(np.float64), np.full(n_s, n_pts, np.int32), np.full(n_s, 0.1))
-        rows, events = _export_and_compare(sb, ref, f)
+        rows, events = export_and_compare(sb, ref, f)
         roster.apply(events)
         most = max(most, int(sb.num_tracks().max()))
     _roster_equals(roster, ref)
@@ -395,34 +339,26 @@ def test_1027_scenes_the_scan_loop_a_short_last_block_and_scenes_without_zones()
     other scene has no zone: no row, and only its REBASED after a reset."""
     from mmwave_msc_amd import _lib
     from mmwave_msc_amd.batch import SceneBatch
-    from mmwave_msc_amd.synth import make_scene
     Sn, Nn, Fn = 1027, 32, 5
-    pts = np.zeros((Fn, Sn, Nn, 8), np.float32)
-    cnt = np.zeros((Fn, Sn), np.int32)
-    dts = np.zeros((Fn, Sn))
-    for s in range(Sn):
-        presence = np.ones((Fn, 1), bool)
-        presence[: s % 3] = False            # arrives at frame 0, 1 or 2
-        presence[2 + s % 3:] = s % 5 != 0    # one scene in five: leaves again
-        pts[:, s], cnt[:, s], dts[:, s] = make_scene(7000 + s, Fn, Nn, 1, presence=presence)
+    pts, cnt, dts = coming_and_going(Sn, Nn, Fn)
     sb = SceneBatch(_lib.default_config(**CFG_KW), Sn, Nn)
     with_zones = list(range(0, Sn, 2))
-    nz, zt = _strips(len(with_zones))
+    nz, zt = strips(len(with_zones))
     sb.set_zones((nz, zt), scenes=with_zones)
     ref = ZoneRef(Sn)
     ref.set_zones(nz, zt, scenes=with_zones)
     n_enter = n_leave = 0
     for f in range(Fn):
-        _step(sb, f, (pts, cnt, dts))
+        step(sb, f, (pts, cnt, dts))
         if f == 3:
             sb.reset_scenes(np.isin(np.arange(Sn) % 64, (1, 2)))    # scenes without a zone among them: a REBASED and nothing else
             ref.rebase([s for s in range(Sn) if s % 64 in (1, 2)])
-        rows, events = _export_and_compare(sb, ref, f)
+        rows, events = export_and_compare(sb, ref, f)
         assert len(rows) == 16 * len(with_zones) and set(rows["scene"] - BASE) == set(with_zones)
-        n_enter += _n_kind(events, _lib.ZEV_ENTER)
-        n_leave += _n_kind(events, _lib.ZEV_LEAVE)
+        n_enter += n_kind(events, _lib.ZEV_ENTER)
+        n_leave += n_kind(events, _lib.ZEV_LEAVE)
         if f == 3:
-            assert _n_kind(events, _lib.ZEV_REBASED) == len([s for s in range(Sn) if s % 64 in (1, 2)])
+            assert n_kind(events, _lib.ZEV_REBASED) == len([s for s in range(Sn) if s % 64 in (1, 2)])
     ntr = sb.num_tracks()
     assert ntr[Sn - 1] or ntr[Sn - 2] or ntr[Sn - 3], "the last, short block holds tracks"
     assert (events["scene"] - BASE >= Sn - 3).any() or (rows["count"][rows["scene"] - BASE >= Sn - 3] > 0).any()
@@ -440,9 +376,9 @@ def test_two_tickets_around_a_step():
     pts, cnt, dts = data
     for sb in (a, b):
         assert len(sb.zones_host()[1]) > 0
-        _step(sb, frames - 2, data)
+        step(sb, frames - 2, data)
     want0 = b.zones_host()
-    _step(b, frames - 1, data)
+    step(b, frames - 1, data)
     want1 = b.zones_host()
     print("two tickets: events", len(want0[1]), len(want1[1]))
     assert want0[0].tobytes() + want0[1].tobytes() != want1[0].tobytes() + want1[1].tobytes()   # the two exports differ: an order mix-up shows
@@ -503,9 +439,9 @@ def _refusals(n_scenes):
 def test_refused_arguments_touch_nothing():
     from mmwave_msc_amd import _lib
     sb = make_checked(S2, N, "per_scene", **CFG_KW)
-    data = _cut(S2)
+    data = cut(S2)
     for f in range(4):
-        _step(sb, f, data)
+        step(sb, f, data)
     buf = sb.alloc(4096)
     L = sb.L
 
@@ -527,11 +463,11 @@ def test_refused_arguments_touch_nothing():
     exports_refused()
     assert not sb.zones()[0].any() and sb.zones()[1].tobytes() == bytes(S2 * 16 * 48)
     # with a table: every refusal leaves table, baseline and generations as they were
-    nz, zt = _strips(S2)
+    nz, zt = strips(S2)
     sb.set_zones((nz, zt))
     ref = ZoneRef(S2)
     ref.set_zones(nz, zt)
-    _export_and_compare(sb, ref, "first")
+    export_and_compare(sb, ref, "first")
     before = sb.zones()
     for name, args in _refusals(S2).items():
         assert set_raw(*args) == _lib.E_ARG, name
@@ -562,8 +498,8 @@ def test_refused_arguments_touch_nothing():
             sb.zones_wait(t)
     sb.synchronize()
     assert np.array_equal(buf.download(sent.shape, np.uint8), sent)
-    _step(sb, 4, data)
-    _export_and_compare(sb, ref, "after the refusals")
+    step(sb, 4, data)
+    export_and_compare(sb, ref, "after the refusals")
     # mmw_clear_zones: as before the first mmw_set_zones; a new table starts from an empty baseline
     sb.clear_zones()
     assert not sb.has_zones and not sb.zones()[0].any()
@@ -572,7 +508,7 @@ def test_refused_arguments_touch_nothing():
     sb.set_zones((nz, zt))
     ref = ZoneRef(S2)
     ref.set_zones(nz, zt)
-    _export_and_compare(sb, ref, "after clear")
+    export_and_compare(sb, ref, "after clear")
     buf.free()
     sb.check()
     sb.close()
@@ -582,30 +518,22 @@ def test_refused_arguments_touch_nothing():
 def test_nothing_else_moves():
     a = make_checked(S2, N, "per_scene", **CFG_KW)
     b = make_checked(S2, N, "per_scene", **CFG_KW)
-    data = _cut(S2)
+    data = cut(S2)
     for sb in (a, b):
         sb.enable_report()
-    a.set_zones(_strips(S2))
+    a.set_zones(strips(S2))
     ref = ZoneRef(S2)
-    ref.set_zones(*_strips(S2))
-    n_events = 0
-    for f in range(8):
-        for sb in (a, b):
-            _step(sb, f, data)
-        n_events += len(_export_and_compare(a, ref, f)[1])
-        assert a.tracks().tobytes() == b.tracks().tobytes() and np.array_equal(a.num_tracks(), b.num_tracks()), f
-        for x, y in zip(a.report_host(), b.report_host()):
-            assert x.tobytes() == y.tobytes(), f
-        assert a.skeletons_host().tobytes() == b.skeletons_host().tobytes(), f
-        for x, y in zip(a.batch_ring(), b.batch_ring()):
-            assert np.array_equal(x, y), f
-    glen, _ = a.batch_ring()
-    for s in range(S2):
-        for k in range(int(glen[s])):
-            assert a.batch_ring_frame(s, k).tobytes() == b.batch_ring_frame(s, k).tobytes(), (s, k)
-        for j in range(int(a.num_tracks()[s])):
-            for k in range(int(a.tracks()["ring_len"][s, j])):
-                assert a.track_ring_frame(s, j, k).tobytes() == b.track_ring_frame(s, j, k).tobytes(), (s, j, k)
-    assert n_events > 3 * S2
+    ref.set_zones(*strips(S2))
+    n_events = []
+
+    def ring_frames(sb):
+        """Every frame of the global ring and of every live track's ring."""
+        (glen, _), ntr, ring_len = sb.batch_ring(), sb.num_tracks(), sb.tracks()["ring_len"]
+        return [[sb.batch_ring_frame(s, k) for k in range(int(glen[s]))] +
+                [sb.track_ring_frame(s, j, k) for j in range(int(ntr[s])) for k in range(int(ring_len[s, j]))] for s in range(S2)]
+
+    nothing_else_moves(a, b, data, 8, lambda f: n_events.append(len(export_and_compare(a, ref, f)[1])),
+                       each_frame=TRACKS + REPORT + (lambda sb: sb.skeletons_host(), lambda sb: sb.batch_ring()), at_end=(ring_frames,))
+    assert sum(n_events) > 3 * S2
     a.check(); b.check()
     a.close(); b.close()
