@@ -869,6 +869,56 @@ def gen_decision_edges():
     np.savez_compressed(os.path.join(GOLDEN_DIR, "decision_edges.npz"), meta=_meta(), **out)
 
 
+def gen_track_exceptions():
+    """tests/golden/track_exceptions.npz: the reference on the error scenes of tests/_error_scenes.py -- finite rows on which track()
+    leaves a frame through numpy's LinAlgError (a singular 6 x 6) or a ZeroDivisionError (_get_Rc, a = n / N_est), and their
+    neighbours that must not raise.  Per scene: the inputs, the configuration and, per frame, either the usual results
+    (association, DBSCAN labels, track list) or the exception's class name (`raised`, with `raised_at`).  Driven as
+    gen_decision_edges drives the reference."""
+    import warnings
+    from tests import _error_scenes as es
+    from tests._fuzz import reference_overrides
+    const, utils, _ = load_reference()
+    cases = [(d, name, sc) for d in es.DIM_X for name, sc in es.scenes(d).items()]
+    K, F, n = len(cases), 6, es.MAX_PTS
+    rec = dict(pts=np.zeros((K, F, n, 8), np.float32), cnt=np.zeros((K, F), np.int32), dt=np.zeros((K, F)), frames=np.zeros(K, np.int32),
+               assoc=np.full((K, F, n), -2, np.int16), db_n=np.full((K, F), -1, np.int32), labels=np.full((K, F, n), -2, np.int16),
+               n_tracks=np.full((K, F), -1, np.int32), tracks=np.zeros((K, F, 4), dtype=TRACK_DTYPE), raised_at=np.full(K, -1, np.int32))
+    raised = []
+    for k, (dim_x, name, sc) in enumerate(cases):
+        over = reference_overrides(sc.cfg)
+        over["MOTION_MODEL"] = getattr(const, over["MOTION_MODEL"])
+        saved = utils.apply_DBscan.__defaults__
+        utils.apply_DBscan.__defaults__ = (float(sc.cfg.get("db_eps", const.DB_EPS)), int(sc.cfg["db_min_samples"]))
+        ref = RefScene(dict(over))
+        f = sc.pts.shape[0]
+        rec["pts"][k, :f], rec["cnt"][k, :f], rec["dt"][k, :f], rec["frames"][k] = sc.pts, sc.cnt, sc.dt, f
+        what = ""
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                for i in range(f):
+                    c = int(sc.cnt[i])
+                    try:
+                        a, lab = ref.track(sc.pts[i, :c], float(sc.dt[i]))
+                    except (np.linalg.LinAlgError, ZeroDivisionError) as e:
+                        what, rec["raised_at"][k] = type(e).__name__, i
+                        break
+                    rec["assoc"][k, i, :c] = a
+                    if lab is not None:
+                        rec["db_n"][k, i] = len(lab)
+                        rec["labels"][k, i, : len(lab)] = lab
+                    rec["n_tracks"][k, i] = ref.n_tracks
+                    rec["tracks"][k, i, : ref.n_tracks] = ref.tracks()
+        finally:
+            ref.close()
+            utils.apply_DBscan.__defaults__ = saved
+        raised.append(what)
+        print(f"  track_exceptions dim_x={dim_x} {name}: " + (f"{what} in frame {rec['raised_at'][k]}" if what else f"{f} frames, no exception"))
+    np.savez_compressed(os.path.join(GOLDEN_DIR, "track_exceptions.npz"), meta=_meta(), names=np.array([f"d{d}__{name}" for d, name, _ in cases]),
+                        cfg=np.array([json.dumps(sc.cfg, sort_keys=True) for _, _, sc in cases]), raised=np.array(raised), **rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -884,6 +934,8 @@ def main():
         gen_scenario(name, sc)
     if not args.only or args.only == "decision_edges":
         gen_decision_edges()
+    if not args.only or args.only == "track_exceptions":
+        gen_track_exceptions()
     if not args.only or args.only == "normalize":
         gen_normalize()
     if not args.only or args.only == "constants":

@@ -27,7 +27,9 @@ F64_FIELDS = ("x", "P", "centroid", "min_vals", "max_vals", "spread_est", "group
 
 
 def scenario_names():
-    return sorted(os.path.basename(p)[len("track_"):-4] for p in glob.glob(os.path.join(GOLDEN, "track_*.npz")))
+    # (track_exceptions.npz is not a scenario: the error scenes of tests/_error_scenes.py, all in one file)
+    names = sorted(os.path.basename(p)[len("track_"):-4] for p in glob.glob(os.path.join(GOLDEN, "track_*.npz")))
+    return [n for n in names if n != "exceptions"]
 
 
 def load_scenario(name):

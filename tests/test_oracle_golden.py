@@ -208,3 +208,40 @@ def test_normalize_edges_recording_is_what_the_generator_writes(tmp_path):
     for k in a.files:
         if k != "meta":
             assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
+
+
+EXCEPTIONS = os.path.join(GOLDEN, "track_exceptions.npz")
+
+
+@pytest.mark.skipif(not os.path.isfile(EXCEPTIONS), reason="tests/golden/track_exceptions.npz is absent")
+def test_oracle_return_codes_match_the_exceptions_the_reference_raised():
+    """tests/golden/track_exceptions.npz (oracle/gen_golden.py gen_track_exceptions): the live reference on the error scenes of
+    tests/_error_scenes.py.  Where it raised LinAlgError the oracle returns -2 on that frame, where it raised ZeroDivisionError
+    -3, where it raised nothing 0; up to there association, labels and track lists are the recording's.  The listed exception is
+    the denormal-pivot band (_error_scenes.BAND_DEVIATES): the reference, through LAPACK, inverts; the oracle's lu6 reports the
+    NaN pivot as singular (tests/test_error_scenes.py, DESIGN.md "Errors")."""
+    import json
+    from tests import _error_scenes as es
+    g = np.load(EXCEPTIONS, allow_pickle=False)
+    names = [str(v) for v in g["names"]]
+    assert sorted(names) == sorted(f"d{d}__{n}" for d in es.DIM_X for n in es.EXPECT), "the recording is of other scenes"
+    want_rc = {"": 0, "LinAlgError": es.RC_SINGULAR, "ZeroDivisionError": es.RC_DIVZERO}
+    for k, full in enumerate(names):
+        dim_x, name = int(full[1]), full[4:]
+        sc, r = es.scenes(dim_x)[name], es.replays(dim_x)[name]
+        f = int(g["frames"][k])
+        assert f == len(sc.cnt) and np.array_equal(g["pts"][k, :f].astype(np.float64), sc.pts) and np.array_equal(g["cnt"][k, :f], sc.cnt), full
+        assert np.array_equal(g["dt"][k, :f], sc.dt) and json.loads(str(g["cfg"][k])) == json.loads(json.dumps(sc.cfg)), full
+        raised, at = str(g["raised"][k]), int(g["raised_at"][k])
+        if name in es.BAND_DEVIATES:
+            assert raised == "" and r.rc == es.RC_SINGULAR, (full, raised, r.rc)         # the known deviation, as it stands
+        else:
+            assert r.rc == want_rc[raised] and (r.at if r.rc else -1) == at, (full, raised, at, r.rc, r.at)
+        for i, fr in enumerate(r.frames):
+            c, ctx = int(sc.cnt[i]), f"{full} f{i}"
+            assert np.array_equal(fr.assoc, g["assoc"][k, i, :c]), ctx
+            dbn = int(g["db_n"][k, i])
+            assert (fr.labels is None) == (dbn < 0) and (dbn < 0 or np.array_equal(fr.labels, g["labels"][k, i, :dbn])), ctx
+            nt = int(g["n_tracks"][k, i])
+            assert fr.n_tracks == nt, ctx
+            assert_tracks_match(fr.tracks, g["tracks"][k, i, :nt], ctx=ctx)
